@@ -10,12 +10,8 @@ import ctypes as C
 import os
 import subprocess
 
-# HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  An RCCL communicator takes
-# queues of its own; with the default, the audio tower's side stream then shares a queue with the main stream
-# and the towers serialise (measured: +0.5..0.9 ms per step the moment a process group exists, collectives or
-# not; 8 queues: no difference to the single-process step).  Read by the HIP runtime when it initialises, so
-# this has to happen before the first HIP call of the process.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# HIP multiplexes streams onto a fixed number of hardware queues (the runtime's default: 4), which the library takes as
+# it finds it: avid_hip/streams.py probes which of its streams really overlap and places the step's streams on those.
 
 # torch must be imported BEFORE libavid_hip.so is dlopen'ed: torch ships its own libamdhip64.so, and a process
 # that loads /opt/rocm's copy first (through this library's DT_NEEDED) ends up with two HIP runtimes — the

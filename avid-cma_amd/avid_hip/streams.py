@@ -1,7 +1,7 @@
 """Placement of the step's streams on the hardware's dispatch pipes.
 
 A training step uses four streams: the compute stream (video tower), the audio tower's, one trailing stream for the
-weight gradients, and one that carries the gradient collectives.  HIP maps streams onto ``GPU_MAX_HW_QUEUES`` hardware
+weight gradients, and one that carries the gradient collectives.  HIP maps streams onto the runtime's hardware
 queues in creation order, and the queues onto FOUR dispatch pipes.  Measured on MI355X (tools/queue_probe2.py,
 DESIGN.md §5b):
 
@@ -10,7 +10,7 @@ DESIGN.md §5b):
   when one of them waits for an event of the other, the pipe sits in the waiting queue's barrier packet until a time
   slice expires: every dispatch of the step then costs ~60 us more (11.3 -> 19-23 ms per step).  Which streams collide
   depends on how many streams the process created before (an RCCL communicator creates its own), i.e. it comes and
-  goes with ``GPU_MAX_HW_QUEUES``, with a process group, with two more streams in a test.
+  goes with the hardware-queue count, with a process group, with two more streams in a test.
 
 So the streams are not taken as created: a pool of candidates is PROBED against the compute stream and against each
 other — a chain of single-wave ~25 us kernels on each of two streams; serialised pairs take twice as long as concurrent

@@ -26,8 +26,6 @@ for _p in (REPO, os.path.join(REPO, "avid-cma_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # see avid_hip/lib.py: must precede HIP runtime initialisation
-
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -235,6 +233,48 @@ def extra_configs(engine, model, video, audio, dev, lib, steps=10, warmup=3):
     return res
 
 
+DUMP_SAMPLE = 1 << 20        # elements kept of an output larger than this (a fixed, seeded sample)
+
+
+def step_outputs(engine, loss, index):
+    """What the timed step hands its caller after its last step, as host float32 arrays: the loss, the updated parameters,
+    their gradients and Adam moments (the flat buffers), the BatchNorm running statistics, and the criterion's state (its
+    normalisation constant; of the two memory banks the rows this step wrote, plus a sample of all rows).  Tensors above
+    DUMP_SAMPLE elements are sampled at positions drawn from a fixed seed, so that two builds dump the same elements;
+    ``sample_index_<n>`` holds the positions used for tensors of n elements."""
+    import numpy as np
+    positions = {}
+
+    def sample(name, t):
+        t = t.detach().reshape(-1)
+        if t.numel() <= DUMP_SAMPLE:
+            return {name: t}
+        n = t.numel()
+        if n not in positions:       # one draw per size: the flat buffers share theirs, and so do the two banks
+            positions[n] = torch.randperm(n, generator=torch.Generator().manual_seed(2024))[:DUMP_SAMPLE].sort().values
+        return {name + "_sample": t[positions[n].to(t.device)]}
+
+    out = {"loss": loss.detach().reshape(1)}
+    out.update(sample("params", engine.flat.flat))
+    out.update(sample("grads", engine.flat.grad))
+    if engine.m is not None:
+        out.update(sample("adam_m", engine.m))
+        out.update(sample("adam_v", engine.v))
+    if engine.flat_buffers.flat is not None:
+        out.update(sample("bn_buffers", engine.flat_buffers.flat))
+    for name, t in engine.criterion.state_dict().items():
+        if not t.is_floating_point():
+            continue
+        name = name.replace(".", "_")
+        if t.dim() == 2 and t.shape[0] > int(index.max()):    # a memory bank: the rows of this step, and a sample
+            out[name + "_step_rows"] = t[index.long()]
+        out.update(sample(name, t))
+    arrays = {k: v.float().cpu().numpy() for k, v in out.items()}
+    for n, pos in positions.items():       # where the samples of a size-n tensor were taken (exact in float64)
+        arrays[f"sample_index_{n}"] = pos.double().numpy()
+    return arrays
+
+
 def reference_loop(model, crit, video, audio, ids, dev, steps=30, warmup=6, dropin=False):
     """clips/s of the REFERENCE's loop shape on the same kernels (main-avid.py:155-180, utils/main_utils.py:112,250):
     torch DistributedDataParallel around the model (one-rank group), torch.optim.Adam, and the host synchronisation
@@ -378,6 +418,9 @@ def main():
     ap.add_argument("--cu-reserve", type=int, default=-1,
                     help="CUs the persistent kernels leave to RCCL's workgroups when gradients are all-reduced (N > 1); "
                          "default: 0 and 8 are both timed during warm-up and the faster is kept")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32; tensors over "
+                         f"{DUMP_SAMPLE} elements as a fixed, seeded sample, its positions in sample_index_<n>.npy)")
     args = ap.parse_args()
 
     cmd = launcher_command(args.gpus, sys.argv[1:], torch.cuda.device_count(), os.environ)
@@ -388,11 +431,6 @@ def main():
         raise SystemExit(subprocess.call(cmd))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world > 1 or os.environ.get("AVID_FORCE_DIST", "0") == "1":
-        # (before the HIP runtime starts) one hardware queue per stream — compute, audio tower, bucket launches, RCCL's
-        # own: with the runtime's default of four, two of them share a queue and wait behind each other (one-rank
-        # RCCL group: 4320 -> 4560 clips/s)
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world and world > 1:
@@ -530,6 +568,8 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     clock_ghz = sampler.stop()
+    # (before anything else runs a step: the host-issue probe below takes five more)
+    dumped = step_outputs(engine, loss, ids[args.warmup + args.steps - 1]) if args.dump_outputs and rank == 0 else None
     # host issue time: how long the host needs to ENQUEUE a step (5 steps issued back to back, nothing waited for) —
     # the margin between it and ms_per_step is what a slower host may eat before the GPU starves
     t0 = time.perf_counter()
@@ -657,6 +697,13 @@ def main():
                 print(f"{k:34s} {v['launches'] / kern_steps:11.1f} {v['ms'] / kern_steps:9.3f} "
                       f"{100 * v['ms'] / tot:6.1f} {tf:9.2f} {gb:10.1f}", file=sys.stderr)
             print(f"timed kernels {tot / kern_steps:.3f} ms/step of {ms:.3f} ms wall", file=sys.stderr)
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for k, v in dumped.items():
+                np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped),
+                                   "bytes": int(sum(v.nbytes for v in dumped.values()))}
         # (side measurements must never cost the line: a failure is reported inside it)
         try:
             out["roofline"]["r2p1d_forward"] = forward_roofline(model, video, lib)

@@ -82,29 +82,34 @@ def test_nce_checkpoint_shape_quirk():
     assert c.avg_exp_score.shape == () and float(c.avg_exp_score) == 3.5
 
 
-def test_reference_factories_resolve_build_classes():
-    """The drop-in claim end to end on the host: with avid-cma_amd ahead of the reference checkout on
-    sys.path, the reference's OWN factories (utils/main_utils.py:74-94, :231-238) build this repo's
-    classes from the reference's own YAML config.  Skipped where the reference is absent (GPU box)."""
+def test_reference_factories_resolve_build_classes(tmp_path):
+    """The drop-in claim end to end on the host: with avid-cma_amd ahead of a reference checkout on sys.path, the
+    reference's factory (utils/main_utils.py:74-94: ``models.__dict__[cfg['arch']](**cfg['args'])``) builds this repo's
+    classes from the reference's YAML config.  The checkout is a stand-in written here with the factory's shape, and the
+    config's ``model`` / ``loss`` sections are stored in tests/golden/cross_n1024_config.json (configs/main/avid/kinetics/
+    Cross-N1024.yaml)."""
     import importlib
+    import json
     import os
     import sys
-    import pytest
-    import yaml
-    ref = "/root/reference"
-    if not os.path.isdir(ref):
-        pytest.skip("reference checkout not present")
+    ref = str(tmp_path / "ref")
+    os.makedirs(os.path.join(ref, "utils"))
+    with open(os.path.join(ref, "utils", "main_utils.py"), "w") as f:     # a stand-in with the factory's shape
+        f.write("def build_model(cfg, logger=None):\n"
+                "    import models\n"
+                "    arch = cfg['arch']\n"
+                "    assert arch in vars(models), arch\n"
+                "    return vars(models)[arch](**cfg['args'])\n")
+    cfg = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cross_n1024_config.json")))
     sys.path.append(ref)                                   # AFTER ours (conftest put avid-cma_amd first)
     try:
         for k in [k for k in sys.modules if k == "utils" or k.startswith("utils.")]:
             del sys.modules[k]
-        main_utils = importlib.import_module("utils.main_utils")          # the reference's file, executed by this package's hook
+        main_utils = importlib.import_module("utils.main_utils")          # the stand-in, executed by this package's hook
         assert main_utils.REFERENCE_FILE.startswith(ref) and main_utils.build_model.__code__.co_filename.startswith(ref)
-        cfg = yaml.safe_load(open(os.path.join(ref, "configs/main/avid/kinetics/Cross-N1024.yaml")))
         model = main_utils.build_model(cfg["model"])
         import models
-        assert type(model).__module__ == "models.av_wrapper" and models.__file__.startswith(os.path.dirname(ref) + "/repo") \
-            or "avid-cma_amd" in models.__file__
+        assert type(model).__module__ == "models.av_wrapper" and "avid-cma_amd" in models.__file__
         assert model.out_dim == 128 and len(model.state_dict()) == 267
         from utils.alias_method import AliasMethod
         assert "avid-cma_amd" in sys.modules["utils.alias_method"].__file__ and AliasMethod(torch.ones(5)).uniform
@@ -173,27 +178,56 @@ def test_bench_launcher_argument_handling():
         bench.launcher_command(8, [], 0, {})
 
 
+def test_bench_dump_outputs_are_a_fixed_sample_of_the_step_state():
+    """`bench.py --dump-outputs`: the arrays are float32 / float64, under 64 MB in all, and a tensor too large to dump whole is
+    sampled at the same positions every time (two builds are compared element for element)."""
+    import importlib.util
+    import os
+    import types
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, rows = 3 * bench.DUMP_SAMPLE + 5, 40000
+    g = torch.Generator().manual_seed(3)
+    crit = torch.nn.Module()
+    crit.register_buffer("view1_mem", torch.randn(rows, 128, generator=g))
+    crit.register_buffer("avg_exp_score", torch.tensor(2.5))
+    engine = types.SimpleNamespace(flat=types.SimpleNamespace(flat=torch.randn(n, generator=g), grad=torch.randn(n, generator=g)),
+                                   m=torch.randn(n, generator=g), v=torch.rand(n, generator=g),
+                                   flat_buffers=types.SimpleNamespace(flat=torch.randn(1000, generator=g)), criterion=crit)
+    index = torch.tensor([7, 3, 39999])
+    a = bench.step_outputs(engine, torch.tensor(1.25), index)
+    b = bench.step_outputs(engine, torch.tensor(1.25), index)
+    assert a.keys() == b.keys() and all((a[k] == b[k]).all() for k in a)
+    assert all(v.dtype.name in ("float32", "float64") for v in a.values()) and sum(v.nbytes for v in a.values()) < 64 << 20
+    assert a["loss"].tolist() == [1.25] and a["avg_exp_score"].tolist() == [2.5] and a["bn_buffers"].shape == (1000,)
+    pos = a[f"sample_index_{n}"].astype("int64")
+    assert len(pos) == bench.DUMP_SAMPLE and len(set(pos.tolist())) == len(pos) and pos.max() < n
+    for k, t in (("params", engine.flat.flat), ("grads", engine.flat.grad), ("adam_m", engine.m), ("adam_v", engine.v)):
+        assert (a[k + "_sample"] == t.numpy()[pos]).all(), k
+    assert (a["view1_mem_step_rows"] == crit.view1_mem[index].numpy()).all()
+    assert (a["view1_mem_sample"] == crit.view1_mem.numpy().reshape(-1)[a[f"sample_index_{rows * 128}"].astype("int64")]).all()
+
+
 def test_utils_main_utils_is_the_references_module_with_the_two_factories_swapped(tmp_path):
     """avid-cma_amd/utils/main_utils.py executes the reference's own utils/main_utils.py (found behind it on the path) in its
     namespace and binds `torch` there to a proxy whose nn.parallel.DistributedDataParallel / optim.Adam are this build's: what
     main-avid.py:95-108 builds through utils/main_utils.py:112,250 are then the flat-buffer objects, with nothing of the reference
-    edited.  Checked here on the real file when the checkout is present (build container), on a stand-in otherwise."""
+    edited.  Checked on a stand-in with the two call sites' shape, written here."""
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ref = "/root/reference"
-    if not os.path.isfile(os.path.join(ref, "utils", "main_utils.py")):
-        ref = str(tmp_path)
-        os.makedirs(os.path.join(ref, "utils"))
-        open(os.path.join(ref, "utils", "__init__.py"), "w").close()
-        with open(os.path.join(ref, "utils", "main_utils.py"), "w") as f:     # a stand-in with the two call sites' shape
-            f.write("import torch\n\ndef build_model(cfg, logger=None):\n    return None\n\n"
-                    "def distribute_model_to_cuda(models, args, batch_size, num_workers, ngpus_per_node):\n"
-                    "    return torch.nn.parallel.DistributedDataParallel(models, device_ids=[args.gpu]), args, batch_size, num_workers\n\n"
-                    "def build_optimizer(params, cfg, logger=None):\n"
-                    "    o = torch.optim.Adam(params=params, lr=cfg['lr']['base_lr'], weight_decay=cfg['weight_decay'], betas=cfg['betas'])\n"
-                    "    return o, torch.optim.lr_scheduler.MultiStepLR(o, milestones=cfg['lr']['milestones'], gamma=cfg['lr']['gamma'])\n")
+    ref = str(tmp_path / "ref")                     # (not the subprocess's cwd, which comes first on its sys.path)
+    os.makedirs(os.path.join(ref, "utils"))
+    open(os.path.join(ref, "utils", "__init__.py"), "w").close()
+    with open(os.path.join(ref, "utils", "main_utils.py"), "w") as f:     # a stand-in with the two call sites' shape
+        f.write("import torch\n\ndef build_model(cfg, logger=None):\n    return None\n\n"
+                "def distribute_model_to_cuda(models, args, batch_size, num_workers, ngpus_per_node):\n"
+                "    return torch.nn.parallel.DistributedDataParallel(models, device_ids=[args.gpu]), args, batch_size, num_workers\n\n"
+                "def build_optimizer(params, cfg, logger=None):\n"
+                "    o = torch.optim.Adam(params=params, lr=cfg['lr']['base_lr'], weight_decay=cfg['weight_decay'], betas=cfg['betas'])\n"
+                "    return o, torch.optim.lr_scheduler.MultiStepLR(o, milestones=cfg['lr']['milestones'], gamma=cfg['lr']['gamma'])\n")
     code = r'''
 import sys, torch
 import utils.main_utils as mu

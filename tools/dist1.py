@@ -1,5 +1,5 @@
 """Dev tool: the step engine on a ONE-rank RCCL group (the only multi-GPU fact measurable on a one-GPU box): ms per step
-for a distributed arrangement.  usage: [AVID_PLAN=0/1] [GPU_MAX_HW_QUEUES=n] python tools/dist1.py <dist|none> [steps]"""
+for a distributed arrangement.  usage: [AVID_PLAN=0/1] python tools/dist1.py <dist|none> [steps]"""
 import os
 import sys
 import time
@@ -60,7 +60,7 @@ def main():
             poke()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / steps * 1e3
-    print(f"mode={mode} plan={os.environ.get('AVID_PLAN', '1')} hwq={os.environ.get('GPU_MAX_HW_QUEUES', 'default(8 via lib)')} "
+    print(f"mode={mode} plan={os.environ.get('AVID_PLAN', '1')} "
           f"extra={os.environ.get('AVID_X', '')}: {ms:.3f} ms/step")
     if "timing" in X:
         from avid_hip import lib

@@ -5,7 +5,6 @@ usage: python tools/interference.py [G=32] [threads=512] [lds_kb=16] [us=1500]""
 import ctypes as C, os, subprocess, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "avid-cma_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch, models, criterions
 from avid_hip.parallel import TrainStep
 so = os.path.join(REPO, "tools", "bin", "libinterfere.so")

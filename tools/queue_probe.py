@@ -1,4 +1,4 @@
-"""Dev tool: which HIP streams slow each other down?  Streams are created in order (GPU_MAX_HW_QUEUES decides how many
+"""Dev tool: which HIP streams slow each other down?  Streams are created in order (the runtime's hardware-queue count decides how many
 hardware queues they spread over); for every pair (a, b) a chain of tiny kernels runs on a and on b concurrently and the
 wall time per kernel is printed relative to a chain running alone."""
 import os
