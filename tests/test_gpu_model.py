@@ -377,6 +377,45 @@ def _full_step_vs_oracle(gpu_device, bs, N, K, video, audio, y, idx, v1, v2, min
     report = lib.timing_report()
     lib.timing_enable(False)
 
+    # the same step unhooked: the launch program (the benchmark's kernels, AFF forms included) — bit-identical to the hooked
+    # per-layer run above, so that every bar below holds for the program path too
+    m2 = _build_model(gpu_device).train()
+    crit2 = criterions.AVID(num_data=N, embedding_dim=128, num_negatives=K, momentum=0.5, device=gpu_device.index)
+    crit2.nce_average.view1_mem.copy_(v1)
+    crit2.nce_average.view2_mem.copy_(v2)
+    crit2.nce_average.sample_negatives = lambda yy, KK: idx_d
+    aff = lib.raw("avid_debug_in_affine_launches")
+    aff0 = aff(1)
+    f1, f2 = m2(video.to(gpu_device), audio.to(gpu_device))
+    assert type(f1.grad_fn).__name__.startswith("NetFn"), type(f1.grad_fn).__name__
+    loss2, _ = crit2(f1, f2, y.to(gpu_device))
+    loss2.backward()
+    torch.cuda.synchronize()
+    if bs == 64:
+        assert aff(1) - aff0 == 8, aff(1) - aff0        # conv2x's four temporal forwards and weight gradients in the AFF forms
+    assert torch.equal(f1.detach(), e1.detach()) and torch.equal(f2.detach(), e2.detach())
+    assert loss2.item() == loss.item()
+    # every gradient bit-identical, except the weights of the small layers the program's grouped weight-gradient launches
+    # serve (avid_conv_wgrad_group, read from the compiled program): outside the step engine the per-layer path gives each its
+    # own launch, the same products summed in another order over pixel chunks (1e-5: test_gpu_ops.test_grouped_weight_gradients)
+    from avid_hip import plan as P_
+    pls = [p for p in m2.__dict__.get("_avid_plans", {}).values() if p]
+    assert len(pls) == 1
+    pl = pls[0]
+    at = {4 * o: i for i, o in enumerate(pl.goff)}
+    grouped_ids = {id(pl.params[at[pl.bwd_prog[k].t[2].off]]) for k in range(pl.n_bwd) if pl.bwd_prog[k].op == P_.OP_WGRAD_ITEM}
+    assert len(grouped_ids) == {4: 39, 64: 33}[bs]
+    same = grouped = 0
+    for (n, p), p2 in zip(m.named_parameters(), m2.parameters()):
+        if id(p2) in grouped_ids:
+            assert float((p2.grad - p.grad).abs().max() / p.grad.abs().max()) < 1e-5, n
+            grouped += 1
+        else:
+            assert torch.equal(p.grad, p2.grad), n
+            same += 1
+    assert (same, grouped) == (141 - len(grouped_ids), len(grouped_ids))
+    del m2, crit2, f1, f2, loss2
+
     P = O.det_state(O.av_wrapper_spec(18), "w")
     pn = [n for n in P if not ("running" in n or "num_batches" in n)]
     for n in pn:

@@ -268,3 +268,105 @@ def test_placed_streams_run_concurrently(gpu_device):
         for b in range(a + 1, 4):
             assert streams.concurrent(four[a], four[b], alone), (a, b, ss.report)
     del clutter
+
+
+def _bench_module():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_benchmark_arrangement_is_bit_identical_to_the_plainest_at_batch_64(gpu_device):
+    """bench.py's workload as it times it — TrainStep.step() at 64 clips over the launch programs: four streams, conv2x's
+    temporal layers applying their input's BatchNorm (AFF forms), deferred weight gradients, the overlapped Adam step — against
+    the plainest arrangement of the same step (per-layer path, one tower stream, no deferred weight gradients,
+    forward_backward() + optimizer_step()), from the same weights and criterion state, three steps: every loss, and after
+    the last step everything ``bench.py --dump-outputs`` reports plus the full flat buffers, bit for bit."""
+    import criterions
+    import models
+    from avid_hip import lib, ops, plan
+    from avid_hip.parallel import TrainStep
+    dev = gpu_device
+    bench = _bench_module()
+    bs, N, steps = 64, 240000, 3
+    g = torch.Generator().manual_seed(1234)
+    video = torch.randn(bs, 3, 8, 112, 112, generator=g).to(dev)
+    audio = torch.randn(bs, 1, 40, 100, generator=g).to(dev)
+    gp = torch.Generator().manual_seed(99)
+    ids = torch.stack([torch.randperm(N, generator=gp)[:bs] for _ in range(steps)]).to(dev)
+    torch.manual_seed(0)
+    m0 = models.av_wrapper("R2Plus1D", {"depth": 18}, "Conv2D", {"depth": 10}, proj_dim=[512, 512, 128])
+    w0 = {k: v.clone() for k, v in m0.state_dict().items()}
+    del m0
+
+    def build():
+        m = models.av_wrapper("R2Plus1D", {"depth": 18}, "Conv2D", {"depth": 10}, proj_dim=[512, 512, 128])
+        m.load_state_dict(w0)
+        m = m.to(dev).train()
+        crit = criterions.AVID(num_data=N, embedding_dim=128, num_negatives=1024, momentum=0.5, xModal_coeff=1.,
+                               wModal_coeff=0., device=dev.index)
+        return m, crit
+
+    # ---- path A: as bench.py times it
+    m, crit = build()
+    c0 = {k: v.clone() for k, v in crit.state_dict().items()}
+    crit.nce_average.multinomial.reseed(11, 0)
+    eng = TrainStep(m, crit, lr=2e-4, weight_decay=1e-5)
+    count = lib.raw("avid_debug_in_affine_launches")
+    la, adam_early = [], []
+    for i in range(steps):
+        before = count(1)
+        la.append(float(eng.step(video, audio, ids[i])))
+        torch.cuda.synchronize()
+        assert count(1) - before == 8, count(1) - before        # 4 temporal forwards + 4 weight gradients of conv2x
+        adam_early.append(eng._step_plan is not None and bool(eng._step_plan.adam_early))
+    assert all(adam_early), "step() did not take the overlapped optimizer path"
+    assert [p for p in m.__dict__.get("_avid_plans", {}).values() if p], "the step did not run through a launch program"
+    loss_t = torch.tensor(la[-1])
+    out_a = bench.step_outputs(eng, loss_t, ids[-1])
+    full_a = {"params": eng.flat.flat.clone(), "grads": eng.flat.grad.clone(), "m": eng.m.clone(), "v": eng.v.clone(),
+              "bn": eng.flat_buffers.flat.clone(), "t": int(eng.t_dev) if eng.t_dev is not None else eng.t,
+              "crit": {k: v.clone() for k, v in crit.state_dict().items()}}
+    v, _ = m(video, audio)                            # (after everything compared was taken)
+    assert type(v.grad_fn).__name__.startswith("NetFn"), "the model call did not go through the launch program"
+    del eng, m, crit, v
+    torch.cuda.empty_cache()
+
+    # ---- path B: the plainest arrangement
+    prev = (plan.ENABLED, ops.DEFER_WGRAD)
+    try:
+        plan.ENABLED, ops.DEFER_WGRAD = False, 0
+        m, crit = build()
+        crit.load_state_dict(c0)
+        crit.nce_average.multinomial.reseed(11, 0)
+        eng = TrainStep(m, crit, lr=2e-4, weight_decay=1e-5)
+        m.overlap_towers = False                      # (after TrainStep, which turns the tower overlap on)
+        lb = []
+        for i in range(steps):
+            lb.append(float(eng.forward_backward(video, audio, ids[i])))
+            eng.optimizer_step()
+        torch.cuda.synchronize()
+        assert m.overlap_towers is False
+        assert not [p for p in m.__dict__.get("_avid_plans", {}).values() if p], "path B compiled a launch program"
+        out_b = bench.step_outputs(eng, torch.tensor(lb[-1]), ids[-1])
+        full_b = {"params": eng.flat.flat.clone(), "grads": eng.flat.grad.clone(), "m": eng.m.clone(), "v": eng.v.clone(),
+                  "bn": eng.flat_buffers.flat.clone(), "t": int(eng.t_dev) if eng.t_dev is not None else eng.t,
+                  "crit": {k: v.clone() for k, v in crit.state_dict().items()}}
+        v, _ = m(video, audio)                        # (after everything compared was taken: it moves the running statistics)
+        assert not type(v.grad_fn).__name__.startswith("NetFn"), "path B's model call went through the launch program"
+        del v
+    finally:
+        plan.ENABLED, ops.DEFER_WGRAD = prev
+    assert la == lb, (la, lb)
+    assert sorted(out_a) == sorted(out_b)
+    for k in out_a:
+        assert np.array_equal(out_a[k], out_b[k]), k
+    assert full_a["t"] == full_b["t"] == steps
+    for k in ("params", "grads", "m", "v", "bn"):
+        assert torch.equal(full_a[k], full_b[k]), k
+    assert sorted(full_a["crit"]) == sorted(full_b["crit"])
+    for k in full_a["crit"]:
+        assert torch.equal(full_a["crit"][k], full_b["crit"][k]), k
