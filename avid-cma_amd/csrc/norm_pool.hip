@@ -1006,9 +1006,12 @@ extern "C" int avid_bn_fwd_train(int64_t M, int C, const float* x, const float* 
                        reinterpret_cast<long long*>(num_batches_tracked), x, y, relu);
     return check_launch("bn_fwd_train");
   }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk, (long long)M,
-                     C, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift,
-                     reinterpret_cast<long long*>(num_batches_tracked));
+  {
+    ScopedTimer t(s, "bn_finalize_kernel", 0.0, 8.0 * nblk * C);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk, (long long)M,
+                       C, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, scale, shift,
+                       reinterpret_cast<long long*>(num_batches_tracked));
+  }
   const long long n4 = (long long)M * p.G;
   if (y) {
     ScopedTimer t(s, "bn_apply_kernel", 0.0, 8.0 * M * C);
@@ -1070,8 +1073,11 @@ extern "C" int avid_bn_bwd(int64_t M, int C, const float* x, const float* dy, co
                        save_scale, save_shift, dy, gamma, save_mean, save_invstd, dgamma, dbeta, dx, relu, frozen);
     return check_launch("bn_bwd");
   }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk,
-                     (long long)M, C, dgamma, dbeta, k1, k2, frozen);
+  {
+    ScopedTimer t(s, "bn_bwd_finalize_kernel", 0.0, 8.0 * nblk * C);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk,
+                       (long long)M, C, dgamma, dbeta, k1, k2, frozen);
+  }
   const long long n4 = (long long)M * p.G;
   {
     ScopedTimer t(s, "bn_bwd_apply_kernel", 0.0, 4.0 * M * C * 3);
@@ -1107,9 +1113,12 @@ extern "C" int avid_bn_relu_maxpool_fwd(int B, int T, int H, int W, int C, const
     hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(p.nblk), dim3(256), 0, s, x, static_cast<float*>(ws), (long long)M,
                        C, p.G, p.rows_per_pass, p.rows_per_block);
   }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk,
-                     (long long)M, C, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
-                     save_scale, save_shift, reinterpret_cast<long long*>(num_batches_tracked));
+  {
+    ScopedTimer t(s, "bn_finalize_kernel", 0.0, 8.0 * nblk * C);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk,
+                       (long long)M, C, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
+                       save_scale, save_shift, reinterpret_cast<long long*>(num_batches_tracked));
+  }
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const long long n = (long long)B * T * Ho * Wo * p.G;
   {
@@ -1148,8 +1157,11 @@ extern "C" int avid_bn_relu_maxpool_bwd(int B, int T, int H, int W, int C, const
     hipLaunchKernelGGL(bn_pool_bwd_partial_kernel, dim3(nblk), dim3(256), 0, s, x, save_scale, save_shift, dy, argmax,
                        save_mean, save_invstd, part, cells, C, p.G, p.rows_per_pass, (int)cpb, H, W, Ho, Wo);
   }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk,
-                     (long long)M, C, dgamma, dbeta, k1, k2, 0);
+  {
+    ScopedTimer t(s, "bn_bwd_finalize_kernel", 0.0, 8.0 * nblk * C);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)ceil_div(C, FIN_CH)), dim3(1024), 0, s, part, nblk,
+                       (long long)M, C, dgamma, dbeta, k1, k2, 0);
+  }
   const long long nc4 = cells * p.G;
   {
     ScopedTimer t(s, "bn_pool_bwd_apply_kernel", 0.0, 4.0 * M * C * 2.3);
@@ -1190,6 +1202,7 @@ extern "C" int avid_global_maxpool_fwd(int B, int S, int C, const float* x, floa
   AVID_REQUIRE(B > 0 && S > 0 && C > 0, AVID_E_SHAPE, "global_maxpool_fwd: bad shape");
   AVID_REQUIRE(x && y && argmax, AVID_E_BADARG, "global_maxpool_fwd: null pointer");
   const long long n = (long long)B * C;
+  ScopedTimer t((hipStream_t)stream, "global_maxpool_fwd_kernel", 0.0, 0.0);
   hipLaunchKernelGGL(global_maxpool_fwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      y, argmax, B, S, C);
   return check_launch("global_maxpool_fwd");
@@ -1200,6 +1213,7 @@ extern "C" int avid_global_maxpool_bwd(int B, int S, int C, const float* dy, con
   AVID_REQUIRE(B > 0 && S > 0 && C > 0, AVID_E_SHAPE, "global_maxpool_bwd: bad shape");
   AVID_REQUIRE(dy && dx && argmax, AVID_E_BADARG, "global_maxpool_bwd: null pointer");
   const long long n = (long long)B * S * C;
+  ScopedTimer t((hipStream_t)stream, "global_maxpool_bwd_kernel", 0.0, 0.0);
   hipLaunchKernelGGL(global_maxpool_bwd_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      dy, argmax, dx, B, S, C);
   return check_launch("global_maxpool_bwd");
@@ -1207,12 +1221,14 @@ extern "C" int avid_global_maxpool_bwd(int B, int S, int C, const float* dy, con
 
 extern "C" int avid_relu_bwd(int64_t n, const float* y, const float* dy, float* dx, avid_stream_t stream) {
   AVID_REQUIRE(n > 0 && y && dy && dx, AVID_E_BADARG, "relu_bwd: bad argument");
+  ScopedTimer t((hipStream_t)stream, "relu_bwd_kernel", 0.0, 0.0);
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, y, dy, dx, (long long)n);
   return check_launch("relu_bwd");
 }
 
 extern "C" int avid_colsum(int64_t M, int C, const float* x, float* out, avid_stream_t stream) {
   AVID_REQUIRE(M > 0 && C > 0 && x && out, AVID_E_BADARG, "colsum: bad argument");
+  ScopedTimer t((hipStream_t)stream, "colsum_kernel", 0.0, 0.0);
   hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)ceil_div(C, 64)), dim3(256), 0, (hipStream_t)stream, x, out,
                      (long long)M, C);
   return check_launch("colsum");

@@ -10,13 +10,12 @@ namespace avid {
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long long n4,
                                                         long long n, float b1, float b2, float eps, float wd,
-                                                        float step_size, float inv_sqrt_bc2, float grad_scale,
-                                                        float lr, const long long* __restrict__ step_dev,
+                                                        float step_size, double inv_bc1, float inv_sqrt_bc2,
+                                                        float grad_scale, float lr, const long long* __restrict__ step_dev,
                                                         const float* __restrict__ lr_dev) {
-  if (lr_dev) {   // graph-replay safe learning rate (scheduler writes the device word)
-    const float nl = *lr_dev;
-    step_size = lr != 0.f ? step_size * (nl / lr) : 0.f;   // (exact when step_dev is given: recomputed below)
-    lr = nl;
+  if (lr_dev) {   // graph-replay safe learning rate (scheduler writes the device word); the host's lr is not used
+    lr = *lr_dev;
+    step_size = (float)((double)lr * inv_bc1);   // (recomputed below when step_dev is given)
   }
   if (step_dev) {  // graph-replay safe: bias corrections from the device-resident step counter
     const double t = (double)*step_dev;
@@ -65,13 +64,14 @@ extern "C" int avid_adam_flat(int64_t n, float* p, const float* g, float* m, flo
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr / bc1);
+  const double inv_bc1 = 1.0 / bc1;
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   const long long n4 = n / 4;
   long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
   if (grid > 4096) grid = 4096;
   ScopedTimer t((hipStream_t)stream, "adam_flat_kernel", 0.0, 28.0 * n);
   hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4,
-                     (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_sqrt_bc2, grad_scale, lr,
+                     (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
                      (const long long*)step_dev, lr_dev);
   return check_launch("adam_flat");
 }
