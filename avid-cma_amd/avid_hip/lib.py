@@ -161,6 +161,11 @@ SIGNATURES = {
     "avid_l2norm_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avid_alias_draw": (_i, [_i64, _i64, _vp, _vp, _i, _u64, _u64, _vp, _vp, _i64, _vp, _vp]),
     "avid_counter_add": (_i, [_vp, _u64, _vp]),
+    "avid_dropout_fwd": (_i, [_i64, _i64, _f, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "avid_dropout_bwd": (_i, [_i64, _f, _vp, _vp, _vp, _vp]),
+    "avid_cls_loss": (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avid_cls_linear_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "avid_cls_linear_bwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_bank_scores_fwd": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "avid_bank_scores_bwd": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "avid_mean_exp": (_i, [_i, _i, _i, _vp, _vp, _vp]),

@@ -207,6 +207,10 @@ def workspace(device, nbytes):
 # ------------------------------------------------------------------------------------------------
 # device-side index errors (include/avid_hip.h AVID_DEVERR_*)
 # ------------------------------------------------------------------------------------------------
+class LabelError(AvidHipError, IndexError):
+    """A classification label outside [0, n_classes) reached ``avid_cls_loss`` (where the reference's cross-entropy raises)."""
+
+
 class DeviceErrors:
     """One int32 error word per device that the gather / scatter kernels OR a code into when they meet an id
     outside [0, N) — where the reference's indexing raises (criterions/avid.py:57-62,124; avid_cma.py:199).
@@ -218,7 +222,8 @@ class DeviceErrors:
     form for callers that synchronise anyway (``loss.item()``)."""
     _MSG = {1: "bank_scores: negative / positive index outside [0, num_data)",
             2: "update_memory: sample index outside [0, num_data)",
-            4: "memory_sampling: sample index outside [0, num_data) (positive_set lookup)"}
+            4: "memory_sampling: sample index outside [0, num_data) (positive_set lookup)",
+            8: "cls_loss: label outside [0, n_classes)"}
     _inst = {}
 
     def __init__(self, device):
@@ -241,7 +246,8 @@ class DeviceErrors:
         self.host.zero_()
         self.event = None
         what = "; ".join(m for b, m in self._MSG.items() if code & b) or f"code {code}"
-        raise IndexError(f"avid_hip: index out of range in a device kernel — {what}")
+        cls = LabelError if code & 8 else IndexError
+        raise cls(f"avid_hip: index out of range in a device kernel — {what}")
 
     def poll(self):
         if torch.cuda.is_current_stream_capturing():
@@ -1460,3 +1466,99 @@ def adam_flat(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, step_
         lib.call("avid_counter_add", _p(step_dev), 1, st)
     lib.call("avid_adam_flat", p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
              float(eps), float(wd), int(step), _p(step_dev), _p(lr_dev), float(grad_scale), st)
+
+
+# ------------------------------------------------------------------------------------------------
+# fine-tuning head (classify.hip): dropout, softmax cross-entropy / clip-averaged confidence
+# ------------------------------------------------------------------------------------------------
+class _Dropout(Function):
+    @staticmethod
+    def forward(ctx, x, p, seed, offset):
+        _need_cuda(x)
+        x = x.contiguous()
+        B = x.shape[0]
+        F = x.numel() // B
+        y = torch.empty_like(x)
+        mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+        lib.call("avid_dropout_fwd", B, F, float(p), int(seed), int(offset), None, _p(x), _p(y), _p(mask), _stream())
+        ctx.save_for_backward(mask)
+        ctx.p = float(p)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (mask,) = ctx.saved_tensors
+        dx = torch.empty(mask.shape, dtype=torch.float32, device=dy.device)
+        lib.call("avid_dropout_bwd", mask.numel(), ctx.p, _p(mask), _p(dy.contiguous()), _p(dx), _stream())
+        return dx, None, None, None
+
+
+def dropout(x, p, seed, offset):
+    """Training-mode dropout of x [B, ...] (include/avid_hip.h avid_dropout_fwd): element i of the flattened tensor is kept iff
+    word i % 4 of Philox4x32-10(counter = (i/4, offset), key = seed) >= floor(p * 2^32).  torch.nn.Dropout's distribution, not
+    its bits."""
+    return _Dropout.apply(x, float(p), int(seed), int(offset))
+
+
+def dropout_mask(B, F, p, seed, offset, device):
+    """The keep-mask [B, F] (uint8) that ``dropout`` applies for (seed, offset) — what a test teacher-forces."""
+    x = torch.zeros((B, F), dtype=torch.float32, device=device)
+    y = torch.empty_like(x)
+    mask = torch.empty((B, F), dtype=torch.uint8, device=device)
+    lib.call("avid_dropout_fwd", B, F, float(p), int(seed), int(offset), None, _p(x), _p(y), _p(mask), _stream())
+    return mask
+
+
+def cls_loss(logits, labels, clips=1, grad_scale=None):
+    """Softmax cross-entropy of ``logits [V * clips, C]`` against ``labels [V]`` in one launch (avid_cls_loss), no host
+    synchronisation: returns device tensors ``(loss [], confidence [V, C], hits [2] int64 (top-1, top-5), dlogits)`` —
+    ``dlogits`` = d(loss * grad_scale) / d(logits), or None when ``grad_scale`` is None.  A label outside [0, C) raises
+    ``LabelError`` at the next poll of the device error word (``check_device_errors()`` blocks for it)."""
+    _need_cuda(logits, labels)
+    logits = logits.contiguous()
+    if logits.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise AvidHipError("cls_loss: float32 logits and int64 labels expected")
+    R, C = logits.shape
+    V = labels.shape[0]
+    if V * clips != R:
+        raise AvidHipError(f"cls_loss: {R} rows of logits for {V} videos x {clips} clips")
+    dev = logits.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    conf = torch.empty((V, C), dtype=torch.float32, device=dev)
+    hits = torch.empty(2, dtype=torch.int64, device=dev)
+    dl = torch.empty_like(logits) if grad_scale is not None else None
+    errs = DeviceErrors.get(dev)
+    lib.call("avid_cls_loss", V, int(clips), C, _p(logits), _p(labels.contiguous()),
+             float(grad_scale if grad_scale is not None else 0.0), _p(out), _p(conf), _p(hits), _p(dl), errs.ptr(), _stream())
+    errs.poll()
+    return out[0], conf, hits, dl
+
+
+class _ClsLinear(Function):
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        _need_cuda(x, w, bias)
+        x = x.contiguous()
+        B, Fin = x.shape
+        C = w.shape[0]
+        y = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        lib.call("avid_cls_linear_fwd", B, Fin, C, _p(x), _p(w.contiguous()), _p(bias), _p(y), _stream())
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        B, Fin = x.shape
+        C = w.shape[0]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty((C, Fin), dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        lib.call("avid_cls_linear_bwd", B, Fin, C, _p(x), _p(w.contiguous()), _p(dy.contiguous()), _p(dx), _p(dw), _p(db),
+                 _stream())
+        return dx, dw, db
+
+
+def cls_linear(x, w, bias):
+    """The classifier ``Linear(Fin, C)`` for any number of classes (avid_cls_linear_fwd / _bwd)."""
+    return _ClsLinear.apply(x, w, bias)

@@ -821,3 +821,112 @@ class Adam(torch.optim.Optimizer):
         self.state.clear()
         if step > 0:
             self._publish_state()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Action-recognition fine-tuning (eval-action-recg.py: run_phase 'train' / 'test_dense', the warm-up epochs of the classifier)
+# ---------------------------------------------------------------------------------------------------------------------
+class FinetuneStep(TrainStep):
+    """One fine-tuning step of a ``models.ClassificationWrapper`` around this package's ``R2Plus1D`` on this rank's GPU:
+    the forward launch program ends in ``avid_cls_loss`` (loss, top-1 / top-5 hits and ``dlogits`` on the device), the
+    backward program starts from ``dlogits``, then one flat Adam launch (``torch.optim.Adam``'s update; lr 1e-4 and weight
+    decay 0 as the shipped benchmark configs).  Nothing synchronises the host.
+
+    ``classifier_only=True``: the reference's warm-up (an optimizer over the classifier's parameters only).  The tower
+    still runs in training mode and updates its BatchNorm running statistics; no tower backward is compiled, because the
+    reference never applies those gradients; Adam touches only the classifier's slice of the flat buffer.
+    With more than one rank, gradients are averaged as DistributedDataParallel does: through ``GradBuckets`` (the full
+    step), or one collective over the classifier's slice (``classifier_only``); Adam's ``grad_scale`` takes the 1 / world.
+    Rank 0's BatchNorm running statistics are broadcast before every step (``broadcast_buffers="step"``, DDP's default).
+    ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``TrainStep``'s."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
+                 bucket_bytes=16 << 20, broadcast_buffers="step"):
+        """``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
+        0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never."""
+        super().__init__(model, None, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bucket_bytes=bucket_bytes,
+                         broadcast_buffers=broadcast_buffers)
+        self.classifier_only = bool(classifier_only)
+        n = len(self.flat.params)
+        self.n_cls = self.flat.offsets[2] if n > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
+
+    def _plan(self, video):
+        from . import plan
+        pl = plan.cls_plan(self.model, video, self.classifier_only, need_grad=False)
+        if pl is None or plan._engine_flat(self, pl) is None:
+            raise NotImplementedError("FinetuneStep: the model is outside the compiled fine-tuning programs (plan.ClsPlan: "
+                                      "ClassificationWrapper(R2Plus1D, feat_name='pool', pooling_op=None), fp32 CUDA "
+                                      "parameters, training mode, no hooks)")
+        return pl
+
+    def step(self, video, labels):
+        """(loss [], hits [2] int64: top-1 / top-5 hits of the batch) as device tensors."""
+        video = video.contiguous()
+        labels = labels.contiguous()
+        B = video.shape[0]
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
+            raise ValueError(f"FinetuneStep.step: labels must be int64 [{B}] on {video.device} "
+                             f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
+        if self.broadcast_buffers == "step":
+            self.sync_buffers()
+        pl = self._plan(video)
+        drop = self.model.dropout if pl.drop_index is not None else None
+        seed, offset = (drop.seed, drop.next_offset()) if drop is not None else (0, 0)
+        out = torch.empty(8, dtype=torch.float32, device=video.device)          # plan.OUT_BYTES
+        dlogits = torch.empty((B, pl.n_classes), dtype=torch.float32, device=video.device)
+        _, fa = pl.forward(video, self.flat.grad, True, seed, offset, labels=labels, out=out, dlogits=dlogits)
+        if not self.buckets.comm:
+            pl.backward(fa, video, dlogits, self.flat.grad)
+        elif self.classifier_only:
+            # only the classifier's leading slice of the gradient buffer is written (and zeroed): ONE collective over it,
+            # behind the backward program (whose streams all join the current one), instead of the buckets over the tower
+            pl.backward(fa, video, dlogits, self.flat.grad)
+            dist.all_reduce(self.flat.grad[:self.n_cls])
+        else:
+            ba, begin = None, 0
+            for end, ready in pl.segments(self.buckets.bucket_of, self.buckets.counts):
+                ba = pl.backward(fa, video, dlogits, self.flat.grad, begin, end, ba)
+                for i, st in ready:
+                    self.buckets.ready(i, pl.stream_objs[st])
+                begin = end
+            self.buckets.finish()
+        self._adam()
+        self._poll_errors()
+        return out[0], out[2:6].view(torch.int64)
+
+    def _adam(self):
+        from . import ops
+        self.t += 1
+        n = self.n_cls if self.classifier_only else self.flat.numel
+        ops.adam_flat(self.flat.flat[:n], self.flat.grad[:n], self.m[:n], self.v[:n], self.lr, self.betas[0], self.betas[1],
+                      self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev, lr_dev=self.lr_dev)
+
+    def _param_order(self):
+        order = super()._param_order()
+        if self.classifier_only:            # the warm-up optimizer holds the classifier's parameters only
+            cls = {id(p) for p in self.model.classifier.parameters()}
+            order = [(k, i, p) for k, (_, i, p) in enumerate(o for o in order if id(o[2]) in cls)]
+        return order
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.classifier_only:
+            sd["param_groups"][0]["params"] = list(range(len(self._param_order())))
+        return sd
+
+    def evaluate(self, video, labels, batch):
+        """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] in eval mode, fed through the model ``batch`` clips at a
+        time (the reference's BatchWrapper), then one ``avid_cls_loss`` over all V * clips logits.  Returns device tensors
+        (confidence [V, C], loss [], hits [2] int64)."""
+        from . import ops
+        V, clips = video.shape[0], video.shape[1]
+        x = video.flatten(0, 1)
+        was = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                logits = torch.cat([self.model(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)], 0)
+                loss, conf, hits, _ = ops.cls_loss(logits, labels, clips)
+        finally:
+            self.model.train(was)
+        return conf, loss, hits

@@ -35,6 +35,7 @@ from .lib import ConvDesc
 OP_WAIT, OP_MEMSET0, OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_WGRAD_GROUP, OP_WGRAD_ITEM = 1, 2, 3, 4, 5, 6, 7
 OP_BN_FWD, OP_BN_BWD, OP_BN_POOL_FWD, OP_BN_POOL_BWD, OP_GPOOL_FWD, OP_GPOOL_BWD = 8, 9, 10, 11, 12, 13
 OP_RELU_BWD, OP_COLSUM, OP_WT_BATCH, OP_ADAM = 14, 15, 16, 17
+OP_DROPOUT_FWD, OP_DROPOUT_BWD, OP_CLS_LOSS, OP_CLS_LINEAR_FWD, OP_CLS_LINEAR_BWD = 18, 19, 20, 21, 22
 NREF = lib.INSTR_REFS
 Ref, Instr, StreamWs = lib.Ref, lib.Instr, lib.StreamWs
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -639,6 +640,12 @@ class Plan:
         for tr in sorted(b.trail_used):
             b.wait(ST_MAIN, tr)
         self.n_bwd = len(b.bwd)
+        self._finalize(b, device)
+        self.params_fwd = params
+        self.vshape, self.ashape = tuple(vshape), tuple(ashape)
+
+    def _finalize(self, b, device):
+        """The weight-transform table, the record arrays, the arenas' sizes and the streams' workspaces."""
         # ------------------------------------------------------------------ the weight-transform table
         self.aux_bytes = _align(b.aux_size) + 32 * len(b.wt_recs) + 256
         self.table_off = _align(b.aux_size)
@@ -652,7 +659,6 @@ class Plan:
         self.bwd_prog = (Instr * max(1, self.n_bwd))(*b.bwd)
         self.fa_bytes, self.ba_bytes = max(b.fa.size, 256), max(b.ba.size, 256)
         self.params, self.goff, self.gnumel = b.params, b.goff, b.gnumel
-        self.params_fwd = params
         self.tensors = b.tensors
         self.n_slots = S_FIRST_TENSOR + len(self.tensors)
         self.grad_ready = b.grad_ready
@@ -669,7 +675,6 @@ class Plan:
         self._table_ptrs = None
         self.slots = (_vp * self.n_slots)()
         self.streams = (_vp * 4)()
-        self.vshape, self.ashape = tuple(vshape), tuple(ashape)
 
     def _video_with_audio(self, b, model, video, audio, A_S):
         """The video tower with the audio tower (and its head) started behind the video stem on stream A_S."""
@@ -914,7 +919,8 @@ def run(model, video, audio):
 
 _OP_NAMES = {0: "nop", 1: "wait", 2: "memset0", 3: "conv_fwd", 4: "conv_dgrad", 5: "conv_wgrad", 6: "wgrad_group", 7: "wgrad_item",
              8: "bn_fwd", 9: "bn_bwd", 10: "bn_pool_fwd", 11: "bn_pool_bwd", 12: "gpool_fwd", 13: "gpool_bwd", 14: "relu_bwd",
-             15: "colsum", 16: "wt_batch", 17: "adam"}
+             15: "colsum", 16: "wt_batch", 17: "adam", 18: "dropout_fwd", 19: "dropout_bwd", 20: "cls_loss",
+             21: "cls_linear_fwd", 22: "cls_linear_bwd"}
 
 
 def dump(prog, n):
@@ -928,3 +934,228 @@ def dump(prog, n):
         refs = " ".join(f"{r.t[j].slot}:{r.t[j].off}" if r.t[j].slot >= 0 else "-" for j in range(NREF))
         lines.append(f"{k:4d} s{r.stream} {_OP_NAMES.get(r.op, r.op):12s}{geo} i={list(r.i)} n={list(r.n)} | {refs}")
     return "\n".join(lines)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# fine-tuning: models.classification.ClassificationWrapper (utils/eval_utils.py:193-214 of the reference)
+# ------------------------------------------------------------------------------------------------------------------
+S_LABELS, S_DLOGITS, S_OUT = S_AUDIO, S_DV, S_DA     # the classifier plan's use of the two-tower plan's input slots
+OUT_BYTES = 32                                       # S_OUT: loss (f32) at 0, hits (2 x i64) at 8
+
+
+def _i32(v):
+    v &= 0xFFFFFFFF
+    return v - (1 << 32) if v >= (1 << 31) else v
+
+
+class ClsPlan(Plan):
+    """The compiled programs of one ``ClassificationWrapper`` around this package's ``R2Plus1D`` for one clip geometry.
+
+    Forward: the tower (``Builder.video_fwd``), dropout, the classifier (``avid_cls_linear_fwd``: any number of classes)
+    — records [0, n_logits) — then ``AVID_OP_CLS_LOSS`` with ``dlogits`` (record n_logits, run by the step engine only).
+    Backward, from ``dlogits``: the classifier's weight, bias and input gradients (one ``avid_cls_linear_bwd``), dropout's
+    backward, the tower's backward (``Builder.video_bwd`` / ``video_stem_bwd``).  ``classifier_only``: the reference's warm-up epochs — the
+    tower still runs in training mode (its BatchNorm running statistics move) but no tower backward is compiled, the
+    classifier's input gradient neither, and only the classifier's slice of the gradient buffer is zeroed."""
+
+    def __init__(self, model, vshape, device, trailing, group, classifier_only=False):
+        from models.classification import ClassificationWrapper, ClsLinear, HipDropout
+        if type(model) is not ClassificationWrapper or model.feat_name != "pool" or model.pooling is not None:
+            raise Unsupported("classification wrapper outside the compiled pattern")
+        cls = model.classifier
+        if type(cls) is not ClsLinear or (model.use_dropout and type(model.dropout) is not HipDropout):
+            raise Unsupported("classifier / dropout")
+        params = [p for p in model.parameters()]
+        dry = device.type != "cuda"
+        if not all(p.requires_grad and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
+            raise Unsupported("frozen / non-fp32 parameters")
+        b = Builder(device, False, trailing, group)
+        b.set_params(params)
+        self.device = device
+        self.classifier_only = classifier_only
+        self.key = (tuple(vshape), trailing, group, classifier_only)
+        self.p = float(model.dropout.p) if model.use_dropout else 0.0
+        # ------------------------------------------------------------------ forward
+        b.cur = b.fwd
+        helper = ST_TRAIL if trailing else ST_MAIN
+        if trailing:
+            b.wait(helper, ST_MAIN)
+        self._zero_index = len(b.fwd)
+        # (parameters in reverse order: the classifier's bias and weight lead the gradient buffer)
+        self.n_cls = b.goff[2] if len(b.params) > 2 else b.gnumel
+        b.emit(OP_MEMSET0, stream=helper, n=(4 * (self.n_cls if classifier_only else b.gnumel),), t=((S_GRAD, 0),))
+        self._wt_rec = b.emit(OP_WT_BATCH, stream=helper, i=(0,), n=(0,), t=((S_AUX, 0),))
+        b.S = ST_MAIN
+        V, feat = b.video_fwd(model.feature_extractor, Sym((S_VIDEO, 0), vshape))
+        B, Fd = feat.shape
+        self.drop_index = None
+        if self.p > 0.0:
+            y = b.fa.alloc(4 * B * Fd)
+            self.mask = b.fa.alloc(B * Fd)
+            self.drop_index = len(b.fwd)
+            b.emit(OP_DROPOUT_FWD, n=(B, 0), i=(Fd, 0, 0), f=(self.p,), t=(feat.ref, y, self.mask, None))
+            feat = Sym(y, (B, Fd))
+        self.n_classes = C = cls.weight.shape[0]
+        if cls.weight.shape[1] != Fd or not cls.weight.is_contiguous():
+            raise Unsupported("classifier")
+        logits = b.fa.alloc(4 * B * C)
+        b.emit(OP_CLS_LINEAR_FWD, i=(B, Fd, C), t=(feat.ref, b.ext(cls.weight), b.ext(cls.bias), logits))
+        self.logits = Sym(logits, (B, C))
+        self.n_logits = len(b.fwd)
+        b.emit(OP_CLS_LOSS, i=(B, 1, self.n_classes), f=(1.0,),
+               t=(self.logits.ref, (S_LABELS, 0), (S_OUT, 0), None, (S_OUT, 8), (S_DLOGITS, 0), self._err_ref(b, device)))
+        self.n_fwd = len(b.fwd)
+        # ------------------------------------------------------------------ backward
+        b.cur = b.bwd
+        if trailing:
+            b.wait(ST_MAIN, helper)
+        b.S = ST_MAIN
+        dlog = (S_DLOGITS, 0)
+        dx = None if classifier_only else b.ba.alloc(4 * B * Fd)
+        b.emit(OP_CLS_LINEAR_BWD, i=(B, Fd, C), t=(feat.ref, b.ext(cls.weight), dlog, dx, b.grad(cls.weight), b.grad(cls.bias)))
+        b._ready(b.S, cls.weight, cls.bias)
+        if not classifier_only:
+            if self.p > 0.0:
+                df = b.ba.alloc(4 * B * Fd)
+                b.emit(OP_DROPOUT_BWD, n=(B * Fd,), f=(self.p,), t=(self.mask, dx, df))
+                dx = df
+            dh = b.video_bwd(V, dx)
+            b.flush_group(ST_MAIN)
+            b.video_stem_bwd(V, dh)
+        b.flush_group(ST_MAIN)
+        for tr in sorted(b.trail_used):
+            b.wait(ST_MAIN, tr)
+        self.n_bwd = len(b.bwd)
+        self.adam_early = None
+        self._finalize(b, device)
+        self.params_fwd = params
+        self.vshape, self.ashape = tuple(vshape), None
+
+    @staticmethod
+    def _err_ref(b, device):
+        """The device error word (ops.DeviceErrors) as an external tensor: a label outside [0, C) is reported there."""
+        flag = ops.DeviceErrors.get(device).flag if device.type == "cuda" else torch.zeros((), dtype=torch.int32)
+        return b.ext(flag)
+
+    def forward(self, video, grad_flat, zero_grad, seed=0, offset=0, labels=None, out=None, dlogits=None, grad_scale=1.0):
+        """Issue the forward program — with ``labels`` also the loss record, which writes ``out`` (OUT_BYTES: loss, hits)
+        and ``dlogits``; returns (logits, arena)."""
+        dev = self.device
+        self._refresh_table()
+        fa = torch.empty(self.fa_bytes, dtype=torch.uint8, device=dev)
+        self._fill_slots(fa, None, grad_flat, video, labels, dlogits, out)
+        self._streams()
+        self.fwd_prog[self._zero_index].op = OP_MEMSET0 if (zero_grad and grad_flat is not None) else 0
+        if self.drop_index is not None:
+            r = self.fwd_prog[self.drop_index]
+            r.i[1], r.i[2], r.n[1] = _i32(seed), _i32(seed >> 32), int(offset)
+        end = self.n_logits
+        if labels is not None:
+            self.fwd_prog[self.n_logits].f[0] = float(grad_scale)
+            end = self.n_fwd
+        lib.call("avid_program_run", self.fwd_prog, 0, end, self.slots, self.n_slots, self.streams, self.ws_arr, 4)
+        B, C = self.vshape[0], self.n_classes
+        off = self.logits.ref[1]
+        return fa[off:off + 4 * B * C].view(torch.float32).view(B, C), fa
+
+    def backward(self, fa, video, dlogits, grad_flat, begin=0, end=None, ba=None):
+        dev = self.device
+        if ba is None:
+            ba = torch.empty(self.ba_bytes, dtype=torch.uint8, device=dev)
+        self._fill_slots(fa, ba, grad_flat, video, None, dlogits, None)
+        self._streams()
+        lib.call("avid_program_run", self.bwd_prog, begin, self.n_bwd if end is None else end, self.slots, self.n_slots,
+                 self.streams, self.ws_arr, 4)
+        return ba
+
+
+class ClsFn(torch.autograd.Function):
+    """video -> logits: ClassificationWrapper.forward in training mode with the tower, dropout, the classifier and all of
+    their backward as two launch programs (``NetFn``'s shape with a single input)."""
+
+    @staticmethod
+    def forward(ctx, video, pl, seed, offset, *params):
+        logits, fa = pl.forward(video, None, False, seed, offset)
+        ctx.pl, ctx.fa, ctx.video = pl, fa, video
+        ctx.versions = sum(p._version for p in params)
+        ctx.params = params
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        pl, params = ctx.pl, ctx.params
+        if ctx.fa is None:
+            raise RuntimeError("avid_hip.plan: backward through the same forward pass a second time (its activations "
+                               "were released)")
+        if sum(p._version for p in params) != ctx.versions:
+            raise RuntimeError("avid_hip.plan: a parameter was modified in place between the forward and the backward pass")
+        g = torch.empty(pl.gnumel, dtype=torch.float32, device=dlogits.device)
+        pl.backward(ctx.fa, ctx.video, dlogits.contiguous(), g)
+        ctx.fa = None
+        views = pl.grad_views(g)
+        return (None, None, None, None) + tuple(views[id(p)] for p in params)
+
+
+def _cls_tree_ok(model):
+    """Every module in training mode and none hooked (a hook on any of them — the classifier included — sends the call to
+    the per-layer path, where each module's own ``__call__`` runs its hooks)."""
+    mods = model.__dict__.get("_avid_modules")
+    if mods is None:
+        mods = model.__dict__["_avid_modules"] = list(model.modules())
+    for m in mods:
+        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks or not m.training:
+            return False
+    return True
+
+
+def _cls_eligible(model, video, need_grad=True):
+    if not ENABLED or not (model.training and video.is_cuda) or (need_grad and not torch.is_grad_enabled()):
+        return False
+    if video.dtype != torch.float32 or video.dim() != 5 or torch.cuda.is_current_stream_capturing():
+        return False
+    return _cls_tree_ok(model)
+
+
+def cls_plan(model, video, classifier_only=False, need_grad=True):
+    """The cached ``ClsPlan`` of this call (same cache key and staleness rules as ``run``), or None: the caller takes the
+    per-layer path."""
+    if not _cls_eligible(model, video, need_grad):
+        return None
+    timing = lib.TIMING
+    trailing = (not timing) and bool(ops.DEFER_WGRAD)
+    mods = model.__dict__.get("_avid_param_list")
+    if mods is None:
+        mods = model.__dict__["_avid_param_list"] = list(model.parameters())
+    fp, dt_ok = 0, True
+    for p in mods:
+        fp = (fp << 1) | int(p.requires_grad)
+        dt_ok = dt_ok and p.dtype == torch.float32 and p.is_cuda
+    if not dt_ok:
+        return None
+    drop = model.dropout.p if model.use_dropout else 0.0
+    # (the BatchNorm buffers' addresses: `.to()` / `.cuda()` re-create them, FlatBuffers re-seats them — a cached plan holds
+    #  the tensors it was compiled with in its slot table)
+    bufs = tuple(b.data_ptr() for m in model.__dict__["_avid_modules"] for b in m._buffers.values() if b is not None)
+    key = ("cls", tuple(video.shape), video.device.index, trailing, bool(ops.GROUP_WGRAD), ops.FUSE_BN_BWD, ops.wino_epoch(),
+           fp, bool(classifier_only), drop, bufs)
+    plans = model.__dict__.setdefault("_avid_plans", {})
+    pl = plans.get(key)
+    if pl is None:
+        try:
+            pl = ClsPlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD), classifier_only)
+        except Unsupported:
+            pl = False
+        plans[key] = pl
+    return pl or None
+
+
+def run_cls(model, video):
+    """``ClassificationWrapper.forward`` through the launch programs, or None (the caller takes the per-layer path)."""
+    if not _cls_eligible(model, video):
+        return None
+    video = video.contiguous()
+    pl = cls_plan(model, video)
+    if pl is None:
+        return None
+    seed, offset = (model.dropout.seed, model.dropout.next_offset()) if pl.drop_index is not None else (0, 0)
+    return ClsFn.apply(video, pl, seed, offset, *pl.params_fwd)

@@ -1,0 +1,253 @@
+// Action-recognition fine-tuning head: dropout and the classifier's softmax cross-entropy / clip-averaged confidence.
+//
+// Reference ops replaced: utils/eval_utils.py:203-213 (torch.nn.Dropout inside ClassificationWrapper),
+// eval-action-recg.py:150-165 (CrossEntropyLoss, Softmax, .view(V, clips, -1).mean(1), metrics_utils.accuracy top-1 / top-5).
+// The classifier Linear(F, C) has kernels of its own below: the heads' igemm (avid_conv_fwd) takes C in multiples of 64 only.
+// No MFMA: the head is a few MFLOP per step; what matters is that it costs few launches and no host synchronisation.
+#include <math.h>
+
+#include "common.h"
+
+namespace avid {
+
+// ---------------------------------------------------------------------------------------------
+// Dropout.  Element i (= b * F + f) is kept iff word i % 4 of Philox4x32-10(counter = (i/4 lo, i/4 hi, off lo, off hi),
+// key = seed) is >= thresh = floor(p * 2^32); y = kept ? x * scale : 0, scale = 1 / (1 - p) in fp32.  One thread per four
+// consecutive elements (one Philox call), the keep-mask stored as one byte per element for the backward.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dropout_fwd_kernel(long long n, const float* __restrict__ x, float* __restrict__ y,
+                                                          uint8_t* __restrict__ mask, uint32_t thresh, float scale,
+                                                          uint64_t seed, uint64_t offset,
+                                                          const unsigned long long* __restrict__ offset_dev) {
+  if (offset_dev) offset = *offset_dev;
+  const long long groups = (n + 3) >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)g, (uint32_t)((uint64_t)g >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), r[0], r[1], r[2], r[3]);
+    const long long i0 = g << 2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long i = i0 + j;
+      if (i < n) {
+        const bool keep = r[j] >= thresh;
+        y[i] = keep ? x[i] * scale : 0.f;
+        mask[i] = keep ? 1 : 0;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(long long n, const uint8_t* __restrict__ mask,
+                                                          const float* __restrict__ dy, float* __restrict__ dx, float scale) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    dx[i] = mask[i] ? dy[i] * scale : 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Softmax cross-entropy over logits [V * clips][C] (C <= 1024), labels [V]: one block of CLS_WAVES waves, wave w takes the
+// videos w, w + CLS_WAVES, ... and each of their clips' rows in order (three passes over a row: max, sum of exponentials,
+// probabilities; lane l owns columns l, l + 64, ... and accumulates their confidence in its wave's slice of LDS).  Per video:
+// the confidence (mean over its clips of the softmax), the rank of its label in it, the sum of its rows' cross-entropies.
+// The wave sums its videos' terms in order (double), the block sums the waves' in order: a fixed summation order and no
+// atomics on the results, so every output is bit-reproducible.
+// ---------------------------------------------------------------------------------------------
+constexpr int CLS_WAVES = 16;
+constexpr int CLS_MAX_C = 1024;
+
+__global__ __launch_bounds__(CLS_WAVES * 64) void cls_loss_kernel(int V, int clips, int C, const float* __restrict__ logits,
+                                                                  const long long* __restrict__ labels, float grad_scale,
+                                                                  float* __restrict__ loss, float* __restrict__ conf,
+                                                                  long long* __restrict__ hits, float* __restrict__ dlogits,
+                                                                  int* __restrict__ err) {
+  __shared__ float s_acc[CLS_WAVES][CLS_MAX_C];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* acc = s_acc[wave];
+  const long long rows = (long long)V * clips;
+  const float dscale = grad_scale / (float)rows;
+  const float inv_clips = 1.f / (float)clips;
+  double wloss = 0.0;
+  long long wtop1 = 0, wtop5 = 0;
+  for (int v = wave; v < V; v += CLS_WAVES) {
+    const long long lab = labels[v];
+    const bool bad = lab < 0 || lab >= C;
+    if (bad && err && lane == 0) atomicOr(err, AVID_DEVERR_CLS_LABEL);
+    const int label = bad ? 0 : (int)lab;
+    for (int c = lane; c < C; c += 64) acc[c] = 0.f;
+    double vloss = 0.0;
+    for (int k = 0; k < clips; ++k) {
+      const long long row = (long long)v * clips + k;
+      const float* src = logits + row * C;
+      float m = -INFINITY;
+      for (int c = lane; c < C; c += 64) m = fmaxf(m, src[c]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+      float s = 0.f;
+      for (int c = lane; c < C; c += 64) s += expf(src[c] - m);
+      s = wave_sum(s);
+      const float inv_s = 1.f / s;
+      vloss += (double)(logf(s) + m - src[label]);
+      for (int c = lane; c < C; c += 64) {
+        const float pr = expf(src[c] - m) * inv_s;
+        acc[c] += pr;
+        if (dlogits) dlogits[row * C + c] = (pr - (c == label ? 1.f : 0.f)) * dscale;
+      }
+    }
+    // confidence, and the label's rank in it: classes with strictly greater confidence, plus equal confidence at a lower index
+    // (a lane reads back only the columns it wrote itself, and the label's column, written by lane label % 64 of this wave)
+    int above = 0;
+    for (int c = lane; c < C; c += 64) acc[c] *= inv_clips;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    const float cl = acc[label];
+    for (int c = lane; c < C; c += 64) {
+      const float a = acc[c];
+      if (conf) conf[(long long)v * C + c] = a;
+      above += (a > cl || (a == cl && c < label)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+    if (!bad) {
+      wtop1 += above < 1 ? 1 : 0;
+      wtop5 += above < 5 ? 1 : 0;
+    }
+    wloss += vloss;
+    __builtin_amdgcn_wave_barrier();     // every lane has read acc[label] before the next video clears it
+  }
+  __shared__ double s_loss[CLS_WAVES];
+  __shared__ long long s_hits[2][CLS_WAVES];
+  if (lane == 0) {
+    s_loss[wave] = wloss;
+    s_hits[0][wave] = wtop1;
+    s_hits[1][wave] = wtop5;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    long long h1 = 0, h5 = 0;
+    for (int w = 0; w < CLS_WAVES; ++w) {
+      t += s_loss[w];
+      h1 += s_hits[0][w];
+      h5 += s_hits[1][w];
+    }
+    if (loss) loss[0] = (float)(t / (double)rows);
+    if (hits) {
+      hits[0] = h1;
+      hits[1] = h5;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The classifier Linear(F, C) for any C (the heads' igemm takes C in multiples of 64; 101 / 51 classes are not).
+// Forward: one wave per output (b, c), a dot product over F.  Backward: one thread per dW / db / dx element, each a sum
+// over the batch (dW, db) or over the classes (dx) in index order.  Deterministic; a few MFLOP per step.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cls_linear_fwd_kernel(int B, int Fin, int C, const float* __restrict__ x,
+                                                             const float* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ y) {
+  const int lane = threadIdx.x & 63;
+  const long long o = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (o >= (long long)B * C) return;
+  const int b = (int)(o / C), c = (int)(o % C);
+  const float* xr = x + (long long)b * Fin;
+  const float* wr = w + (long long)c * Fin;
+  float acc = 0.f;
+  for (int f = lane; f < Fin; f += 64) acc = fmaf(xr[f], wr[f], acc);
+  acc = wave_sum(acc);
+  if (lane == 0) y[o] = acc + (bias ? bias[c] : 0.f);
+}
+
+__global__ __launch_bounds__(256) void cls_linear_bwd_kernel(int B, int Fin, int C, const float* __restrict__ x,
+                                                             const float* __restrict__ w, const float* __restrict__ dy,
+                                                             float* __restrict__ dx, float* __restrict__ dw,
+                                                             float* __restrict__ db) {
+  const long long nw = (long long)C * Fin, nb = C, nx = dx ? (long long)B * Fin : 0;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nw + nb + nx; i += stride) {
+    if (i < nw) {
+      const int c = (int)(i / Fin), f = (int)(i % Fin);
+      float acc = 0.f;
+      for (int b = 0; b < B; ++b) acc = fmaf(dy[(long long)b * C + c], x[(long long)b * Fin + f], acc);
+      dw[i] = acc;
+    } else if (i < nw + nb) {
+      const int c = (int)(i - nw);
+      float acc = 0.f;
+      for (int b = 0; b < B; ++b) acc += dy[(long long)b * C + c];
+      if (db) db[c] = acc;
+    } else {
+      const long long j = i - nw - nb;
+      const int b = (int)(j / Fin), f = (int)(j % Fin);
+      float acc = 0.f;
+      for (int c = 0; c < C; ++c) acc = fmaf(dy[(long long)b * C + c], w[(long long)c * Fin + f], acc);
+      dx[j] = acc;
+    }
+  }
+}
+
+}  // namespace avid
+
+using namespace avid;
+
+extern "C" int avid_cls_linear_fwd(int B, int Fin, int C, const float* x, const float* w, const float* bias, float* y,
+                                   avid_stream_t stream) {
+  AVID_REQUIRE(B > 0 && Fin > 0 && C > 0 && x && w && y, AVID_E_BADARG, "cls_linear_fwd: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const long long outs = (long long)B * C;
+  ScopedTimer t(s, "cls_linear_fwd_kernel", 2.0 * outs * Fin, 4.0 * ((double)B * Fin + (double)C * Fin + outs));
+  hipLaunchKernelGGL(cls_linear_fwd_kernel, dim3((unsigned)ceil_div(outs, 4)), dim3(256), 0, s, B, Fin, C, x, w, bias, y);
+  return check_launch("cls_linear_fwd");
+}
+
+extern "C" int avid_cls_linear_bwd(int B, int Fin, int C, const float* x, const float* w, const float* dy, float* dx, float* dw,
+                                   float* db, avid_stream_t stream) {
+  AVID_REQUIRE(B > 0 && Fin > 0 && C > 0 && x && w && dy && dw, AVID_E_BADARG, "cls_linear_bwd: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const long long n = (long long)C * Fin + C + (dx ? (long long)B * Fin : 0);
+  long long g = ceil_div(n, 256);
+  if (g > 4096) g = 4096;
+  ScopedTimer t(s, "cls_linear_bwd_kernel", 2.0 * B * (double)C * Fin * (dx ? 2.0 : 1.0), 4.0 * (double)n);
+  hipLaunchKernelGGL(cls_linear_bwd_kernel, dim3((unsigned)g), dim3(256), 0, s, B, Fin, C, x, w, dy, dx, dw, db);
+  return check_launch("cls_linear_bwd");
+}
+
+static uint32_t dropout_threshold(float p) { return (uint32_t)floor((double)p * 4294967296.0); }
+
+extern "C" int avid_dropout_fwd(int64_t B, int64_t F, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                                const float* x, float* y, uint8_t* mask, avid_stream_t stream) {
+  AVID_REQUIRE(B > 0 && F > 0 && x && y && mask, AVID_E_BADARG, "dropout_fwd: bad arguments");
+  AVID_REQUIRE(p >= 0.f && p < 1.f, AVID_E_BADARG, "dropout_fwd: p = %g outside [0, 1)", (double)p);
+  const long long n = (long long)B * F;
+  long long g = ceil_div(ceil_div(n, 4), 256);
+  if (g > 4096) g = 4096;
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(s, "dropout_fwd_kernel", 0.0, 9.0 * n);
+  hipLaunchKernelGGL(dropout_fwd_kernel, dim3((unsigned)g), dim3(256), 0, s, n, x, y, mask, dropout_threshold(p),
+                     1.0f / (1.0f - p), seed, offset, (const unsigned long long*)offset_dev);
+  return check_launch("dropout_fwd");
+}
+
+extern "C" int avid_dropout_bwd(int64_t n, float p, const uint8_t* mask, const float* dy, float* dx, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && mask && dy && dx, AVID_E_BADARG, "dropout_bwd: bad arguments");
+  AVID_REQUIRE(p >= 0.f && p < 1.f, AVID_E_BADARG, "dropout_bwd: p = %g outside [0, 1)", (double)p);
+  long long g = ceil_div(n, 256);
+  if (g > 4096) g = 4096;
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(s, "dropout_bwd_kernel", 0.0, 9.0 * n);
+  hipLaunchKernelGGL(dropout_bwd_kernel, dim3((unsigned)g), dim3(256), 0, s, (long long)n, mask, dy, dx, 1.0f / (1.0f - p));
+  return check_launch("dropout_bwd");
+}
+
+extern "C" int avid_cls_loss(int V, int clips, int C, const float* logits, const int64_t* labels, float grad_scale,
+                             float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err, avid_stream_t stream) {
+  AVID_REQUIRE(V > 0 && clips > 0 && C > 0 && C <= CLS_MAX_C && logits && labels, AVID_E_BADARG,
+               "cls_loss: bad arguments (V %d, clips %d, C %d: C must be in [1, %d])", V, clips, C, CLS_MAX_C);
+  hipStream_t s = (hipStream_t)stream;
+  const double elems = (double)V * clips * C;
+  ScopedTimer t(s, "cls_loss_kernel", 0.0, elems * (dlogits ? 8.0 : 4.0));
+  hipLaunchKernelGGL(cls_loss_kernel, dim3(1), dim3(CLS_WAVES * 64), 0, s, V, clips, C, logits, (const long long*)labels,
+                     grad_scale, loss, conf, (long long*)hits, dlogits, err);
+  return check_launch("cls_loss");
+}

@@ -87,6 +87,26 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// Philox4x32-10 (Salmon et al.): counter = (c0, c1, c2, c3), key = (k0, k1); the four output words.  avid_alias_draw
+// (criterion.hip) reads words 0 and 1 of counter (i_lo, i_hi, off_lo, off_hi); avid_dropout_fwd (classify.hip) reads word
+// i % 4 of counter (i/4 lo, i/4 hi, off_lo, off_hi).
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t& r0, uint32_t& r1, uint32_t& r2, uint32_t& r3) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  r0 = c0;
+  r1 = c1;
+  r2 = c2;
+  r3 = c3;
+}
+
 // XCD-aware bijective remap of a linear workgroup id: XCD k (= hardware id % 8) receives one
 // contiguous chunk of the logical tile space so neighbouring tiles share that XCD's L2.
 __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {

@@ -41,24 +41,6 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
   for (int d = lane; d < D; d += 64) dx[o + d] = (dy[o + d] - y[o + d] * dot) * inv;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al.): counter = (i_lo, i_hi, off_lo, off_hi), key = (seed_lo, seed_hi)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t& r0, uint32_t& r1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  r0 = c0;
-  r1 = c1;
-}
-
 __global__ void counter_add_kernel(unsigned long long* ctr, unsigned long long inc) { *ctr += inc; }
 
 __global__ void alias_draw_kernel(long long n, long long K, const float* __restrict__ prob,
@@ -68,9 +50,9 @@ __global__ void alias_draw_kernel(long long n, long long K, const float* __restr
   if (offset_dev) offset = *offset_dev;  // graph-replay safe: the draw counter lives in device memory
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    uint32_t r0, r1;
+    uint32_t r0, r1, r2, r3;
     philox4x32_10((uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)offset, (uint32_t)(offset >> 32),
-                  (uint32_t)seed, (uint32_t)(seed >> 32), r0, r1);
+                  (uint32_t)seed, (uint32_t)(seed >> 32), r0, r1, r2, r3);
     const long long kk = (long long)(((uint64_t)r0 * (uint64_t)K) >> 32);
     long long v = kk;
     if (!uniform) {

@@ -303,6 +303,25 @@ extern "C" int avid_program_run(const avid_instr* prog, int begin, int end, void
                               reinterpret_cast<const int64_t*>(step_dev), F(t[5]), in.f[5], s);
         break;
       }
+      case AVID_OP_DROPOUT_FWD: {
+        const uint64_t seed = (uint64_t)(uint32_t)in.i[1] | ((uint64_t)(uint32_t)in.i[2] << 32);
+        rc = avid_dropout_fwd(in.n[0], in.i[0], in.f[0], seed, (uint64_t)in.n[1], reinterpret_cast<const uint64_t*>(P(t[3])),
+                              F(t[0]), F(t[1]), reinterpret_cast<uint8_t*>(P(t[2])), s);
+        break;
+      }
+      case AVID_OP_DROPOUT_BWD:
+        rc = avid_dropout_bwd(in.n[0], in.f[0], reinterpret_cast<const uint8_t*>(P(t[0])), F(t[1]), F(t[2]), s);
+        break;
+      case AVID_OP_CLS_LOSS:
+        rc = avid_cls_loss(in.i[0], in.i[1], in.i[2], F(t[0]), reinterpret_cast<const int64_t*>(P(t[1])), in.f[0], F(t[2]), F(t[3]),
+                           reinterpret_cast<int64_t*>(P(t[4])), F(t[5]), reinterpret_cast<int32_t*>(P(t[6])), s);
+        break;
+      case AVID_OP_CLS_LINEAR_FWD:
+        rc = avid_cls_linear_fwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), s);
+        break;
+      case AVID_OP_CLS_LINEAR_BWD:
+        rc = avid_cls_linear_bwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), F(t[5]), s);
+        break;
       default:
         set_error("program record %d: unknown kind %d", k, in.op);
         return AVID_E_BADARG;

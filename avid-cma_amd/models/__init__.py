@@ -6,3 +6,4 @@
 from .video import *  # noqa: F401,F403
 from .audio import *  # noqa: F401,F403
 from .av_wrapper import *  # noqa: F401,F403
+from .classification import *  # noqa: F401,F403

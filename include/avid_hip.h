@@ -362,6 +362,37 @@ int avid_counter_add(uint64_t* counter, uint64_t inc, avid_stream_t stream);
 #define AVID_DEVERR_BANK_INDEX 1   /* avid_bank_scores_fwd: idx outside [0, N) */
 #define AVID_DEVERR_UPDATE_INDEX 2 /* avid_bank_update: y outside [0, N) */
 #define AVID_DEVERR_CMA_INDEX 4    /* avid_cma_negatives: y outside [0, N) */
+#define AVID_DEVERR_CLS_LABEL 8    /* avid_cls_loss: label outside [0, C) */
+
+/* Action-recognition fine-tuning head (utils/eval_utils.py:193-214, eval-action-recg.py:150-165) — classify.hip.
+ *
+ * Dropout over x [B, F]: element i = b * F + f is kept iff word i % 4 of Philox4x32-10 with counter
+ * (i / 4 lo, i / 4 hi, offset lo, offset hi) and key seed is >= floor(p * 2^32); y = x * mask * (1 / (1 - p)), the scale
+ * computed in fp32.  mask [B * F] bytes (0 / 1) is kept for the backward.  offset_dev != NULL: the offset is read from
+ * device memory, as avid_alias_draw does.  The masks follow torch.nn.Dropout's distribution, not its bits.  0 <= p < 1. */
+int avid_dropout_fwd(int64_t B, int64_t F, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                     const float* x, float* y, uint8_t* mask, avid_stream_t stream);
+/* dx = dy * mask * (1 / (1 - p)) over n elements. */
+int avid_dropout_bwd(int64_t n, float p, const uint8_t* mask, const float* dy, float* dx, avid_stream_t stream);
+/* Softmax cross-entropy of logits [V * clips][C] (1 <= C <= 1024; rows v * clips .. v * clips + clips - 1 are video v's
+ * clips) against labels [V] (int64), one launch:
+ *   loss[0]     = mean over all V * clips rows of -log softmax(row)[labels[v]]  (clips = 1: the train / test loss)
+ *   conf [V][C] = mean over each video's clips of softmax(row)                 (nullable)
+ *   hits[2]     = (top-1, top-5) hit counts of conf, int64                      (nullable; written on the device, no sync)
+ *   dlogits     = (softmax(row) - onehot(label)) * grad_scale / (V * clips)     (nullable: the training case)
+ * Rank rule of the hit counts: a label's rank is the number of classes with strictly greater confidence plus the number
+ * with equal confidence at a lower class index; top-k hits rank < k.  A label outside [0, C) ORs AVID_DEVERR_CLS_LABEL into
+ * err (nullable) and scores no hit.  The summation order is fixed and no result is accumulated with atomics: every output
+ * is bit-reproducible from run to run. */
+int avid_cls_loss(int V, int clips, int C, const float* logits, const int64_t* labels, float grad_scale, float* loss,
+                  float* conf, int64_t* hits, float* dlogits, int32_t* err, avid_stream_t stream);
+/* The classifier Linear(Fin, C) for any C (avid_conv_fwd's igemm takes Cout in multiples of 64):
+ * y [B][C] = x [B][Fin] . w [C][Fin]^T + bias (bias nullable).  Backward: dw = dy^T . x, db = column sums of dy (nullable),
+ * dx = dy . w (nullable).  Each output is one sum in index order: deterministic. */
+int avid_cls_linear_fwd(int B, int Fin, int C, const float* x, const float* w, const float* bias, float* y,
+                        avid_stream_t stream);
+int avid_cls_linear_bwd(int B, int Fin, int C, const float* x, const float* w, const float* dy, float* dx, float* dw,
+                        float* db, avid_stream_t stream);
 
 /* scores[b][j] = <bank[idx[b][j]], emb[b]> * inv_T — the gather + bmm of criterions/avid.py:57-71.
  * idx [bs][R] int64, bank [N][D], emb [bs][D], D in {64,128,256,512}.  rows_out (nullable,
@@ -542,6 +573,11 @@ enum {
   AVID_OP_WT_BATCH = 16,     /* i0 descriptors, n0 max_elems; t: table (avid_wt_desc[] in device memory) */
   AVID_OP_ADAM = 17,         /* n0 elements; f0 lr, f1 beta1, f2 beta2, f3 eps, f4 weight_decay, f5 grad_scale; n1 step;
                                 t: p g m v step_dev lr_dev (step_dev, if given, is advanced by one first) */
+  AVID_OP_DROPOUT_FWD = 18,  /* n0 B, n1 offset; i0 F, i1 seed lo, i2 seed hi; f0 p; t: x y mask offset_dev */
+  AVID_OP_DROPOUT_BWD = 19,  /* n0 elements; f0 p; t: mask dy dx */
+  AVID_OP_CLS_LOSS = 20,     /* i0 V, i1 clips, i2 C; f0 grad_scale; t: logits labels loss conf hits dlogits err */
+  AVID_OP_CLS_LINEAR_FWD = 21, /* i0 B, i1 Fin, i2 C; t: x w bias y */
+  AVID_OP_CLS_LINEAR_BWD = 22, /* i0 B, i1 Fin, i2 C; t: x w dy dx dw db */
   AVID_OP_COUNT_
 };
 
