@@ -333,22 +333,26 @@ def wino_epoch():
     return _WINO_EPOCH[0]
 
 
+def _dispatch_changed():
+    """The kernels' dispatch switches changed: drop the per-layer plans cached here and bump the epoch the compiled launch
+    programs are keyed by."""
+    _DESC_CACHE.clear()
+    _GROUP_WS_BYTES.clear()
+    _WINO_EPOCH[0] += 1
+
+
 def wino_configure(enabled=-1, min_pixels=-1, max_channels=-1):
     """Dispatch switches of the Winograd kernels (``avid_wino_configure``; negative = environment / default) — and
     drop the per-layer plans cached here, which depend on them."""
     lib.call("avid_wino_configure", int(enabled), int(min_pixels), int(max_channels))
-    _DESC_CACHE.clear()
-    _GROUP_WS_BYTES.clear()
-    _WINO_EPOCH[0] += 1
+    _dispatch_changed()
 
 
 def wino2_configure(min_rounds_x10=-1):
     """Which Winograd forward / input-gradient kernel a layer takes (``avid_wino2_configure``): 0 = always
     ``wino2_kernel``, negative = environment / default (layers with >= 1.5 rounds of 64-tile units)."""
     lib.call("avid_wino2_configure", int(min_rounds_x10))
-    _DESC_CACHE.clear()
-    _GROUP_WS_BYTES.clear()
-    _WINO_EPOCH[0] += 1
+    _dispatch_changed()
 
 
 def set_cu_budget(cus=0):
@@ -356,9 +360,7 @@ def set_cu_budget(cus=0):
     RCCL's collectives.  Drops the cached per-layer plans and bumps the epoch the compiled launch programs are keyed by;
     returns the effective count."""
     got = int(lib.raw("avid_set_cu_budget")(int(cus)))
-    _DESC_CACHE.clear()
-    _GROUP_WS_BYTES.clear()
-    _WINO_EPOCH[0] += 1
+    _dispatch_changed()
     return got
 
 

@@ -393,16 +393,17 @@ class TrainStep:
         evaluating the model or saving it on a rank other than 0."""
         self.flat_buffers.broadcast(0)
 
-    def _plan_backward(self, pl, fa, video, audio, dv, da):
-        """The backward launch program of the model (called from its autograd node): in one piece, or — with gradient
-        collectives — cut where a bucket becomes complete, so that its all-reduce starts under the rest of the pass."""
+    def _plan_backward(self, pl, fa, inputs):
+        """A backward launch program into the flat gradient buffer (``pl.backward``'s ``fa`` / ``inputs``; called from the
+        model's autograd node or by ``FinetuneStep``): in one piece, or — with gradient collectives — cut where a bucket
+        becomes complete, so that its all-reduce starts under the rest of the pass."""
         self._step_plan = pl
         if not self.buckets.comm or self.buckets._capturing():
-            pl.backward(fa, video, audio, dv, da, self.flat.grad)
+            pl.backward(fa, inputs, self.flat.grad)
             return
         ba, begin = None, 0
         for end, ready in pl.segments(self.buckets.bucket_of, self.buckets.counts):
-            ba = pl.backward(fa, video, audio, dv, da, self.flat.grad, begin, end, ba)
+            ba = pl.backward(fa, inputs, self.flat.grad, begin, end, ba)
             for i, st in ready:
                 self.buckets.ready(i, pl.stream_objs[st])
             begin = end
@@ -493,28 +494,33 @@ class TrainStep:
         placed on a dispatch pipe of its own, avid_hip/streams.py; a captured step decides for itself in ops)."""
         return True
 
-    def optimizer_step(self):
+    def _adam(self, begin=0, end=None, advance=True):
+        """One flat-Adam launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (step
+        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays)."""
         from . import ops
-        self.t += 1
-        ops.adam_flat(self.flat.flat, self.flat.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1],
+        s = slice(begin, end)
+        ops.adam_flat(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0], self.betas[1],
                       self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev,
-                      lr_dev=self.lr_dev)
+                      lr_dev=self.lr_dev, advance=advance)
+
+    def optimizer_step(self):
+        self.t += 1
+        self._adam()
 
     def _optimizer_step_overlapped(self, pl):
         """The same update in two launches: every parameter but the video stem's three on the fourth stream, which the
         backward program made wait for exactly their gradients (plan.Plan: ``adam_early``) — it runs beside the stem's
         weight gradient, the step's last kernel — then the stem's on the compute stream.  Same arithmetic per element."""
-        from . import ops
         self.t += 1
-        n0 = pl.adam_early
-        f, g, m, v = self.flat.flat, self.flat.grad, self.m, self.v
-        kw = dict(grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev, lr_dev=self.lr_dev)
         main, fourth = torch.cuda.current_stream(), pl.stream_objs[3]
         with torch.cuda.stream(fourth):
-            ops.adam_flat(f[:n0], g[:n0], m[:n0], v[:n0], self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t, **kw)
+            self._adam(0, pl.adam_early)
         main.wait_stream(fourth)
-        ops.adam_flat(f[n0:], g[n0:], m[n0:], v[n0:], self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
-                      advance=False, **kw)
+        self._adam(pl.adam_early, advance=False)
+
+    def _sampler(self):
+        """The criterion's negative sampler (``nce_average.multinomial``), or None."""
+        return getattr(getattr(self.criterion, "nce_average", None), "multinomial", None)
 
     # ---- optimizer / sampler state in torch.optim.Adam's format (main-avid.py:115,127,138 save and restore
     # ``optimizer.state_dict()``; utils/main_utils.py:250-261 builds Adam over model.parameters())
@@ -543,7 +549,7 @@ class TrainStep:
                                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
                                 "differentiable": False, "fused": None, "decoupled_weight_decay": False,
                                 "params": list(range(nparams))}]}
-        mult = getattr(getattr(self.criterion, "nce_average", None), "multinomial", None)
+        mult = self._sampler()
         if mult is not None:       # the negative sampler's stream position (not part of the reference's checkpoint:
             off = int(mult.offset_dev) if getattr(mult, "offset_dev", None) is not None else int(mult.offset)
             sd["avid_sampler"] = {"seed": int(mult.seed), "offset": off}   # torch's global RNG is not saved either)
@@ -567,7 +573,7 @@ class TrainStep:
         self.t = step
         if self.t_dev is not None:
             self.t_dev.fill_(step)
-        mult = getattr(getattr(self.criterion, "nce_average", None), "multinomial", None)
+        mult = self._sampler()
         if mult is not None and "avid_sampler" in sd:
             mult.reseed(sd["avid_sampler"]["seed"], sd["avid_sampler"]["offset"])
 
@@ -599,7 +605,7 @@ class TrainStep:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         t_host = self.t
-        mult = getattr(getattr(self.criterion, "nce_average", None), "multinomial", None)
+        mult = self._sampler()
         off_host = mult.offset if mult is not None else None
         # (thread-local capture mode: the NCCL process group's watchdog thread polls the events of earlier collectives with
         #  hipEventQuery — under the default global mode that call is illegal while ANY thread captures and aborts the process)
@@ -622,7 +628,7 @@ class TrainStep:
         self.graph.replay()
         self._poll_errors()
         self.t += 1
-        mult = getattr(getattr(self.criterion, "nce_average", None), "multinomial", None)
+        mult = self._sampler()
         if mult is not None:
             mult.offset += 1
         return self._sloss
@@ -677,9 +683,9 @@ class _WrapperEngine(TrainStep):
         self._armed = False
         self.buckets.reset()
 
-    def _plan_backward(self, pl, fa, video, audio, dv, da):
+    def _plan_backward(self, pl, fa, inputs):
         self._arm()
-        super()._plan_backward(pl, fa, video, audio, dv, da)
+        super()._plan_backward(pl, fa, inputs)
 
 
 class DistributedDataParallel(torch.nn.Module):
@@ -875,31 +881,20 @@ class FinetuneStep(TrainStep):
         out = torch.empty(8, dtype=torch.float32, device=video.device)          # plan.OUT_BYTES
         dlogits = torch.empty((B, pl.n_classes), dtype=torch.float32, device=video.device)
         _, fa = pl.forward(video, self.flat.grad, True, seed, offset, labels=labels, out=out, dlogits=dlogits)
-        if not self.buckets.comm:
-            pl.backward(fa, video, dlogits, self.flat.grad)
-        elif self.classifier_only:
+        inputs = (video, None, dlogits, None)
+        if self.buckets.comm and self.classifier_only:
             # only the classifier's leading slice of the gradient buffer is written (and zeroed): ONE collective over it,
             # behind the backward program (whose streams all join the current one), instead of the buckets over the tower
-            pl.backward(fa, video, dlogits, self.flat.grad)
+            pl.backward(fa, inputs, self.flat.grad)
             dist.all_reduce(self.flat.grad[:self.n_cls])
         else:
-            ba, begin = None, 0
-            for end, ready in pl.segments(self.buckets.bucket_of, self.buckets.counts):
-                ba = pl.backward(fa, video, dlogits, self.flat.grad, begin, end, ba)
-                for i, st in ready:
-                    self.buckets.ready(i, pl.stream_objs[st])
-                begin = end
-            self.buckets.finish()
-        self._adam()
+            self._plan_backward(pl, fa, inputs)
+            if self.buckets.comm:
+                self.buckets.finish()
+        self.t += 1
+        self._adam(0, self.n_cls if self.classifier_only else self.flat.numel)
         self._poll_errors()
         return out[0], out[2:6].view(torch.int64)
-
-    def _adam(self):
-        from . import ops
-        self.t += 1
-        n = self.n_cls if self.classifier_only else self.flat.numel
-        ops.adam_flat(self.flat.flat[:n], self.flat.grad[:n], self.m[:n], self.v[:n], self.lr, self.betas[0], self.betas[1],
-                      self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev, lr_dev=self.lr_dev)
 
     def _param_order(self):
         order = super()._param_order()

@@ -431,15 +431,11 @@ class Builder:
 
     # ---- module walkers --------------------------------------------------------------------------------------------
     def r2p1d_block_fwd(self, blk, x):
-        from models.network_blocks import BasicR2P1DBlock
+        from models.network_blocks import BasicR2P1DBlock, res_fusable
         if type(blk) is not BasicR2P1DBlock:
             raise Unsupported(type(blk).__name__)
-        if blk.res:
-            from models import network_blocks as nb
-            rs, ss = blk.res_conv.stride3, blk.spt_conv1.stride3
-            if not (nb._FUSE_RES and any(v == 2 for v in rs) and all(v in (1, 2) for v in rs)
-                    and any(v == 2 for v in ss) and all(v in (1, 2) for v in ss) and x.numel * 4 < (1 << 31)):
-                raise Unsupported("residual convolution outside the fused pattern")
+        if blk.res and not res_fusable(blk, x.numel):
+            raise Unsupported("residual convolution outside the fused pattern")
         # (spt_bn1 -> tmp_conv1 and spt_bn2 -> tmp_conv2: each BatchNorm's output has exactly one reader, the next convolution)
         L1 = self.conv_bn_fwd(blk.spt_conv1, blk.spt_bn1, x, res=blk.res_conv if blk.res else None,
                               next_conv=None if blk.res else blk.tmp_conv1)
@@ -556,36 +552,26 @@ class Builder:
         return dy
 
 
-def _hooked(model):
-    for m in model.modules():
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
-            return True
-    return False
+class Programs:
+    """A compiled pair of launch programs — forward and backward — over all of one model's parameters: what the two-tower
+    ``Plan`` and the classifier's ``ClsPlan`` share.  A subclass compiles its own graph between ``_open`` (the checks, the
+    forward's leading records), ``_backward_begins`` and ``_close`` (the backward's tail), and issues its own forward;
+    the backward program runs the same way for both (``backward``)."""
 
+    adam_early = None        # gradient offset from which the optimizer may start before the backward program ends (Plan)
 
-class Plan:
-    """The compiled forward / backward programs of one ``AV_Wrapper`` for one input geometry and stream arrangement."""
-
-    def __init__(self, model, vshape, ashape, device, overlap_towers, trailing, group):
-        if not model.use_linear_proj:
-            raise Unsupported("no projection heads")
+    def _open(self, model, device, overlap_towers, trailing, group):
+        """The Builder of the model's parameters and the forward's leading records: what the backward needs but the forward
+        does not — the gradient fill, the transposed / Winograd-transformed weights — runs on the trailing stream beside
+        the forward; the table is known only after the backward is compiled, so ``_finalize`` patches it in."""
         params = [p for p in model.parameters()]
         dry = device.type != "cuda"                  # (compile only: tests/test_plan_compile.py, no GPU)
         if not all(p.requires_grad and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
             raise Unsupported("frozen / non-fp32 parameters")
         b = Builder(device, overlap_towers, trailing, group)
         b.set_params(params)
-        self.device = device
-        self.key = (tuple(vshape), tuple(ashape), overlap_towers, trailing, group)
-        B = vshape[0]
-        video = Sym((S_VIDEO, 0), vshape)
-        audio = Sym((S_AUDIO, 0), (ashape[0], ashape[1], 1, ashape[2], ashape[3]))   # [B,1,1,H,W]: T = kt = 1
-        A_S = ST_AUDIO if overlap_towers else ST_MAIN
-        # ------------------------------------------------------------------ forward
+        self.device, self.params_fwd = device, params
         b.cur = b.fwd
-        # (what the backward needs but the forward does not — the transposed / Winograd-transformed weights — runs on
-        #  the video tower's trailing stream beside the forward; the table is known only after the backward is
-        #  compiled, so the record is patched in below)
         helper = ST_TRAIL if trailing else ST_MAIN
         if trailing:
             b.wait(helper, ST_MAIN)
@@ -593,58 +579,25 @@ class Plan:
         b.emit(OP_MEMSET0, stream=helper, n=(4 * b.gnumel,), t=((S_GRAD, 0),))
         self._wt_rec = b.emit(OP_WT_BATCH, stream=helper, i=(0,), n=(0,), t=((S_AUX, 0),))
         b.S = ST_MAIN
-        # the video stem first, then the audio tower starts on its own stream (beside conv2x.., not beside the stem:
-        # models/av_wrapper.py AUDIO_AFTER)
-        V, vfeat = self._video_with_audio(b, model, video, audio, A_S)
-        A, afeat = self._A, self._afeat
-        b.S = ST_MAIN
-        VH, vemb = b.head_fwd(model.video_proj, vfeat)
-        if A_S != ST_MAIN:
-            b.wait(ST_MAIN, A_S)
-        self.vemb, self.aemb = vemb, self._aemb
-        self.n_fwd = len(b.fwd)
-        # ------------------------------------------------------------------ backward (autograd's order: the video
-        # tower from its head down to conv2x, the audio tower, the video stem last — sequence numbers of the forward)
-        b.cur = b.bwd
-        if trailing:
-            b.wait(ST_MAIN, helper)                   # the transposed weights are complete
-        if A_S != ST_MAIN:
-            b.wait(A_S, ST_MAIN)                      # the criterion's gradients (and the transposed weights)
-        b.S = ST_MAIN
-        dv = b.head_bwd(VH, (S_DV, 0))
-        dh = b.video_bwd(V, dv)
-        b.S = A_S
-        da = b.head_bwd(self._AH, (S_DA, 0))
-        b.audio_bwd(A, da)
-        # Everything but the video stem's three parameters has its gradient here: the engine's optimizer can update those
-        # (nearly all of the 134 MB) on the fourth stream WHILE the stem's backward — one LDS-bound full-chip kernel of
-        # 0.57 ms on the trailing stream, the step's last — still runs (parallel.TrainStep.step; the HBM-bound Adam pass and
-        # that kernel overlap).  The fourth stream waits here for the three streams that hold those gradients.
-        for S in (ST_MAIN, ST_AUDIO):
-            b.S = S
-            b.flush_group(S)
-        b.S = ST_MAIN
-        self.adam_early = None
-        if trailing and A_S != ST_MAIN:
-            stem_conv, stem_bn = model.video_model.conv1[0], model.video_model.conv1[1]
-            idx = sorted(b.pindex[id(p)] for p in (stem_conv.weight, stem_bn.weight, stem_bn.bias))
-            n = len(b.params)
-            if idx == [n - 3, n - 2, n - 1]:                   # (the engine's flat layout: parameters in reverse order)
-                for S in (ST_MAIN, A_S, ST_TRAIL):
-                    b.wait(ST_COMM, S)
-                self.adam_early = b.goff[n - 3]
-        b.video_stem_bwd(V, dh)
-        b.flush_group(ST_MAIN)
-        if A_S != ST_MAIN:
-            b.wait(ST_MAIN, A_S)
-        for tr in sorted(b.trail_used):
-            b.wait(ST_MAIN, tr)
-        self.n_bwd = len(b.bwd)
-        self._finalize(b, device)
-        self.params_fwd = params
-        self.vshape, self.ashape = tuple(vshape), tuple(ashape)
+        return b
 
-    def _finalize(self, b, device):
+    def _backward_begins(self, b):
+        """The forward program ends here; the backward starts once the transposed weights are complete."""
+        self.n_fwd = len(b.fwd)
+        b.cur = b.bwd
+        if b.trailing:
+            b.wait(ST_MAIN, ST_TRAIL)
+        b.S = ST_MAIN
+
+    def _close(self, b, *joined):
+        """The backward's last weight-gradient group, then the compute stream joins ``joined`` and every trailing stream."""
+        b.flush_group(ST_MAIN)
+        for S in joined + tuple(sorted(b.trail_used)):
+            b.wait(ST_MAIN, S)
+        self.n_bwd = len(b.bwd)
+        self._finalize(b)
+
+    def _finalize(self, b):
         """The weight-transform table, the record arrays, the arenas' sizes and the streams' workspaces."""
         # ------------------------------------------------------------------ the weight-transform table
         self.aux_bytes = _align(b.aux_size) + 32 * len(b.wt_recs) + 256
@@ -667,41 +620,22 @@ class Plan:
         lib.call("avid_program_workspace_bytes", self.fwd_prog, 0, self.n_fwd, 4, need_f)
         lib.call("avid_program_workspace_bytes", self.bwd_prog, 0, self.n_bwd, 4, need_b)
         self.ws_bytes = [max(int(need_f[k]), int(need_b[k]), 1 << 20) for k in range(4)]
-        self.ws = [torch.empty(n, dtype=torch.uint8, device=device) for n in self.ws_bytes]
+        self.ws = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in self.ws_bytes]
         self.ws_arr = (StreamWs * 4)()
         for k in range(4):
             self.ws_arr[k].ptr, self.ws_arr[k].bytes = self.ws[k].data_ptr(), self.ws_bytes[k]
-        self.aux = torch.empty(self.aux_bytes, dtype=torch.uint8, device=device)
+        self.aux = torch.empty(self.aux_bytes, dtype=torch.uint8, device=self.device)
         self._table_ptrs = None
         self.slots = (_vp * self.n_slots)()
         self.streams = (_vp * 4)()
 
-    def _video_with_audio(self, b, model, video, audio, A_S):
-        """The video tower with the audio tower (and its head) started behind the video stem on stream A_S."""
-        def start_audio():
-            S0 = b.S
-            if A_S != ST_MAIN:
-                b.wait(A_S, ST_MAIN)
-            b.S = A_S
-            self._A, self._afeat = b.audio_fwd(model.audio_model, audio)
-            self._AH, self._aemb = b.head_fwd(model.audio_proj, self._afeat)
-            b.S = S0
-        return b.video_fwd(model.video_model, video, after_stem=start_audio)
-
     # ---- per-run plumbing ------------------------------------------------------------------------------------------
-    def _fill_slots(self, fa, ba, grad, video, audio, dv, da):
+    def _fill_slots(self, fa, ba, grad, inputs):
+        """``inputs``: the tensors of slots S_VIDEO, S_AUDIO, S_DV, S_DA (None: unused by the records run)."""
         s = self.slots
-        s[S_FWD] = fa.data_ptr() if fa is not None else None
-        s[S_BWD] = ba.data_ptr() if ba is not None else None
-        s[S_GRAD] = grad.data_ptr() if grad is not None else None
-        s[S_AUX] = self.aux.data_ptr()
-        s[S_VIDEO] = video.data_ptr() if video is not None else None
-        s[S_AUDIO] = audio.data_ptr() if audio is not None else None
-        s[S_DV] = dv.data_ptr() if dv is not None else None
-        s[S_DA] = da.data_ptr() if da is not None else None
-        ptrs = [t.data_ptr() for t in self.tensors]
-        s[S_FIRST_TENSOR:self.n_slots] = ptrs
-        return ptrs
+        for k, t in enumerate((fa, ba, grad, self.aux) + tuple(inputs)):     # S_FWD .. S_DA
+            s[k] = t.data_ptr() if t is not None else None
+        s[S_FIRST_TENSOR:self.n_slots] = [t.data_ptr() for t in self.tensors]
 
     def _refresh_table(self):
         """The device table of weight-transform descriptors follows the parameters' current addresses."""
@@ -721,30 +655,133 @@ class Plan:
         st[0], st[1], st[2], st[3] = ss.main.cuda_stream, ss.side.cuda_stream, ss.trail.cuda_stream, ss.comm.cuda_stream
         self.stream_objs = (ss.main, ss.side, ss.trail, ss.comm)
 
-    def forward(self, video, audio, grad_flat, zero_grad):
-        """Issue the forward program; returns (v_emb, a_emb, arena)."""
-        dev = self.device
+    def _forward_arena(self, grad_flat, zero_grad, inputs):
+        """A run of the forward program set up: weight table, arena, slots, streams, gradient fill on or off.  Returns the arena."""
         self._refresh_table()
-        fa = torch.empty(self.fa_bytes, dtype=torch.uint8, device=dev)
-        self._fill_slots(fa, None, grad_flat, video, audio, None, None)
+        fa = torch.empty(self.fa_bytes, dtype=torch.uint8, device=self.device)
+        self._fill_slots(fa, None, grad_flat, inputs)
         self._streams()
         self.fwd_prog[self._zero_index].op = OP_MEMSET0 if (zero_grad and grad_flat is not None) else 0
-        lib.call("avid_program_run", self.fwd_prog, 0, self.n_fwd, self.slots, self.n_slots, self.streams, self.ws_arr, 4)
+        return fa
+
+    def _run(self, prog, begin, end):
+        """Issue records [begin, end) of ``prog`` with the slots and streams set."""
+        lib.call("avid_program_run", prog, begin, end, self.slots, self.n_slots, self.streams, self.ws_arr, 4)
+
+    def backward(self, fa, inputs, grad_flat, begin=0, end=None, ba=None):
+        """Issue records [begin, end) of the backward program (default: all of them) after the forward that returned ``fa``;
+        ``inputs`` as ``_fill_slots``'.  Returns the backward arena (pass it back as ``ba`` for the next segment)."""
+        if ba is None:
+            ba = torch.empty(self.ba_bytes, dtype=torch.uint8, device=self.device)
+        self._fill_slots(fa, ba, grad_flat, inputs)
+        self._streams()
+        self._run(self.bwd_prog, begin, self.n_bwd if end is None else end)
+        return ba
+
+    def grad_views(self, g):
+        """{id(parameter): its gradient in the flat buffer ``g``}."""
+        out = {}
+        for p, o in zip(self.params, self.goff):
+            out[id(p)] = g[o:o + p.numel()].as_strided(p.shape, p.stride())
+        return out
+
+    def segments(self, bucket_of, counts):
+        """Cut the backward program where a gradient bucket becomes complete: [(end record, [(param index, stream)])] —
+        the engine runs the records up to ``end``, reports those gradients (which launches the bucket's all-reduce) and
+        goes on.  ``bucket_of[i]`` = bucket of parameter i (the plan's order), ``counts[b]`` = parameters in bucket b."""
+        key = (tuple(bucket_of), tuple(counts))
+        hit = self.__dict__.setdefault("_segments", {}).get(key)
+        if hit is not None:
+            return hit
+        left = list(counts)
+        segs, cur = [], []
+        for end, stream, ps in self.grad_ready:
+            cut = False
+            for i in ps:
+                cur.append((i, stream))
+                left[bucket_of[i]] -= 1
+                cut |= left[bucket_of[i]] == 0
+            if cut:
+                segs.append((end, cur))
+                cur = []
+        if cur or not segs or segs[-1][0] != self.n_bwd:
+            segs.append((self.n_bwd, cur))
+        self._segments[key] = segs
+        return segs
+
+
+class Plan(Programs):
+    """The compiled forward / backward programs of one ``AV_Wrapper`` for one input geometry and stream arrangement."""
+
+    def __init__(self, model, vshape, ashape, device, overlap_towers, trailing, group):
+        if not model.use_linear_proj:
+            raise Unsupported("no projection heads")
+        b = self._open(model, device, overlap_towers, trailing, group)
+        self.key = (tuple(vshape), tuple(ashape), overlap_towers, trailing, group)
+        self.vshape, self.ashape = tuple(vshape), tuple(ashape)
+        video = Sym((S_VIDEO, 0), vshape)
+        audio = Sym((S_AUDIO, 0), (ashape[0], ashape[1], 1, ashape[2], ashape[3]))   # [B,1,1,H,W]: T = kt = 1
+        A_S = ST_AUDIO if overlap_towers else ST_MAIN
+        # ------------------------------------------------------------------ forward
+        # the video stem first, then the audio tower starts on its own stream (beside conv2x.., not beside the stem:
+        # models/av_wrapper.py AUDIO_AFTER)
+        V, vfeat = self._video_with_audio(b, model, video, audio, A_S)
+        A = self._A
+        b.S = ST_MAIN
+        VH, self.vemb = b.head_fwd(model.video_proj, vfeat)
+        if A_S != ST_MAIN:
+            b.wait(ST_MAIN, A_S)
+        self.aemb = self._aemb
+        # ------------------------------------------------------------------ backward (autograd's order: the video
+        # tower from its head down to conv2x, the audio tower, the video stem last — sequence numbers of the forward)
+        self._backward_begins(b)
+        if A_S != ST_MAIN:
+            b.wait(A_S, ST_MAIN)                      # the criterion's gradients (and the transposed weights)
+        dv = b.head_bwd(VH, (S_DV, 0))
+        dh = b.video_bwd(V, dv)
+        b.S = A_S
+        da = b.head_bwd(self._AH, (S_DA, 0))
+        b.audio_bwd(A, da)
+        # Everything but the video stem's three parameters has its gradient here: the engine's optimizer can update those
+        # (nearly all of the 134 MB) on the fourth stream WHILE the stem's backward — one LDS-bound full-chip kernel of
+        # 0.57 ms on the trailing stream, the step's last — still runs (parallel.TrainStep.step; the HBM-bound Adam pass and
+        # that kernel overlap).  The fourth stream waits here for the three streams that hold those gradients.
+        for S in (ST_MAIN, ST_AUDIO):
+            b.S = S
+            b.flush_group(S)
+        b.S = ST_MAIN
+        if trailing and A_S != ST_MAIN:
+            stem_conv, stem_bn = model.video_model.conv1[0], model.video_model.conv1[1]
+            idx = sorted(b.pindex[id(p)] for p in (stem_conv.weight, stem_bn.weight, stem_bn.bias))
+            n = len(b.params)
+            if idx == [n - 3, n - 2, n - 1]:                   # (the engine's flat layout: parameters in reverse order)
+                for S in (ST_MAIN, A_S, ST_TRAIL):
+                    b.wait(ST_COMM, S)
+                self.adam_early = b.goff[n - 3]
+        b.video_stem_bwd(V, dh)
+        self._close(b, A_S)
+
+    def _video_with_audio(self, b, model, video, audio, A_S):
+        """The video tower with the audio tower (and its head) started behind the video stem on stream A_S."""
+        def start_audio():
+            S0 = b.S
+            if A_S != ST_MAIN:
+                b.wait(A_S, ST_MAIN)
+            b.S = A_S
+            self._A, afeat = b.audio_fwd(model.audio_model, audio)
+            self._AH, self._aemb = b.head_fwd(model.audio_proj, afeat)
+            b.S = S0
+        return b.video_fwd(model.video_model, video, after_stem=start_audio)
+
+    def forward(self, video, audio, grad_flat, zero_grad):
+        """Issue the forward program; returns (v_emb, a_emb, arena)."""
+        fa = self._forward_arena(grad_flat, zero_grad, (video, audio, None, None))
+        self._run(self.fwd_prog, 0, self.n_fwd)
         B = self.vshape[0]
         D = self.vemb.shape[1]
         ve = fa[self.vemb.ref[1]:self.vemb.ref[1] + 4 * B * D].view(torch.float32).view(B, D)
         ae = fa[self.aemb.ref[1]:self.aemb.ref[1] + 4 * B * D].view(torch.float32).view(B, D)
         return ve, ae, fa
-
-    def backward(self, fa, video, audio, dv, da, grad_flat, begin=0, end=None, ba=None):
-        dev = self.device
-        if ba is None:
-            ba = torch.empty(self.ba_bytes, dtype=torch.uint8, device=dev)
-        self._fill_slots(fa, ba, grad_flat, video, audio, dv, da)
-        self._streams()
-        lib.call("avid_program_run", self.bwd_prog, begin, self.n_bwd if end is None else end, self.slots, self.n_slots,
-                 self.streams, self.ws_arr, 4)
-        return ba
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -782,6 +819,21 @@ def _engine_flat(eng, pl):
     return flat.grad if ok[1] else None
 
 
+def _remember(ctx, pl, fa, params):
+    ctx.pl, ctx.fa, ctx.params = pl, fa, params
+    ctx.versions = sum(p._version for p in params)
+
+
+def _check_backward(ctx):
+    """The guards of a backward pass through a launch program: the forward's activations are still there, and no parameter
+    the programs read was modified in place since."""
+    if ctx.fa is None:
+        raise RuntimeError("avid_hip.plan: backward through the same forward pass a second time (its activations "
+                           "were released)")
+    if sum(p._version for p in ctx.params) != ctx.versions:
+        raise RuntimeError("avid_hip.plan: a parameter was modified in place between the forward and the backward pass")
+
+
 class NetFn(torch.autograd.Function):
     """(video, audio) -> (video_emb, audio_emb): models/av_wrapper.py:50-61 with both towers, both heads and all of
     their backward as two launch programs."""
@@ -791,90 +843,94 @@ class NetFn(torch.autograd.Function):
         eng = _ENGINE
         gflat = _engine_flat(eng, pl) if eng is not None else None
         ve, ae, fa = pl.forward(video, audio, gflat, zero_grad=gflat is not None)
-        ctx.pl, ctx.fa, ctx.video, ctx.audio = pl, fa, video, audio
+        _remember(ctx, pl, fa, params)
+        ctx.video, ctx.audio = video, audio
         ctx.in_engine = gflat is not None
         # the engine of THIS forward pass: the reference's loop calls loss.backward() itself, outside any `with plan.engine`
         # (parallel.DistributedDataParallel), and the gradients still have to land in the flat buffer this forward zeroed
         ctx.eng = eng if gflat is not None else None
-        ctx.versions = sum(p._version for p in params)
-        ctx.params = params
         return ve, ae
 
     @staticmethod
     def backward(ctx, dv, da):
+        _check_backward(ctx)
         pl, params = ctx.pl, ctx.params
-        if ctx.fa is None:
-            raise RuntimeError("avid_hip.plan: backward through the same forward pass a second time (its activations "
-                               "were released)")
-        if sum(p._version for p in params) != ctx.versions:
-            raise RuntimeError("avid_hip.plan: a parameter was modified in place between the forward and the backward pass")
-        dv, da = dv.contiguous(), da.contiguous()
+        inputs = (ctx.video, ctx.audio, dv.contiguous(), da.contiguous())
         eng = ctx.eng
         gflat = _engine_flat(eng, pl) if eng is not None else None
         if gflat is not None:
-            eng._plan_backward(pl, ctx.fa, ctx.video, ctx.audio, dv, da)
+            eng._plan_backward(pl, ctx.fa, inputs)
             ctx.fa = None
             return (None, None, None) + (None,) * len(params)
         g = torch.empty(pl.gnumel, dtype=torch.float32, device=dv.device)
-        pl.backward(ctx.fa, ctx.video, ctx.audio, dv, da, g)
+        pl.backward(ctx.fa, inputs, g)
         ctx.fa = None
         views = pl.grad_views(g)
         return (None, None, None) + tuple(views[id(p)] for p in params)
 
 
-def _plan_grad_views(self, g):
-    out = {}
-    for p, o in zip(self.params, self.goff):
-        out[id(p)] = g[o:o + p.numel()].as_strided(p.shape, p.stride())
-    return out
+def _cached(model, name, make):
+    """``model.__dict__[name]``, made by ``make()`` on first use (the module / parameter lists the per-call checks walk)."""
+    v = model.__dict__.get(name)
+    if v is None:
+        v = model.__dict__[name] = make()
+    return v
 
 
-Plan.grad_views = _plan_grad_views
-
-
-def _plan_segments(self, bucket_of, counts):
-    """Cut the backward program where a gradient bucket becomes complete: [(end record, [(param index, stream)])] —
-    the engine runs the records up to ``end``, reports those gradients (which launches the bucket's all-reduce) and
-    goes on.  ``bucket_of[i]`` = bucket of parameter i (the plan's order), ``counts[b]`` = parameters in bucket b."""
-    key = (tuple(bucket_of), tuple(counts))
-    hit = self.__dict__.setdefault("_segments", {}).get(key)
-    if hit is not None:
-        return hit
-    left = list(counts)
-    segs, cur = [], []
-    for end, stream, ps in self.grad_ready:
-        cut = False
-        for i in ps:
-            cur.append((i, stream))
-            left[bucket_of[i]] -= 1
-            cut |= left[bucket_of[i]] == 0
-        if cut:
-            segs.append((end, cur))
-            cur = []
-    if cur or not segs or segs[-1][0] != self.n_bwd:
-        segs.append((self.n_bwd, cur))
-    self._segments[key] = segs
-    return segs
-
-
-Plan.segments = _plan_segments
-
-
-def eligible(model, video, audio):
-    """The launch-program path applies: training step on the GPU through the stock module tree, nothing hooked."""
-    if not ENABLED or not (model.training and torch.is_grad_enabled() and video.is_cuda and audio.is_cuda):
-        return False
-    if video.dtype != torch.float32 or audio.dtype != torch.float32 or video.dim() != 5 or audio.dim() != 4:
-        return False
-    if torch.cuda.is_current_stream_capturing():
-        return False
-    mods = model.__dict__.get("_avid_modules")
-    if mods is None:
-        mods = model.__dict__["_avid_modules"] = list(model.modules())
-    for m in mods:
+def _tree_ok(model):
+    """Every module in training mode and none hooked (a hook on any of them sends the call to the per-layer path, where
+    each module's own ``__call__`` runs its hooks)."""
+    for m in _cached(model, "_avid_modules", lambda: list(model.modules())):
         if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks or not m.training:
             return False
     return True
+
+
+def eligible(model, *inputs, need_grad=True):
+    """The launch-program path applies: a training call (gradients on, unless ``need_grad`` is False: ``FinetuneStep`` runs
+    the programs itself) on float32 GPU inputs — video [B,3,T,H,W], then audio [B,1,F,T] if the model has one — through
+    the stock module tree, nothing hooked, no graph being captured."""
+    if not ENABLED or not model.training or (need_grad and not torch.is_grad_enabled()):
+        return False
+    if not all(x.is_cuda and x.dtype == torch.float32 and x.dim() == rank for x, rank in zip(inputs, (5, 4))):
+        return False
+    if torch.cuda.is_current_stream_capturing():
+        return False
+    return _tree_ok(model)
+
+
+def _bn_identity(model):
+    """The identity of the BatchNorm buffers a compiled plan's slot table points at: the address of the model's flat buffer
+    when it keeps one (``AV_Wrapper._bn_flat``: the buffers are re-seated as its views), else every buffer's address
+    (`.to()` / `.cuda()` re-create them)."""
+    flat = getattr(model, "_bn_flat", None)
+    if flat is not None:
+        return flat.data_ptr()
+    return tuple(b.data_ptr() for m in _cached(model, "_avid_modules", lambda: list(model.modules()))
+                 for b in m._buffers.values() if b is not None)
+
+
+def _plan_for(model, key, make):
+    """The model's compiled plan for ``key`` (``make()`` compiles it on first use), or None: the caller takes the per-layer
+    path.  (what a compiled plan froze besides shapes and switches — which parameters take gradients, their dtype,
+    and the identity of the BatchNorm buffers its slot table points at: parameters frozen after the first step, `.double()`,
+    `.cpu().cuda()` must not meet a stale program.  ~20 us per call for 141 parameters.)"""
+    fp, dt_ok = 0, True
+    for p in _cached(model, "_avid_param_list", lambda: list(model.parameters())):
+        fp = (fp << 1) | int(p.requires_grad)
+        dt_ok = dt_ok and p.dtype == torch.float32 and p.is_cuda
+    if not dt_ok:
+        return None
+    key += (bool(ops.GROUP_WGRAD), ops.FUSE_BN_BWD, ops.wino_epoch(), fp, _bn_identity(model))
+    plans = model.__dict__.setdefault("_avid_plans", {})
+    pl = plans.get(key)
+    if pl is None:
+        try:
+            pl = make()
+        except Unsupported:
+            pl = False
+        plans[key] = pl
+    return pl or None
 
 
 def run(model, video, audio):
@@ -887,33 +943,10 @@ def run(model, video, audio):
     overlap = (not timing) and os.environ.get("AVID_OVERLAP_TOWERS", "1") == "1" and (eng is None or model.overlap_towers)
     trailing = (not timing) and bool(ops.DEFER_WGRAD) and (eng is None or eng._defer_ok())
     video, audio = video.contiguous(), audio.contiguous()
-    # (what a compiled Plan froze besides shapes and switches — which parameters take gradients, their dtype, and
-    #  the identity of the BatchNorm buffers its slot table points at: parameters frozen after the first step, `.double()`,
-    #  `.cpu().cuda()` must not meet a stale program.  ~20 us per call for 141 parameters.)
-    mods = model.__dict__.get("_avid_param_list")
-    if mods is None:
-        mods = model.__dict__["_avid_param_list"] = list(model.parameters())
-    fp, dt_ok = 0, True
-    for p in mods:
-        fp = (fp << 1) | int(p.requires_grad)
-        dt_ok = dt_ok and p.dtype == torch.float32 and p.is_cuda
-    if not dt_ok:
-        return None
-    flat = getattr(model, "_bn_flat", None)
-    key = (tuple(video.shape), tuple(audio.shape), video.device.index, overlap, trailing, bool(ops.GROUP_WGRAD),
-           ops.FUSE_BN_BWD, ops.wino_epoch(), fp, flat.data_ptr() if flat is not None else 0)
-    plans = model.__dict__.setdefault("_avid_plans", {})
-    pl = plans.get(key)
-    if pl is not None and pl is not False and eng is not None and _engine_flat(eng, pl) is None:
-        return None                                   # (the engine's gradient buffer is laid out differently)
-    if pl is None:
-        try:
-            pl = Plan(model, video.shape, audio.shape, video.device, overlap, trailing, bool(ops.GROUP_WGRAD))
-        except Unsupported:
-            pl = False
-        plans[key] = pl
-    if pl is False:
-        return None
+    pl = _plan_for(model, (tuple(video.shape), tuple(audio.shape), video.device.index, overlap, trailing),
+                   lambda: Plan(model, video.shape, audio.shape, video.device, overlap, trailing, bool(ops.GROUP_WGRAD)))
+    if pl is None or (eng is not None and _engine_flat(eng, pl) is None):
+        return None                                   # (or the engine's gradient buffer is laid out differently)
     return NetFn.apply(video, audio, pl, *pl.params_fwd)
 
 
@@ -948,7 +981,7 @@ def _i32(v):
     return v - (1 << 32) if v >= (1 << 31) else v
 
 
-class ClsPlan(Plan):
+class ClsPlan(Programs):
     """The compiled programs of one ``ClassificationWrapper`` around this package's ``R2Plus1D`` for one clip geometry.
 
     Forward: the tower (``Builder.video_fwd``), dropout, the classifier (``avid_cls_linear_fwd``: any number of classes)
@@ -965,27 +998,16 @@ class ClsPlan(Plan):
         cls = model.classifier
         if type(cls) is not ClsLinear or (model.use_dropout and type(model.dropout) is not HipDropout):
             raise Unsupported("classifier / dropout")
-        params = [p for p in model.parameters()]
-        dry = device.type != "cuda"
-        if not all(p.requires_grad and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
-            raise Unsupported("frozen / non-fp32 parameters")
-        b = Builder(device, False, trailing, group)
-        b.set_params(params)
-        self.device = device
+        b = self._open(model, device, False, trailing, group)
         self.classifier_only = classifier_only
         self.key = (tuple(vshape), trailing, group, classifier_only)
+        self.vshape, self.ashape = tuple(vshape), None
         self.p = float(model.dropout.p) if model.use_dropout else 0.0
-        # ------------------------------------------------------------------ forward
-        b.cur = b.fwd
-        helper = ST_TRAIL if trailing else ST_MAIN
-        if trailing:
-            b.wait(helper, ST_MAIN)
-        self._zero_index = len(b.fwd)
         # (parameters in reverse order: the classifier's bias and weight lead the gradient buffer)
         self.n_cls = b.goff[2] if len(b.params) > 2 else b.gnumel
-        b.emit(OP_MEMSET0, stream=helper, n=(4 * (self.n_cls if classifier_only else b.gnumel),), t=((S_GRAD, 0),))
-        self._wt_rec = b.emit(OP_WT_BATCH, stream=helper, i=(0,), n=(0,), t=((S_AUX, 0),))
-        b.S = ST_MAIN
+        if classifier_only:
+            b.fwd[self._zero_index].n[0] = 4 * self.n_cls
+        # ------------------------------------------------------------------ forward
         V, feat = b.video_fwd(model.feature_extractor, Sym((S_VIDEO, 0), vshape))
         B, Fd = feat.shape
         self.drop_index = None
@@ -1004,12 +1026,8 @@ class ClsPlan(Plan):
         self.n_logits = len(b.fwd)
         b.emit(OP_CLS_LOSS, i=(B, 1, self.n_classes), f=(1.0,),
                t=(self.logits.ref, (S_LABELS, 0), (S_OUT, 0), None, (S_OUT, 8), (S_DLOGITS, 0), self._err_ref(b, device)))
-        self.n_fwd = len(b.fwd)
         # ------------------------------------------------------------------ backward
-        b.cur = b.bwd
-        if trailing:
-            b.wait(ST_MAIN, helper)
-        b.S = ST_MAIN
+        self._backward_begins(b)
         dlog = (S_DLOGITS, 0)
         dx = None if classifier_only else b.ba.alloc(4 * B * Fd)
         b.emit(OP_CLS_LINEAR_BWD, i=(B, Fd, C), t=(feat.ref, b.ext(cls.weight), dlog, dx, b.grad(cls.weight), b.grad(cls.bias)))
@@ -1022,14 +1040,7 @@ class ClsPlan(Plan):
             dh = b.video_bwd(V, dx)
             b.flush_group(ST_MAIN)
             b.video_stem_bwd(V, dh)
-        b.flush_group(ST_MAIN)
-        for tr in sorted(b.trail_used):
-            b.wait(ST_MAIN, tr)
-        self.n_bwd = len(b.bwd)
-        self.adam_early = None
-        self._finalize(b, device)
-        self.params_fwd = params
-        self.vshape, self.ashape = tuple(vshape), None
+        self._close(b)
 
     @staticmethod
     def _err_ref(b, device):
@@ -1040,12 +1051,7 @@ class ClsPlan(Plan):
     def forward(self, video, grad_flat, zero_grad, seed=0, offset=0, labels=None, out=None, dlogits=None, grad_scale=1.0):
         """Issue the forward program — with ``labels`` also the loss record, which writes ``out`` (OUT_BYTES: loss, hits)
         and ``dlogits``; returns (logits, arena)."""
-        dev = self.device
-        self._refresh_table()
-        fa = torch.empty(self.fa_bytes, dtype=torch.uint8, device=dev)
-        self._fill_slots(fa, None, grad_flat, video, labels, dlogits, out)
-        self._streams()
-        self.fwd_prog[self._zero_index].op = OP_MEMSET0 if (zero_grad and grad_flat is not None) else 0
+        fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out))
         if self.drop_index is not None:
             r = self.fwd_prog[self.drop_index]
             r.i[1], r.i[2], r.n[1] = _i32(seed), _i32(seed >> 32), int(offset)
@@ -1053,20 +1059,10 @@ class ClsPlan(Plan):
         if labels is not None:
             self.fwd_prog[self.n_logits].f[0] = float(grad_scale)
             end = self.n_fwd
-        lib.call("avid_program_run", self.fwd_prog, 0, end, self.slots, self.n_slots, self.streams, self.ws_arr, 4)
+        self._run(self.fwd_prog, 0, end)
         B, C = self.vshape[0], self.n_classes
         off = self.logits.ref[1]
         return fa[off:off + 4 * B * C].view(torch.float32).view(B, C), fa
-
-    def backward(self, fa, video, dlogits, grad_flat, begin=0, end=None, ba=None):
-        dev = self.device
-        if ba is None:
-            ba = torch.empty(self.ba_bytes, dtype=torch.uint8, device=dev)
-        self._fill_slots(fa, ba, grad_flat, video, None, dlogits, None)
-        self._streams()
-        lib.call("avid_program_run", self.bwd_prog, begin, self.n_bwd if end is None else end, self.slots, self.n_slots,
-                 self.streams, self.ws_arr, 4)
-        return ba
 
 
 class ClsFn(torch.autograd.Function):
@@ -1076,82 +1072,34 @@ class ClsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, video, pl, seed, offset, *params):
         logits, fa = pl.forward(video, None, False, seed, offset)
-        ctx.pl, ctx.fa, ctx.video = pl, fa, video
-        ctx.versions = sum(p._version for p in params)
-        ctx.params = params
+        _remember(ctx, pl, fa, params)
+        ctx.video = video
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
+        _check_backward(ctx)
         pl, params = ctx.pl, ctx.params
-        if ctx.fa is None:
-            raise RuntimeError("avid_hip.plan: backward through the same forward pass a second time (its activations "
-                               "were released)")
-        if sum(p._version for p in params) != ctx.versions:
-            raise RuntimeError("avid_hip.plan: a parameter was modified in place between the forward and the backward pass")
         g = torch.empty(pl.gnumel, dtype=torch.float32, device=dlogits.device)
-        pl.backward(ctx.fa, ctx.video, dlogits.contiguous(), g)
+        pl.backward(ctx.fa, (ctx.video, None, dlogits.contiguous(), None), g)
         ctx.fa = None
         views = pl.grad_views(g)
         return (None, None, None, None) + tuple(views[id(p)] for p in params)
 
 
-def _cls_tree_ok(model):
-    """Every module in training mode and none hooked (a hook on any of them — the classifier included — sends the call to
-    the per-layer path, where each module's own ``__call__`` runs its hooks)."""
-    mods = model.__dict__.get("_avid_modules")
-    if mods is None:
-        mods = model.__dict__["_avid_modules"] = list(model.modules())
-    for m in mods:
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks or not m.training:
-            return False
-    return True
-
-
-def _cls_eligible(model, video, need_grad=True):
-    if not ENABLED or not (model.training and video.is_cuda) or (need_grad and not torch.is_grad_enabled()):
-        return False
-    if video.dtype != torch.float32 or video.dim() != 5 or torch.cuda.is_current_stream_capturing():
-        return False
-    return _cls_tree_ok(model)
-
-
 def cls_plan(model, video, classifier_only=False, need_grad=True):
-    """The cached ``ClsPlan`` of this call (same cache key and staleness rules as ``run``), or None: the caller takes the
-    per-layer path."""
-    if not _cls_eligible(model, video, need_grad):
+    """The cached ``ClsPlan`` of this call (same staleness rules as ``run``), or None: the caller takes the per-layer path."""
+    if not eligible(model, video, need_grad=need_grad):
         return None
-    timing = lib.TIMING
-    trailing = (not timing) and bool(ops.DEFER_WGRAD)
-    mods = model.__dict__.get("_avid_param_list")
-    if mods is None:
-        mods = model.__dict__["_avid_param_list"] = list(model.parameters())
-    fp, dt_ok = 0, True
-    for p in mods:
-        fp = (fp << 1) | int(p.requires_grad)
-        dt_ok = dt_ok and p.dtype == torch.float32 and p.is_cuda
-    if not dt_ok:
-        return None
+    trailing = (not lib.TIMING) and bool(ops.DEFER_WGRAD)
     drop = model.dropout.p if model.use_dropout else 0.0
-    # (the BatchNorm buffers' addresses: `.to()` / `.cuda()` re-create them, FlatBuffers re-seats them — a cached plan holds
-    #  the tensors it was compiled with in its slot table)
-    bufs = tuple(b.data_ptr() for m in model.__dict__["_avid_modules"] for b in m._buffers.values() if b is not None)
-    key = ("cls", tuple(video.shape), video.device.index, trailing, bool(ops.GROUP_WGRAD), ops.FUSE_BN_BWD, ops.wino_epoch(),
-           fp, bool(classifier_only), drop, bufs)
-    plans = model.__dict__.setdefault("_avid_plans", {})
-    pl = plans.get(key)
-    if pl is None:
-        try:
-            pl = ClsPlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD), classifier_only)
-        except Unsupported:
-            pl = False
-        plans[key] = pl
-    return pl or None
+    return _plan_for(model, ("cls", tuple(video.shape), video.device.index, trailing, bool(classifier_only), drop),
+                     lambda: ClsPlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD), classifier_only))
 
 
 def run_cls(model, video):
     """``ClassificationWrapper.forward`` through the launch programs, or None (the caller takes the per-layer path)."""
-    if not _cls_eligible(model, video):
+    if not eligible(model, video):
         return None
     video = video.contiguous()
     pl = cls_plan(model, video)

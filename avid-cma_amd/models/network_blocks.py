@@ -92,6 +92,18 @@ class no_bn_handover:
 _FUSE_RES = os.environ.get("AVID_FUSE_RES", "1") == "1"
 
 
+def res_fusable(blk, numel):
+    """The residual convolution of a ``BasicR2P1DBlock`` whose input has ``numel`` elements can ride inside spt_conv1's op
+    (its input gradient stays on the sub-sampled grid and is added in spt_conv1's strided dgrad): strides of 1 / 2,
+    spt_conv1 itself strided, 32-bit offsets.  The per-layer path and the launch-program compiler (avid_hip/plan.py) both
+    take the fused form exactly when this holds."""
+    if not blk.res:
+        return False
+    rs, ss = blk.res_conv.stride3, blk.spt_conv1.stride3
+    return (_FUSE_RES and any(v == 2 for v in rs) and all(v in (1, 2) for v in rs)
+            and any(v == 2 for v in ss) and all(v in (1, 2) for v in ss) and numel * 4 < (1 << 31))
+
+
 def _conv_bn(conv, bn, x, addend=None, tap=False, sole=True, res=None):
     """ReLU(bn(conv(x) [+ addend])).  In training the conv epilogue hands the BatchNorm its batch statistics
     as partial sums, so the BN does not re-read the activation for them.  ``tap``: also return an alias of x
@@ -157,18 +169,9 @@ class BasicR2P1DBlock(nn.Module):
         else:
             self.res = False
 
-    def _res_fusable(self, x):
-        """The residual convolution can ride inside spt_conv1's op (its input gradient stays on the sub-sampled grid
-        and is added in spt_conv1's strided dgrad): strides of 1 / 2, spt_conv1 itself strided, 32-bit offsets."""
-        if not self.res:
-            return False
-        rs, ss = self.res_conv.stride3, self.spt_conv1.stride3
-        return (_FUSE_RES and any(v == 2 for v in rs) and all(v in (1, 2) for v in rs)
-                and any(v == 2 for v in ss) and all(v in (1, 2) for v in ss) and x.numel() * 4 < (1 << 31))
-
     def forward(self, x):
         tap = x.is_cuda and x.requires_grad and torch.is_grad_enabled()
-        if tap and self._res_fusable(x):
+        if tap and res_fusable(self, x.numel()):
             h, x_res = _conv_bn(self.spt_conv1, self.spt_bn1, x, res=(self.res_conv.weight, self.res_conv.stride3))
             h = _conv_bn(self.tmp_conv1, self.tmp_bn1, h)
             h = _conv_bn(self.spt_conv2, self.spt_bn2, h)

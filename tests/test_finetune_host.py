@@ -106,7 +106,7 @@ def test_classifier_only_backward_has_no_tower_convolutions(compiled):
     assert _ops(warm, warm.fwd_prog, warm.n_fwd) == _ops(full, full.fwd_prog, full.n_fwd)
 
 
-def test_hooked_pooled_or_other_features_fall_back():
+def test_hooked_eval_pooled_or_other_features_fall_back():
     from avid_hip import plan
     dev = torch.device("cpu")
     with pytest.raises(plan.Unsupported):
@@ -114,20 +114,20 @@ def test_hooked_pooled_or_other_features_fall_back():
     with pytest.raises(plan.Unsupported):
         plan.ClsPlan(_wrapper(feat_name="conv5x", feat_dim=512 * 7 * 7), SHAPES[0], dev, True, True)
     m = _wrapper()
-    assert plan._cls_eligible(m, torch.zeros(1, 3, 8, 16, 16)) is False                 # CPU tensor
+    assert plan.eligible(m, torch.zeros(1, 3, 8, 16, 16)) is False                      # CPU tensor
     # the module-tree rule (the device checks aside): any hook, on the classifier or inside the tower, or eval mode
-    assert plan._cls_tree_ok(m)
+    assert plan._tree_ok(m)
     for mod in (m.classifier, m.feature_extractor.conv3x[1].spt_bn1):
         for reg in (mod.register_forward_hook, mod.register_forward_pre_hook):
             h = reg(lambda *a: None)
-            assert not plan._cls_tree_ok(m), (type(mod).__name__, reg.__name__)
+            assert not plan._tree_ok(m), (type(mod).__name__, reg.__name__)
             h.remove()
-            assert plan._cls_tree_ok(m)
+            assert plan._tree_ok(m)
     h = m.classifier.register_full_backward_hook(lambda *a: None)
-    assert not plan._cls_tree_ok(m)
+    assert not plan._tree_ok(m)
     h.remove()
     m.eval()
-    assert not plan._cls_tree_ok(m)
+    assert not plan._tree_ok(m)
     assert plan.run_cls(m, torch.zeros(1, 3, 8, 16, 16)) is None                         # evaluation
     m.train()
     # the classifier is a module of its own type: hooks on it run on the per-layer path; anything else is not compiled
