@@ -1,10 +1,12 @@
-"""Test helpers shared by tests/test_bs64_table.py (host) and tests/test_gpu_bs64_layers.py (GPU).
+"""Test helpers shared by tests/test_bs64_table.py, tests/test_ft_table.py (host) and tests/test_gpu_bs64_layers.py,
+tests/test_gpu_ft_layers.py (GPU).
 
 * A float64 reference of one 3-D convolution — forward, input gradient, weight gradient — by explicit im2col and float64
   matmul over channels-last tensors [B,T,H,W,C].  It calls no avid_hip op (torch only), runs wherever its inputs live, and
   is chunked over clips so that a batch-64 layer never materialises its whole column matrix.
 * The convolution geometries of the benchmark's batch-64 step, read from the compiled launch programs (avid_hip/plan.py,
-  compiled on the host), with what the step fuses into each: the layer table the batch-64 tests run.
+  compiled on the host), with what the step fuses into each: the layer table the batch-64 tests run.  The same trace of the
+  fine-tuning programs (plan.ClsPlan) at the two shipped per-GPU clip shapes: the tables tests/test_gpu_ft_layers.py runs.
 * A float64 reference of training-mode BatchNorm (+ReLU): forward, backward and the running-statistics update.
 * Every other launch of the same programs — BatchNorm, the stem's BatchNorm + max-pool, global max-pool, the heads' ReLU
   backward and bias sums — and the flat Adam buffer with its split: the table tests/test_gpu_bs64_norm.py runs."""
@@ -20,6 +22,11 @@ NORM_TABLE_PATH = os.path.join(HERE, "golden", "bs64_norm_ops.json")
 MODEL = 'av_wrapper("R2Plus1D", {"depth": 18}, "Conv2D", {"depth": 10}, proj_dim=[512, 512, 128])'
 BENCH_VIDEO = (64, 3, 8, 112, 112)
 BENCH_AUDIO = (64, 1, 40, 100)
+FT_TABLE_PATH = os.path.join(HERE, "golden", "ft_conv_layers.json")
+FT_MODEL = ('ClassificationWrapper(R2Plus1D(18), 101, feat_name="pool", feat_dim=512, pooling_op=None, use_dropout=True, '
+            'dropout=0.5)')
+# the per-GPU clip shapes of the shipped fine-tuning configs, by the key of their table in the fixture
+FT_SHAPES = {"8x8x224": (8, 3, 8, 224, 224), "4x32x224": (4, 3, 32, 224, 224)}
 
 
 # ---- float64 reference ----------------------------------------------------------------------------------------------
@@ -111,17 +118,14 @@ def _bs64_plan():
     return plan.Plan(m, BENCH_VIDEO, BENCH_AUDIO, torch.device("cpu"), True, True, True)
 
 
-def trace_bs64_table():
-    """Every distinct convolution geometry of the benchmark's batch-64 step (the launch programs of
-    models.av_wrapper("R2Plus1D", {"depth": 18}, "Conv2D", {"depth": 10}, proj_dim=[512, 512, 128]) at the benchmark's
-    input shapes), each with what the step does with it:
+def trace_conv_table(pl):
+    """Every distinct convolution geometry of a compiled plan's launch programs, each with what the programs do with it:
       fwd: list of epilogue forms [addend, bn_stats, bias, relu, in_affine] the forward launches use;
       dgrad: list of forms [bn_bwd_sums, addend, st, sh, sw] — (st, sh, sw): the strides of a compact addend (the gradient
         of the block's strided 1x1x1 residual convolution of the same input), 0 0 0 for a dense one or none;
       wgrad: "own", "grouped" or "in_affine" launches;
-    and "groups": the table indices of the items of each grouped weight-gradient launch, in program order."""
+    and the table indices of the items of each grouped weight-gradient launch, in program order: (layers, groups)."""
     from avid_hip import plan
-    pl = _bs64_plan()
     table, index = [], {}
 
     def entry(d):
@@ -160,11 +164,42 @@ def trace_bs64_table():
             groups.append(members)
             k += r.i[0]
         k += 1
+    return table, groups
+
+
+def trace_bs64_table():
+    """The convolution table (trace_conv_table) of the benchmark's batch-64 step: the launch programs of
+    models.av_wrapper("R2Plus1D", {"depth": 18}, "Conv2D", {"depth": 10}, proj_dim=[512, 512, 128]) at the benchmark's
+    input shapes."""
+    table, groups = trace_conv_table(_bs64_plan())
     return {"model": MODEL, "video": list(BENCH_VIDEO), "audio": list(BENCH_AUDIO), "layers": table, "groups": groups}
 
 
 def load_bs64_table():
     with open(TABLE_PATH) as f:
+        return json.load(f)
+
+
+# ---- the fine-tuning programs' layer tables -------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def ft_plan(shape):
+    """The full-mode launch programs of the shipped fine-tuning configs' wrapper at one per-GPU clip shape, compiled on
+    the host."""
+    import models
+    from avid_hip import plan
+    m = models.ClassificationWrapper(models.R2Plus1D(18), 101, feat_name="pool", feat_dim=512, pooling_op=None,
+                                     use_dropout=True, dropout=0.5).train()
+    return plan.ClsPlan(m, tuple(shape), torch.device("cpu"), True, True, False)
+
+
+def trace_ft_table(shape):
+    """The convolution table (trace_conv_table) of the fine-tuning programs at one of FT_SHAPES' clip shapes."""
+    table, groups = trace_conv_table(ft_plan(tuple(shape)))
+    return {"model": FT_MODEL, "video": list(shape), "layers": table, "groups": groups}
+
+
+def load_ft_tables():
+    with open(FT_TABLE_PATH) as f:
         return json.load(f)
 
 

@@ -18,7 +18,10 @@ see there.  ``pytest -s`` prints the measured error of every geometry and direct
 
 Which kernels serve each direction is pinned per entry (tests/golden/bs64_conv_kernels.json, recorded on an MI355X under the
 default dispatch): a silent dispatch change fails here, and test_layer_table_covers_the_steps_convolution_kernels keeps the
-table complete against a real step."""
+table complete against a real step.
+
+The checks themselves (check_layer, check_in_affine, check_group) take the table entry and the pinned kernels as arguments:
+tests/test_gpu_ft_layers.py runs the fine-tuning programs' tables through the same code."""
 import json
 import os
 import ctypes as C
@@ -36,8 +39,10 @@ with open(os.path.join(R.HERE, "golden", "bs64_conv_kernels.json")) as _f:
     KERNELS = json.load(_f)
 N_GEOMETRIES = 32
 CONV_FAMILIES = ("igemm_pk_kernel", "wino", "tconv64", "twgrad64", "stem_", "wgrad_", "splitk_reduce")
-SIX_PRODUCT = ("igemm_pk_kernel", "stem_fwd3p_kernel", "stem_wgrad3_kernel", "tconv64_kernel", "twgrad64_kernel",
-               "wino2p_kernel", "wgrad_tab_kernel")
+# (stem_fwd3_kernel: the video stem's forward where the pre-split patch of stem_fwd3p_kernel does not fit — the 224 x 224 clips
+# of tests/test_gpu_ft_layers.py; the same six products)
+SIX_PRODUCT = ("igemm_pk_kernel", "stem_fwd3_kernel", "stem_fwd3p_kernel", "stem_wgrad3_kernel", "tconv64_kernel",
+               "twgrad64_kernel", "wino2p_kernel", "wgrad_tab_kernel")
 # kernels that only add up slabs a product kernel wrote (no products of their own): left out when the family is decided
 REDUCE = ("splitk_reduce", "wgrad_reduce", "wgrad_group_reduce", "stem_wgrad_reduce")
 # Weight gradients whose rms error against float64 is above RMS_BAR because the contraction itself is long — RMS_BAR was set
@@ -173,9 +178,9 @@ def _check(tag, name, got, want, bar, kernels, results, fp32=None):
         assert rms <= RMS_BAR, (tag, name, rms)
 
 
-def _expect_kernels(name, key, ks):
-    """The kernels that served one direction are the ones pinned for it."""
-    want = KERNELS["layers"][name][key] if name is not None else key
+def _expect_kernels(pins, name, key, ks):
+    """The kernels that served one direction are the ones pinned for it (``pins``: a table's pinned-kernels file)."""
+    want = pins["layers"][name][key] if name is not None else key
     assert ks == want, (name, key, ks, want)
 
 
@@ -210,17 +215,17 @@ def test_table_has_every_geometry():
     assert all(e["fwd"] or e["dgrad"] for e in LAYERS)
 
 
-@pytest.mark.parametrize("idx", range(len(LAYERS)), ids=[R.layer_id(e) for e in LAYERS])
-def test_layer_against_float64(idx, gpu_device, kernel_log):
+def check_layer(e, idx, pins, dev, kernel_log, long_wgrad=(), chunk=8):
+    """One table entry in every form the programs use, against float64 and the pinned kernels (the module docstring's
+    checks).  ``long_wgrad``: the ids whose weight gradient is held to 3x float32 (LONG_WGRAD's rule); ``chunk``: clips per
+    slice of the float64 reference."""
     from avid_hip import ops
-    dev = gpu_device
-    e = LAYERS[idx]
     name = R.layer_id(e)
     d = _desc(e)[0]
     x, w, dy = _inputs(e, dev, 1000 + idx)
     x_cl = x.permute(0, 2, 3, 4, 1) if e["channel_first"] else x
     want = tuple(n for n, use in (("y", e["fwd"]), ("dx", e["dgrad"]), ("dw", e["wgrad"])) if use)
-    ref = R.conv_ref(x_cl, w, tuple(e["stride"]), tuple(e["pad"]), dy=dy, want=want)
+    ref = R.conv_ref(x_cl, w, tuple(e["stride"]), tuple(e["pad"]), dy=dy, want=want, chunk=chunk)
     res = []
     print(f"\n{name}: fwd {e['fwd']} dgrad {e['dgrad']} wgrad {e['wgrad']}")
     g = _gen(dev, 2000 + idx)
@@ -240,7 +245,7 @@ def test_layer_against_float64(idx, gpu_device, kernel_log):
             yd = y.double().reshape(-1, e["Cout"])
             _check_sums("fwd bn sums", name, stats[:, 0], yd, res)
             _check_sums("fwd bn squares", name, stats[:, 1], yd * yd, res)
-        _expect_kernels(name, _form_key("fwd", form), ks)
+        _expect_kernels(pins, name, _form_key("fwd", form), ks)
     for form in e["dgrad"]:
         bn_sums, has_add = form[:2]
         strided = any(form[2:])
@@ -266,11 +271,13 @@ def test_layer_against_float64(idx, gpu_device, kernel_log):
             dx = _dgrad(e, dy, w, addend=addend, add_stride=add_stride, fuse=fuse)
         ks = conv_names(log.report)
         _check(f"dgrad{form}", name, dx, want_dx, BAR["dx"], ks, res)
-        _expect_kernels(name, _form_key("dgrad", form), ks)
+        _expect_kernels(pins, name, _form_key("dgrad", form), ks)
         if bn_sums:
-            # sum dy_m and sum dy_m * xhat over all rows, dy_m = the device's own dx masked by the producer's ReLU
+            # sum dy_m and sum dy_m * xhat over all rows, dy_m = the device's own dx masked by the producer's ReLU: the sign of
+            # fma(x, scale, shift), which float64 gives exactly (a float32 multiply-then-add rounds twice and flips about one
+            # element in 25 million, a whole term of the sum)
             xbd = xb.double().reshape(-1, e["Cin"])
-            mask = (torch.addcmul(shift, xb, scale).reshape(-1, e["Cin"]) > 0).double()
+            mask = ((xbd * scale.double() + shift.double()) > 0).double()
             dym = dx.double().reshape(-1, e["Cin"]) * mask
             xhat = (xbd - mean.double()) * invstd.double()
             _check_sums("dgrad bn-bwd sum dy", name, part[:, 0], dym, res)
@@ -280,15 +287,21 @@ def test_layer_against_float64(idx, gpu_device, kernel_log):
             dw = _wgrad(e, x, dy, w)
         ks = conv_names(log.report)
         fp32 = None
-        if name in LONG_WGRAD:
+        if name in long_wgrad:
             fp32 = lambda: R.conv_ref(x_cl, w, tuple(e["stride"]), tuple(e["pad"]), dy=dy, want=("dw",),  # noqa: E731
-                                      dtype=torch.float32)["dw"]
+                                      chunk=chunk, dtype=torch.float32)["dw"]
         _check("wgrad", name, dw, ref["dw"], BAR["dw"], ks, res, fp32=fp32)
-        _expect_kernels(name, "wgrad", ks)
+        _expect_kernels(pins, name, "wgrad", ks)
+    return res
 
 
-def _conv2x_temporal():
-    es = [e for e in LAYERS if any(f[4] for f in e["fwd"])]
+@pytest.mark.parametrize("idx", range(len(LAYERS)), ids=[R.layer_id(e) for e in LAYERS])
+def test_layer_against_float64(idx, gpu_device, kernel_log):
+    check_layer(LAYERS[idx], idx, KERNELS, gpu_device, kernel_log, long_wgrad=LONG_WGRAD)
+
+
+def _conv2x_temporal(layers=LAYERS):
+    es = [e for e in layers if any(f[4] for f in e["fwd"])]
     assert len(es) == 1
     return es[0]
 
@@ -299,11 +312,18 @@ def test_conv2x_temporal_layer_in_the_programs_form(relu, gpu_device, kernel_log
     BatchNorm (+ReLU) in front applied while staging): against float64 of conv(relu(x * scale + shift)) with negative scales,
     with and without the residual addend, BatchNorm partial sums included; bit-identical to the same layer reading the
     normalised tensor; tconv64_kernel / twgrad64_kernel under the default dispatch; the in-affine launch counter moves."""
-    from avid_hip import lib, ops
-    dev = gpu_device
     e = _conv2x_temporal()
-    name = R.layer_id(e)
     assert e["x"] == [64, 8, 28, 28] and e["Cin"] == e["Cout"] == 64 and e["wgrad"] == ["in_affine"]
+    assert R.layer_id(e) in LONG_WGRAD
+    check_in_affine(e, relu, KERNELS, gpu_device, kernel_log, long_wgrad=LONG_WGRAD)
+
+
+def check_in_affine(e, relu, pins, dev, kernel_log, long_wgrad=(), chunk=8):
+    """A 64-channel temporal layer in the in-affine forms of the programs (the checks of
+    test_conv2x_temporal_layer_in_the_programs_form), against float64 and the pinned kernels."""
+    from avid_hip import lib, ops
+    name = R.layer_id(e)
+    assert e["Cin"] == e["Cout"] == 64
     stride, pad = tuple(e["stride"]), tuple(e["pad"])
     x, w, dy = _inputs(e, dev, 77)
     xb = _bn_producer(e, dev, 78)[0]
@@ -317,7 +337,7 @@ def test_conv2x_temporal_layer_in_the_programs_form(relu, gpu_device, kernel_log
     zd = xb.double() * scale.double() + shift.double()
     if relu:
         zd = zd.clamp_min(0)
-    ref = R.conv_ref(zd, w, stride, pad, dy=dy, want=("y", "dw"))
+    ref = R.conv_ref(zd, w, stride, pad, dy=dy, want=("y", "dw"), chunk=chunk)
     count = lib.raw("avid_debug_in_affine_launches")
     add = torch.randn(tuple(ref["y"].shape), generator=_gen(dev, 79), device=dev)
     res = []
@@ -331,7 +351,7 @@ def test_conv2x_temporal_layer_in_the_programs_form(relu, gpu_device, kernel_log
         assert (count(1) - before[0], count(0) - before[1]) == (1, 0)
         ks = conv_names(log.report)
         assert log.launches("tconv64_kernel<0>") == 1
-        _expect_kernels(None, KERNELS["in_affine"]["fwd"], ks)
+        _expect_kernels(pins, None, pins["in_affine"]["fwd"], ks)
         assert torch.equal(y, y_ref) and torch.equal(part, p_ref)
         want_y = ref["y"] + (addend.double() if addend is not None else 0)
         _check(f"fwd_in add={addend is not None}", name, y, want_y, BAR["y"], ks, res)
@@ -344,19 +364,21 @@ def test_conv2x_temporal_layer_in_the_programs_form(relu, gpu_device, kernel_log
         dw = ops.conv_wgrad_in(xb, dy, w, stride, pad, scale, shift, relu=relu)
     assert count(1) - before == 1
     ks = conv_names(log.report)
-    _expect_kernels(None, KERNELS["in_affine"]["wgrad"], ks)
+    _expect_kernels(pins, None, pins["in_affine"]["wgrad"], ks)
     assert torch.equal(dw, plain)
-    assert name in LONG_WGRAD
-    _check("wgrad_in", name, dw, ref["dw"], BAR["dw"], ks, res,
-           fp32=lambda: R.conv_ref(z, w, stride, pad, dy=dy, want=("dw",), dtype=torch.float32)["dw"])
+    fp32 = None
+    if name in long_wgrad:
+        fp32 = lambda: R.conv_ref(z, w, stride, pad, dy=dy, want=("dw",), chunk=chunk, dtype=torch.float32)["dw"]  # noqa: E731
+    _check("wgrad_in", name, dw, ref["dw"], BAR["dw"], ks, res, fp32=fp32)
+    return res
 
 
-def _group_items(members, dev, seed):
+def _group_items(members, dev, seed, layers=LAYERS):
     from avid_hip import lib, ops
     items = (lib.WgradItem * len(members))()
     keep, outs = [], []
     for j, i in enumerate(members):
-        e = LAYERS[i]
+        e = layers[i]
         x, w, dy = _inputs(e, dev, seed + 17 * j + i)
         d = _desc(e)[0]
         assert d.groupable, R.layer_id(e)
@@ -379,18 +401,23 @@ def _run_group(items, n, ws):
 def test_grouped_weight_gradients_of_the_step(gi, gpu_device, kernel_log):
     """Each grouped weight-gradient launch of the batch-64 backward program (avid_conv_wgrad_group), with the step's own
     items in the step's order, every item against float64 (5e-5 of its scale)."""
-    dev = gpu_device
-    members = TABLE["groups"][gi]
-    items, keep, outs, ws = _group_items(members, dev, 500 * gi)
+    check_group(TABLE, gi, KERNELS, gpu_device, kernel_log)
+
+
+def check_group(table, gi, pins, dev, kernel_log, chunk=8):
+    """Grouped weight-gradient launch ``gi`` of a table with the programs' own items, every item against float64."""
+    layers, members = table["layers"], table["groups"][gi]
+    items, keep, outs, ws = _group_items(members, dev, 500 * gi, layers)
     with kernel_log() as log:
         _run_group(items, len(members), ws)
     ks = conv_names(log.report)
-    _expect_kernels(None, KERNELS["groups"][gi], ks)
-    print(f"\ngroup {gi}: {[R.layer_id(LAYERS[i]) for i in members]}")
+    _expect_kernels(pins, None, pins["groups"][gi], ks)
+    print(f"\ngroup {gi}: {[R.layer_id(layers[i]) for i in members]}")
     res = []
     for (e, x, w, dy), dw in zip(keep, outs):
-        ref = R.conv_ref(x, w, tuple(e["stride"]), tuple(e["pad"]), dy=dy, want=("dw",))
+        ref = R.conv_ref(x, w, tuple(e["stride"]), tuple(e["pad"]), dy=dy, want=("dw",), chunk=chunk)
         _check("grouped wgrad", R.layer_id(e), dw, ref["dw"], BAR["dw"], ks, res)
+    return res
 
 
 def test_layer_table_covers_the_steps_convolution_kernels(gpu_device, kernel_log):

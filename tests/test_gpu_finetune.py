@@ -1,6 +1,6 @@
-"""Action-recognition fine-tuning on the GPU: the new kernels (dropout, softmax cross-entropy) against host restatements in
-float64, the compiled classifier programs against the per-layer path and the float64 oracle, the FinetuneStep engine against
-a plain torch loop, and the reference's eval script shape through the launcher."""
+"""Action-recognition fine-tuning on the GPU: the new kernels (dropout, softmax cross-entropy, the classifier's linear
+layer) against host restatements in float64, the compiled classifier programs against the per-layer path and the float64
+oracle, the FinetuneStep engine against a plain torch loop, and the reference's eval script shape through the launcher."""
 import copy
 import json
 import os
@@ -35,8 +35,19 @@ def _host_mask(B, Fd, p, seed, offset):
 @pytest.mark.parametrize("p", [0.0, 0.5])
 @pytest.mark.parametrize("B", [1, 4, 8, 64, 320])
 def test_dropout_mask_is_the_philox_restatement(gpu_device, B, p):
+    _dropout_against_the_restatement(gpu_device, B, 512, p, 0x1234_5678_9ABC_DEF1 + B, 7 + B)
+
+
+def test_dropout_past_the_grid_caps(gpu_device):
+    """n = 4099 x 2049 elements: n mod 4 = 3 (a ragged last group of four), more than 4096 x 256 groups of four in the
+    forward and more than 4096 x 256 elements in the backward, so both kernels go round their grid-stride loops."""
+    B, Fd = 4099, 2049
+    assert (B * Fd) % 4 == 3 and (B * Fd + 3) // 4 > 4096 * 256
+    _dropout_against_the_restatement(gpu_device, B, Fd, 0.5, 0x0FED_CBA9_8765_4321, 11)
+
+
+def _dropout_against_the_restatement(gpu_device, B, Fd, p, seed, offset):
     from avid_hip import ops
-    Fd, seed, offset = 512, 0x1234_5678_9ABC_DEF1 + B, 7 + B
     x = torch.randn(B, Fd, device=gpu_device, requires_grad=True)
     y = ops.dropout(x, p, seed, offset)
     want = torch.from_numpy(_host_mask(B, Fd, p, seed, offset)).to(gpu_device)
@@ -91,6 +102,76 @@ def test_cls_loss_against_float64(gpu_device, B, C):
         assert torch.equal(again[0], loss) and torch.equal(again[1], conf) and torch.equal(again[2], hits)
         assert torch.equal(again[3], dl)
     ops.check_device_errors(gpu_device)
+
+
+# B, C, Fin: the batch sizes and class counts of test_cls_loss_against_float64 at the tower's 512 features; fewer features
+# than lanes (37) and a ragged count (100); one case whose backward (C * Fin + C + B * Fin = 1 474 960 elements, one thread
+# each) is past its cap of 4096 blocks of 256
+LINEAR_CASES = [(B, C, 512) for B in (1, 4, 8, 64, 320) for C in (51, 101, 400)] + \
+               [(8, 101, 37), (8, 101, 100), (320, 400, 2048)]
+
+
+def _relerr(got, want):
+    return float((got.double() - want).abs().max() / (want.abs().max() + 1e-300))
+
+
+@pytest.mark.parametrize("B,C,Fin", LINEAR_CASES, ids=["%dx%dx%d" % c for c in LINEAR_CASES])
+def test_cls_linear_against_float64(gpu_device, B, C, Fin):
+    """avid_cls_linear_fwd / avid_cls_linear_bwd on their own, every output filled with NaN first, against float64 F.linear
+    and its autograd at the per-op bars (max|err| / max|ref| below 2e-5 for y and dx, 5e-5 for dw and db).  x is what the
+    step feeds: positive (post-ReLU, max-pooled) features through dropout, about half of them zero and the rest doubled; w
+    and bias at torch.nn.Linear's initial scale; dy the dlogits of ops.cls_loss on the forward's own logits.  bias = NULL,
+    dx = NULL (the classifier-only program) and db = NULL leave the other outputs bit-identical; so does a repeated call."""
+    from avid_hip import lib, ops
+    dev = gpu_device
+    assert C * Fin + C + B * Fin > 4096 * 256 or (B, C, Fin) != (320, 400, 2048)
+    g = torch.Generator(device=dev).manual_seed(B * 100000 + C * 100 + Fin % 100)
+    x = ops.dropout(torch.randn(B, Fin, generator=g, device=dev).abs(), 0.5, 0xC1A5 + B, C).contiguous()
+    zeros = float((x == 0).double().mean())
+    assert B * Fin < 4096 or 0.4 < zeros < 0.6, zeros
+    bound = Fin ** -0.5
+    w = ((torch.rand(C, Fin, generator=g, device=dev) * 2 - 1) * bound).contiguous()
+    bias = ((torch.rand(C, generator=g, device=dev) * 2 - 1) * bound).contiguous()
+    labels = torch.randint(0, C, (B,), generator=g, device=dev)
+    nan = lambda *shape: torch.full(shape, float("nan"), device=dev)                  # noqa: E731
+
+    def fwd(b):
+        y = nan(B, C)
+        lib.call("avid_cls_linear_fwd", B, Fin, C, ops._p(x), ops._p(w), ops._p(b), ops._p(y), ops._stream())
+        return y
+
+    def bwd(dy, want_dx=True, want_db=True):
+        dx, dw, db = nan(B, Fin), nan(C, Fin), nan(C)
+        lib.call("avid_cls_linear_bwd", B, Fin, C, ops._p(x), ops._p(w), ops._p(dy), ops._p(dx if want_dx else None),
+                 ops._p(dw), ops._p(db if want_db else None), ops._stream())
+        return dx, dw, db
+
+    y = fwd(bias)
+    assert bool(torch.isfinite(y).all()), "an element of y was never written"
+    dy = ops.cls_loss(y, labels, grad_scale=1.0)[3].contiguous()
+    dx, dw, db = bwd(dy)
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, bias))
+    yr = F.linear(xr, wr, br)
+    (yr * dy.double()).sum().backward()
+    for name, got, want, bar in (("y", y, yr.detach(), 2e-5), ("dx", dx, xr.grad, 2e-5), ("dw", dw, wr.grad, 5e-5),
+                                 ("db", db, br.grad, 5e-5)):
+        assert bool(torch.isfinite(got).all()), (name, "an element was never written")
+        err = _relerr(got, want)
+        print(f"  cls_linear {B}x{C}x{Fin} {name:2s} max {err:.2e} / {bar:.0e}")
+        assert err < bar, (name, err)
+    # bias = NULL
+    y0 = fwd(None)
+    assert bool(torch.isfinite(y0).all())
+    assert _relerr(y0, F.linear(x.double(), w.double())) < 2e-5
+    # dx = NULL / db = NULL: the other outputs are the full call's bits, the absent one is not touched
+    dx1, dw1, db1 = bwd(dy, want_dx=False)
+    assert torch.equal(dw1, dw) and torch.equal(db1, db) and bool(torch.isnan(dx1).all())
+    dx2, dw2, db2 = bwd(dy, want_db=False)
+    assert torch.equal(dx2, dx) and torch.equal(dw2, dw) and bool(torch.isnan(db2).all())
+    # bit-reproducible
+    assert torch.equal(fwd(bias), y)
+    assert all(torch.equal(a, b) for a, b in zip(bwd(dy), (dx, dw, db)))
+    ops.check_device_errors(dev)
 
 
 def test_cls_loss_tie_rule(gpu_device):
@@ -170,7 +251,8 @@ def _program_vs_per_layer(dev, shape):
     return m1, pls[0]
 
 
-@pytest.mark.parametrize("shape", [(4, 3, 8, 112, 112), (2, 3, 16, 112, 112), (1, 3, 32, 224, 224)], ids=["4x8", "2x16", "1x32"])
+@pytest.mark.parametrize("shape", [(4, 3, 8, 112, 112), (2, 3, 16, 112, 112), (1, 3, 32, 224, 224), (8, 3, 8, 224, 224),
+                                   (4, 3, 32, 224, 224)], ids=["4x8", "2x16", "1x32", "8x8x224", "4x32x224"])
 def test_programs_match_the_per_layer_path(gpu_device, shape):
     _program_vs_per_layer(gpu_device, shape)
 
