@@ -13,9 +13,12 @@ What the reference does with ``DistributedDataParallel`` + ``torch.optim.Adam``
                      folded into the optimizer kernel's ``grad_scale``.
 * ``FlatBuffers``  — the BatchNorm running statistics as views of one flat buffer: DDP's buffer broadcast
                      (``broadcast_buffers=True``, the default of utils/main_utils.py:112) is ONE 78 KB collective.
-* ``TrainStep``    — fwd -> criterion -> bwd (+ overlapped all-reduce) -> one fused flat-Adam launch;
-                     ``state_dict`` / ``load_state_dict`` in torch.optim.Adam's format (the reference's
-                     CheckpointManager saves ``optimizer.state_dict()``, main-avid.py:115,127,138).
+* ``EngineCore``   — what the step engines share: the model in those buffers, the backward launch program cut at bucket
+                     ends.  No optimizer, no criterion (``DistributedDataParallel``'s engine is this and little else).
+* ``AdamStep``     — the core + one fused flat-Adam launch; ``state_dict`` / ``load_state_dict`` in torch.optim.Adam's
+                     format (the reference's CheckpointManager saves ``optimizer.state_dict()``, main-avid.py:115,127,138).
+* ``TrainStep``    — AdamStep for pretraining: fwd -> criterion -> bwd (+ overlapped all-reduce) -> Adam; hipGraph capture
+                     (``FinetuneStep``: for action-recognition fine-tuning).
 
 The comm layer is backend-agnostic (gloo on CPU in tests/test_distributed_cpu.py); only the Adam
 kernel needs the GPU.  BatchNorm statistics stay per-rank — the reference has no SyncBN.
@@ -26,6 +29,7 @@ import os
 import weakref
 import torch
 import torch.distributed as dist
+from . import lib
 
 
 _FLAT_OF = {}           # id(parameter) -> weakref(FlatParams it is a view of)
@@ -50,7 +54,6 @@ def flat_of(params):
 def _dist_on():
     """Collectives are in play: more than one rank (or AVID_FORCE_DIST=1, which drives the RCCL path on a
     single-rank group so it can be exercised on a one-GPU box)."""
-    import os
     if not (dist.is_available() and dist.is_initialized()):
         return False
     return dist.get_world_size() > 1 or os.environ.get("AVID_FORCE_DIST", "0") == "1"
@@ -75,26 +78,42 @@ class FlatParams:
         self.flat = torch.zeros(off, dtype=dt, device=dev)
         self.grad = torch.zeros(off, dtype=dt, device=dev)
         self.grad_views = []
-        for p, o in zip(self.params, self.offsets):
-            view = self.flat[o:o + p.numel()].as_strided(p.shape, p.stride())
+        for i, p in enumerate(self.params):
+            view = self.view(self.flat, i)
             view.copy_(p.data)
             p.data = view
-            p.grad = self.grad[o:o + p.numel()].as_strided(p.shape, p.stride())
+            p.grad = self.view(self.grad, i)
             self.grad_views.append(p.grad)
             _FLAT_OF[id(p)] = weakref.ref(self)
 
+    def view(self, buf, i):
+        """Parameter i's view (its shape and strides) of ``buf``, a flat tensor laid out like ``flat``: a gradient, an Adam moment."""
+        p, o = self.params[i], self.offsets[i]
+        return buf[o:o + p.numel()].as_strided(p.shape, p.stride())
+
     def seat_grads(self):
-        """`.grad` of every parameter is its view of the flat gradient buffer again (after a zero_grad(set_to_none=True):
-        the kernels wrote the buffer, not the attribute)."""
+        """`.grad` of every parameter is its view of the flat gradient buffer again (it was None after a
+        zero_grad(set_to_none=True), or something pointed it elsewhere: the kernels wrote the buffer, not the attribute)."""
         for p, v in zip(self.params, self.grad_views):
             if p.grad is not v:
                 p.grad = v
 
     def zero_grad(self):
         self.grad.zero_()
-        for p, o in zip(self.params, self.offsets):     # re-seat if something replaced .grad (set_to_none)
-            if p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + 4 * o:
-                p.grad = self.grad_views[self.offsets.index(o)]
+        self.seat_grads()
+
+    def load_moments(self, m, v, states):
+        """Fill the flat Adam moments ``m`` / ``v`` from ``states``: (slot in the flat layout, that parameter's entry of a
+        torch.optim.Adam ``state``, or None: zero moments) pairs.  Returns the largest ``step`` among them."""
+        m.zero_()
+        v.zero_()
+        step = 0
+        for i, st in states:
+            if st:
+                self.view(m, i).copy_(st["exp_avg"])
+                self.view(v, i).copy_(st["exp_avg_sq"])
+                step = max(step, int(float(st["step"])))
+        return step
 
 
 class FlatBuffers:
@@ -147,11 +166,6 @@ class FlatBuffers:
         if self.flat is None or not _dist_on():
             return None
         return dist.broadcast(self.flat, src, async_op=async_op)
-
-
-def lib_timing():
-    from . import lib
-    return lib.TIMING
 
 
 class GradBuckets:
@@ -226,6 +240,18 @@ class GradBuckets:
             self.ready(i)
         return hook
 
+    def _mean_by_division(self):
+        """Averaging on a backend without ReduceOp.AVG (gloo: CPU tensors, the two-ranks-on-one-GPU tests; RCCL has it): the
+        collective sums, and with more than one rank the sum is divided behind it."""
+        return self.average and dist.get_backend() != "nccl"
+
+    def _reduce(self, grad):
+        """All-reduce ``grad`` (the flat gradient buffer or a slice) on the current stream: the sum, or the mean with ``average``."""
+        divide = self._mean_by_division()
+        dist.all_reduce(grad, op=dist.ReduceOp.AVG if self.average and not divide else dist.ReduceOp.SUM)
+        if divide and self.world > 1:
+            grad.div_(self.world)
+
     def _launch(self, b):
         self.launched[b] = True
         self._issue(b)
@@ -243,7 +269,7 @@ class GradBuckets:
             # (gloo has no AVG: the mean is taken in finish(), behind the wait)
             self.works.append(dist.all_reduce(self.flat.grad[s:e], async_op=True))
             return
-        from . import lib, streams
+        from . import streams
         dev = self.flat.grad.device
         # ONE StreamSet per step: the first bucket resolves it (from whichever of the set's streams is current — the
         # per-layer path reports deferred weight gradients with the trailing stream current), the rest of the step reuses
@@ -255,11 +281,8 @@ class GradBuckets:
         cs = ss.comm
         for st in prod:
             lib.call("avid_stream_wait", cs.cuda_stream, st.cuda_stream)
-        native = self.average and dist.get_backend() == "nccl"       # (RCCL averages; gloo — the two-ranks-on-one-GPU tests — cannot)
         with torch.cuda.stream(cs):
-            dist.all_reduce(self.flat.grad[s:e], op=dist.ReduceOp.AVG if native else dist.ReduceOp.SUM)
-            if self.average and not native and self.world > 1:
-                self.flat.grad[s:e].div_(self.world)
+            self._reduce(self.flat.grad[s:e])
         if all(cs is not c for c in self.comm_used):
             self.comm_used.append(cs)
 
@@ -285,10 +308,7 @@ class GradBuckets:
             dev = self.flat.grad.device
             cur = torch.cuda.current_stream(dev)
             cur.wait_stream(ops.side_stream(dev, 1))         # the audio tower's gradients
-            native = self.average and dist.get_backend() == "nccl"
-            dist.all_reduce(self.flat.grad, op=dist.ReduceOp.AVG if native else dist.ReduceOp.SUM)
-            if self.average and not native and self.world > 1:
-                self.flat.grad.div_(self.world)
+            self._reduce(self.flat.grad)
             self.launched = [True] * len(self.bounds)
         if self.comm:
             for b, left in enumerate(self.pending):
@@ -303,8 +323,8 @@ class GradBuckets:
                 e0.record()
             for w in self.works:
                 w.wait()                             # (CPU tensors: gloo)
-            if self.works and self.average and self.world > 1:
-                self.flat.grad.div_(self.world)
+            if self.works and self._mean_by_division() and self.world > 1:
+                self.flat.grad.div_(self.world)          # (the works are asynchronous: the division _reduce does, deferred)
             for cs in self.comm_used:
                 torch.cuda.current_stream(self.flat.grad.device).wait_stream(cs)
             self.comm_used = []
@@ -327,25 +347,19 @@ class GradBuckets:
             p.clear()
 
 
-class TrainStep:
-    """One AVID training step (main-avid.py:155-180) on this rank's GPU.
+class EngineCore:
+    """What every step engine on this rank's GPU shares: the model in flat buffers, the gradient buckets, the backward kernels'
+    transposed weights and gradient slots, the hand-over of a backward launch program.  No criterion and no optimizer."""
 
-    ``step(video, audio, index)`` returns the (device) loss tensor; nothing synchronises the host.
-    Adam hyper-parameters follow the shipped configs (lr 2e-4, betas (0.9, 0.999), L2 wd 1e-5).
-    """
-
-    def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
-                 bucket_bytes=16 << 20, broadcast_buffers="step", _wrapper=False):
+    def __init__(self, model, bucket_bytes=16 << 20, broadcast_buffers="step", average=False, hooks=None):
         """``broadcast_buffers``: DistributedDataParallel broadcasts rank 0's BatchNorm buffers before EVERY
         forward (utils/main_utils.py:112, default ``broadcast_buffers=True``).  A training-mode forward never
         reads them (it normalises with the batch statistics), and rank 0's own buffers are never overwritten, so
         the only observable effect is what a non-zero rank evaluates / saves with.  ``"step"`` (default) reproduces
         DDP literally with ONE flat 78 KB broadcast per step (the running statistics are views of one buffer);
         ``"lazy"`` broadcasts at ``sync_buffers()`` only — the caller must invoke it before evaluating or saving on a
-        rank other than 0 — ``"off"`` never broadcasts."""
-        import os
-        self.model, self.criterion = model, criterion
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        rank other than 0 — ``"off"`` never broadcasts.  ``average`` / ``hooks``: ``GradBuckets``'s."""
+        self.model = model
         if broadcast_buffers not in ("lazy", "step", "off"):
             raise ValueError("broadcast_buffers must be 'lazy', 'step' or 'off'")
         self.broadcast_buffers = broadcast_buffers
@@ -362,31 +376,14 @@ class TrainStep:
             model.overlap_towers = True
         if os.environ.get("AVID_BUCKET_MB"):             # tuning knob: gradient all-reduce bucket size
             bucket_bytes = int(float(os.environ["AVID_BUCKET_MB"]) * (1 << 20))
-        # (_wrapper: the engine inside DistributedDataParallel below — the optimizer is somebody else's, so the collectives
-        #  average, every parameter carries an autograd hook for gradients that do not come out of a launch program, and
-        #  there is no Adam state here)
-        self.buckets = GradBuckets(self.flat, bucket_bytes, average=_wrapper, hooks=True if _wrapper else None)
-        self.m = None if _wrapper else torch.zeros_like(self.flat.flat)
-        self.v = None if _wrapper else torch.zeros_like(self.flat.flat)
-        self.t = 0
-        self.t_dev = torch.zeros((), dtype=torch.int64, device=self.flat.flat.device) \
-            if self.flat.flat.is_cuda else None
-        # the learning rate lives in device memory as well: a captured graph freezes by-value arguments
-        self.lr_dev = torch.full((), float(lr), dtype=torch.float32, device=self.flat.flat.device) \
-            if self.flat.flat.is_cuda else None
-        self.graph = None
+        self.buckets = GradBuckets(self.flat, bucket_bytes, average=average, hooks=hooks)
+        self._step_plan = None                           # the launch program the current step's backward ran through
         self.twt = self.slots = None
         if self.flat.flat.is_cuda:
             from . import ops
             self.twt = ops.TransposedWeights(self.flat.params)   # dgrad weight repack: one launch per step
             # backward kernels write parameter gradients straight into the flat buffer (no per-parameter add)
             self.slots = ops.GradSlots(self.flat.params, self.flat.grad_views, on_ready=self.buckets.ready)
-
-    def set_lr(self, lr):
-        """Change the learning rate (an LR scheduler's hook; also reaches a captured graph)."""
-        self.lr = float(lr)
-        if self.lr_dev is not None:
-            self.lr_dev.fill_(self.lr)
 
     def sync_buffers(self):
         """Every rank takes rank 0's BatchNorm running statistics (see ``broadcast_buffers``): call before
@@ -407,6 +404,100 @@ class TrainStep:
             for i, st in ready:
                 self.buckets.ready(i, pl.stream_objs[st])
             begin = end
+
+    def _poll_errors(self):
+        """Out-of-range sample ids raise here (non-blocking look at the device error word, ops.DeviceErrors): the
+        criterion's own polls do not run when a captured graph is replayed.  The error surfaces about one step after
+        the offending kernels, i.e. after Adam has applied that step — ``ops.check_device_errors()`` is the blocking
+        form for checkpoint time."""
+        if self.flat.flat.is_cuda:
+            from . import ops
+            ops.poll_device_errors(self.flat.flat.device)
+
+
+class AdamStep(EngineCore):
+    """The core plus Adam over the flat buffers: one fused launch per step (or per slice of the buffers), moments ``m`` / ``v``,
+    the step count and learning rate in device memory as well (a captured graph reads them there)."""
+
+    def __init__(self, model, lr, betas, eps, weight_decay, **core):
+        super().__init__(model, **core)
+        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self.m = torch.zeros_like(self.flat.flat)
+        self.v = torch.zeros_like(self.flat.flat)
+        self.t = 0
+        dev = self.flat.flat.device if self.flat.flat.is_cuda else None
+        self.t_dev = torch.zeros((), dtype=torch.int64, device=dev) if dev is not None else None
+        # the learning rate lives in device memory as well: a captured graph freezes by-value arguments
+        self.lr_dev = torch.full((), float(lr), dtype=torch.float32, device=dev) if dev is not None else None
+
+    def set_lr(self, lr):
+        """Change the learning rate (an LR scheduler's hook; also reaches a captured graph)."""
+        self.lr = float(lr)
+        if self.lr_dev is not None:
+            self.lr_dev.fill_(self.lr)
+
+    def _adam(self, begin=0, end=None, advance=True):
+        """One flat-Adam launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (step
+        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays)."""
+        from . import ops
+        s = slice(begin, end)
+        ops.adam_flat(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0], self.betas[1],
+                      self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev,
+                      lr_dev=self.lr_dev, advance=advance)
+
+    def optimizer_step(self):
+        self.t += 1
+        self._adam()
+
+    # ---- optimizer state in torch.optim.Adam's format (main-avid.py:115,127,138 save and restore
+    # ``optimizer.state_dict()``; utils/main_utils.py:250-261 builds Adam over model.parameters())
+    def _param_order(self):
+        """[(index in ``list(model.parameters())`` — frozen parameters included, as torch.optim.Adam built over
+        ``model.parameters()`` numbers them (utils/main_utils.py:250-261) —, slot in the flat layout, parameter)]
+        for the trainable parameters."""
+        slot = {id(p): i for i, p in enumerate(self.flat.params)}
+        return [(k, slot[id(p)], p) for k, p in enumerate(self.model.parameters()) if id(p) in slot]
+
+    def _slice(self, flat_tensor, i):
+        return self.flat.view(flat_tensor, i)
+
+    def state_dict(self):
+        step = float(int(self.t_dev) if self.t_dev is not None else self.t)
+        state = {}
+        if step > 0:
+            for k, i, _ in self._param_order():                 # (a frozen parameter has an index but no state, as in torch)
+                state[k] = {"step": torch.tensor(step), "exp_avg": self._slice(self.m, i).detach().clone(),
+                            "exp_avg_sq": self._slice(self.v, i).detach().clone()}
+        nparams = sum(1 for _ in self.model.parameters())
+        return {"state": state,
+                "param_groups": [{"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
+                                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
+                                  "differentiable": False, "fused": None, "decoupled_weight_decay": False,
+                                  "params": list(range(nparams))}]}
+
+    def load_state_dict(self, sd):
+        g = sd["param_groups"][0]
+        self.betas, self.eps, self.wd = tuple(g["betas"]), g["eps"], g["weight_decay"]
+        self.set_lr(g["lr"])
+        self.t = self.flat.load_moments(self.m, self.v, ((i, sd["state"].get(k, sd["state"].get(str(k))))
+                                                         for k, i, _ in self._param_order()))
+        if self.t_dev is not None:
+            self.t_dev.fill_(self.t)
+
+
+class TrainStep(AdamStep):
+    """One AVID training step (main-avid.py:155-180) on this rank's GPU.
+
+    ``step(video, audio, index)`` returns the (device) loss tensor; nothing synchronises the host.
+    Adam hyper-parameters follow the shipped configs (lr 2e-4, betas (0.9, 0.999), L2 wd 1e-5).
+    """
+
+    def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
+                 bucket_bytes=16 << 20, broadcast_buffers="step"):
+        """``broadcast_buffers``: see ``EngineCore``."""
+        super().__init__(model, lr, betas, eps, weight_decay, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+        self.criterion = criterion
+        self.graph = None
 
     def _forward_backward_plan(self, video, audio, index):
         """The step through the compiled launch programs (avid_hip/plan.py); None if the model is outside them."""
@@ -433,7 +524,7 @@ class TrainStep:
         if self.twt is not None:
             self.twt.prepare_wino()
             self.twt.uready = False
-        if self.twt is not None and self.flat.grad.is_cuda and ops.DEFER_WGRAD and self._defer_ok() and not lib_timing():
+        if self.twt is not None and self.flat.grad.is_cuda and ops.DEFER_WGRAD and not lib.TIMING:
             # What the backward needs but the forward does not — zeroed gradients, the transposed weight copies, the
             # Winograd transforms of the weights — runs on a helper stream next to the forward instead of in front of /
             # behind it (the weights cannot change in between: this method owns the step).
@@ -481,31 +572,12 @@ class TrainStep:
             else:
                 self.twt.refresh()                   # after the forward: whatever the weights are now
                 self.twt.refresh_wino(True)
-            with self.twt.armed(), self.twt.armed_wino(), self.slots.armed(), \
-                    ops.deferred_wgrads(enabled=self._defer_ok()):
+            with self.twt.armed(), self.twt.armed_wino(), self.slots.armed(), ops.deferred_wgrads():
                 loss.backward()
         else:
             loss.backward()
         self.buckets.finish()
         return loss
-
-    def _defer_ok(self):
-        """Trailing weight-gradient stream: always (with or without gradient collectives — the collectives' stream is
-        placed on a dispatch pipe of its own, avid_hip/streams.py; a captured step decides for itself in ops)."""
-        return True
-
-    def _adam(self, begin=0, end=None, advance=True):
-        """One flat-Adam launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (step
-        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays)."""
-        from . import ops
-        s = slice(begin, end)
-        ops.adam_flat(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0], self.betas[1],
-                      self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev,
-                      lr_dev=self.lr_dev, advance=advance)
-
-    def optimizer_step(self):
-        self.t += 1
-        self._adam()
 
     def _optimizer_step_overlapped(self, pl):
         """The same update in two launches: every parameter but the video stem's three on the fourth stream, which the
@@ -522,33 +594,8 @@ class TrainStep:
         """The criterion's negative sampler (``nce_average.multinomial``), or None."""
         return getattr(getattr(self.criterion, "nce_average", None), "multinomial", None)
 
-    # ---- optimizer / sampler state in torch.optim.Adam's format (main-avid.py:115,127,138 save and restore
-    # ``optimizer.state_dict()``; utils/main_utils.py:250-261 builds Adam over model.parameters())
-    def _param_order(self):
-        """[(index in ``list(model.parameters())`` — frozen parameters included, as torch.optim.Adam built over
-        ``model.parameters()`` numbers them (utils/main_utils.py:250-261) —, slot in the flat layout, parameter)]
-        for the trainable parameters."""
-        slot = {id(p): i for i, p in enumerate(self.flat.params)}
-        return [(k, slot[id(p)], p) for k, p in enumerate(self.model.parameters()) if id(p) in slot]
-
-    def _slice(self, flat_tensor, i):
-        p, o = self.flat.params[i], self.flat.offsets[i]
-        return flat_tensor[o:o + p.numel()].as_strided(p.shape, p.stride())
-
     def state_dict(self):
-        order = self._param_order()
-        step = float(int(self.t_dev) if self.t_dev is not None else self.t)
-        state = {}
-        if step > 0:
-            for k, i, _ in order:                  # (a frozen parameter has an index but no state, as in torch)
-                state[k] = {"step": torch.tensor(step), "exp_avg": self._slice(self.m, i).detach().clone(),
-                            "exp_avg_sq": self._slice(self.v, i).detach().clone()}
-        nparams = sum(1 for _ in self.model.parameters())
-        sd = {"state": state,
-              "param_groups": [{"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
-                                "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
-                                "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                                "params": list(range(nparams))}]}
+        sd = super().state_dict()
         mult = self._sampler()
         if mult is not None:       # the negative sampler's stream position (not part of the reference's checkpoint:
             off = int(mult.offset_dev) if getattr(mult, "offset_dev", None) is not None else int(mult.offset)
@@ -556,41 +603,16 @@ class TrainStep:
         return sd
 
     def load_state_dict(self, sd):
-        order = self._param_order()
-        g = sd["param_groups"][0]
-        self.betas, self.eps, self.wd = tuple(g["betas"]), g["eps"], g["weight_decay"]
-        self.set_lr(g["lr"])
-        self.m.zero_()
-        self.v.zero_()
-        step = 0
-        for k, i, _ in order:
-            st = sd["state"].get(k, sd["state"].get(str(k)))
-            if st is None:
-                continue
-            self._slice(self.m, i).copy_(st["exp_avg"])
-            self._slice(self.v, i).copy_(st["exp_avg_sq"])
-            step = max(step, int(float(st["step"])))
-        self.t = step
-        if self.t_dev is not None:
-            self.t_dev.fill_(step)
+        super().load_state_dict(sd)
         mult = self._sampler()
         if mult is not None and "avid_sampler" in sd:
             mult.reseed(sd["avid_sampler"]["seed"], sd["avid_sampler"]["offset"])
-
-    def _poll_errors(self):
-        """Out-of-range sample ids raise here (non-blocking look at the device error word, ops.DeviceErrors): the
-        criterion's own polls do not run when a captured graph is replayed.  The error surfaces about one step after
-        the offending kernels, i.e. after Adam has applied that step — ``ops.check_device_errors()`` is the blocking
-        form for checkpoint time."""
-        if self.flat.flat.is_cuda:
-            from . import ops
-            ops.poll_device_errors(self.flat.flat.device)
 
     def step(self, video, audio, index):
         self._step_plan = None
         loss = self.forward_backward(video, audio, index)
         pl = self._step_plan
-        if pl is not None and pl.adam_early and not self.buckets.comm and not lib_timing():
+        if pl is not None and pl.adam_early and not self.buckets.comm and not lib.TIMING:
             self._optimizer_step_overlapped(pl)
         else:
             self.optimizer_step()
@@ -639,13 +661,13 @@ class TrainStep:
 # optimizer.step()) on the engine's pieces: the two objects its factories build — utils/main_utils.py:112
 # `DistributedDataParallel(model, device_ids=[gpu])` and :250 `torch.optim.Adam(params, lr, weight_decay, betas)` — with the same
 # constructors and the same behaviour towards that loop.  Swapping the two names in main_utils.py is the whole change.
-class _WrapperEngine(TrainStep):
-    """TrainStep's flat buffers / buckets / launch-program hand-over without its criterion and optimizer: what runs under
-    `DistributedDataParallel.forward` and the `loss.backward()` the caller issues later."""
+class _WrapperEngine(EngineCore):
+    """The core under `DistributedDataParallel.forward` and the `loss.backward()` the caller issues later.  The optimizer is
+    somebody else's, so the collectives average (``TrainStep`` folds 1 / world into its Adam launch instead) and every
+    parameter carries an autograd hook for gradients that do not come out of a launch program."""
 
     def __init__(self, model, bucket_bytes, broadcast_buffers):
-        super().__init__(model, None, bucket_bytes=bucket_bytes, broadcast_buffers="step" if broadcast_buffers else "off",
-                         _wrapper=True)
+        super().__init__(model, bucket_bytes, "step" if broadcast_buffers else "off", average=True, hooks=True)
         self._armed = False
         self.buckets.on_autograd = self._arm
 
@@ -767,22 +789,16 @@ class Adam(torch.optim.Optimizer):
         self._t = 0
         self._step_t = torch.tensor(0.0)
 
-    def _views(self, i):
-        p, o = self.flat.params[i], self.flat.offsets[i]
-        return (self.m[o:o + p.numel()].as_strided(p.shape, p.stride()), self.v[o:o + p.numel()].as_strided(p.shape, p.stride()))
-
     def _publish_state(self):
         """`self.state` in torch.optim.Adam's shape: views of the flat moments, one shared step tensor."""
         if self.state:
             return
         for i, p in enumerate(self.flat.params):
-            m, v = self._views(i)
-            self.state[p] = {"step": self._step_t, "exp_avg": m, "exp_avg_sq": v}
+            self.state[p] = {"step": self._step_t, "exp_avg": self.flat.view(self.m, i), "exp_avg_sq": self.flat.view(self.v, i)}
 
     def zero_grad(self, set_to_none=True):
         """One fill of the flat gradient buffer; `.grad` stays seated (a launch program writes the buffer, not the attribute)."""
-        self.flat.grad.zero_()
-        self.flat.seat_grads()
+        self.flat.zero_grad()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -811,18 +827,7 @@ class Adam(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)              # (torch: casts, re-keys by parameter, replaces self.state)
-        self.m.zero_()
-        self.v.zero_()
-        step = 0
-        for i, p in enumerate(self.flat.params):
-            st = self.state.get(p)
-            if not st:
-                continue
-            m, v = self._views(i)
-            m.copy_(st["exp_avg"])
-            v.copy_(st["exp_avg_sq"])
-            step = max(step, int(float(st["step"])))
-        self._t = step
+        self._t = step = self.flat.load_moments(self.m, self.v, ((i, self.state.get(p)) for i, p in enumerate(self.flat.params)))
         self._step_t = torch.tensor(float(step))
         self.state.clear()
         if step > 0:
@@ -832,7 +837,7 @@ class Adam(torch.optim.Optimizer):
 # ---------------------------------------------------------------------------------------------------------------------
 # Action-recognition fine-tuning (eval-action-recg.py: run_phase 'train' / 'test_dense', the warm-up epochs of the classifier)
 # ---------------------------------------------------------------------------------------------------------------------
-class FinetuneStep(TrainStep):
+class FinetuneStep(AdamStep):
     """One fine-tuning step of a ``models.ClassificationWrapper`` around this package's ``R2Plus1D`` on this rank's GPU:
     the forward launch program ends in ``avid_cls_loss`` (loss, top-1 / top-5 hits and ``dlogits`` on the device), the
     backward program starts from ``dlogits``, then one flat Adam launch (``torch.optim.Adam``'s update; lr 1e-4 and weight
@@ -844,17 +849,15 @@ class FinetuneStep(TrainStep):
     With more than one rank, gradients are averaged as DistributedDataParallel does: through ``GradBuckets`` (the full
     step), or one collective over the classifier's slice (``classifier_only``); Adam's ``grad_scale`` takes the 1 / world.
     Rank 0's BatchNorm running statistics are broadcast before every step (``broadcast_buffers="step"``, DDP's default).
-    ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``TrainStep``'s."""
+    ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``AdamStep``'s, shared with ``TrainStep``."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
                  bucket_bytes=16 << 20, broadcast_buffers="step"):
         """``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
         0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never."""
-        super().__init__(model, None, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bucket_bytes=bucket_bytes,
-                         broadcast_buffers=broadcast_buffers)
+        super().__init__(model, lr, betas, eps, weight_decay, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
-        n = len(self.flat.params)
-        self.n_cls = self.flat.offsets[2] if n > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
+        self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
 
     def _plan(self, video):
         from . import plan

@@ -167,9 +167,6 @@ class Builder:
         if waiter != waited:
             self.emit(OP_WAIT, stream=0, i=(waiter, waited))
 
-    def trail(self):
-        return ST_TRAIL
-
     # ---- transposed weights / Winograd transforms for the input gradients (ops.TransposedWeights)
     def want_wt(self, w):
         key = (id(w), 0)
@@ -342,11 +339,10 @@ class Builder:
         if flush_check and self.group and len(self.pending[self.S]) >= ops.GROUP_MIN_FLUSH:
             self.flush_group()                        # the small layers queued so far go first
         if self.trailing:
-            tr = self.trail()
-            self.wait(tr, self.S)
-            self.emit(OP_CONV_WGRAD, stream=tr, d=d, **self._wgrad_args(xr, dyr, w, xa))
-            self._ready(tr, w)
-            self.trail_used.add(tr)
+            self.wait(ST_TRAIL, self.S)
+            self.emit(OP_CONV_WGRAD, stream=ST_TRAIL, d=d, **self._wgrad_args(xr, dyr, w, xa))
+            self._ready(ST_TRAIL, w)
+            self.trail_used.add(ST_TRAIL)
             return True
         return False                                   # the caller emits it behind the input gradient
 
@@ -787,11 +783,11 @@ class Plan(Programs):
 # ------------------------------------------------------------------------------------------------------------------
 # autograd node + dispatch
 # ------------------------------------------------------------------------------------------------------------------
-_ENGINE = None          # the parallel.TrainStep driving the current step (flat gradient buffer, buckets), or None
+_ENGINE = None          # the parallel.EngineCore driving the current step (flat gradient buffer, buckets), or None
 
 
 class engine:
-    """``with plan.engine(train_step): ...`` — model calls inside write their parameter gradients into the engine's
+    """``with plan.engine(eng): ...`` — model calls inside write their parameter gradients into the engine's
     flat gradient buffer (and report them to its gradient buckets) instead of handing tensors to autograd."""
 
     def __init__(self, eng):
@@ -941,7 +937,7 @@ def run(model, video, audio):
     eng = _ENGINE
     timing = lib.TIMING
     overlap = (not timing) and os.environ.get("AVID_OVERLAP_TOWERS", "1") == "1" and (eng is None or model.overlap_towers)
-    trailing = (not timing) and bool(ops.DEFER_WGRAD) and (eng is None or eng._defer_ok())
+    trailing = (not timing) and bool(ops.DEFER_WGRAD)
     video, audio = video.contiguous(), audio.contiguous()
     pl = _plan_for(model, (tuple(video.shape), tuple(audio.shape), video.device.index, overlap, trailing),
                    lambda: Plan(model, video.shape, audio.shape, video.device, overlap, trailing, bool(ops.GROUP_WGRAD)))

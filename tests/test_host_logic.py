@@ -315,3 +315,19 @@ def test_grad_buckets_reset_drops_what_a_failed_backward_left_behind():
     b.reported[0] = True
     b.reset()
     assert b.pending == counts and not any(b.launched) and not any(b.reported) and b.works == [] and b.step_set is None
+
+
+def test_step_engines_share_a_core_not_the_pretraining_step():
+    """The fine-tuning step and the engine under DistributedDataParallel derive from what they use (flat buffers and buckets;
+    flat Adam), not from TrainStep: neither carries a method that cannot work for it."""
+    from avid_hip import parallel
+    assert parallel.TrainStep not in parallel.FinetuneStep.__mro__ and parallel.TrainStep not in parallel._WrapperEngine.__mro__
+    for name in ("optimizer_step", "state_dict", "load_state_dict", "set_lr", "capture", "replay", "step", "forward_backward"):
+        assert not hasattr(parallel._WrapperEngine, name), name
+    for name in ("forward_backward", "capture", "replay"):
+        assert not hasattr(parallel.FinetuneStep, name), name
+    for name in ("step", "optimizer_step", "set_lr", "state_dict", "load_state_dict", "sync_buffers", "_plan_backward", "_poll_errors"):
+        assert hasattr(parallel.TrainStep, name) and hasattr(parallel.FinetuneStep, name), name
+    lin = torch.nn.Linear(4, 4)
+    eng = parallel._WrapperEngine(lin, 16 << 20, True)
+    assert not any(hasattr(eng, a) for a in ("m", "v", "t", "criterion", "graph")) and eng.buckets.average and len(eng.buckets.hooks) == 2
