@@ -166,6 +166,13 @@ SIGNATURES = {
     "avid_cls_loss": (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_cls_linear_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avid_cls_linear_bwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avid_adaptive_maxpool_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "avid_bn1d_fwd_train": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
+    "avid_bn1d_fwd_eval": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    "avid_bn1d_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp]),
+    "avid_probe_linear_workspace_bytes": (_sz, [_i, _i, _i]),
+    "avid_probe_linear_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avid_probe_linear_bwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avid_bank_scores_fwd": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "avid_bank_scores_bwd": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     "avid_mean_exp": (_i, [_i, _i, _i, _vp, _vp, _vp]),

@@ -1564,3 +1564,108 @@ class _ClsLinear(Function):
 def cls_linear(x, w, bias):
     """The classifier ``Linear(Fin, C)`` for any number of classes (avid_cls_linear_fwd / _bwd)."""
     return _ClsLinear.apply(x, w, bias)
+
+
+# ------------------------------------------------------------------------------------------------
+# linear-probe heads (probe.hip): adaptive max pooling into the reference's flatten order, BatchNorm1d, the probe's Linear
+# ------------------------------------------------------------------------------------------------
+def adaptive_window(i, n_in, n_out):
+    """Input range [start, end) of output index ``i`` of ``nn.AdaptiveMaxPool``: floor(i * In / Out) .. ceil((i + 1) * In / Out)."""
+    return (i * n_in) // n_out, -((-(i + 1) * n_in) // n_out)
+
+
+def adaptive_maxpool(x, output_size):
+    """``nn.AdaptiveMaxPool3d(output_size)(x_ncdhw).view(B, -1)`` of a channels-last tap ``x [B, T, H, W, C]`` (a contiguous
+    tensor, or the NCDHW view of one that the tower's ``return_embs`` hands out): ``[B, C * To * Ho * Wo]`` in the reference's
+    flatten order.  Not an autograd function: the reference pools under ``no_grad`` (no argmax is kept)."""
+    _need_cuda(x)
+    if x.dim() != 5 or x.dtype != torch.float32:
+        raise AvidHipError("adaptive_maxpool: a float32 [B, T, H, W, C] tensor expected")
+    if not x.is_contiguous():
+        raise AvidHipError("adaptive_maxpool: x must be a contiguous channels-last [B, T, H, W, C] tensor")
+    To, Ho, Wo = (int(v) for v in output_size)
+    B, T, H, W, Cc = x.shape
+    y = torch.empty((B, Cc * To * Ho * Wo), dtype=torch.float32, device=x.device)
+    lib.call("avid_adaptive_maxpool_fwd", B, T, H, W, Cc, To, Ho, Wo, _p(x), _p(y), _stream())
+    return y
+
+
+class _Bn1d(Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, stats, training, momentum, eps):
+        running_mean, running_var, counter = stats
+        _need_cuda(x, gamma, beta, running_mean, running_var)
+        x = x.contiguous()
+        if x.dim() != 2 or x.dtype != torch.float32:
+            raise AvidHipError("bn1d: a float32 [B, F] tensor expected")
+        B, F = x.shape
+        y = torch.empty_like(x)
+        save2 = torch.empty((2, F), dtype=torch.float32, device=x.device)
+        if training:
+            if B < 2:
+                raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+            lib.call("avid_bn1d_fwd_train", B, F, _p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(momentum),
+                     float(eps), _p(y), _p(save2), _p(counter), _stream())
+        else:
+            lib.call("avid_bn1d_fwd_eval", B, F, _p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps),
+                     _p(y), _p(save2), _stream())
+        ctx.save_for_backward(x, gamma, save2)
+        ctx.frozen, ctx.eps = not training, float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, save2 = ctx.saved_tensors
+        B, F = x.shape
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dg = torch.empty(F, dtype=torch.float32, device=x.device)
+        db = torch.empty(F, dtype=torch.float32, device=x.device)
+        lib.call("avid_bn1d_bwd", B, F, _p(x), _p(dy.contiguous()), _p(gamma), _p(save2), ctx.eps, int(ctx.frozen), _p(dx), _p(dg),
+                 _p(db),
+                 _stream())
+        return dx, dg, db, None, None, None, None
+
+
+def bn1d(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, num_batches_tracked=None):
+    """``nn.BatchNorm1d`` over ``x [B, F]`` (avid_bn1d_fwd_train / _eval / _bwd): any F.  Training mode updates the running
+    statistics in place and bumps ``num_batches_tracked`` on the device."""
+    return _Bn1d.apply(x, gamma, beta, (running_mean, running_var, num_batches_tracked), bool(training), float(momentum), float(eps))
+
+
+def _probe_ws(device, B, Fin, C):
+    n = lib.raw("avid_probe_linear_workspace_bytes")(B, Fin, C)
+    ws = workspace(device, n) if n else None
+    return ws, n
+
+
+class _ProbeLinear(Function):
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        _need_cuda(x, w, bias)
+        x = x.contiguous()
+        B, Fin = x.shape
+        C = w.shape[0]
+        y = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        ws, n = _probe_ws(x.device, B, Fin, C)
+        lib.call("avid_probe_linear_fwd", B, Fin, C, _p(x), _p(w.contiguous()), _p(bias), _p(y), _p(ws), n, _stream())
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        B, Fin = x.shape
+        C = w.shape[0]
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw = torch.empty((C, Fin), dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+        ws, n = _probe_ws(x.device, B, Fin, C)
+        lib.call("avid_probe_linear_bwd", B, Fin, C, _p(x), _p(w.contiguous()), _p(dy.contiguous()), _p(dx), _p(dw), _p(db),
+                 _p(ws), n, _stream())
+        return dx, dw, db
+
+
+def probe_linear(x, w, bias):
+    """The probe's ``Linear(Fin, C)`` on the matrix pipe (avid_probe_linear_fwd / _bwd): B <= 256, Fin <= 16384, any C."""
+    return _ProbeLinear.apply(x, w, bias)

@@ -928,3 +928,66 @@ class FinetuneStep(AdamStep):
         finally:
             self.model.train(was)
         return conf, loss, hits
+
+
+class ProbeStep(AdamStep):
+    """One linear-probe training step of a ``models.MOSTModel`` around this package's ``R2Plus1D`` (eval-action-recg-linear.py:
+    the summed cross-entropy of every tap's logits, Adam over ``model.parameters()`` with lr 1e-4 and weight decay 0): the
+    forward launch program runs the training-mode tower, pools every tap, runs the heads and ends in one ``avid_cls_loss`` per
+    tap (loss, top-1 / top-5 hits and ``dlogits`` on the device); the backward program holds the heads only; then one flat
+    Adam launch.  The tower is frozen: the flat parameter, gradient and moment buffers hold the classifiers' parameters only
+    (its BatchNorm running statistics still move: the reference trains the probe with the tower in training mode).  Nothing
+    synchronises the host.  Single process: the shipped config is not distributed.
+    ``set_lr`` and ``state_dict`` / ``load_state_dict`` are ``AdamStep``'s — ``torch.optim.Adam(model.parameters())``'s format,
+    the frozen tower parameters listed without state."""
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
+        super().__init__(model, lr, betas, eps, weight_decay, broadcast_buffers="off")
+        self.n_taps = len(model.classifiers)
+
+    def _plan(self, video):
+        from . import plan
+        pl = plan.probe_plan(self.model, video, need_grad=False)
+        if pl is None or plan._engine_flat(self, pl) is None:
+            raise NotImplementedError("ProbeStep: the model is outside the compiled probe programs (plan.ProbePlan: MOSTModel("
+                                      "R2Plus1D, AdaptiveMaxPool3d heads on conv2x..conv5x, use_bn, no l2_norm / dropout), fp32 "
+                                      "CUDA parameters, batch 2..256, training mode, no hooks)")
+        return pl
+
+    def step(self, video, labels):
+        """(losses [n_taps], hits [n_taps, 2] int64: top-1 / top-5 hits of the batch per tap) as device tensors."""
+        video = video.contiguous()
+        labels = labels.contiguous()
+        B = video.shape[0]
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
+            raise ValueError(f"ProbeStep.step: labels must be int64 [{B}] on {video.device} "
+                             f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
+        pl = self._plan(video)
+        out = torch.empty((self.n_taps, 8), dtype=torch.float32, device=video.device)     # plan.PROBE_OUT_BYTES per tap
+        dlogits = torch.empty((self.n_taps, B, pl.n_classes), dtype=torch.float32, device=video.device)
+        _, fa = pl.forward(video, self.flat.grad, True, labels=labels, out=out, dlogits=dlogits)
+        self._plan_backward(pl, fa, (video, None, dlogits, None))
+        self.t += 1
+        self._adam()
+        self._poll_errors()
+        return out[:, 0], out[:, 2:6].view(torch.int64)
+
+    def evaluate(self, video, labels, batch):
+        """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] in eval mode, fed through the model ``batch`` clips at a
+        time, then one ``avid_cls_loss`` per tap over all V * clips logits.  Returns device tensors
+        (confidence [n_taps, V, C], losses [n_taps], hits [n_taps, 2] int64)."""
+        from . import ops
+        clips = video.shape[1]
+        x = video.flatten(0, 1)
+        was = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                outs = [self.model(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)]
+                res = [ops.cls_loss(torch.cat([o[ft] for o in outs], 0), labels, clips)
+                       for ft in self.model.feat_names]
+        finally:
+            self.model.train(was)
+        return (torch.stack([r[1] for r in res]), torch.stack([r[0] for r in res]), torch.stack([r[2] for r in res]))

@@ -36,6 +36,7 @@ OP_WAIT, OP_MEMSET0, OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_WGRAD_GROUP, 
 OP_BN_FWD, OP_BN_BWD, OP_BN_POOL_FWD, OP_BN_POOL_BWD, OP_GPOOL_FWD, OP_GPOOL_BWD = 8, 9, 10, 11, 12, 13
 OP_RELU_BWD, OP_COLSUM, OP_WT_BATCH, OP_ADAM = 14, 15, 16, 17
 OP_DROPOUT_FWD, OP_DROPOUT_BWD, OP_CLS_LOSS, OP_CLS_LINEAR_FWD, OP_CLS_LINEAR_BWD = 18, 19, 20, 21, 22
+OP_ADAPTIVE_MAXPOOL, OP_BN1D_FWD, OP_BN1D_BWD, OP_PROBE_LINEAR_FWD, OP_PROBE_LINEAR_BWD = 23, 24, 25, 26, 27
 NREF = lib.INSTR_REFS
 Ref, Instr, StreamWs = lib.Ref, lib.Instr, lib.StreamWs
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -556,14 +557,17 @@ class Programs:
 
     adam_early = None        # gradient offset from which the optimizer may start before the backward program ends (Plan)
 
-    def _open(self, model, device, overlap_towers, trailing, group):
+    def _open(self, model, device, overlap_towers, trailing, group, frozen_ok=False):
         """The Builder of the model's parameters and the forward's leading records: what the backward needs but the forward
         does not — the gradient fill, the transposed / Winograd-transformed weights — runs on the trailing stream beside
-        the forward; the table is known only after the backward is compiled, so ``_finalize`` patches it in."""
+        the forward; the table is known only after the backward is compiled, so ``_finalize`` patches it in.
+        ``frozen_ok``: parameters without ``requires_grad`` are allowed (the linear probe's tower); the gradient buffer
+        then holds the trainable ones only, as ``parallel.FlatParams`` lays them out."""
         params = [p for p in model.parameters()]
         dry = device.type != "cuda"                  # (compile only: tests/test_plan_compile.py, no GPU)
-        if not all(p.requires_grad and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
+        if not all((p.requires_grad or frozen_ok) and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
             raise Unsupported("frozen / non-fp32 parameters")
+        params = [p for p in params if p.requires_grad]
         b = Builder(device, overlap_towers, trailing, group)
         b.set_params(params)
         self.device, self.params_fwd = device, params
@@ -949,7 +953,8 @@ def run(model, video, audio):
 _OP_NAMES = {0: "nop", 1: "wait", 2: "memset0", 3: "conv_fwd", 4: "conv_dgrad", 5: "conv_wgrad", 6: "wgrad_group", 7: "wgrad_item",
              8: "bn_fwd", 9: "bn_bwd", 10: "bn_pool_fwd", 11: "bn_pool_bwd", 12: "gpool_fwd", 13: "gpool_bwd", 14: "relu_bwd",
              15: "colsum", 16: "wt_batch", 17: "adam", 18: "dropout_fwd", 19: "dropout_bwd", 20: "cls_loss",
-             21: "cls_linear_fwd", 22: "cls_linear_bwd"}
+             21: "cls_linear_fwd", 22: "cls_linear_bwd", 23: "adaptive_maxpool", 24: "bn1d_fwd", 25: "bn1d_bwd",
+             26: "probe_linear_fwd", 27: "probe_linear_bwd"}
 
 
 def dump(prog, n):
@@ -1103,3 +1108,147 @@ def run_cls(model, video):
         return None
     seed, offset = (model.dropout.seed, model.dropout.next_offset()) if pl.drop_index is not None else (0, 0)
     return ClsFn.apply(video, pl, seed, offset, *pl.params_fwd)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# linear probe: models.linear_probe.MOSTModel (utils/eval_utils.py:217-242, 298-329 of the reference)
+# ------------------------------------------------------------------------------------------------------------------
+PROBE_OUT_BYTES = 32                                 # per tap in S_OUT: loss (f32) at 0, hits (2 x i64) at 8
+_PROBE_TAPS = ("conv2x", "conv3x", "conv4x", "conv5x")
+
+
+class ProbePlan(Programs):
+    """The compiled programs of one ``MOSTModel`` in its stock form around this package's ``R2Plus1D`` for one clip geometry.
+
+    Forward: the training-mode tower (``Builder.video_fwd``; the stage outputs it materialises anyway are the taps), then per
+    tap ``avid_adaptive_maxpool_fwd`` (channels-last tap -> the reference's flatten order), ``avid_bn1d_fwd_train`` and
+    ``avid_probe_linear_fwd`` — records [0, n_logits) — then one ``AVID_OP_CLS_LOSS`` with ``dlogits`` per tap (run by the step
+    engine only).  Backward, from ``dlogits``, per tap: ``avid_probe_linear_bwd`` (weight, bias and input gradient),
+    ``avid_bn1d_bwd`` (no input gradient: the pooled features are constants).  No tower record: the tower is frozen.  The
+    gradient buffer holds the classifiers' parameters only (``FlatParams`` over the trainable ones)."""
+
+    def __init__(self, model, vshape, device, trailing, group):
+        from models.linear_probe import MOSTModel, Classifier, ProbeBatchNorm1d, ProbeLinear
+        if type(model) is not MOSTModel or not len(model.classifiers):
+            raise Unsupported("linear probe outside the compiled pattern")
+        for c in model.classifiers:
+            if (type(c) is not Classifier or c.pool_size is None or c.use_dropout or c.l2_norm or not c.use_bn
+                    or type(c.pooling) is not torch.nn.AdaptiveMaxPool3d or c.feat_name not in _PROBE_TAPS
+                    or type(c.bn) is not ProbeBatchNorm1d or c.bn.momentum is None or not c.bn.affine
+                    or not c.bn.track_running_stats or type(c.classifier) is not ProbeLinear or c.classifier.bias is None):
+                raise Unsupported("probe head outside the compiled pattern")
+        if any(p.requires_grad for p in model.feature_extractor.parameters()):
+            raise Unsupported("the probe's tower is not frozen")
+        if list(model.feat_names) != [c.feat_name for c in model.classifiers]:
+            raise Unsupported("feat_names")
+        b = self._open(model, device, False, trailing, group, frozen_ok=True)
+        self.key = (tuple(vshape), trailing, group)
+        self.vshape, self.ashape = tuple(vshape), None
+        self.n_taps = len(model.classifiers)
+        # ------------------------------------------------------------------ forward
+        vm = model.feature_extractor
+        V, _ = b.video_fwd(vm, Sym((S_VIDEO, 0), vshape))
+        taps, k = {}, 0
+        for name in _PROBE_TAPS:
+            stage = getattr(vm, name)
+            k += len(stage) if isinstance(stage, torch.nn.Sequential) else 1
+            taps[name] = V["blocks"][k - 1][3]["h"]
+        B = vshape[0]
+        self.n_classes = C = model.classifiers[0].classifier.weight.shape[0]
+        if C > 1024:
+            raise Unsupported("more classes than avid_cls_loss takes")
+        heads, self.logits = [], []
+        for c in model.classifiers:
+            h = taps[c.feat_name]
+            if h.affine is not None:
+                raise Unsupported("tap not materialised")
+            _, T, H, W, Cc = h.shape
+            To, Ho, Wo = c.pool_size
+            Fd = Cc * To * Ho * Wo
+            bn, lin = c.bn, c.classifier
+            if (tuple(lin.weight.shape) != (C, Fd) or not lin.weight.is_contiguous() or bn.num_features != Fd or B < 2
+                    or B > 256 or Fd > 16384):
+                raise Unsupported("probe head geometry")
+            pooled, normed, save2 = b.fa.alloc(4 * B * Fd), b.fa.alloc(4 * B * Fd), b.fa.alloc(8 * Fd)
+            d = ConvDesc()
+            d.To, d.Ho, d.Wo = To, Ho, Wo
+            b.emit(OP_ADAPTIVE_MAXPOOL, d=d, i=(B, T, H, W, Cc), t=(h.ref, pooled))
+            b.emit(OP_BN1D_FWD, i=(B, Fd, 1), f=(bn.momentum, bn.eps),
+                   t=(pooled, b.ext(bn.weight), b.ext(bn.bias), b.ext(bn.running_mean), b.ext(bn.running_var), normed, save2,
+                      b.ext(bn.num_batches_tracked)))
+            logits = b.fa.alloc(4 * B * C)
+            b.emit(OP_PROBE_LINEAR_FWD, i=(B, Fd, C), t=(normed, b.ext(lin.weight), b.ext(lin.bias), logits))
+            self.logits.append(Sym(logits, (B, C)))
+            heads.append((c, Fd, pooled, normed, save2))
+        self.n_logits = len(b.fwd)
+        err = ClsPlan._err_ref(b, device)
+        for i, lg in enumerate(self.logits):
+            b.emit(OP_CLS_LOSS, i=(B, 1, C), f=(1.0,),
+                   t=(lg.ref, (S_LABELS, 0), (S_OUT, PROBE_OUT_BYTES * i), None, (S_OUT, PROBE_OUT_BYTES * i + 8),
+                      (S_DLOGITS, 4 * B * C * i), err))
+        # ------------------------------------------------------------------ backward
+        self._backward_begins(b)
+        for i, (c, Fd, pooled, normed, save2) in enumerate(heads):
+            bn, lin = c.bn, c.classifier
+            dn = b.ba.alloc(4 * B * Fd)
+            b.emit(OP_PROBE_LINEAR_BWD, i=(B, Fd, C),
+                   t=(normed, b.ext(lin.weight), (S_DLOGITS, 4 * B * C * i), dn, b.grad(lin.weight), b.grad(lin.bias)))
+            b._ready(b.S, lin.weight, lin.bias)
+            b.emit(OP_BN1D_BWD, i=(B, Fd, 0), f=(0.0, bn.eps),
+                   t=(pooled, dn, b.ext(bn.weight), save2, None, b.grad(bn.weight), b.grad(bn.bias)))
+            b._ready(b.S, bn.weight, bn.bias)
+        self._close(b)
+
+    def forward(self, video, grad_flat, zero_grad, labels=None, out=None, dlogits=None):
+        """Issue the forward program — with ``labels`` also the loss records, which write ``out`` ([n_taps] x PROBE_OUT_BYTES:
+        loss, hits) and ``dlogits [n_taps, B, C]``; returns ([logits per tap], arena)."""
+        fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out))
+        self._run(self.fwd_prog, 0, self.n_fwd if labels is not None else self.n_logits)
+        B, C = self.vshape[0], self.n_classes
+        return [fa[lg.ref[1]:lg.ref[1] + 4 * B * C].view(torch.float32).view(B, C) for lg in self.logits], fa
+
+
+class ProbeFn(torch.autograd.Function):
+    """video -> logits of every tap: ``MOSTModel.forward`` in training mode with the tower, the pools, the heads and the heads'
+    backward as two launch programs."""
+
+    @staticmethod
+    def forward(ctx, video, pl, *params):
+        logits, fa = pl.forward(video, None, False)
+        _remember(ctx, pl, fa, params)
+        ctx.video = video
+        return tuple(logits)
+
+    @staticmethod
+    def backward(ctx, *dlogits):
+        _check_backward(ctx)
+        pl, params = ctx.pl, ctx.params
+        B, C = pl.vshape[0], pl.n_classes
+        dl = torch.stack([d.contiguous() if d is not None else torch.zeros((B, C), dtype=torch.float32, device=ctx.video.device)
+                          for d in dlogits])
+        g = torch.empty(pl.gnumel, dtype=torch.float32, device=dl.device)
+        pl.backward(ctx.fa, (ctx.video, None, dl, None), g)
+        ctx.fa = None
+        views = pl.grad_views(g)
+        return (None, None) + tuple(views[id(p)] for p in params)
+
+
+def probe_plan(model, video, need_grad=True):
+    """The cached ``ProbePlan`` of this call (same staleness rules as ``run``), or None: the caller takes the per-layer path."""
+    if not eligible(model, video, need_grad=need_grad):
+        return None
+    trailing = (not lib.TIMING) and bool(ops.DEFER_WGRAD)
+    return _plan_for(model, ("probe", tuple(video.shape), video.device.index, trailing),
+                     lambda: ProbePlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD)))
+
+
+def run_probe(model, video):
+    """``MOSTModel.forward`` through the launch programs: {feat_name: logits}, or None (the caller takes the per-layer path)."""
+    if not eligible(model, video):
+        return None
+    video = video.contiguous()
+    pl = probe_plan(model, video)
+    if pl is None:
+        return None
+    logits = ProbeFn.apply(video, pl, *pl.params_fwd)
+    return dict(zip(model.feat_names, logits))

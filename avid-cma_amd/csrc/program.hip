@@ -68,6 +68,8 @@ static size_t instr_ws_bytes(const avid_instr* prog, int k, int end) {
     case AVID_OP_BN_BWD: return avid_bn_workspace_bytes(in.n[0], in.i[0]);
     case AVID_OP_BN_POOL_FWD:
     case AVID_OP_BN_POOL_BWD: return avid_bn_workspace_bytes((int64_t)in.i[0] * in.i[1] * in.i[2] * in.i[3], in.i[4]);
+    case AVID_OP_PROBE_LINEAR_FWD:
+    case AVID_OP_PROBE_LINEAR_BWD: return avid_probe_linear_workspace_bytes(in.i[0], in.i[1], in.i[2]);
     default: return 0;
   }
 }
@@ -321,6 +323,25 @@ extern "C" int avid_program_run(const avid_instr* prog, int begin, int end, void
         break;
       case AVID_OP_CLS_LINEAR_BWD:
         rc = avid_cls_linear_bwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), F(t[5]), s);
+        break;
+      case AVID_OP_ADAPTIVE_MAXPOOL:
+        rc = avid_adaptive_maxpool_fwd(in.i[0], in.i[1], in.i[2], in.i[3], in.i[4], in.d.To, in.d.Ho, in.d.Wo, F(t[0]), F(t[1]), s);
+        break;
+      case AVID_OP_BN1D_FWD: {
+        int64_t* counter = reinterpret_cast<int64_t*>(P(t[7]));
+        rc = in.i[2] ? avid_bn1d_fwd_train(in.i[0], in.i[1], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), in.f[0], in.f[1], F(t[5]),
+                                           F(t[6]), counter, s)
+                     : avid_bn1d_fwd_eval(in.i[0], in.i[1], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), in.f[1], F(t[5]), F(t[6]), s);
+        break;
+      }
+      case AVID_OP_BN1D_BWD:
+        rc = avid_bn1d_bwd(in.i[0], in.i[1], F(t[0]), F(t[1]), F(t[2]), F(t[3]), in.f[1], in.i[2], F(t[4]), F(t[5]), F(t[6]), s);
+        break;
+      case AVID_OP_PROBE_LINEAR_FWD:
+        rc = avid_probe_linear_fwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), w, wb, s);
+        break;
+      case AVID_OP_PROBE_LINEAR_BWD:
+        rc = avid_probe_linear_bwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), F(t[5]), w, wb, s);
         break;
       default:
         set_error("program record %d: unknown kind %d", k, in.op);

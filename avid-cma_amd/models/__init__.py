@@ -7,3 +7,4 @@ from .video import *  # noqa: F401,F403
 from .audio import *  # noqa: F401,F403
 from .av_wrapper import *  # noqa: F401,F403
 from .classification import *  # noqa: F401,F403
+from .linear_probe import *  # noqa: F401,F403

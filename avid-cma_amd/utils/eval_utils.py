@@ -1,10 +1,12 @@
-"""``utils.eval_utils`` for a run of the reference's ``eval-action-recg.py`` on this package: the reference's OWN module, executed
+"""``utils.eval_utils`` for a run of the reference's ``eval-action-recg.py`` / ``eval-action-recg-linear.py`` on this package: the reference's OWN module, executed
 unmodified from wherever it lies on ``sys.path`` (``main_utils``' approach), with one name resolved differently.
 
 ``build_model`` (utils/eval_utils.py:332-343 of the reference) looks up the module-level name ``ClassificationWrapper`` when it is
 CALLED; it is rebound here to ``models.classification.ClassificationWrapper`` — same constructor, ``state_dict`` and ``forward``,
-and a training call through the stock tree runs as compiled launch programs (avid_hip/plan.py: ``ClsPlan``).  ``MOSTModel``,
-``Classifier``, ``BatchWrapper`` and the rest stay the reference's.  ``AVID_DROPIN=0`` leaves the module as it is.
+and a training call through the stock tree runs as compiled launch programs (avid_hip/plan.py: ``ClsPlan``).  ``MOSTModel``
+and ``Classifier`` (the linear probe, model ``MOSTWrapper``; utils/eval_utils.py:217-242, 298-329) are rebound the same way to
+``models.linear_probe``: the heads' pooling, BatchNorm1d and Linear run on the kernels of csrc/probe.hip.  ``BatchWrapper``,
+the checkpoint managers and the rest stay the reference's.  ``AVID_DROPIN=0`` leaves the module as it is.
 
 Run the script through ``python -m avid_hip.run_reference eval-action-recg.py ...`` so that ``utils`` and ``models`` resolve
 here first."""
@@ -29,3 +31,4 @@ with open(REFERENCE_FILE, "rb") as _f:
 DROPIN = _os.environ.get("AVID_DROPIN", "1") != "0"
 if DROPIN:
     from models.classification import ClassificationWrapper  # noqa: E402,F811
+    from models.linear_probe import MOSTModel, Classifier  # noqa: E402,F811

@@ -394,6 +394,47 @@ int avid_cls_linear_fwd(int B, int Fin, int C, const float* x, const float* w, c
 int avid_cls_linear_bwd(int B, int Fin, int C, const float* x, const float* w, const float* dy, float* dx, float* dw,
                         float* db, avid_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Linear-probe heads (utils/eval_utils.py:217-242, 298-329: Classifier / MOSTModel; eval-action-recg-linear.py) — probe.hip.
+ * Version >= 140.
+ * ---------------------------------------------------------------------------------------------- */
+/* nn.AdaptiveMaxPool3d((To, Ho, Wo)) of a channels-last tap x [B,T,H,W,C] straight into the reference's flatten order:
+ * y [B][C][To][Ho][Wo] (= pooling(x_ncdhw).view(B, -1), utils/eval_utils.py:237-239), so classifier weights interchange with
+ * the reference's.  Output index i of an axis covers floor(i * In / Out) .. ceil((i + 1) * In / Out) (torch's rule), for any
+ * output size, Out > In included.  A NaN in a window makes its output NaN, as torch's does.  One workgroup owns a (b, to,
+ * channel chunk) and walks its rows once: every input element is fetched from HBM once (overlapping windows re-read it from
+ * cache).  NO argmax and NO backward: the reference pools under torch.no_grad(), nothing ever differentiates through it. */
+int avid_adaptive_maxpool_fwd(int B, int T, int H, int W, int C, int To, int Ho, int Wo, const float* x, float* y,
+                              avid_stream_t stream);
+/* nn.BatchNorm1d(F) over x [B, F] (utils/eval_utils.py:225,241), any F, B >= 2 in training mode.
+ * Train: batch mean / biased variance per feature (accumulated in double) -> save2 [2][F] = mean | invstd; running statistics
+ * updated in place (momentum, unbiased variance); num_batches_tracked (device int64, nullable) bumped by one;
+ * y = (x - mean) * invstd * gamma + beta.
+ * Eval: the running statistics; save2 (nullable) receives running_mean | invstd for a backward with frozen = 1.
+ * Backward: dx, dgamma, dbeta from (x, dy, gamma); dx nullable (the probe's input takes no gradient).  In training mode it
+ * rebuilds the batch statistics in double from x and eps (with two rows dx cancels to eps / (var + eps) of its terms, more
+ * than float32 statistics carry; save2 is then not read and may be NULL).
+ * frozen != 0: the statistics were constants (eval mode), read from save2: dx = gamma * invstd * dy.
+ * One workgroup owns 64 features and sums over the batch in a fixed order: bit-reproducible. */
+int avid_bn1d_fwd_train(int B, int F, const float* x, const float* gamma, const float* beta, float* running_mean,
+                        float* running_var, float momentum, float eps, float* y, float* save2,
+                        int64_t* num_batches_tracked, avid_stream_t stream);
+int avid_bn1d_fwd_eval(int B, int F, const float* x, const float* gamma, const float* beta, const float* running_mean,
+                       const float* running_var, float eps, float* y, float* save2, avid_stream_t stream);
+int avid_bn1d_bwd(int B, int F, const float* x, const float* dy, const float* gamma, const float* save2, float eps,
+                  int frozen, float* dx, float* dgamma, float* dbeta, avid_stream_t stream);
+/* The probe's Linear(Fin, C) on the matrix pipe (v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation), B <= 256,
+ * Fin <= 16384, any C:  y [B][C] = x [B][Fin] . w [C][Fin]^T + bias (nullable);  backward: dw [C][Fin] = dy^T . x,
+ * db [C] = column sums of dy (nullable), dx [B][Fin] = dy . w (nullable).  64 x 64 output tiles; the reduction axis is cut
+ * into slices of 512 (the forward has only ceil(B/64) * ceil(C/64) tiles), each slice's partial tile goes to ws and a second
+ * launch adds the slices in index order — no atomics, every output bit-reproducible from run to run.
+ * ws: avid_probe_linear_workspace_bytes(B, Fin, C) bytes (covers the forward and the backward). */
+size_t avid_probe_linear_workspace_bytes(int B, int Fin, int C);
+int avid_probe_linear_fwd(int B, int Fin, int C, const float* x, const float* w, const float* bias, float* y, void* ws,
+                          size_t ws_bytes, avid_stream_t stream);
+int avid_probe_linear_bwd(int B, int Fin, int C, const float* x, const float* w, const float* dy, float* dx, float* dw,
+                          float* db, void* ws, size_t ws_bytes, avid_stream_t stream);
+
 /* scores[b][j] = <bank[idx[b][j]], emb[b]> * inv_T — the gather + bmm of criterions/avid.py:57-71.
  * idx [bs][R] int64, bank [N][D], emb [bs][D], D in {64,128,256,512}.  rows_out (nullable,
  * [bs][R][D]) receives a snapshot of the gathered rows: the reference's autograd keeps the
@@ -578,6 +619,11 @@ enum {
   AVID_OP_CLS_LOSS = 20,     /* i0 V, i1 clips, i2 C; f0 grad_scale; t: logits labels loss conf hits dlogits err */
   AVID_OP_CLS_LINEAR_FWD = 21, /* i0 B, i1 Fin, i2 C; t: x w bias y */
   AVID_OP_CLS_LINEAR_BWD = 22, /* i0 B, i1 Fin, i2 C; t: x w dy dx dw db */
+  AVID_OP_ADAPTIVE_MAXPOOL = 23, /* i0..4 B T H W C; d.To d.Ho d.Wo the output size; t: x y */
+  AVID_OP_BN1D_FWD = 24,      /* i0 B, i1 F, i2 training; f0 momentum, f1 eps; t: x gamma beta running_mean running_var y save2 counter */
+  AVID_OP_BN1D_BWD = 25,      /* i0 B, i1 F, i2 frozen; f1 eps; t: x dy gamma save2 dx dgamma dbeta */
+  AVID_OP_PROBE_LINEAR_FWD = 26, /* i0 B, i1 Fin, i2 C; t: x w bias y */
+  AVID_OP_PROBE_LINEAR_BWD = 27, /* i0 B, i1 Fin, i2 C; t: x w dy dx dw db */
   AVID_OP_COUNT_
 };
 
