@@ -55,6 +55,16 @@ class WtDesc(C.Structure):
                 ("mode", C.c_int32)]
 
 
+class AugDesc(C.Structure):
+    """Mirror of ``avid_aug_desc`` (include/avid_hip.h): one clip of ``avid_clip_augment``."""
+    _fields_ = [("frames", C.c_void_p), ("factor", C.c_double * 4)] + [(n, C.c_int32) for n in (
+        "T", "H", "W", "i", "j", "h", "w", "RH", "RW", "y1", "x1", "flip", "nops")] + [("ops", C.c_int32 * 4),
+                                                                                      ("reserved", C.c_int32)]
+
+
+AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE, AUG_CONTRAST = 0, 1, 2, 3
+
+
 class Ref(C.Structure):
     """Mirror of ``avid_ref``: (slot, byte offset); slot < 0 = NULL."""
     _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("off", C.c_int64)]
@@ -147,6 +157,8 @@ SIGNATURES = {
     "avid_bn_relu_maxpool_bwd": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                       _vp]),
     "avid_clip_normalize": (_i, [_i, _i, _i, _i, _vp, C.POINTER(_f), C.POINTER(_f), _vp, _vp]),
+    "avid_clip_augment_workspace_bytes": (_sz, [_i, C.POINTER(AugDesc), _i, _i, _i]),
+    "avid_clip_augment": (_i, [_i, C.POINTER(AugDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp]),
     "avid_logspec_basis_floats": (_sz, [_i]),
     "avid_logspec_basis": (_i, [_i, _vp, _vp]),
     "avid_logspec_workspace_bytes": (_sz, [_i, _i, _i]),

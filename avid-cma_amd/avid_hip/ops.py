@@ -1075,6 +1075,49 @@ def clip_normalize(frames, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)
     return out
 
 
+def clip_augment(clips, descs, num_frames, out_size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """The reference's per-frame PIL augmentation + ``ClipToTensor`` + ``Normalize`` for a whole batch in one call
+    (avid_clip_augment, bit-identical to Pillow).  ``clips``: a list of uint8 ``[T_b, H_b, W_b, 3]`` GPU tensors (sizes may
+    differ) or one dense ``[B, T, H, W, 3]`` tensor; ``descs``: one mapping or object per clip with ``box`` (i, j, h, w),
+    ``resize`` (RH, RW), ``window`` (y1, x1), ``flip`` and ``ops`` [(AUG_* code, factor), ...] (datasets/gpu_video.py:
+    ClipAugParams); ``out_size`` (ch, cw) -> fp32 ``[B, 3, num_frames, ch, cw]``; output frame t is source frame t % T_b.
+    No gradient."""
+    if isinstance(clips, torch.Tensor):
+        if clips.dim() != 5:
+            raise AvidHipError("clip_augment: a dense batch must be uint8 [B, T, H, W, 3]")
+        clips = list(clips.unbind(0))
+    clips = list(clips)
+    _need_cuda(*clips)
+    if len(clips) == 0 or len(clips) != len(descs):
+        raise AvidHipError(f"clip_augment: {len(clips)} clips but {len(descs)} descriptors")
+    dev = clips[0].device
+    ch, cw = int(out_size[0]), int(out_size[1])
+    arr = (lib.AugDesc * len(clips))()
+    for b, (f, p) in enumerate(zip(clips, descs)):
+        if f.dim() != 4 or f.shape[-1] != 3 or f.dtype != torch.uint8 or not f.is_contiguous() or f.device != dev:
+            raise AvidHipError(f"clip_augment: clip {b} must be a contiguous uint8 [T, H, W, 3] tensor on {dev}")
+        get = p.get if isinstance(p, dict) else lambda k, _p=p: getattr(_p, k)
+        d, ops_ = arr[b], list(get("ops"))
+        d.frames = f.data_ptr()
+        d.T, d.H, d.W = f.shape[0], f.shape[1], f.shape[2]
+        d.i, d.j, d.h, d.w = (int(v) for v in get("box"))
+        d.RH, d.RW = (int(v) for v in get("resize"))
+        d.y1, d.x1 = (int(v) for v in get("window"))
+        d.flip = 1 if get("flip") else 0
+        if len(ops_) > 4:
+            raise AvidHipError(f"clip_augment: clip {b}: {len(ops_)} colour operations (at most 4)")
+        d.nops = len(ops_)
+        for k, (code, factor) in enumerate(ops_):
+            d.ops[k], d.factor[k] = int(code), float(factor)
+    need = lib.raw("avid_clip_augment_workspace_bytes")(len(clips), arr, int(num_frames), ch, cw)
+    out = torch.empty((len(clips), 3, int(num_frames), ch, cw), dtype=torch.float32, device=dev)
+    ws = workspace(dev, max(need, 16))
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    lib.call("avid_clip_augment", len(clips), arr, int(num_frames), ch, cw, m, s, _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # audio front end (SURVEY §8(f) rank 4)
 # ------------------------------------------------------------------------------------------------

@@ -538,6 +538,32 @@ int avid_adam_flat(int64_t n, float* p, const float* g, float* m, float* v, floa
 int avid_clip_normalize(int B, int T, int H, int W, const uint8_t* frames, const float* mean3, const float* std3,
                         float* out, avid_stream_t stream);
 
+/* Clip augmentation on the GPU: the reference's per-frame PIL chain (datasets/preprocessing.py:15-113 through
+ * utils/videotransforms/video_transforms.py) for a ragged batch of decoded clips, bit-identical to Pillow:
+ *   crop box (i, j, h, w) of the source -> Pillow's two-pass BILINEAR resize to RH x RW (horizontal first, rounded to uint8)
+ *   -> window (y1, x1, ch, cw) of that image -> optional horizontal flip -> nops colour operations in the given order
+ *   (ImageEnhance.Brightness / Color / Contrast = Image.blend in unfused fp32; torchvision's hue shift through Pillow's
+ *   RGB <-> HSV) -> ((u / 255) - mean) / std as avid_clip_normalize.  Output frame t reads source frame t % T.
+ * One descriptor per clip; frames: DEVICE pointer to uint8 [T][H][W][3]; factor[k] belongs to ops[k]. */
+enum { AVID_AUG_BRIGHTNESS = 0, AVID_AUG_SATURATION = 1, AVID_AUG_HUE = 2, AVID_AUG_CONTRAST = 3 };
+typedef struct avid_aug_desc {
+  const uint8_t* frames;
+  double factor[4];
+  int32_t T, H, W;
+  int32_t i, j, h, w;
+  int32_t RH, RW;
+  int32_t y1, x1;
+  int32_t flip;
+  int32_t nops, ops[4];
+  int32_t reserved;
+} avid_aug_desc;
+/* descs: HOST array of B descriptors; out [B][3][num_frames][ch][cw] fp32; mean3 / std3: HOST pointers to 3 floats.
+ * The resample tables are built on the host in double, staged in pinned memory and copied into ws on the stream (no host
+ * synchronisation); ws also holds the uint8 intermediate and the per-frame grey sums of the clips that use contrast. */
+size_t avid_clip_augment_workspace_bytes(int B, const avid_aug_desc* descs, int num_frames, int ch, int cw);
+int avid_clip_augment(int B, const avid_aug_desc* descs, int num_frames, int ch, int cw, const float* mean3,
+                      const float* std3, float* out, void* ws, size_t ws_bytes, avid_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Audio front end on the GPU — datasets/preprocessing.py:158-186 LogSpectrogram:
  * out[b][0][t][f] = z-score( top_db-floored dB( bin-pair mean( |STFT(sig[b])|^2 ) ) ), STFT = librosa.stft
