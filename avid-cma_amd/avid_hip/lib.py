@@ -37,6 +37,17 @@ class InAffine(C.Structure):
     _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p), ("relu", C.c_int32)]
 
 
+class OutAffine(C.Structure):
+    """Mirror of ``avid_out_affine`` (include/avid_hip.h): the eval-mode BatchNorm (+ReLU) a convolution applies to its output."""
+    _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p), ("relu", C.c_int32)]
+
+
+class BnEvalItem(C.Structure):
+    """Mirror of ``avid_bn_eval_item`` (include/avid_hip.h): one BatchNorm of ``avid_bn_eval_coeffs_batched``."""
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
+                ("out", C.c_void_p), ("eps", C.c_float), ("C", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     """Mirror of ``avid_conv_desc`` (include/avid_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -124,6 +135,9 @@ SIGNATURES = {
     "avid_conv_takes_in_affine": (_i, [_dp]),
     "avid_conv_fwd_in": (_i, [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "avid_debug_in_affine_launches": (C.c_longlong, [_i]),
+    "avid_conv_takes_out_affine": (_i, [_dp]),
+    "avid_conv_fwd_out": (_i, [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avid_debug_out_affine_launches": (C.c_longlong, []),
     "avid_conv_dgrad_workspace_bytes": (_sz, [_dp]),
     "avid_conv_dgrad_bn_rows": (_i, [_dp]),
     "avid_conv_dgrad": (_i, [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -151,6 +165,9 @@ SIGNATURES = {
     "avid_bn_workspace_bytes": (_sz, [_i64, _i]),
     "avid_bn_fwd_train": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "avid_bn_fwd_eval": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
+    "avid_bn_eval_coeffs_batched": (_i, [_i, _vp, _vp]),
+    "avid_bn_apply_eval": (_i, [_i64, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "avid_bn_relu_maxpool_fwd_eval": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avid_bn_bwd": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "avid_bn_relu_maxpool_fwd": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _i, _vp, _sz, _vp]),

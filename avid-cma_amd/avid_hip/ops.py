@@ -321,6 +321,8 @@ def _desc_cached(xs, cin, cout, k, stride, pad, channel_first):
         # the layer can read the INPUT of the BatchNorm (+ReLU) in front of it and apply the map while staging (forward and weight
         # gradient): avid_conv_fwd_in / avid_conv_wgrad_in — the launch programs then never write the normalised tensor
         d.in_affine = bool(lib.raw("avid_conv_takes_in_affine")(C.byref(d)))
+        # inference: the layer's forward can apply the eval-mode BatchNorm (+ReLU) of its OUTPUT in the epilogue (avid_conv_fwd_out)
+        d.out_affine = bool(lib.raw("avid_conv_takes_out_affine")(C.byref(d)))
         _DESC_CACHE[key] = hit
     return hit
 
@@ -353,6 +355,16 @@ def wino2_configure(min_rounds_x10=-1):
     ``wino2_kernel``, negative = environment / default (layers with >= 1.5 rounds of 64-tile units)."""
     lib.call("avid_wino2_configure", int(min_rounds_x10))
     _dispatch_changed()
+
+
+def tconv_configure(mode=-1):
+    """Which layers take ``tconv64_kernel`` / ``twgrad64_kernel`` (``avid_tconv_configure``: 0 none, 1 layers with three rounds
+    of tiles, 2 every layer that can, negative = environment / default).  The answer decides ``in_affine`` / ``out_affine`` of the
+    cached per-layer plans and with them the records of a compiled launch program: both are dropped / re-keyed, so no program
+    meets a changed answer.  Returns the effective mode."""
+    got = int(lib.raw("avid_tconv_configure")(int(mode)))
+    _dispatch_changed()
+    return got
 
 
 def set_cu_budget(cus=0):
@@ -889,6 +901,23 @@ def conv_fwd_in(x, w, stride, pad, scale, shift, relu=True, addend=None, bn_stat
     return (y, stats) if bn_stats else y
 
 
+def conv_fwd_out(x, w, stride, pad, out_scale, out_shift, out_relu=True, addend=None, in_scale=None, in_shift=None, in_relu=True):
+    """``avid_conv_fwd_out`` as a plain call (no autograd): [ReLU](bn_eval(conv(x') [+ addend])) with the eval-mode BatchNorm of the
+    layer's OUTPUT given as its scale / shift vectors and applied in the convolution's epilogue; x' = x, or ReLU?(x * in_scale +
+    in_shift) as in ``conv_fwd_in``.  What the inference programs emit for conv2x's temporal layers.  Raises for a layer that
+    cannot (``_desc_cached(...)[0].out_affine``)."""
+    _need_cuda(x, w, addend, out_scale, out_shift, in_scale, in_shift)
+    B, Ti, Hi, Wi, cin = x.shape
+    d, nb, _, _, _ = _desc_cached((B, Ti, Hi, Wi), cin, w.shape[0], _kdims(w), tuple(stride), tuple(pad), False)
+    y = torch.empty((B, d.To, d.Ho, d.Wo, w.shape[0]), dtype=torch.float32, device=x.device)
+    ws = workspace(x.device, nb) if nb else None
+    aff = lib.InAffine(in_scale.data_ptr(), in_shift.data_ptr(), int(bool(in_relu))) if in_scale is not None else None
+    out = lib.OutAffine(out_scale.data_ptr(), out_shift.data_ptr(), int(bool(out_relu)))
+    lib.call("avid_conv_fwd_out", C.byref(d), _p(x), C.byref(aff) if aff is not None else None, _p(w), _p(_fwd_u(w, d)), _p(addend),
+             None, 0, C.byref(out), _p(y), None, _p(ws), ws.numel() if ws is not None else 0, _stream())
+    return y
+
+
 def conv_wgrad_in(x, dy, w_like, stride, pad, scale, shift, relu=True):
     """``avid_conv_wgrad_in`` as a plain call: the weight gradient of conv(ReLU?(x * scale + shift), w) given dy."""
     _need_cuda(x, dy, scale, shift)
@@ -994,6 +1023,54 @@ class _BatchNormCL(Function):
             _grad_done(sb)
             dbeta = None
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
+
+
+def bn_eval_coeffs(bns):
+    """The eval-mode coefficient vectors of several BatchNorms in ONE launch (``avid_bn_eval_coeffs_batched``).  ``bns``: a list
+    of (gamma, beta, running_mean, running_var, eps); returns one ``[4, C]`` tensor each — mean, invstd, scale, shift, the bits
+    ``avid_bn_fwd_eval`` writes to its ``save4``."""
+    dev = bns[0][0].device
+    outs, recs = [], []
+    for gamma, beta, rm, rv, eps in bns:
+        _need_cuda(gamma, beta, rm, rv)
+        o = torch.empty((4, gamma.numel()), dtype=torch.float32, device=dev)
+        outs.append(o)
+        recs.append(lib.BnEvalItem(gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), o.data_ptr(), float(eps),
+                                   gamma.numel()))
+    table = bn_eval_table(recs, dev)
+    lib.call("avid_bn_eval_coeffs_batched", len(recs), _p(table), _stream())
+    return outs
+
+
+def bn_eval_table(recs, device, out=None):
+    """``avid_bn_eval_item`` records as a device table (a uint8 tensor; ``out``: write into this one)."""
+    arr = (lib.BnEvalItem * len(recs))(*recs)
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    if out is None:
+        return host.to(device)
+    out[:host.numel()].copy_(host)
+    return out
+
+
+def bn_apply_eval(x, scale, shift, relu=False):
+    """[ReLU](x * scale + shift) with an eval-mode BatchNorm's coefficient vectors (``avid_bn_apply_eval``): the apply half of
+    ``avid_bn_fwd_eval``."""
+    _need_cuda(x, scale, shift)
+    if not x.is_contiguous():
+        raise AvidHipError("bn: x must be contiguous channels-last")
+    Cc = x.shape[-1]
+    y = torch.empty_like(x)
+    lib.call("avid_bn_apply_eval", x.numel() // Cc, Cc, _p(x), _p(scale), _p(shift), int(bool(relu)), _p(y), _stream())
+    return y
+
+
+def bn_relu_maxpool_eval(x, scale, shift):
+    """The video stem's tail in eval mode: maxpool_hw3s2(ReLU(x * scale + shift)) in one pass (``avid_bn_relu_maxpool_fwd_eval``)."""
+    _need_cuda(x, scale, shift)
+    B, T, H, W, Cc = x.shape
+    y = torch.empty((B, T, (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1, Cc), dtype=torch.float32, device=x.device)
+    lib.call("avid_bn_relu_maxpool_fwd_eval", B, T, H, W, Cc, _p(x), _p(scale), _p(shift), _p(y), _stream())
+    return y
 
 
 def batch_norm_cl(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, relu=False,

@@ -835,6 +835,43 @@ class Adam(torch.optim.Optimizer):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Inference: an eval-mode forward as one launch program
+# ---------------------------------------------------------------------------------------------------------------------
+class Inference:
+    """``Inference(model)(*inputs)`` returns what ``model.eval()(*inputs)`` returns under ``torch.no_grad()`` — a tensor for
+    ``R2Plus1D`` and ``ClassificationWrapper``, the tuple of embeddings for ``AV_Wrapper``, whatever the model returns otherwise —
+    bit for bit, without touching the modules' ``training`` flags and without synchronising the host.
+
+    Models the inference compiler knows (``plan.EvalPlan``) run as ONE launch program per input geometry: the eval-mode
+    BatchNorms' coefficients from one launch, conv2x's BatchNorms inside the temporal convolutions, the stem's tail in one
+    pass, activations in a recycled arena.  Anything else — hooks on a module, frozen BatchNorm parameters, another model,
+    CPU or non-fp32 tensors, a stream capture, ``AVID_EVAL_PLAN=0`` — takes the per-layer path.  ``used_programs`` says which
+    path the last call took.  ``model(x)`` in eval mode is not affected: the programs are reached through this class (and the
+    step engines' ``evaluate``) only."""
+
+    def __init__(self, model):
+        self.model = model
+        self.used_programs = None
+
+    def __call__(self, *inputs):
+        from . import plan
+        out = plan.run_eval(self.model, *inputs)
+        self.used_programs = out is not None
+        return out if out is not None else self._per_layer(*inputs)
+
+    def _per_layer(self, *inputs):
+        mods = [m for m in self.model.modules() if m.training]
+        for m in mods:
+            m.training = False
+        try:
+            with torch.no_grad():
+                return self.model(*inputs)
+        finally:
+            for m in mods:
+                m.training = True
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Action-recognition fine-tuning (eval-action-recg.py: run_phase 'train' / 'test_dense', the warm-up epochs of the classifier)
 # ---------------------------------------------------------------------------------------------------------------------
 class FinetuneStep(AdamStep):
@@ -922,8 +959,9 @@ class FinetuneStep(AdamStep):
         was = self.model.training
         self.model.eval()
         try:
+            infer = Inference(self.model)           # one inference program per distinct chunk size (plans are cached on the model)
             with torch.no_grad():
-                logits = torch.cat([self.model(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)], 0)
+                logits = torch.cat([infer(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)], 0)
                 loss, conf, hits, _ = ops.cls_loss(logits, labels, clips)
         finally:
             self.model.train(was)
@@ -984,8 +1022,9 @@ class ProbeStep(AdamStep):
         was = self.model.training
         self.model.eval()
         try:
+            infer = Inference(self.model)           # (the probe's frozen tower stays on the per-layer path: plan.EvalBuilder.coeffs)
             with torch.no_grad():
-                outs = [self.model(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)]
+                outs = [infer(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)]
                 res = [ops.cls_loss(torch.cat([o[ft] for o in outs], 0), labels, clips)
                        for ft in self.model.feat_names]
         finally:

@@ -37,6 +37,7 @@ OP_BN_FWD, OP_BN_BWD, OP_BN_POOL_FWD, OP_BN_POOL_BWD, OP_GPOOL_FWD, OP_GPOOL_BWD
 OP_RELU_BWD, OP_COLSUM, OP_WT_BATCH, OP_ADAM = 14, 15, 16, 17
 OP_DROPOUT_FWD, OP_DROPOUT_BWD, OP_CLS_LOSS, OP_CLS_LINEAR_FWD, OP_CLS_LINEAR_BWD = 18, 19, 20, 21, 22
 OP_ADAPTIVE_MAXPOOL, OP_BN1D_FWD, OP_BN1D_BWD, OP_PROBE_LINEAR_FWD, OP_PROBE_LINEAR_BWD = 23, 24, 25, 26, 27
+OP_BN_EVAL_COEFFS, OP_BN_EVAL_APPLY, OP_BN_POOL_FWD_EVAL, OP_BN_EVAL_DIRECT, OP_MAXPOOL_FWD = 28, 29, 30, 31, 32   # inference programs only
 NREF = lib.INSTR_REFS
 Ref, Instr, StreamWs = lib.Ref, lib.Instr, lib.StreamWs
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
@@ -49,6 +50,7 @@ NULL = (-1, 0)
 ST_MAIN, ST_AUDIO, ST_TRAIL, ST_COMM = 0, 1, 2, 3
 
 ENABLED = os.environ.get("AVID_PLAN", "1") == "1"
+EVAL_ENABLED = os.environ.get("AVID_EVAL_PLAN", "1") != "0"      # 0: parallel.Inference always takes the per-layer path
 
 
 class Unsupported(Exception):
@@ -288,21 +290,22 @@ class Builder:
         L["h"] = Sym(y, ysh, bn=rec, affine=(s4, 1, Cc)) if defer else Sym(h, ysh, bn=rec)
         return L
 
-    def linear_fwd(self, lin, x, relu):
-        """nn.Linear (+ReLU) as a 1x1x1 convolution over [B,1,1,1,C] (ops.linear)."""
+    def linear_fwd(self, lin, x, relu, arena=None):
+        """nn.Linear (+ReLU) as a 1x1x1 convolution over [B,1,1,1,C] (ops.linear).  ``arena``: where the output goes (default:
+        the forward arena)."""
         w = lin.weight
         B, Cin = x.shape
         d = ops._desc_cached((B, 1, 1, 1), w.shape[1], w.shape[0], (1, 1, 1), (1, 1, 1), (0, 0, 0), False)[0]
         if Cin != w.shape[1] or not ops.weight_layout_ok(w):
             raise Unsupported("linear")
-        y = self.fa.alloc(4 * B * d.Cout)
+        y = (arena or self.fa).alloc(4 * B * d.Cout)
         self.emit(OP_CONV_FWD, d=d, i=(1 if relu else 0,), t=(x.ref, self.ext(w), None, None, self.ext(lin.bias), y, None))
         return {"lin": lin, "d": d, "x": x, "y": Sym(y, (B, d.Cout)), "relu": relu, "w": w}
 
-    def gpool_fwd(self, x):
+    def gpool_fwd(self, x, arena=None):
         B, Cc = x.shape[0], x.shape[-1]
         S = x.numel // (B * Cc)
-        y = self.fa.alloc(4 * B * Cc)
+        y = (arena or self.fa).alloc(4 * B * Cc)
         am = self.fa.alloc(4 * B * Cc)
         self.emit(OP_GPOOL_FWD, i=(B, S, Cc), t=(x.ref, y, am))
         return {"x": x, "y": Sym(y, (B, Cc)), "am": am, "S": S}
@@ -954,7 +957,8 @@ _OP_NAMES = {0: "nop", 1: "wait", 2: "memset0", 3: "conv_fwd", 4: "conv_dgrad", 
              8: "bn_fwd", 9: "bn_bwd", 10: "bn_pool_fwd", 11: "bn_pool_bwd", 12: "gpool_fwd", 13: "gpool_bwd", 14: "relu_bwd",
              15: "colsum", 16: "wt_batch", 17: "adam", 18: "dropout_fwd", 19: "dropout_bwd", 20: "cls_loss",
              21: "cls_linear_fwd", 22: "cls_linear_bwd", 23: "adaptive_maxpool", 24: "bn1d_fwd", 25: "bn1d_bwd",
-             26: "probe_linear_fwd", 27: "probe_linear_bwd"}
+             26: "probe_linear_fwd", 27: "probe_linear_bwd", 28: "bn_eval_coeffs", 29: "bn_eval_apply", 30: "bn_pool_fwd_eval",
+             31: "bn_eval_direct", 32: "maxpool_fwd"}
 
 
 def dump(prog, n):
@@ -1252,3 +1256,408 @@ def run_probe(model, video):
         return None
     logits = ProbeFn.apply(video, pl, *pl.params_fwd)
     return dict(zip(model.feat_names, logits))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# inference: eval-mode forward programs (parallel.Inference, the engines' evaluate())
+# ------------------------------------------------------------------------------------------------------------------
+class EvalArena:
+    """The activation arena of an inference program while it is compiled: ``alloc`` hands out VIRTUAL offsets that never
+    overlap; ``EvalPlan._recycle`` then maps every buffer to a physical offset, re-using the bytes of buffers whose last
+    reader has been emitted on the same stream (nothing runs backward, nothing trails on another stream)."""
+
+    def __init__(self, slot):
+        self.slot, self.size, self.bufs = slot, 0, []
+
+    def alloc(self, nbytes):
+        off, n = self.size, _align(max(int(nbytes), 4))
+        self.size += n
+        self.bufs.append((off, n))
+        return (self.slot, off)
+
+
+class EvalBuilder(Builder):
+    """The eval form of the forward emitters: BatchNorms use their running statistics — every coefficient vector comes out of ONE
+    launch at the head of the program (``AVID_OP_BN_EVAL_COEFFS``), a (3,1,1) layer of conv2x applies its own BatchNorm in its
+    epilogue (``d.out_affine``) and the one in front of it while staging (``d.in_affine``), everything else is a convolution
+    followed by ``AVID_OP_BN_EVAL_APPLY``; the stem's tail is one pass.  No statistics, no argmax of the stem's pool, no saved
+    vectors for a backward.  Each record is the call the per-layer path makes in eval mode with trainable BatchNorm parameters
+    (``avid_bn_fwd_eval`` with ``save4``: y = fma(x, scale, shift)) or a fusion that is bit-identical to it.
+    A BatchNorm whose weight and bias take NO gradient (the linear probe's frozen tower) is another case: the per-layer path then
+    calls ``avid_bn_fwd_eval`` without ``save4``, which evaluates ``(x - mean) * invstd * gamma + beta`` — other bits than the
+    fma.  Such a BatchNorm is never fused: it is one ``AVID_OP_BN_EVAL_DIRECT`` record (the same call), the stem's pool behind it
+    an ``AVID_OP_MAXPOOL_FWD`` record, and it has no entry in the coefficient table."""
+
+    def __init__(self, device):
+        super().__init__(device, False, False, False)
+        self.fa, self.oa = EvalArena(S_FWD), Arena(S_OUT)
+        self.bn_recs, self.bn_off = [], {}         # (BatchNorm module, aux offset of its [4][C] vectors)
+
+    @staticmethod
+    def frozen(bn):
+        """The per-layer path computes this BatchNorm without coefficient vectors (ops._BatchNormCL.forward: no gradient can flow)."""
+        return not (bn.weight.requires_grad or bn.bias.requires_grad)
+
+    def bn_direct(self, bn, x, M, Cc, relu=1):
+        """The unfused eval-mode BatchNorm (+ReLU) of a frozen BatchNorm: x -> a new tensor."""
+        from models.network_blocks import BatchNormCL
+        if type(bn) is not BatchNormCL or bn.weight.dtype != torch.float32:
+            raise Unsupported("BatchNorm")
+        h = self.fa.alloc(4 * M * Cc)
+        self.emit(OP_BN_EVAL_DIRECT, n=(M,), i=(Cc, relu), f=(0.0, bn.eps),
+                  t=(x, self.ext(bn.weight), self.ext(bn.bias), self.ext(bn.running_mean), self.ext(bn.running_var), h))
+        return h
+
+    def coeffs(self, bn):
+        from models.network_blocks import BatchNormCL
+        off = self.bn_off.get(id(bn))
+        if off is None:
+            if type(bn) is not BatchNormCL or bn.weight.dtype != torch.float32:
+                raise Unsupported("BatchNorm")
+            off = self.bn_off[id(bn)] = self.aux_size
+            self.bn_recs.append((bn, off))
+            self.aux_size += _align(16 * bn.num_features)
+        return (S_AUX, off)
+
+    def conv_bn_fwd(self, conv, bn, x, addend=None, next_conv=None):
+        """ReLU(bn_eval(conv(x) [+ addend])); returns the Sym of the result (``affine`` set: its only consumer applies the map)."""
+        w = conv.weight
+        d = self.desc(x.shape, w, conv.stride3, conv.padding3, conv.channel_first)[0]
+        ysh = (d.B, d.To, d.Ho, d.Wo, d.Cout)
+        M, Cc = d.B * d.To * d.Ho * d.Wo, d.Cout
+        xa = x.affine
+        if xa is not None and not d.in_affine:
+            raise Unsupported("a tensor with a pending BatchNorm reached a layer that cannot apply it")
+        iv = (0, 0, 0) if xa is None else (0, 2 if xa[1] else 1, xa[2])
+        t = [x.ref, self.ext(w), self.fwd_u(w, d), addend.ref if addend is not None else None, None]
+        xr = None if xa is None else xa[0]
+        if self.frozen(bn):                        # convolution, then the call the per-layer path makes: nothing fused
+            y = self.fa.alloc(4 * M * Cc)
+            self.emit(OP_CONV_FWD, d=d, i=iv, t=t + [y, None, xr])
+            return Sym(self.bn_direct(bn, y, M, Cc), ysh)
+        c4 = self.coeffs(bn)
+        if d.out_affine:
+            h = self.fa.alloc(4 * M * Cc)
+            self.emit(OP_CONV_FWD, d=d, i=iv + (2,), t=t + [h, None, xr, c4])
+            return Sym(h, ysh)
+        y = self.fa.alloc(4 * M * Cc)
+        self.emit(OP_CONV_FWD, d=d, i=iv, t=t + [y, None, xr])
+        if next_conv is not None and addend is None:
+            nw = next_conv.weight
+            if (ops.weight_layout_ok(nw) and nw.dtype == torch.float32 and nw.shape[1] == Cc and not next_conv.channel_first
+                    and self.desc(ysh, nw, next_conv.stride3, next_conv.padding3, False)[0].in_affine):
+                return Sym(y, ysh, affine=(c4, 1, Cc))
+        h = self.fa.alloc(4 * M * Cc)
+        self.emit(OP_BN_EVAL_APPLY, n=(M,), i=(Cc, 1), t=(y, c4, h))
+        return Sym(h, ysh)
+
+    def r2p1d_block_fwd(self, blk, x):
+        from models.network_blocks import BasicR2P1DBlock
+        if type(blk) is not BasicR2P1DBlock:
+            raise Unsupported(type(blk).__name__)
+        h = self.conv_bn_fwd(blk.spt_conv1, blk.spt_bn1, x, next_conv=blk.tmp_conv1)
+        h = self.conv_bn_fwd(blk.tmp_conv1, blk.tmp_bn1, h)
+        h = self.conv_bn_fwd(blk.spt_conv2, blk.spt_bn2, h, next_conv=blk.tmp_conv2)
+        res = x
+        if blk.res:                                # the 1x1x1 strided residual convolution: a record of its own
+            rc = blk.res_conv
+            dr = self.desc(x.shape, rc.weight, rc.stride3, rc.padding3, False)[0]
+            yr = self.fa.alloc(4 * dr.B * dr.To * dr.Ho * dr.Wo * dr.Cout)
+            self.emit(OP_CONV_FWD, d=dr, i=(0,), t=(x.ref, self.ext(rc.weight), self.fwd_u(rc.weight, dr), None, None, yr, None))
+            res = Sym(yr, (dr.B, dr.To, dr.Ho, dr.Wo, dr.Cout))
+        return None, self.conv_bn_fwd(blk.tmp_conv2, blk.out_bn, h, addend=res)
+
+    def video_fwd(self, vm, x, after_stem=None, arena=None):
+        """The tower; ``arena``: where the pooled output goes.  Returns ({stage name: Sym of its output}, pooled Sym)."""
+        from models.video import R2Plus1D
+        from models.network_blocks import BatchNormCL, ConvCL
+        if type(vm) is not R2Plus1D:
+            raise Unsupported(type(vm).__name__)
+        conv, bn = vm.conv1[0], vm.conv1[1]
+        if type(conv) is not ConvCL or type(bn) is not BatchNormCL:
+            raise Unsupported("video stem")
+        w = conv.weight
+        d = self.desc(x.shape, w, conv.stride3, conv.padding3, True)[0]
+        B, T, H, W, Cc = d.B, d.To, d.Ho, d.Wo, d.Cout
+        y = self.fa.alloc(4 * B * T * H * W * Cc)
+        self.emit(OP_CONV_FWD, d=d, i=(0,), t=(x.ref, self.ext(w), None, None, None, y, None))
+        Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+        p = self.fa.alloc(4 * B * T * Ho * Wo * Cc)
+        if self.frozen(bn):                        # bn -> maxpool as the per-layer path runs them (its pool writes an argmax)
+            am = self.fa.alloc(B * T * Ho * Wo * Cc)
+            self.emit(OP_MAXPOOL_FWD, i=(B, T, H, W, Cc), t=(self.bn_direct(bn, y, B * T * H * W, Cc), p, am))
+        else:
+            self.emit(OP_BN_POOL_FWD_EVAL, i=(B, T, H, W, Cc), t=(y, self.coeffs(bn), p))
+        h = Sym(p, (B, T, Ho, Wo, Cc))
+        if after_stem is not None:
+            after_stem()
+        stages = {}
+        for name in ("conv2x", "conv3x", "conv4x", "conv5x"):
+            stage = getattr(vm, name)
+            for blk in (stage if isinstance(stage, torch.nn.Sequential) else [stage]):
+                _, h = self.r2p1d_block_fwd(blk, h)
+            stages[name] = h
+        return stages, self.gpool_fwd(h, arena=arena)["y"]
+
+    def audio_fwd(self, am, x):
+        from models.audio import Conv2D
+        from models.network_blocks import Basic2DBlock
+        if type(am) is not Conv2D:
+            raise Unsupported(type(am).__name__)
+        h = self.conv_bn_fwd(am.conv1[0], am.conv1[1], x)
+        for blk in (am.block1, am.block2, am.block3, am.block4):
+            if type(blk) is not Basic2DBlock:
+                raise Unsupported(type(blk).__name__)
+            h = self.conv_bn_fwd(blk.conv2, blk.bn2, self.conv_bn_fwd(blk.conv1, blk.bn1, h))
+        return None, self.gpool_fwd(h)["y"]
+
+    def head_fwd(self, head, x, arena=None):
+        """The projection head; ``arena``: where the LAST layer's output goes."""
+        from models.av_wrapper import Head, LinearCL
+        if type(head) is not Head:
+            raise Unsupported(type(head).__name__)
+        mods, k = list(head.projection), 0
+        while k < len(mods):
+            if type(mods[k]) is not LinearCL:
+                raise Unsupported("head")
+            relu = k + 1 < len(mods) and isinstance(mods[k + 1], torch.nn.ReLU)
+            k_next = k + (2 if relu else 1)
+            x = self.linear_fwd(mods[k], x, relu, arena=arena if k_next >= len(mods) else None)["y"]
+            k = k_next
+        return None, x
+
+
+class EvalPlan(Programs):
+    """The compiled inference program of one model for one input geometry: ``R2Plus1D`` (pooled features), ``AV_Wrapper`` (the two
+    embeddings; the audio tower on its own stream and its own buffers), ``ClassificationWrapper(R2Plus1D, feat_name='pool',
+    pooling_op=None)`` (logits; dropout is the identity in eval mode) or the stock ``MOSTModel`` (every tap's logits).  Record 0 is the batched BatchNorm-coefficient launch — it
+    runs on every call, because running statistics move between evaluations — record 1 the weight-transform launch (the
+    pre-split weights of the layers that read them).  Activations live in a RECYCLED arena (``_recycle``); what leaves the program
+    lives in a buffer of its own (slot ``S_OUT``), so the caller's results do not keep the arena alive."""
+
+    def __init__(self, model, vshape, ashape, device):
+        from models.av_wrapper import AV_Wrapper
+        from models.classification import ClassificationWrapper, ClsLinear
+        from models.linear_probe import MOSTModel
+        from models.video import R2Plus1D
+        dry = device.type != "cuda"
+        if not all((p.is_cuda or dry) and p.dtype == torch.float32 for p in model.parameters()):
+            raise Unsupported("non-fp32 / CPU parameters")
+        self.device, self.vshape, self.ashape = device, tuple(vshape), None if ashape is None else tuple(ashape)
+        b = EvalBuilder(device)
+        self._coef_rec = b.emit(OP_BN_EVAL_COEFFS, i=(0,), t=((S_AUX, 0),))
+        self._wt_rec = b.emit(OP_WT_BATCH, i=(0,), n=(0,), t=((S_AUX, 0),))
+        video = Sym((S_VIDEO, 0), vshape)
+        B = vshape[0]
+        if type(model) is R2Plus1D:
+            _, feat = b.video_fwd(model, video, arena=b.oa)
+            self.outputs = [(feat.ref[1], (B, feat.shape[1], 1, 1, 1))]
+        elif type(model) is ClassificationWrapper:
+            cls = model.classifier
+            if model.feat_name != "pool" or model.pooling is not None or type(cls) is not ClsLinear:
+                raise Unsupported("classification wrapper outside the compiled pattern")
+            _, feat = b.video_fwd(model.feature_extractor, video)
+            Fd, Cn = feat.shape[1], cls.weight.shape[0]
+            if cls.weight.shape[1] != Fd or not cls.weight.is_contiguous():
+                raise Unsupported("classifier")
+            logits = b.oa.alloc(4 * B * Cn)
+            b.emit(OP_CLS_LINEAR_FWD, i=(B, Fd, Cn), t=(feat.ref, b.ext(cls.weight), b.ext(cls.bias), logits))
+            self.outputs = [(logits[1], (B, Cn))]
+        elif type(model) is AV_Wrapper:
+            if not model.use_linear_proj or ashape is None:
+                raise Unsupported("no projection heads")
+            audio = Sym((S_AUDIO, 0), (ashape[0], ashape[1], 1, ashape[2], ashape[3]))
+            A_S = ST_MAIN if lib.TIMING else ST_AUDIO
+            out = {}
+
+            def start_audio():                      # behind the video stem, as in training (models/av_wrapper.py AUDIO_AFTER)
+                b.wait(A_S, ST_MAIN)
+                b.S = A_S
+                _, afeat = b.audio_fwd(model.audio_model, audio)
+                out["a"] = b.head_fwd(model.audio_proj, afeat, arena=b.oa)[1]
+                b.S = ST_MAIN
+            _, vfeat = b.video_fwd(model.video_model, video, after_stem=start_audio)
+            vemb = b.head_fwd(model.video_proj, vfeat, arena=b.oa)[1]
+            b.wait(ST_MAIN, A_S)
+            self.outputs = [(vemb.ref[1], vemb.shape), (out["a"].ref[1], out["a"].shape)]
+        elif type(model) is MOSTModel:
+            self._most(b, model, video)
+        else:
+            raise Unsupported(type(model).__name__)
+        self._finalize_eval(b)
+
+    def _most(self, b, model, video):
+        """The stock linear probe (``ProbePlan``'s pattern) in eval mode: the tower, then per tap ``AVID_OP_ADAPTIVE_MAXPOOL``,
+        ``AVID_OP_BN1D_FWD`` with training = 0 and ``AVID_OP_PROBE_LINEAR_FWD``; the logits of every tap leave the program."""
+        from models.linear_probe import Classifier, ProbeBatchNorm1d, ProbeLinear
+        if not len(model.classifiers) or list(model.feat_names) != [c.feat_name for c in model.classifiers]:
+            raise Unsupported("linear probe outside the compiled pattern")
+        for c in model.classifiers:
+            if (type(c) is not Classifier or c.pool_size is None or c.use_dropout or c.l2_norm or not c.use_bn
+                    or type(c.pooling) is not torch.nn.AdaptiveMaxPool3d or c.feat_name not in _PROBE_TAPS
+                    or type(c.bn) is not ProbeBatchNorm1d or c.bn.momentum is None or not c.bn.affine
+                    or not c.bn.track_running_stats or type(c.classifier) is not ProbeLinear or c.classifier.bias is None):
+                raise Unsupported("probe head outside the compiled pattern")
+        stages, _ = b.video_fwd(model.feature_extractor, video)
+        B = self.vshape[0]
+        Cn = model.classifiers[0].classifier.weight.shape[0]
+        self.outputs, self.out_names = [], list(model.feat_names)
+        for c in model.classifiers:
+            h = stages[c.feat_name]
+            _, T, H, W, Cc = h.shape
+            To, Ho, Wo = c.pool_size
+            Fd = Cc * To * Ho * Wo
+            bn, lin = c.bn, c.classifier
+            if tuple(lin.weight.shape) != (Cn, Fd) or not lin.weight.is_contiguous() or bn.num_features != Fd or B > 256 or Fd > 16384:
+                raise Unsupported("probe head geometry")
+            pooled, normed, save2 = b.fa.alloc(4 * B * Fd), b.fa.alloc(4 * B * Fd), b.fa.alloc(8 * Fd)
+            d = ConvDesc()
+            d.To, d.Ho, d.Wo = To, Ho, Wo
+            b.emit(OP_ADAPTIVE_MAXPOOL, d=d, i=(B, T, H, W, Cc), t=(h.ref, pooled))
+            b.emit(OP_BN1D_FWD, i=(B, Fd, 0), f=(bn.momentum, bn.eps),
+                   t=(pooled, b.ext(bn.weight), b.ext(bn.bias), b.ext(bn.running_mean), b.ext(bn.running_var), normed, save2, None))
+            logits = b.oa.alloc(4 * B * Cn)
+            b.emit(OP_PROBE_LINEAR_FWD, i=(B, Fd, Cn), t=(normed, b.ext(lin.weight), b.ext(lin.bias), logits))
+            self.outputs.append((logits[1], (B, Cn)))
+
+    @staticmethod
+    def _recycle(recs, bufs, slot):
+        """Map the virtual buffers of ``slot`` to physical offsets: a buffer takes the bytes of an earlier one of the same aligned
+        size whose last record has been emitted on the same stream, else new bytes.  A record's outputs are placed BEFORE the
+        buffers it reads last are released.  Returns (arena bytes, [(physical offset, bytes, stream, first, last record)])."""
+        import bisect
+        starts = [o for o, _ in bufs]
+        first, last, streams = {}, {}, {}
+        refs = []
+        for k, r in enumerate(recs):
+            if r.op in (0, OP_WAIT):
+                continue
+            for j in range(NREF):
+                if r.t[j].slot == slot:
+                    bi = bisect.bisect_right(starts, r.t[j].off) - 1
+                    refs.append((k, j, bi))
+                    first.setdefault(bi, k)
+                    last[bi] = k
+                    streams.setdefault(bi, set()).add(r.stream)
+        release = {}
+        for bi, k in last.items():
+            release.setdefault(k, []).append(bi)
+        last_ref = {k: j for k, j, _ in refs}                # a record's last reference into the slot
+        free, phys, top = {}, {}, 0
+        for k, j, bi in refs:
+            if bi not in phys:
+                n = bufs[bi][1]
+                pool = free.get((recs[k].stream, n)) if len(streams[bi]) == 1 else None
+                if pool:
+                    phys[bi] = pool.pop()
+                else:
+                    phys[bi], top = top, top + n
+            recs[k].t[j].off = phys[bi] + (recs[k].t[j].off - bufs[bi][0])
+            if j == last_ref[k] and k in release:            # every buffer of the record is placed: release what it read last
+                for b2 in release[k]:
+                    if len(streams[b2]) == 1:
+                        free.setdefault((recs[k].stream, bufs[b2][1]), []).append(phys[b2])
+        return top, [(phys[bi], bufs[bi][1], min(streams[bi]), first[bi], last[bi]) for bi in sorted(phys)]
+
+    def _finalize_eval(self, b):
+        self.n_fwd = len(b.fwd)
+        self.virtual_bytes = b.fa.size                       # what a bump allocator would take
+        self.fa_bytes, self.buffers = self._recycle(b.fwd, b.fa.bufs, S_FWD)
+        self.fa_bytes = max(self.fa_bytes, 256)
+        self.out_bytes = max(b.oa.size, 256)
+        # aux: transformed weights | BatchNorm vectors (both at the Builder's offsets) | weight-transform table | BatchNorm table
+        self.wt_recs, self.bn_recs = b.wt_recs, b.bn_recs
+        self.table_off = _align(b.aux_size)
+        self.bn_table_off = self.table_off + _align(32 * len(b.wt_recs) + 32)
+        self.aux_bytes = self.bn_table_off + C.sizeof(lib.BnEvalItem) * len(b.bn_recs) + 256
+        self._wt_rec.i[0] = len(b.wt_recs)
+        self._wt_rec.n[0] = max([r[2] * r[3] * r[4] for r in b.wt_recs] + [1])
+        self._wt_rec.t[0].off = self.table_off
+        if not b.wt_recs:
+            self._wt_rec.op = 0
+        self._coef_rec.i[0] = len(b.bn_recs)
+        self._coef_rec.t[0].off = self.bn_table_off
+        if not b.bn_recs:
+            self._coef_rec.op = 0
+        self.fwd_prog = (Instr * self.n_fwd)(*b.fwd)
+        self.tensors = b.tensors
+        self.n_slots = S_FIRST_TENSOR + len(self.tensors)
+        need = (_sz * 4)()
+        lib.call("avid_program_workspace_bytes", self.fwd_prog, 0, self.n_fwd, 4, need)
+        self.ws_bytes = [max(int(need[k]), 1 << 20) for k in range(4)]
+        self.ws = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in self.ws_bytes]
+        self.ws_arr = (StreamWs * 4)()
+        for k in range(4):
+            self.ws_arr[k].ptr, self.ws_arr[k].bytes = self.ws[k].data_ptr(), self.ws_bytes[k]
+        self.aux = torch.empty(self.aux_bytes, dtype=torch.uint8, device=self.device)
+        self._table_ptrs = self._bn_ptrs = None
+        self.slots = (_vp * self.n_slots)()
+        self.streams = (_vp * 4)()
+
+    def _refresh_bn_table(self):
+        """The device table of the coefficient launch follows the BatchNorms' current parameter and buffer addresses."""
+        ptrs = tuple(t.data_ptr() for bn, _ in self.bn_recs for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        if ptrs != self._bn_ptrs and self.bn_recs:
+            base = self.aux.data_ptr()
+            recs = [lib.BnEvalItem(ptrs[4 * k], ptrs[4 * k + 1], ptrs[4 * k + 2], ptrs[4 * k + 3], base + off, float(bn.eps),
+                                   bn.num_features) for k, (bn, off) in enumerate(self.bn_recs)]
+            ops.bn_eval_table(recs, self.device, out=self.aux[self.bn_table_off:])
+            self._bn_ptrs = ptrs
+
+    def forward(self, video, audio=None):
+        """Issue the program; returns the outputs (views of a fresh output buffer)."""
+        self._refresh_table()
+        self._refresh_bn_table()
+        fa = torch.empty(self.fa_bytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty(self.out_bytes, dtype=torch.uint8, device=self.device)
+        self._fill_slots(fa, None, None, (video, audio, None, out))
+        self._streams()
+        self._run(self.fwd_prog, 0, self.n_fwd)
+        res = []
+        for off, shape in self.outputs:
+            n = 1
+            for v in shape:
+                n *= v
+            res.append(out[off:off + 4 * n].view(torch.float32).view(shape))
+        return res
+
+
+def _unhooked(model):
+    for m in _cached(model, "_avid_modules", lambda: list(model.modules())):
+        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
+            return False
+    return True
+
+
+def eval_plan(model, *inputs):
+    """The cached ``EvalPlan`` of this call, or None: the caller takes the per-layer path.  Staleness as the training plans'
+    (``_plan_for``: dtype, device, which parameters take gradients, BatchNorm buffer identity, the dispatch epoch that
+    ``ops.wino_configure`` / ``tconv_configure`` / ``set_cu_budget`` bump); the key's leading "eval" keeps it apart from theirs."""
+    if not EVAL_ENABLED or not ENABLED or not inputs or len(inputs) > 2:
+        return None
+    if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == rank for x, rank in zip(inputs, (5, 4))):
+        return None
+    if torch.cuda.is_current_stream_capturing() or not _unhooked(model):
+        return None
+    shapes = tuple(tuple(x.shape) for x in inputs)
+    dev = inputs[0].device
+    return _plan_for(model, ("eval",) + shapes + (dev.index, bool(lib.TIMING)),
+                     lambda: EvalPlan(model, shapes[0], shapes[1] if len(shapes) > 1 else None, dev))
+
+
+def run_eval(model, *inputs):
+    """``model.eval()(*inputs)`` under ``torch.no_grad()`` through an inference program: the output tensor (``R2Plus1D``,
+    ``ClassificationWrapper``), the tuple of embeddings (``AV_Wrapper``) or the dict of logits (``MOSTModel``); None when the model / call is outside what the
+    compiler knows.  Reached only from ``parallel.Inference``: ``model(x)`` in eval mode stays on the per-layer path."""
+    pl = eval_plan(model, *inputs)
+    if pl is None:
+        return None
+    seat = getattr(model, "_seat_flat_buffers", None)
+    if seat is not None:
+        seat()
+    with torch.no_grad():
+        res = pl.forward(*[x.contiguous() for x in inputs])
+    names = getattr(pl, "out_names", None)
+    if names is not None:                          # MOSTModel: {feat_name: logits}
+        return dict(zip(names, res))
+    return res[0] if len(res) == 1 else tuple(res)

@@ -79,6 +79,11 @@ struct ConvArgs {
   const float* bnb_x;        // the BN's input (this dgrad's dx has its shape), or null
   const float *bnb_scale, *bnb_shift, *bnb_mean, *bnb_invstd;
   int bnb_relu;
+  // FORWARD (mode 0, avid_conv_fwd_out): bnb_scale / bnb_shift / bnb_relu hold the eval-mode BatchNorm (+ReLU) of the OUTPUT
+  // instead — the epilogue writes [max(., 0)](fma(acc [+ addend], scale[c], shift[c])), bn_apply_kernel's expression on the value
+  // the plain epilogue would have stored, bit for bit, and the un-normalised tensor is never written (tconv64_kernel<0, EPI | 2,
+  // .> only; has_out_affine()).  The two uses never meet, and the struct keeps its layout: every kernel that takes it by value
+  // keeps its argument offsets.
   int pk_rot;      // tail unit u runs on workgroup (u + pk_rot) mod G: the ones that got one full tile less
   int pk_paired;   // grid = 2 workgroups per CU: number them so that v and v + G/2 share a CU
   // Weight-stationary order of the tail units (0: tile-major — unit u = (tile u / f, piece u % f): the pieces and column blocks
@@ -98,6 +103,10 @@ struct ConvArgs {
   const float* in_shift;
   int in_relu;
 };
+
+// INVARIANT the test below rests on: a forward entry builds its ConvArgs zero-initialised (`ConvArgs a{}`) and sets bnb_scale only
+// from an avid_out_affine (avid_conv_fwd_out); a forward path that COPIES a ConvArgs must come from such a one.
+static inline bool has_out_affine(const ConvArgs& a) { return a.mode == 0 && a.bnb_scale != nullptr; }
 
 constexpr int BK = 32;
 constexpr int LDK = BK + 4;  // padded LDS row (floats): 144 B => b128 fragment reads conflict-free
@@ -1210,9 +1219,13 @@ constexpr int TC_STAGE = TC_ROWS * LDK;       // floats per A stage (one 32-chan
 constexpr size_t TC_LDS = TC_B_BYTES + (2 * TC_STAGE + TC_P * LDK + 128) * sizeof(float);     // weights | two A stages | a frame of zeros | AFF: scale, shift
 
 // AFF (forward): the staged rows are the input of a BatchNorm (+ReLU); the staging threads apply it (ConvArgs::in_scale)
+// EPI & 2 (forward, inference: OAFF): the output is the input of an eval-mode BatchNorm (+ReLU); the epilogue applies it
+// (ConvArgs::bnb_scale in a forward).  No BatchNorm partial sums in this form: the statistics are the running ones.
 template <int MODE, int EPI, bool AFF = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void tconv64_kernel(const ConvArgs p) {
+  constexpr bool OAFF = (EPI & 2) != 0;
   static_assert(!AFF || MODE == 0, "the input affine map belongs to the forward");
+  static_assert(!OAFF || (MODE == 0 && (EPI & 8) == 0), "the output affine map belongs to the forward");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char* Bs = reinterpret_cast<char*>(smem);
   float* As = smem + TC_B_BYTES / 4;
@@ -1234,7 +1247,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
   for (int j = 0; j < 2; ++j) cs[j][0] = cs[j][1] = cq[j][0] = cq[j][1] = 0.f;
   auto write_stats = [&]() {                                // one partial row [2][64] per workgroup + zero rows up to the promise
-    if (!p.stats) return;
+    if (OAFF || !p.stats) return;
     float* red = As;                                        // [2][8 waves][64]
     __syncthreads();
 #pragma unroll
@@ -1359,6 +1372,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       bsc[j] = p.bnb_scale[col]; bsh[j] = p.bnb_shift[col]; bmu[j] = p.bnb_mean[col]; bis[j] = p.bnb_invstd[col];
     }
   }
+  float osc[2] = {0.f, 0.f}, osh[2] = {0.f, 0.f};           // OAFF: scale / shift of this lane's two columns
+  if (OAFF) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      osc[j] = p.bnb_scale[j * 32 + l31];
+      osh[j] = p.bnb_shift[j * 32 + l31];
+    }
+  }
 
   // products of one staged block: six steps s = (tap d = s >> 1, k-step st = s & 1) of 12 matrix instructions each,
   // software-pipelined inside the wave: the fragments of step s + 2 are requested from LDS and the input rows of step s + 1
@@ -1465,7 +1486,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int r = 0; r < 16; ++r) {
         float v = res[j][r];
         if (HAS_ADD) v += ad[r];
-        if (MODE == 0) { cs[j][r & 1] += v; cq[j][r & 1] = fmaf(v, v, cq[j][r & 1]); }   // rows past the end are exact zeros
+        if (OAFF) {                                         // bn_apply_kernel's expression on the value the plain form stores
+          v = fmaf(v, osc[j], osh[j]);
+          if (p.bnb_relu) v = fmaxf(v, 0.f);
+        } else if (MODE == 0) { cs[j][r & 1] += v; cq[j][r & 1] = fmaf(v, v, cq[j][r & 1]); }   // rows past the end are exact zeros
         if (BNB) {
           const float dm = (!p.bnb_relu || fmaf(xb[r], bsc[j], bsh[j]) > 0.f) ? v : 0.f;
           cs[j][r & 1] += dm;
@@ -3377,6 +3401,13 @@ static void launch_tconv_ea(const ConvArgs& a, int grid, hipStream_t s) {
 }
 template <int MODE, int EPI>
 static void launch_tconv_e(const ConvArgs& a, int grid, hipStream_t s) {
+  if constexpr (MODE == 0 && (EPI & 8) == 0) {
+    if (has_out_affine(a)) {                                // inference: the output's eval-mode BatchNorm in the epilogue
+      if (a.in_scale) launch_tconv_ea<MODE, EPI | 2, true>(a, grid, s);
+      else launch_tconv_ea<MODE, EPI | 2, false>(a, grid, s);
+      return;
+    }
+  }
   if constexpr (MODE == 0) {
     if (a.in_scale) { launch_tconv_ea<MODE, EPI, true>(a, grid, s); return; }
   }
@@ -3386,6 +3417,8 @@ static void launch_tconv_e(const ConvArgs& a, int grid, hipStream_t s) {
 // launches of tconv64_kernel / twgrad64_kernel since the library was loaded: [0] reading their input as it is, [1] applying a
 // BatchNorm to it while staging (avid_debug_in_affine_launches: tests assert that the fused form is what ran)
 static std::atomic<long long> g_tconv_launches[2];
+// ... and of tconv64_kernel's forward applying an eval-mode BatchNorm to its OUTPUT (avid_debug_out_affine_launches)
+static std::atomic<long long> g_tconv_out_launches{0};
 template <int MODE>
 static int launch_tconv(ConvArgs& a, hipStream_t s) {
   magic_for(a.Hs * a.Ws, a.mgW, a.shW);       // position -> clip
@@ -3397,6 +3430,7 @@ static int launch_tconv(ConvArgs& a, hipStream_t s) {
   }
   const double K = 3.0 * 64;
   ++g_tconv_launches[MODE == 0 && a.in_scale ? 1 : 0];
+  if (MODE == 0 && has_out_affine(a)) ++g_tconv_out_launches;
   ScopedTimer t(s, MODE == 0 ? "tconv64_kernel<0>" : "tconv64_kernel<1>", 2.0 * a.M * 64 * K,
                 4.0 * ((double)a.M * 64 + 64 * K + (double)a.M * 64 * (1 + (a.addend ? 1 : 0) + (a.bnb_x ? 1 : 0))));
   const int epi = (a.addend ? 1 : 0) | ((MODE == 1 && a.bnb_x) ? 8 : 0);
@@ -3632,6 +3666,8 @@ static int dispatch_igemm(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t s)
     PkPlan pk = plan_pk(a.M, a.Cd, nk_total, MODE);
     if (tconv_takes(a, MODE)) {   // conv2x's temporal layers: taps staged once, weights resident in LDS
       const int rows = pk.grid + (pk.f > 1 ? (int)ceil_div(a.M - pk.tail_row0, stats_rpb(a.M - pk.tail_row0, a.Cd)) : 0);
+      AVID_REQUIRE(!(MODE == 0 && has_out_affine(a) && a.stats), AVID_E_UNSUPPORTED,
+                   "conv_fwd_out: BatchNorm partial sums of a tensor that is not written");
       if (!(a.stats && (MODE == 0 || a.bnb_x)) || rows >= tconv_grid(a)) {
         ConvArgs k = a;
         k.stats = (MODE == 0 || a.bnb_x) ? a.stats : nullptr;
@@ -3641,6 +3677,8 @@ static int dispatch_igemm(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t s)
     }
     AVID_REQUIRE(!a.in_scale, AVID_E_UNSUPPORTED,
                  "conv_fwd_in: this layer does not run on a kernel that applies the input's BatchNorm (avid_conv_takes_in_affine)");
+    AVID_REQUIRE(!(MODE == 0 && has_out_affine(a)), AVID_E_UNSUPPORTED,
+                 "conv_fwd_out: this layer does not run on a kernel that applies the output's BatchNorm (avid_conv_takes_out_affine)");
     if (pk.f > 1 && (ws == nullptr || ws_bytes < sizeof(float) * pk.ws_floats)) {   // no scratch: unsplit
       AVID_REQUIRE(!a.stats, AVID_E_BADARG, "conv: BatchNorm partials need the planned workspace");
       pk.tail_units /= pk.f;
@@ -3920,6 +3958,15 @@ extern "C" int avid_conv_takes_in_affine(const avid_conv_desc* d) {
 
 extern "C" long long avid_debug_in_affine_launches(int fused) { return g_tconv_launches[fused ? 1 : 0].load(std::memory_order_relaxed); }
 
+// the layers whose forward can apply the eval-mode BatchNorm (+ReLU) of their OUTPUT in the epilogue: exactly those whose
+// forward tconv_takes() sends to tconv64_kernel, given their pre-split weights (inference has no weight gradient to agree with)
+extern "C" int avid_conv_takes_out_affine(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return tconv_layer(d, 0) && conv_takes_split(d, 0) ? 1 : 0;
+}
+
+extern "C" long long avid_debug_out_affine_launches(void) { return g_tconv_out_launches.load(std::memory_order_relaxed); }
+
 extern "C" int avid_conv_fwd(const avid_conv_desc* d, const float* x, const float* w, const float* u, const float* addend,
                              const float* bias, int relu, float* y, float* bn_partials, void* ws, size_t ws_bytes,
                              avid_stream_t stream) {
@@ -3929,17 +3976,30 @@ extern "C" int avid_conv_fwd(const avid_conv_desc* d, const float* x, const floa
 extern "C" int avid_conv_fwd_in(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
                                 const float* addend, const float* bias, int relu, float* y, float* bn_partials, void* ws,
                                 size_t ws_bytes, avid_stream_t stream) {
+  return avid_conv_fwd_out(d, x, in, w, u, addend, bias, relu, nullptr, y, bn_partials, ws, ws_bytes, stream);
+}
+
+extern "C" int avid_conv_fwd_out(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
+                                 const float* addend, const float* bias, int relu, const avid_out_affine* out, float* y,
+                                 float* bn_partials, void* ws, size_t ws_bytes, avid_stream_t stream) {
   int rc = validate(d);
   if (rc) return rc;
   AVID_REQUIRE(x && w && y, AVID_E_BADARG, "conv_fwd: null pointer");
+  if (out) {
+    AVID_REQUIRE(out->scale && out->shift, AVID_E_BADARG, "conv_fwd_out: null scale / shift");
+    AVID_REQUIRE(avid_conv_takes_out_affine(d) && u, AVID_E_UNSUPPORTED,
+                 "conv_fwd_out: this layer does not apply its output's BatchNorm (avid_conv_takes_out_affine; needs its pre-split weights)");
+    AVID_REQUIRE(!bias && !relu && !bn_partials, AVID_E_UNSUPPORTED,
+                 "conv_fwd_out: no bias, no ReLU in front of the BatchNorm and no BatchNorm partial sums (the un-normalised tensor is not written)");
+  }
   if (in) {
     AVID_REQUIRE(in->scale && in->shift, AVID_E_BADARG, "conv_fwd_in: null scale / shift");
     AVID_REQUIRE(avid_conv_takes_in_affine(d) && u, AVID_E_UNSUPPORTED,
                  "conv_fwd_in: this layer does not apply its input's BatchNorm (avid_conv_takes_in_affine; needs its pre-split weights)");
   }
-  if (stem_fwd_supported(d) && !addend && !bias && !relu && ws && ws_bytes >= stem_fwd_ws_bytes(d))
+  if (!out && stem_fwd_supported(d) && !addend && !bias && !relu && ws && ws_bytes >= stem_fwd_ws_bytes(d))
     return stem_fwd(d, x, w, y, bn_partials, ws, (hipStream_t)stream);
-  if (wino_supported(d, 0) && !bias && !relu) {
+  if (!out && wino_supported(d, 0) && !bias && !relu) {
     // (avid_conv_fwd_stats_rows promised this kernel's rows: without its workspace the partials would not match)
     AVID_REQUIRE(!bn_partials || u || (ws && ws_bytes >= wino_ws_bytes(d, 0)), AVID_E_BADARG,
                  "conv_fwd: BatchNorm partials of this layer need the planned workspace (avid_conv_fwd_workspace_bytes)");
@@ -3963,6 +4023,7 @@ extern "C" int avid_conv_fwd_in(const avid_conv_desc* d, const float* x, const a
   a.mode = 0;
   a.relu = relu;
   if (in) { a.in_scale = in->scale; a.in_shift = in->shift; a.in_relu = in->relu; }
+  if (out) { a.bnb_scale = out->scale; a.bnb_shift = out->shift; a.bnb_relu = out->relu; }   // (has_out_affine)
   fill_src_strides(d, a.ssB, a.ssT, a.ssH, a.ssW, a.ssC);
   const bool vec = (d->Cin % 32 == 0) && !d->x_channel_first;
   if (bn_partials) {

@@ -178,6 +178,27 @@ __global__ void bn_eval_coeff_kernel(int C, const float* __restrict__ gamma, con
   shift[c] = beta[c] - rm[c] * sc;
 }
 
+// The same coefficients for n BatchNorms in one launch (inference programs: every eval-mode BatchNorm of a tower; the running
+// statistics move between evaluations, so the launch runs on every call).  Block (x, y): channels [256 x, 256 x + 256) of item
+// y.  The expressions are bn_eval_coeff_kernel's, operation for operation: the vectors are the same bits.
+struct BnEvalItem {   // mirror of avid_bn_eval_item
+  const float* gamma; const float* beta; const float* rm; const float* rv;
+  float* out;         // [4][C]: mean | invstd | scale | shift
+  float eps;
+  int C;
+};
+__global__ void bn_eval_coeff_batched_kernel(const BnEvalItem* __restrict__ items) {
+  const BnEvalItem it = items[blockIdx.y];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= it.C) return;
+  const float invstd = 1.f / sqrtf(it.rv[c] + it.eps);
+  const float sc = it.gamma[c] * invstd;
+  it.out[c] = it.rm[c];
+  it.out[it.C + c] = invstd;
+  it.out[2 * it.C + c] = sc;
+  it.out[3 * it.C + c] = it.beta[c] - it.rm[c] * sc;
+}
+
 // The grid stride is a multiple of G (= C/4, a divisor of 256 for every width of the two towers) whenever
 // possible: a thread then stays on one channel group, its coefficients are loaded once, and the loop body is
 // load / 4 fma / store — no 64-bit modulo and no coefficient re-reads per element.
@@ -733,6 +754,46 @@ __global__ __launch_bounds__(256) void bn_pool_fwd_kernel(const float* __restric
   }
 }
 
+// The stem tail in eval mode: the same window walk with the coefficients of the running statistics (bn_eval_coeff_kernel's
+// scale / shift); no argmax (nothing runs backward).  Values as bn_apply_kernel followed by maxpool_fwd_kernel: the same fma
+// and max on every window element, the first maximum in scan order kept.
+__global__ __launch_bounds__(256) void bn_pool_fwd_eval_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, float* __restrict__ y,
+                                                               int BT, int H, int W, int Ho, int Wo, int G) {
+  const long long n = (long long)BT * Ho * Wo * G;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int g = (int)(i % G);
+    long long r = i / G;
+    const int wo = (int)(r % Wo);
+    r /= Wo;
+    const int ho = (int)(r % Ho);
+    const long long bt = r / Ho;
+    const floatx4 sc = reinterpret_cast<const floatx4*>(scale)[g];
+    const floatx4 sh = reinterpret_cast<const floatx4*>(shift)[g];
+    floatx4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    bool first = true;
+#pragma unroll
+    for (int dh = 0; dh < 3; ++dh) {
+      const int h = ho * 2 - 1 + dh;
+      if ((unsigned)h >= (unsigned)H) continue;
+#pragma unroll
+      for (int dw = 0; dw < 3; ++dw) {
+        const int w = wo * 2 - 1 + dw;
+        if ((unsigned)w >= (unsigned)W) continue;
+        const floatx4 xv = *reinterpret_cast<const floatx4*>(x + (((bt * H + h) * W + w) * (long long)G + g) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float v = fmaxf(fmaf(xv[j], sc[j], sh[j]), 0.f);
+          if (first || v > best[j] || v != v) best[j] = v;
+        }
+        first = false;
+      }
+    }
+    reinterpret_cast<floatx4*>(y)[i] = best;
+  }
+}
+
 // A thread owns a 2x2 cell of un-pooled positions (h = 2a, 2a+1; w = 2b, 2b+1) of one channel group: the four
 // pooling windows (a|a+1, b|b+1) that can have selected them are loaded once (argmax slots + pooled gradient)
 // and serve all four positions — 3 loads per position instead of 5.5, four positions in flight per thread.
@@ -1038,6 +1099,43 @@ extern "C" int avid_bn_fwd_eval(int64_t M, int C, const float* x, const float* g
   hipLaunchKernelGGL(bn_apply_eval_kernel, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, x, y, gamma, beta,
                      running_mean, running_var, eps, n4, C / 4, relu);
   return check_launch("bn_fwd_eval");
+}
+
+extern "C" int avid_bn_eval_coeffs_batched(int n, const avid_bn_eval_item* items_dev, avid_stream_t stream) {
+  static_assert(sizeof(BnEvalItem) == sizeof(avid_bn_eval_item), "BnEvalItem mirrors avid_bn_eval_item");
+  AVID_REQUIRE(n > 0 && n <= 65535, AVID_E_SHAPE, "bn_eval_coeffs_batched: n=%d outside [1, 65535]", n);
+  AVID_REQUIRE(items_dev, AVID_E_BADARG, "bn_eval_coeffs_batched: null table");
+  // (every item has C <= 1024, bn_check's bound: four blocks of 256 channels; blocks past an item's C leave at once)
+  ScopedTimer t((hipStream_t)stream, "bn_eval_coeff_batched_kernel", 0.0, 32.0 * n * 256);
+  hipLaunchKernelGGL(bn_eval_coeff_batched_kernel, dim3(4, (unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const BnEvalItem*>(items_dev));
+  return check_launch("bn_eval_coeffs_batched");
+}
+
+extern "C" int avid_bn_apply_eval(int64_t M, int C, const float* x, const float* scale, const float* shift, int relu, float* y,
+                                  avid_stream_t stream) {
+  int rc = bn_check(M, C, "bn_apply_eval");
+  if (rc) return rc;
+  AVID_REQUIRE(x && scale && shift && y, AVID_E_BADARG, "bn_apply_eval: null pointer");
+  const long long n4 = (long long)M * (C / 4);
+  ScopedTimer t((hipStream_t)stream, "bn_apply_kernel", 0.0, 8.0 * M * C);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(n4)), dim3(256), 0, (hipStream_t)stream, x, y, scale, shift, n4, C / 4, relu);
+  return check_launch("bn_apply_eval");
+}
+
+extern "C" int avid_bn_relu_maxpool_fwd_eval(int B, int T, int H, int W, int C, const float* x, const float* scale,
+                                             const float* shift, float* y, avid_stream_t stream) {
+  const int64_t M = (int64_t)B * T * H * W;
+  int rc = bn_check(M, C, "bn_relu_maxpool_fwd_eval");
+  if (rc) return rc;
+  AVID_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0, AVID_E_SHAPE, "bn_relu_maxpool_fwd_eval: bad shape");
+  AVID_REQUIRE(x && scale && shift && y, AVID_E_BADARG, "bn_relu_maxpool_fwd_eval: null pointer");
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  const long long n = (long long)B * T * Ho * Wo * (C / 4);
+  ScopedTimer t((hipStream_t)stream, "bn_pool_fwd_eval_kernel", 0.0, 4.0 * B * T * C * ((double)H * W + Ho * Wo));
+  hipLaunchKernelGGL(bn_pool_fwd_eval_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, scale, shift, y, B * T, H,
+                     W, Ho, Wo, C / 4);
+  return check_launch("bn_relu_maxpool_fwd_eval");
 }
 
 extern "C" int avid_bn_bwd(int64_t M, int C, const float* x, const float* dy, const float* gamma,

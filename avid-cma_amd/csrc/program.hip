@@ -213,8 +213,13 @@ extern "C" int avid_program_run(const avid_instr* prog, int begin, int end, void
           const float* s4 = F(t[7]);
           aff.scale = s4 + 2 * in.i[2]; aff.shift = s4 + 3 * in.i[2]; aff.relu = in.i[1] == 2;
         }
-        rc = avid_conv_fwd_in(&in.d, F(t[0]), in.i[1] ? &aff : nullptr, F(t[1]), F(t[2]), F(t[3]), F(t[4]), in.i[0], F(t[5]), F(t[6]),
-                              w, wb, s);
+        avid_out_affine oaff;     // i[3]: 0 none, 1 the output's eval-mode BatchNorm, 2 ... + ReLU; t[8]: its [4][Cout] vectors
+        if (in.i[3]) {
+          const float* s4 = F(t[8]);
+          oaff.scale = s4 + 2 * in.d.Cout; oaff.shift = s4 + 3 * in.d.Cout; oaff.relu = in.i[3] == 2;
+        }
+        rc = avid_conv_fwd_out(&in.d, F(t[0]), in.i[1] ? &aff : nullptr, F(t[1]), F(t[2]), F(t[3]), F(t[4]), in.i[0],
+                               in.i[3] ? &oaff : nullptr, F(t[5]), F(t[6]), w, wb, s);
         break;
       }
       case AVID_OP_CONV_DGRAD: {
@@ -342,6 +347,27 @@ extern "C" int avid_program_run(const avid_instr* prog, int begin, int end, void
         break;
       case AVID_OP_PROBE_LINEAR_BWD:
         rc = avid_probe_linear_bwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), F(t[5]), w, wb, s);
+        break;
+      case AVID_OP_BN_EVAL_COEFFS:
+        rc = avid_bn_eval_coeffs_batched(in.i[0], reinterpret_cast<const avid_bn_eval_item*>(P(t[0])), s);
+        break;
+      case AVID_OP_BN_EVAL_APPLY: {
+        const int C = in.i[0];
+        const float* s4 = F(t[1]);
+        rc = avid_bn_apply_eval(in.n[0], C, F(t[0]), s4 + 2 * C, s4 + 3 * C, in.i[1], F(t[2]), s);
+        break;
+      }
+      case AVID_OP_BN_POOL_FWD_EVAL: {
+        const int C = in.i[4];
+        const float* s4 = F(t[1]);
+        rc = avid_bn_relu_maxpool_fwd_eval(in.i[0], in.i[1], in.i[2], in.i[3], C, F(t[0]), s4 + 2 * C, s4 + 3 * C, F(t[2]), s);
+        break;
+      }
+      case AVID_OP_BN_EVAL_DIRECT:
+        rc = avid_bn_fwd_eval(in.n[0], in.i[0], F(t[0]), F(t[1]), F(t[2]), F(t[3]), F(t[4]), in.f[1], in.i[1], F(t[5]), nullptr, s);
+        break;
+      case AVID_OP_MAXPOOL_FWD:
+        rc = avid_maxpool_hw3s2_fwd(in.i[0], in.i[1], in.i[2], in.i[3], in.i[4], F(t[0]), F(t[1]), reinterpret_cast<uint8_t*>(P(t[2])), s);
         break;
       default:
         set_error("program record %d: unknown kind %d", k, in.op);

@@ -112,6 +112,26 @@ int avid_conv_fwd_in(const avid_conv_desc* d, const float* x, const avid_in_affi
  * (fused = 0) or applied a BatchNorm to it while staging (fused = 1): tests assert which form ran. */
 long long avid_debug_in_affine_launches(int fused);
 
+/* Inference (version >= 160): the same convolution with the eval-mode BatchNorm (+ReLU) of its OUTPUT applied in the epilogue:
+ * y = [max(., 0)](fma(conv(x) [+ addend], out->scale[c], out->shift[c])), scale / shift [Cout] from the running statistics
+ * (avid_bn_eval_coeffs_batched, or avid_bn_fwd_eval's save4 rows 2 and 3).  Bit-identical to avid_conv_fwd[_in] followed by
+ * avid_bn_fwd_eval(save4) with the same vectors: the same fma on the same fp32 value, the addend added in front of it as a
+ * separate operation.  The un-normalised tensor is never written, so there are no BatchNorm partial sums of it: bn_partials
+ * (and bias, relu) must be NULL / 0 when out is given.  `in` (nullable) as in avid_conv_fwd_in; out = NULL: avid_conv_fwd_in.
+ * Only layers for which avid_conv_takes_out_affine() answers 1 (those whose forward runs on tconv64_kernel: (3,1,1), stride 1,
+ * 64 -> 64 channels, 8 frames, given their pre-split weights as u); anything else returns AVID_E_UNSUPPORTED. */
+typedef struct avid_out_affine {
+  const float* scale;
+  const float* shift;
+  int32_t relu;
+} avid_out_affine;
+int avid_conv_takes_out_affine(const avid_conv_desc* d);
+int avid_conv_fwd_out(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
+                      const float* addend, const float* bias, int relu, const avid_out_affine* out, float* y,
+                      float* bn_partials, void* ws, size_t ws_bytes, avid_stream_t stream);
+/* Launches of tconv64_kernel's forward since the library was loaded that applied a BatchNorm to their output. */
+long long avid_debug_out_affine_launches(void);
+
 /* dx = conv_transpose(dy, w) [+ addend].  ws: scratch for the transposed weights (+ split-K slabs).
  * wt (nullable): the weights already repacked as [Cin][taps][Cout] by avid_weight_transpose_batched (mode 0, current
  * for this w); NULL = repack inside the call (one extra small launch per layer).
@@ -291,6 +311,23 @@ int avid_bn_fwd_train(int64_t M, int C, const float* x, const float* gamma, cons
 int avid_bn_fwd_eval(int64_t M, int C, const float* x, const float* gamma, const float* beta,
                      const float* running_mean, const float* running_var, float eps, int relu,
                      float* y, float* save4, avid_stream_t stream);
+/* Inference (version >= 160).  The two halves of avid_bn_fwd_eval(save4) as calls of their own:
+ * avid_bn_eval_coeffs_batched — ONE launch that writes the [4][C] vectors (mean = running_mean, invstd = 1 / sqrt(var + eps),
+ * scale = gamma * invstd, shift = beta - mean * scale: the bits avid_bn_fwd_eval writes to save4) of n BatchNorms from a table
+ * in DEVICE memory; every C a power of two in [4, 1024];
+ * avid_bn_apply_eval — y = [relu](fma(x, scale[c], shift[c])) with such vectors (x == y allowed). */
+typedef struct avid_bn_eval_item {
+  const float* gamma;
+  const float* beta;
+  const float* running_mean;
+  const float* running_var;
+  float* out;                 /* [4][C] */
+  float eps;
+  int32_t C;
+} avid_bn_eval_item;
+int avid_bn_eval_coeffs_batched(int n, const avid_bn_eval_item* items_dev, avid_stream_t stream);
+int avid_bn_apply_eval(int64_t M, int C, const float* x, const float* scale, const float* shift, int relu, float* y,
+                       avid_stream_t stream);
 /* Backward of train-mode BN(+ReLU).  The ReLU mask is fma(x, scale, shift) > 0 recomputed from the conv
  * output x (the forward's exact expression), so the saved activation is not re-read: 2 + 3 passes.
  * partials / nparts: the partial sums the dgrad that produced dy already made (avid_conv_dgrad's `bn`), or
@@ -320,6 +357,11 @@ int avid_bn_relu_maxpool_bwd(int B, int T, int H, int W, int C, const float* x, 
                              const uint8_t* argmax, const float* gamma, const float* save_mean,
                              const float* save_invstd, const float* save_scale, const float* save_shift, float* dx,
                              float* dgamma, float* dbeta, void* ws, size_t ws_bytes, avid_stream_t stream);
+/* The stem tail in eval mode (version >= 160): y = maxpool(relu(fma(x, scale[c], shift[c]))) in one pass, scale / shift [C]
+ * from the running statistics (avid_bn_eval_coeffs_batched).  No argmax, no saved vectors.  The values of
+ * avid_bn_fwd_eval(save4, relu = 1) followed by avid_maxpool_hw3s2_fwd, bit for bit (signed zeros and ties included). */
+int avid_bn_relu_maxpool_fwd_eval(int B, int T, int H, int W, int C, const float* x, const float* scale, const float* shift,
+                                  float* y, avid_stream_t stream);
 int avid_maxpool_hw3s2_fwd(int B, int T, int H, int W, int C, const float* x, float* y,
                            uint8_t* argmax, avid_stream_t stream);
 int avid_maxpool_hw3s2_bwd(int B, int T, int H, int W, int C, const float* dy,
@@ -620,7 +662,9 @@ enum {
   AVID_OP_WAIT = 1,          /* stream i[0] waits for everything issued so far on stream i[1] (event record + wait) */
   AVID_OP_MEMSET0 = 2,       /* t0 <- zeros, n[0] bytes */
   AVID_OP_CONV_FWD = 3,      /* d; t: x w u addend bias y bn_partials [in_s4]; i0 relu, i1 input BatchNorm (0 none, 1 affine, 2 + ReLU:
-                                x is then that BatchNorm's input and t7 its saved [4][C] vectors, i2 = C: avid_conv_fwd_in) */
+                                x is then that BatchNorm's input and t7 its saved [4][C] vectors, i2 = C: avid_conv_fwd_in);
+                                inference programs: [... out_s4], i3 output BatchNorm (0 none, 1 affine, 2 + ReLU: t8 = the eval-mode
+                                BatchNorm's [4][Cout] vectors, y its OUTPUT: avid_conv_fwd_out) */
   AVID_OP_CONV_DGRAD = 4,    /* d; t: dy w wt u addend dx bn.x bn.scale bn.shift bn.mean bn.invstd bn.partials;
                                 i0..2 addend strides (0 = dense addend), i3 bn.relu, i4 bn present */
   AVID_OP_CONV_WGRAD = 5,    /* d; t: x dy dw [in_s4]; i0 input BatchNorm as AVID_OP_CONV_FWD's i1 (t3, i1 = C: avid_conv_wgrad_in) */
@@ -650,6 +694,14 @@ enum {
   AVID_OP_BN1D_BWD = 25,      /* i0 B, i1 F, i2 frozen; f1 eps; t: x dy gamma save2 dx dgamma dbeta */
   AVID_OP_PROBE_LINEAR_FWD = 26, /* i0 B, i1 Fin, i2 C; t: x w bias y */
   AVID_OP_PROBE_LINEAR_BWD = 27, /* i0 B, i1 Fin, i2 C; t: x w dy dx dw db */
+  /* inference programs (version >= 160); no training program holds a record of these kinds */
+  AVID_OP_BN_EVAL_COEFFS = 28,   /* i0 n; t: table (avid_bn_eval_item[] in device memory): avid_bn_eval_coeffs_batched */
+  AVID_OP_BN_EVAL_APPLY = 29,    /* n0 M; i0 C, i1 relu; t: x coeffs4 y (coeffs4 = mean | invstd | scale | shift): avid_bn_apply_eval */
+  AVID_OP_BN_POOL_FWD_EVAL = 30, /* i0..4 B T H W C; t: x coeffs4 y: avid_bn_relu_maxpool_fwd_eval */
+  AVID_OP_BN_EVAL_DIRECT = 31,   /* n0 M; i0 C, i1 relu; f1 eps; t: x gamma beta running_mean running_var y: avid_bn_fwd_eval WITHOUT save4 —
+                                    what the per-layer path calls for a BatchNorm whose parameters take no gradient (another expression
+                                    than fma(x, scale, shift): such a BatchNorm is never fused) */
+  AVID_OP_MAXPOOL_FWD = 32,      /* i0..4 B T H W C; t: x y argmax: avid_maxpool_hw3s2_fwd (the stem's pool behind such a BatchNorm) */
   AVID_OP_COUNT_
 };
 
