@@ -449,6 +449,30 @@ class AdamStep(EngineCore):
         self.t += 1
         self._adam()
 
+    # ---- what the supervised steps (FinetuneStep, ProbeStep) share
+    def _labelled(self, video, labels):
+        """A supervised step's inputs, contiguous, the labels checked: int64 [B] on the video's device."""
+        video, labels = video.contiguous(), labels.contiguous()
+        B = video.shape[0]
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
+            raise ValueError(f"{type(self).__name__}.step: labels must be int64 [{B}] on {video.device} "
+                             f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
+        return video, labels
+
+    def _evaluate(self, video, batch, finish):
+        """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] through the model in eval mode, ``batch`` clips at a time (the
+        reference's BatchWrapper; ``Inference``: one program per distinct chunk size, cached on the model).  Returns
+        ``finish([the chunks' outputs])``, evaluated before the model's mode is restored."""
+        x = video.flatten(0, 1)
+        was = self.model.training
+        self.model.eval()
+        try:
+            infer = Inference(self.model)
+            with torch.no_grad():
+                return finish([infer(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)])
+        finally:
+            self.model.train(was)
+
     # ---- optimizer state in torch.optim.Adam's format (main-avid.py:115,127,138 save and restore
     # ``optimizer.state_dict()``; utils/main_utils.py:250-261 builds Adam over model.parameters())
     def _param_order(self):
@@ -907,12 +931,8 @@ class FinetuneStep(AdamStep):
 
     def step(self, video, labels):
         """(loss [], hits [2] int64: top-1 / top-5 hits of the batch) as device tensors."""
-        video = video.contiguous()
-        labels = labels.contiguous()
+        video, labels = self._labelled(video, labels)
         B = video.shape[0]
-        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
-            raise ValueError(f"FinetuneStep.step: labels must be int64 [{B}] on {video.device} "
-                             f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
         if self.broadcast_buffers == "step":
             self.sync_buffers()
         pl = self._plan(video)
@@ -954,17 +974,8 @@ class FinetuneStep(AdamStep):
         time (the reference's BatchWrapper), then one ``avid_cls_loss`` over all V * clips logits.  Returns device tensors
         (confidence [V, C], loss [], hits [2] int64)."""
         from . import ops
-        V, clips = video.shape[0], video.shape[1]
-        x = video.flatten(0, 1)
-        was = self.model.training
-        self.model.eval()
-        try:
-            infer = Inference(self.model)           # one inference program per distinct chunk size (plans are cached on the model)
-            with torch.no_grad():
-                logits = torch.cat([infer(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)], 0)
-                loss, conf, hits, _ = ops.cls_loss(logits, labels, clips)
-        finally:
-            self.model.train(was)
+        clips = video.shape[1]
+        loss, conf, hits, _ = self._evaluate(video, batch, lambda outs: ops.cls_loss(torch.cat(outs, 0), labels, clips))
         return conf, loss, hits
 
 
@@ -996,12 +1007,8 @@ class ProbeStep(AdamStep):
 
     def step(self, video, labels):
         """(losses [n_taps], hits [n_taps, 2] int64: top-1 / top-5 hits of the batch per tap) as device tensors."""
-        video = video.contiguous()
-        labels = labels.contiguous()
+        video, labels = self._labelled(video, labels)
         B = video.shape[0]
-        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
-            raise ValueError(f"ProbeStep.step: labels must be int64 [{B}] on {video.device} "
-                             f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
         pl = self._plan(video)
         out = torch.empty((self.n_taps, 8), dtype=torch.float32, device=video.device)     # plan.PROBE_OUT_BYTES per tap
         dlogits = torch.empty((self.n_taps, B, pl.n_classes), dtype=torch.float32, device=video.device)
@@ -1018,15 +1025,6 @@ class ProbeStep(AdamStep):
         (confidence [n_taps, V, C], losses [n_taps], hits [n_taps, 2] int64)."""
         from . import ops
         clips = video.shape[1]
-        x = video.flatten(0, 1)
-        was = self.model.training
-        self.model.eval()
-        try:
-            infer = Inference(self.model)           # (the probe's frozen tower stays on the per-layer path: plan.EvalBuilder.coeffs)
-            with torch.no_grad():
-                outs = [infer(x[i:i + batch].contiguous()) for i in range(0, x.shape[0], batch)]
-                res = [ops.cls_loss(torch.cat([o[ft] for o in outs], 0), labels, clips)
-                       for ft in self.model.feat_names]
-        finally:
-            self.model.train(was)
+        res = self._evaluate(video, batch, lambda outs: [ops.cls_loss(torch.cat([o[ft] for o in outs], 0), labels, clips)
+                                                         for ft in self.model.feat_names])
         return (torch.stack([r[1] for r in res]), torch.stack([r[0] for r in res]), torch.stack([r[2] for r in res]))

@@ -9,11 +9,17 @@ shape, stream arrangement) into an ``avid_instr`` array (include/avid_hip.h, "La
 ``avid_program_run`` in C: same entry points, same arguments, same order per stream as the per-layer path — bit-identical
 results (tests/test_gpu_plan.py) — and the whole model is one autograd node.
 
-* ``Builder`` walks the module tree (R2Plus1D / Conv2D / Head, i.e. models/*.py of this package) and emits the forward
-  records, then the backward records in autograd's order, with every fusion decision of the per-layer path taken at
-  compile time: BatchNorm statistics from the convolution epilogue, BatchNorm-backward sums from the consumer's
-  input-gradient kernel, residual add in the epilogue, compact gradient of the strided 1x1x1 residual convolution,
-  grouped weight gradients, weight gradients on trailing streams, the audio tower on its own stream.
+* ``Builder`` walks the module tree (R2Plus1D / Conv2D / Head, i.e. models/*.py of this package) ONCE for every kind of
+  program: ``video_fwd`` / ``audio_fwd`` / ``head_fwd`` call the per-mode layer emitters (``stem_fwd``, ``conv_bn_fwd``,
+  ``r2p1d_block_fwd``) of ``TrainBuilder`` (training-mode BatchNorm, everything kept for the backward) or ``EvalBuilder``
+  (running statistics, a recycled arena).  ``TrainBuilder`` then emits the backward records in autograd's order, with every
+  fusion decision of the per-layer path taken at compile time: BatchNorm statistics from the convolution epilogue,
+  BatchNorm-backward sums from the consumer's input-gradient kernel, residual add in the epilogue, compact gradient of the
+  strided 1x1x1 residual convolution, grouped weight gradients, weight gradients on trailing streams, the audio tower on
+  its own stream.
+* ``Programs`` seals what a builder emitted (weight-transform table, record arrays, workspaces, slots) and runs it;
+  ``TrainPrograms`` adds the forward / backward pair over a flat gradient buffer (``Plan``, ``ClsPlan``, ``ProbePlan``),
+  ``EvalPlan`` is a single forward program.
 * tensors are ``(slot, byte offset)`` references: activations live in ONE arena per pass (a torch tensor the autograd
   node keeps alive), parameters / buffers / inputs are slots re-read from the tensors on every run — the program holds
   no address, so re-seated parameters (``FlatParams``), a new batch or a different allocator block just work.
@@ -38,12 +44,16 @@ OP_RELU_BWD, OP_COLSUM, OP_WT_BATCH, OP_ADAM = 14, 15, 16, 17
 OP_DROPOUT_FWD, OP_DROPOUT_BWD, OP_CLS_LOSS, OP_CLS_LINEAR_FWD, OP_CLS_LINEAR_BWD = 18, 19, 20, 21, 22
 OP_ADAPTIVE_MAXPOOL, OP_BN1D_FWD, OP_BN1D_BWD, OP_PROBE_LINEAR_FWD, OP_PROBE_LINEAR_BWD = 23, 24, 25, 26, 27
 OP_BN_EVAL_COEFFS, OP_BN_EVAL_APPLY, OP_BN_POOL_FWD_EVAL, OP_BN_EVAL_DIRECT, OP_MAXPOOL_FWD = 28, 29, 30, 31, 32   # inference programs only
+_OP_NAMES = {0: "nop", **{v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}}   # (``dump``)
 NREF = lib.INSTR_REFS
 Ref, Instr, StreamWs = lib.Ref, lib.Instr, lib.StreamWs
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 
 # ---- slots ---------------------------------------------------------------------------------------------------------
 S_FWD, S_BWD, S_GRAD, S_AUX, S_VIDEO, S_AUDIO, S_DV, S_DA, S_FIRST_TENSOR = 0, 1, 2, 3, 4, 5, 6, 7, 8
+S_LABELS, S_DLOGITS, S_OUT = S_AUDIO, S_DV, S_DA     # the single-tower plans' use of the two-tower plan's input slots
+OUT_BYTES = 32                                       # S_OUT of a classifier step: loss (f32) at 0, hits (2 x i64) at 8
+PROBE_OUT_BYTES = 32                                 # the same per tap of a probe step
 NULL = (-1, 0)
 # streams of a run (avid_hip/streams.py: one per dispatch pipe): compute (video tower), audio tower, the trailing
 # weight-gradient stream of both, the collectives' stream (not used by the programs themselves)
@@ -71,6 +81,21 @@ class Arena:
     def alloc(self, nbytes):
         off = self.size
         self.size += _align(max(int(nbytes), 4))
+        return (self.slot, off)
+
+
+class EvalArena:
+    """The activation arena of an inference program while it is compiled: ``alloc`` hands out VIRTUAL offsets that never
+    overlap; ``EvalPlan._recycle`` then maps every buffer to a physical offset, re-using the bytes of buffers whose last
+    reader has been emitted on the same stream (nothing runs backward, nothing trails on another stream)."""
+
+    def __init__(self, slot):
+        self.slot, self.size, self.bufs = slot, 0, []
+
+    def alloc(self, nbytes):
+        off, n = self.size, _align(max(int(nbytes), 4))
+        self.size += n
+        self.bufs.append((off, n))
         return (self.slot, off)
 
 
@@ -104,23 +129,57 @@ def _off(ref, nbytes):
     return (ref[0], ref[1] + nbytes)
 
 
+_STAGES = ("conv2x", "conv3x", "conv4x", "conv5x")   # R2Plus1D's stages: the linear probe's taps
+
+
+def _classifier(model):
+    """The classifier of a ``ClassificationWrapper`` in the compiled pattern: pooled features -> [dropout ->] ``ClsLinear``."""
+    from models.classification import ClassificationWrapper, ClsLinear
+    if type(model) is not ClassificationWrapper or model.feat_name != "pool" or model.pooling is not None:
+        raise Unsupported("classification wrapper outside the compiled pattern")
+    if type(model.classifier) is not ClsLinear:
+        raise Unsupported("classifier")
+    return model.classifier
+
+
+def _probe_heads(model):
+    """The heads of a ``MOSTModel`` in its stock form: per tap AdaptiveMaxPool3d -> BatchNorm1d -> Linear, no dropout, no l2 norm."""
+    from models.linear_probe import MOSTModel, Classifier, ProbeBatchNorm1d, ProbeLinear
+    if type(model) is not MOSTModel or not len(model.classifiers):
+        raise Unsupported("linear probe outside the compiled pattern")
+    for c in model.classifiers:
+        if (type(c) is not Classifier or c.pool_size is None or c.use_dropout or c.l2_norm or not c.use_bn
+                or type(c.pooling) is not torch.nn.AdaptiveMaxPool3d or c.feat_name not in _STAGES
+                or type(c.bn) is not ProbeBatchNorm1d or c.bn.momentum is None or not c.bn.affine
+                or not c.bn.track_running_stats or type(c.classifier) is not ProbeLinear or c.classifier.bias is None):
+            raise Unsupported("probe head outside the compiled pattern")
+    if list(model.feat_names) != [c.feat_name for c in model.classifiers]:
+        raise Unsupported("feat_names")
+    return list(model.classifiers)
+
+
 class Builder:
-    def __init__(self, device, overlap_towers, trailing, group):
+    """What every compiler shares: the forward records, the references of external tensors, the weight-transform table, the
+    emitters that do not depend on the BatchNorm mode (linear, pools, the classifier and probe heads) and the MODULE WALKERS —
+    ``video_fwd``, ``audio_fwd``, ``head_fwd`` — which decide what the compiler accepts and call the mode's layer emitters:
+
+    * ``stem_fwd(w, bn, x, d, srows, psh)`` -> (stem record, reference of the pooled output [psh]),
+    * ``conv_bn_fwd(conv, bn, x, addend=None, next_conv=None, ...)`` -> layer record with at least ``"h"``,
+    * ``r2p1d_block_fwd(blk, x)`` -> (the block's layer records, Sym of its output)."""
+
+    trailing = False                               # (TrainBuilder: weight gradients and weight tables on the trailing stream)
+
+    def __init__(self, device, arena):
         self.device = device
-        self.overlap, self.trailing, self.group = overlap_towers, trailing, group
-        self.fa, self.ba = Arena(S_FWD), Arena(S_BWD)
-        self.fwd, self.bwd = [], []
+        self.fa = arena
+        self.fwd = []
         self.cur = self.fwd
         self.tensors, self.tslot = [], {}          # external tensors (parameters, buffers) -> slot
-        self.params, self.pindex = [], {}          # trainable parameters in gradient-buffer order
         self.S = ST_MAIN                           # compute stream of the records being emitted
-        self.pending = {ST_MAIN: [], ST_AUDIO: []}  # queued weight gradients per compute stream
-        self.trail_used = set()
         self.tables_waited = set()                 # streams whose forward has waited for the weight-transform launch
-        self.wt, self.wt_off = {}, {}              # transposed weights / Winograd transforms: param slot -> aux offset
+        self.wt_off = {}                           # transposed weights / Winograd transforms: (id(param), mode) -> aux offset
         self.aux_size = 0
         self.wt_recs = []                          # (param tensor, aux offset, Cout, taps, Cin, mode)
-        self.grad_ready = []                       # (index of the backward record that completes them, [param index])
 
     # ---- references
     def ext(self, t):
@@ -131,20 +190,6 @@ class Builder:
             s = self.tslot[key] = S_FIRST_TENSOR + len(self.tensors)
             self.tensors.append(t)
         return (s, 0)
-
-    def grad(self, p):
-        """Reference of parameter p's slice of the flat gradient buffer."""
-        return (S_GRAD, 4 * self.goff[self.pindex[id(p)]])
-
-    def set_params(self, params):
-        """Gradient-buffer layout = ``parallel.FlatParams``': reverse registration order, 16-byte aligned slices."""
-        self.params = list(reversed(params))
-        self.goff, off = [], 0
-        for k, p in enumerate(self.params):
-            self.pindex[id(p)] = k
-            self.goff.append(off)
-            off += (p.numel() + 3) // 4 * 4
-        self.gnumel = off
 
     def emit(self, op, stream=None, d=None, i=(), n=(), f=(), t=()):
         ins = Instr()
@@ -170,38 +215,29 @@ class Builder:
         if waiter != waited:
             self.emit(OP_WAIT, stream=0, i=(waiter, waited))
 
-    # ---- transposed weights / Winograd transforms for the input gradients (ops.TransposedWeights)
-    def want_wt(self, w):
-        key = (id(w), 0)
+    # ---- transposed weights / Winograd transforms / pre-split weights (ops.TransposedWeights): one table entry per form
+    def _want(self, w, mode, taps, nbytes):
+        key = (id(w), mode)
         if key not in self.wt_off:
-            if not (w.shape[1] % 64 == 0 and w.shape[0] % 32 == 0):
-                return None
-            k = ops._kdims(w)
             self.wt_off[key] = self.aux_size
-            self.wt_recs.append((w, self.aux_size, w.shape[0], k[0] * k[1] * k[2], w.shape[1], 0))
-            self.aux_size += _align(4 * w.numel())
+            self.wt_recs.append((w, self.aux_size, w.shape[0], taps, w.shape[1], mode))
+            self.aux_size += _align(nbytes)
         return (S_AUX, self.wt_off[key])
+
+    def want_wt(self, w):
+        if not (w.shape[1] % 64 == 0 and w.shape[0] % 32 == 0):
+            return None
+        k = ops._kdims(w)
+        return self._want(w, 0, k[0] * k[1] * k[2], 4 * w.numel())
 
     def want_u(self, w, variant, forward=False):
         code = (1 if forward else 2) + 2 * (variant - 1)   # forward (1 / 3) or input gradient (2 / 4), wino_kernel's / wino2_kernel's order
-        key = (id(w), code)
-        if key not in self.wt_off:
-            self.wt_off[key] = self.aux_size
-            self.wt_recs.append((w, self.aux_size, w.shape[0], 9, w.shape[1], code))
-            self.aux_size += _align(4 * ops.U_FLOATS * w.shape[0] * w.shape[1])
-        return (S_AUX, self.wt_off[key])
+        return self._want(w, code, 9, 4 * ops.U_FLOATS * w.shape[0] * w.shape[1])
 
     def want_split(self, w, mode):
         """The weights pre-split into bf16 terms for igemm_pk_kernel's 128 x 64 tile (mode 5: forward, 6: input gradient)."""
-        key = (id(w), mode)
-        if key not in self.wt_off:
-            k = ops._kdims(w)
-            self.wt_off[key] = self.aux_size
-            self.wt_recs.append((w, self.aux_size, w.shape[0], k[0] * k[1] * k[2], w.shape[1], mode))
-            self.aux_size += _align(6 * w.numel())
-            if mode == 5:
-                self.fwd_tables = True
-        return (S_AUX, self.wt_off[key])
+        k = ops._kdims(w)
+        return self._want(w, mode, k[0] * k[1] * k[2], 6 * w.numel())
 
     def fwd_u(self, w, d):
         """`u` of a forward convolution on stream self.S.  The pre-split weights (want_split mode 5) come out of the step's
@@ -209,7 +245,7 @@ class Builder:
         persistent workgroups (parallel.py: forward_backward): the FIRST layer of a stream that reads a table waits for
         that launch — on the video tower that is conv2x's temporal convolution, 0.2 ms behind the stem, and costs nothing;
         a wait right behind the stem stalled the compute stream for the time the tables were late (10.07-10.3 against
-        10.03-10.09 ms per step on one box)."""
+        10.03-10.09 ms per step on one box).  (An inference program has no trailing stream: its tables come out of record 1.)"""
         if d.wino_fwd:
             # a Winograd layer behind that wait takes its transformed weights from the same launch (mode 1 / 3) instead of
             # transforming them in front of its own kernel (one 6 us launch per layer on the compute stream); the first
@@ -224,15 +260,7 @@ class Builder:
             self.tables_waited.add(self.S)
         return self.want_split(w, 5)
 
-    def dgrad_wt_u(self, w, d):
-        """(wt, u) of an input gradient: the Winograd transform, the pre-split transpose, or the plain transpose."""
-        if d.wino_dgrad:
-            return self.want_wt(w), self.want_u(w, d.wino_dgrad)
-        if d.split_dgrad:
-            return None, self.want_split(w, 6)
-        return self.want_wt(w), None
-
-    # ---- forward emitters ------------------------------------------------------------------------------------------
+    # ---- forward emitters of both modes ----------------------------------------------------------------------------
     def desc(self, x_shape, conv_w, stride, pad, channel_first):
         if channel_first:
             B, c, Ti, Hi, Wi = x_shape
@@ -245,11 +273,186 @@ class Builder:
             raise Unsupported("weight layout")
         return ops._desc_cached((B, Ti, Hi, Wi), cin, cout, ops._kdims(conv_w), tuple(stride), tuple(pad), channel_first)
 
-    def conv_bn_fwd(self, conv, bn, x, addend=None, res=None, sole=True, next_conv=None):
+    def applies_bn(self, next_conv, ysh):
+        """``next_conv``, the only consumer of a layer's output [ysh], can apply that layer's BatchNorm (+ReLU) to its input while
+        it stages it (``d.in_affine``: conv2x's temporal layers)."""
+        if next_conv is None:
+            return False
+        nw = next_conv.weight
+        return bool(ops.weight_layout_ok(nw) and nw.dtype == torch.float32 and nw.shape[1] == ysh[-1] and not next_conv.channel_first
+                    and self.desc(ysh, nw, next_conv.stride3, next_conv.padding3, False)[0].in_affine)
+
+    def linear_fwd(self, lin, x, relu, arena=None):
+        """nn.Linear (+ReLU) as a 1x1x1 convolution over [B,1,1,1,C] (ops.linear).  ``arena``: where the output goes (default:
+        the forward arena)."""
+        w = lin.weight
+        B, Cin = x.shape
+        d = ops._desc_cached((B, 1, 1, 1), w.shape[1], w.shape[0], (1, 1, 1), (1, 1, 1), (0, 0, 0), False)[0]
+        if Cin != w.shape[1] or not ops.weight_layout_ok(w):
+            raise Unsupported("linear")
+        y = (arena or self.fa).alloc(4 * B * d.Cout)
+        self.emit(OP_CONV_FWD, d=d, i=(1 if relu else 0,), t=(x.ref, self.ext(w), None, None, self.ext(lin.bias), y, None))
+        return {"lin": lin, "d": d, "x": x, "y": Sym(y, (B, d.Cout)), "relu": relu, "w": w}
+
+    def gpool_fwd(self, x, arena=None):
+        B, Cc = x.shape[0], x.shape[-1]
+        S = x.numel // (B * Cc)
+        y = (arena or self.fa).alloc(4 * B * Cc)
+        am = self.fa.alloc(4 * B * Cc)
+        self.emit(OP_GPOOL_FWD, i=(B, S, Cc), t=(x.ref, y, am))
+        return {"x": x, "y": Sym(y, (B, Cc)), "am": am, "S": S}
+
+    def cls_linear_fwd(self, cls, feat, arena=None):
+        """The classifier of ``_classifier`` (``avid_cls_linear_fwd``: any number of classes) on features [B, Fd]; returns the logits."""
+        B, Fd = feat.shape
+        Cn = cls.weight.shape[0]
+        if cls.weight.shape[1] != Fd or not cls.weight.is_contiguous():
+            raise Unsupported("classifier")
+        logits = (arena or self.fa).alloc(4 * B * Cn)
+        self.emit(OP_CLS_LINEAR_FWD, i=(B, Fd, Cn), t=(feat.ref, self.ext(cls.weight), self.ext(cls.bias), logits))
+        return Sym(logits, (B, Cn))
+
+    def probe_head_fwd(self, c, h, Cn, training, arena=None):
+        """One head of ``_probe_heads`` on its tap ``h``: ``avid_adaptive_maxpool_fwd`` (channels-last tap -> the reference's flatten
+        order), BatchNorm1d on batch (``training``) or running statistics, ``avid_probe_linear_fwd`` into ``arena``.  Returns the
+        head record (``"logits"``: Sym [B, Cn])."""
+        B, T, H, W, Cc = h.shape
+        To, Ho, Wo = c.pool_size
+        Fd = Cc * To * Ho * Wo
+        bn, lin = c.bn, c.classifier
+        if tuple(lin.weight.shape) != (Cn, Fd) or not lin.weight.is_contiguous() or bn.num_features != Fd or B > 256 or Fd > 16384:
+            raise Unsupported("probe head geometry")
+        pooled, normed, save2 = self.fa.alloc(4 * B * Fd), self.fa.alloc(4 * B * Fd), self.fa.alloc(8 * Fd)
+        d = ConvDesc()
+        d.To, d.Ho, d.Wo = To, Ho, Wo
+        self.emit(OP_ADAPTIVE_MAXPOOL, d=d, i=(B, T, H, W, Cc), t=(h.ref, pooled))
+        self.emit(OP_BN1D_FWD, i=(B, Fd, 1 if training else 0), f=(bn.momentum, bn.eps),
+                  t=(pooled, self.ext(bn.weight), self.ext(bn.bias), self.ext(bn.running_mean), self.ext(bn.running_var), normed, save2,
+                     self.ext(bn.num_batches_tracked) if training else None))
+        logits = (arena or self.fa).alloc(4 * B * Cn)
+        self.emit(OP_PROBE_LINEAR_FWD, i=(B, Fd, Cn), t=(normed, self.ext(lin.weight), self.ext(lin.bias), logits))
+        return {"c": c, "Fd": Fd, "pooled": pooled, "normed": normed, "save2": save2, "logits": Sym(logits, (B, Cn))}
+
+    # ---- module walkers --------------------------------------------------------------------------------------------
+    def video_fwd(self, vm, x, after_stem=None, arena=None):
+        """The tower; ``after_stem()`` runs behind the stem's records, ``arena``: where the pooled output goes (default: the forward
+        arena).  Returns ({"stem", "blocks": the blocks' layer records, "stages": {stage name: Sym of its output}, "pool"},
+        Sym of the pooled features)."""
+        from models.video import R2Plus1D
+        from models.network_blocks import BasicR2P1DBlock, BatchNormCL, ConvCL
+        if type(vm) is not R2Plus1D:
+            raise Unsupported(type(vm).__name__)
+        conv, bn = vm.conv1[0], vm.conv1[1]
+        if type(conv) is not ConvCL or type(bn) is not BatchNormCL:
+            raise Unsupported("video stem")
+        d, _, _, _, srows = self.desc(x.shape, conv.weight, conv.stride3, conv.padding3, True)
+        psh = (d.B, d.To, (d.Ho + 2 - 3) // 2 + 1, (d.Wo + 2 - 3) // 2 + 1, d.Cout)     # behind the stem's (1,3,3) / (1,2,2) max pool
+        stem, p = self.stem_fwd(conv.weight, bn, x, d, srows, psh)
+        h = Sym(p, psh)
+        if after_stem is not None:
+            after_stem()
+        blocks, stages = [], {}
+        for name in _STAGES:
+            stage = getattr(vm, name)
+            for blk in (stage if isinstance(stage, torch.nn.Sequential) else [stage]):
+                if type(blk) is not BasicR2P1DBlock:
+                    raise Unsupported(type(blk).__name__)
+                Ls, h = self.r2p1d_block_fwd(blk, h)
+                blocks.append(Ls)
+            stages[name] = h
+        pool = self.gpool_fwd(h, arena=arena)
+        return {"stem": stem, "blocks": blocks, "stages": stages, "pool": pool}, pool["y"]
+
+    def audio_fwd(self, am, x):
+        from models.audio import Conv2D
+        from models.network_blocks import Basic2DBlock
+        if type(am) is not Conv2D:
+            raise Unsupported(type(am).__name__)
+        Ls = [self.conv_bn_fwd(am.conv1[0], am.conv1[1], x)]
+        for blk in (am.block1, am.block2, am.block3, am.block4):
+            if type(blk) is not Basic2DBlock:
+                raise Unsupported(type(blk).__name__)
+            for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
+                Ls.append(self.conv_bn_fwd(conv, bn, Ls[-1]["h"]))
+        pool = self.gpool_fwd(Ls[-1]["h"])
+        return {"layers": Ls, "pool": pool}, pool["y"]
+
+    def head_fwd(self, head, x, arena=None):
+        """The projection head; ``arena``: where the LAST layer's output goes (default: the forward arena)."""
+        from models.av_wrapper import Head, LinearCL
+        if type(head) is not Head:
+            raise Unsupported(type(head).__name__)
+        mods = list(head.projection)
+        Ls, k = [], 0
+        while k < len(mods):
+            if type(mods[k]) is not LinearCL:
+                raise Unsupported("head")
+            relu = k + 1 < len(mods) and isinstance(mods[k + 1], torch.nn.ReLU)
+            k_next = k + (2 if relu else 1)
+            L = self.linear_fwd(mods[k], x, relu, arena=arena if k_next >= len(mods) else None)
+            Ls.append(L)
+            x, k = L["y"], k_next
+        return Ls, x
+
+
+class TrainBuilder(Builder):
+    """The training form: BatchNorms on batch statistics, every activation kept in a bump arena, then the backward records,
+    the flat gradient buffer's layout and the order in which its slices complete."""
+
+    def __init__(self, device, overlap_towers, trailing, group):
+        super().__init__(device, Arena(S_FWD))
+        self.overlap, self.trailing, self.group = overlap_towers, trailing, group
+        self.ba = Arena(S_BWD)
+        self.bwd = []
+        self.params, self.pindex = [], {}          # trainable parameters in gradient-buffer order
+        self.pending = {ST_MAIN: [], ST_AUDIO: []}  # queued weight gradients per compute stream
+        self.trail_used = set()
+        self.grad_ready = []                       # (index of the backward record that completes them, [param index])
+        self._err = None
+
+    def grad(self, p):
+        """Reference of parameter p's slice of the flat gradient buffer."""
+        return (S_GRAD, 4 * self.goff[self.pindex[id(p)]])
+
+    def set_params(self, params):
+        """Gradient-buffer layout = ``parallel.FlatParams``': reverse registration order, 16-byte aligned slices."""
+        self.params = list(reversed(params))
+        self.goff, off = [], 0
+        for k, p in enumerate(self.params):
+            self.pindex[id(p)] = k
+            self.goff.append(off)
+            off += (p.numel() + 3) // 4 * 4
+        self.gnumel = off
+
+    def dgrad_wt_u(self, w, d):
+        """(wt, u) of an input gradient: the Winograd transform, the pre-split transpose, or the plain transpose."""
+        if d.wino_dgrad:
+            return self.want_wt(w), self.want_u(w, d.wino_dgrad)
+        if d.split_dgrad:
+            return None, self.want_split(w, 6)
+        return self.want_wt(w), None
+
+    # ---- forward emitters ------------------------------------------------------------------------------------------
+    def stem_fwd(self, w, bn, x, d, srows, psh):
+        """The video stem: convolution with BatchNorm partial sums, then BatchNorm + ReLU + max pool in one pass."""
+        B, T, H, W, Cc = d.B, d.To, d.Ho, d.Wo, d.Cout
+        n = B * psh[1] * psh[2] * psh[3] * Cc
+        y = self.fa.alloc(4 * B * T * H * W * Cc)
+        stats = self.fa.alloc(4 * srows * 2 * Cc) if srows > 0 else None
+        self.emit(OP_CONV_FWD, d=d, i=(0,), t=(x.ref, self.ext(w), None, None, None, y, stats))
+        p = self.fa.alloc(4 * n)
+        am = self.fa.alloc(n)
+        s4 = self.fa.alloc(16 * Cc)
+        self.emit(OP_BN_POOL_FWD, i=(B, T, H, W, Cc, srows if stats is not None else 0), f=(bn.momentum, bn.eps),
+                  t=(y, self.ext(bn.weight), self.ext(bn.bias), self.ext(bn.running_mean), self.ext(bn.running_var), p, am, s4,
+                     self.ext(bn.num_batches_tracked), stats))
+        return {"d": d, "w": w, "x": x, "y": y, "am": am, "s4": s4, "bn": bn, "dims": (B, T, H, W, Cc)}, p
+
+    def conv_bn_fwd(self, conv, bn, x, addend=None, next_conv=None, res=None, sole=True):
         """ReLU(bn(conv(x) [+ addend])) (network_blocks._conv_bn in training mode).  Returns the layer record.
 
         ``next_conv``: the ONLY consumer of this layer's output, if that is known to be a convolution.  When its kernels can apply
-        a BatchNorm (+ReLU) to their input while they stage it (``d.in_affine``: conv2x's temporal layers), this layer's
+        a BatchNorm (+ReLU) to their input while they stage it (``applies_bn``), this layer's
         BatchNorm makes its statistics only and the returned ``h`` is the convolution's OUTPUT tagged with the map
         (``Sym.affine``): the normalised tensor is never written or read."""
         w = conv.weight
@@ -275,11 +478,7 @@ class Builder:
             self.emit(OP_CONV_FWD, d=dr, i=(0,), t=(x.ref, self.ext(rw), self.fwd_u(rw, dr), None, None, y_res, None))
             L["res"] = {"conv": rconv, "d": dr, "w": rw, "y": Sym(y_res, (d.B, dr.To, dr.Ho, dr.Wo, dr.Cout))}
         Cc = d.Cout
-        defer = False
-        if next_conv is not None and addend is None and res is None:
-            nw = next_conv.weight
-            if ops.weight_layout_ok(nw) and nw.dtype == torch.float32 and nw.shape[1] == Cc and not next_conv.channel_first:
-                defer = self.desc(ysh, nw, next_conv.stride3, next_conv.padding3, False)[0].in_affine
+        defer = addend is None and res is None and self.applies_bn(next_conv, ysh)
         h = None if defer else self.fa.alloc(4 * M * Cc)
         s4 = self.fa.alloc(4 * 4 * Cc)
         self.emit(OP_BN_FWD, n=(M,), i=(Cc, 1, srows if stats is not None else 0), f=(bn.momentum, bn.eps),
@@ -290,25 +489,30 @@ class Builder:
         L["h"] = Sym(y, ysh, bn=rec, affine=(s4, 1, Cc)) if defer else Sym(h, ysh, bn=rec)
         return L
 
-    def linear_fwd(self, lin, x, relu, arena=None):
-        """nn.Linear (+ReLU) as a 1x1x1 convolution over [B,1,1,1,C] (ops.linear).  ``arena``: where the output goes (default:
-        the forward arena)."""
-        w = lin.weight
-        B, Cin = x.shape
-        d = ops._desc_cached((B, 1, 1, 1), w.shape[1], w.shape[0], (1, 1, 1), (1, 1, 1), (0, 0, 0), False)[0]
-        if Cin != w.shape[1] or not ops.weight_layout_ok(w):
-            raise Unsupported("linear")
-        y = (arena or self.fa).alloc(4 * B * d.Cout)
-        self.emit(OP_CONV_FWD, d=d, i=(1 if relu else 0,), t=(x.ref, self.ext(w), None, None, self.ext(lin.bias), y, None))
-        return {"lin": lin, "d": d, "x": x, "y": Sym(y, (B, d.Cout)), "relu": relu, "w": w}
+    def r2p1d_block_fwd(self, blk, x):
+        """The strided 1x1x1 residual convolution is emitted right behind ``spt_conv1`` (the same input, ``conv_bn_fwd(res=...)``)."""
+        from models.network_blocks import res_fusable
+        if blk.res and not res_fusable(blk, x.numel):
+            raise Unsupported("residual convolution outside the fused pattern")
+        # (spt_bn1 -> tmp_conv1 and spt_bn2 -> tmp_conv2: each BatchNorm's output has exactly one reader, the next convolution)
+        L1 = self.conv_bn_fwd(blk.spt_conv1, blk.spt_bn1, x, res=blk.res_conv if blk.res else None,
+                              next_conv=None if blk.res else blk.tmp_conv1)
+        L2 = self.conv_bn_fwd(blk.tmp_conv1, blk.tmp_bn1, L1["h"])
+        L3 = self.conv_bn_fwd(blk.spt_conv2, blk.spt_bn2, L2["h"], next_conv=blk.tmp_conv2)
+        addend = L1["res"]["y"] if blk.res else x
+        L4 = self.conv_bn_fwd(blk.tmp_conv2, blk.out_bn, L3["h"], addend=addend)
+        return (L1, L2, L3, L4), L4["h"]
 
-    def gpool_fwd(self, x, arena=None):
-        B, Cc = x.shape[0], x.shape[-1]
-        S = x.numel // (B * Cc)
-        y = (arena or self.fa).alloc(4 * B * Cc)
-        am = self.fa.alloc(4 * B * Cc)
-        self.emit(OP_GPOOL_FWD, i=(B, S, Cc), t=(x.ref, y, am))
-        return {"x": x, "y": Sym(y, (B, Cc)), "am": am, "S": S}
+    def cls_loss(self, logits, tap=0):
+        """``AVID_OP_CLS_LOSS`` of head ``tap`` (run by the step engine only): loss and hits into its OUT_BYTES of S_OUT, its
+        [B, C] of ``dlogits``; a label outside [0, C) is reported in the device error word (ops.DeviceErrors)."""
+        B, Cn = logits.shape
+        if self._err is None:
+            dry = self.device.type != "cuda"
+            self._err = self.ext(torch.zeros((), dtype=torch.int32) if dry else ops.DeviceErrors.get(self.device).flag)
+        self.emit(OP_CLS_LOSS, i=(B, 1, Cn), f=(1.0,),
+                  t=(logits.ref, (S_LABELS, 0), (S_OUT, OUT_BYTES * tap), None, (S_OUT, OUT_BYTES * tap + 8),
+                     (S_DLOGITS, 4 * B * Cn * tap), self._err))
 
     # ---- backward emitters -----------------------------------------------------------------------------------------
     def _ready(self, stream, *ps):
@@ -429,22 +633,6 @@ class Builder:
         self.emit(OP_GPOOL_BWD, i=(x.shape[0], P["S"], x.shape[-1]), t=(dy, P["am"], dx))
         return dx
 
-    # ---- module walkers --------------------------------------------------------------------------------------------
-    def r2p1d_block_fwd(self, blk, x):
-        from models.network_blocks import BasicR2P1DBlock, res_fusable
-        if type(blk) is not BasicR2P1DBlock:
-            raise Unsupported(type(blk).__name__)
-        if blk.res and not res_fusable(blk, x.numel):
-            raise Unsupported("residual convolution outside the fused pattern")
-        # (spt_bn1 -> tmp_conv1 and spt_bn2 -> tmp_conv2: each BatchNorm's output has exactly one reader, the next convolution)
-        L1 = self.conv_bn_fwd(blk.spt_conv1, blk.spt_bn1, x, res=blk.res_conv if blk.res else None,
-                              next_conv=None if blk.res else blk.tmp_conv1)
-        L2 = self.conv_bn_fwd(blk.tmp_conv1, blk.tmp_bn1, L1["h"])
-        L3 = self.conv_bn_fwd(blk.spt_conv2, blk.spt_bn2, L2["h"], next_conv=blk.tmp_conv2)
-        addend = L1["res"]["y"] if blk.res else x
-        L4 = self.conv_bn_fwd(blk.tmp_conv2, blk.out_bn, L3["h"], addend=addend)
-        return (L1, L2, L3, L4), L4["h"]
-
     def r2p1d_block_bwd(self, Ls, dout):
         L1, L2, L3, L4 = Ls
         g4, dh3 = self.conv_bn_bwd(L4, dout)
@@ -455,41 +643,6 @@ class Builder:
         else:
             _, dx = self.conv_bn_bwd(L1, dh1, add=g4)       # identity residual: its gradient rides in the dgrad's addend
         return dx
-
-    def video_fwd(self, vm, x, after_stem=None):
-        from models.video import R2Plus1D
-        from models.network_blocks import BatchNormCL, ConvCL
-        if type(vm) is not R2Plus1D:
-            raise Unsupported(type(vm).__name__)
-        conv, bn = vm.conv1[0], vm.conv1[1]
-        if type(conv) is not ConvCL or type(bn) is not BatchNormCL:
-            raise Unsupported("video stem")
-        w = conv.weight
-        d, _, _, _, srows = self.desc(x.shape, w, conv.stride3, conv.padding3, True)
-        M = d.B * d.To * d.Ho * d.Wo
-        y = self.fa.alloc(4 * M * d.Cout)
-        stats = self.fa.alloc(4 * srows * 2 * d.Cout) if srows > 0 else None
-        self.emit(OP_CONV_FWD, d=d, i=(0,), t=(x.ref, self.ext(w), None, None, None, y, stats))
-        B, T, H, W, Cc = d.B, d.To, d.Ho, d.Wo, d.Cout
-        Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-        p = self.fa.alloc(4 * B * T * Ho * Wo * Cc)
-        am = self.fa.alloc(B * T * Ho * Wo * Cc)
-        s4 = self.fa.alloc(16 * Cc)
-        self.emit(OP_BN_POOL_FWD, i=(B, T, H, W, Cc, srows if stats is not None else 0), f=(bn.momentum, bn.eps),
-                  t=(y, self.ext(bn.weight), self.ext(bn.bias), self.ext(bn.running_mean), self.ext(bn.running_var), p, am, s4,
-                     self.ext(bn.num_batches_tracked), stats))
-        stem = {"d": d, "w": w, "x": x, "y": y, "am": am, "s4": s4, "bn": bn, "dims": (B, T, H, W, Cc)}
-        h = Sym(p, (B, T, Ho, Wo, Cc))
-        if after_stem is not None:
-            after_stem()
-        blocks = []
-        for name in ("conv2x", "conv3x", "conv4x", "conv5x"):
-            stage = getattr(vm, name)
-            for blk in (stage if isinstance(stage, torch.nn.Sequential) else [stage]):
-                Ls, h = self.r2p1d_block_fwd(blk, h)
-                blocks.append(Ls)
-        pool = self.gpool_fwd(h)
-        return {"stem": stem, "blocks": blocks, "pool": pool}, pool["y"]
 
     def video_bwd(self, V, dy):
         dh = self.gpool_bwd(V["pool"], dy)
@@ -507,44 +660,11 @@ class Builder:
         self._ready(self.S, bn.weight, bn.bias)
         self.conv_bwd(st["d"], st["w"], st["x"], dx, False)
 
-    def audio_fwd(self, am, x):
-        from models.audio import Conv2D
-        from models.network_blocks import Basic2DBlock
-        if type(am) is not Conv2D:
-            raise Unsupported(type(am).__name__)
-        Ls = [self.conv_bn_fwd(am.conv1[0], am.conv1[1], x)]
-        h = Ls[0]["h"]
-        for blk in (am.block1, am.block2, am.block3, am.block4):
-            if type(blk) is not Basic2DBlock:
-                raise Unsupported(type(blk).__name__)
-            for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
-                L = self.conv_bn_fwd(conv, bn, h)
-                Ls.append(L)
-                h = L["h"]
-        pool = self.gpool_fwd(h)
-        return {"layers": Ls, "pool": pool}, pool["y"]
-
     def audio_bwd(self, A, dy):
         dh = self.gpool_bwd(A["pool"], dy)
         Ls = A["layers"]
         for k in range(len(Ls) - 1, -1, -1):
             _, dh = self.conv_bn_bwd(Ls[k], dh, need_dx=k > 0)
-
-    def head_fwd(self, head, x):
-        from models.av_wrapper import Head, LinearCL
-        if type(head) is not Head:
-            raise Unsupported(type(head).__name__)
-        mods = list(head.projection)
-        Ls, k = [], 0
-        while k < len(mods):
-            if type(mods[k]) is not LinearCL:
-                raise Unsupported("head")
-            relu = k + 1 < len(mods) and isinstance(mods[k + 1], torch.nn.ReLU)
-            L = self.linear_fwd(mods[k], x, relu)
-            Ls.append(L)
-            x = L["y"]
-            k += 2 if relu else 1
-        return Ls, x
 
     def head_bwd(self, Ls, dy):
         for L in reversed(Ls):
@@ -552,85 +672,145 @@ class Builder:
         return dy
 
 
+class EvalBuilder(Builder):
+    """The eval form of the layer emitters: BatchNorms use their running statistics — every coefficient vector comes out of ONE
+    launch at the head of the program (``AVID_OP_BN_EVAL_COEFFS``), a (3,1,1) layer of conv2x applies its own BatchNorm in its
+    epilogue (``d.out_affine``) and the one in front of it while staging (``d.in_affine``), everything else is a convolution
+    followed by ``AVID_OP_BN_EVAL_APPLY``; the stem's tail is one pass.  No statistics, no argmax of the stem's pool, no saved
+    vectors for a backward.  Each record is the call the per-layer path makes in eval mode with trainable BatchNorm parameters
+    (``avid_bn_fwd_eval`` with ``save4``: y = fma(x, scale, shift)) or a fusion that is bit-identical to it.
+    A BatchNorm whose weight and bias take NO gradient (the linear probe's frozen tower) is another case: the per-layer path then
+    calls ``avid_bn_fwd_eval`` without ``save4``, which evaluates ``(x - mean) * invstd * gamma + beta`` — other bits than the
+    fma.  Such a BatchNorm is never fused: it is one ``AVID_OP_BN_EVAL_DIRECT`` record (the same call), the stem's pool behind it
+    an ``AVID_OP_MAXPOOL_FWD`` record, and it has no entry in the coefficient table.
+    Activations go to an ``EvalArena`` (``self.fa``), what leaves the program to ``self.oa`` (slot ``S_OUT``)."""
+
+    def __init__(self, device):
+        super().__init__(device, EvalArena(S_FWD))
+        self.oa = Arena(S_OUT)
+        self.bn_recs, self.bn_off = [], {}         # (BatchNorm module, aux offset of its [4][C] vectors)
+
+    @staticmethod
+    def frozen(bn):
+        """The per-layer path computes this BatchNorm without coefficient vectors (ops._BatchNormCL.forward: no gradient can flow)."""
+        return not (bn.weight.requires_grad or bn.bias.requires_grad)
+
+    def bn_direct(self, bn, x, M, Cc, relu=1):
+        """The unfused eval-mode BatchNorm (+ReLU) of a frozen BatchNorm: x -> a new tensor."""
+        from models.network_blocks import BatchNormCL
+        if type(bn) is not BatchNormCL or bn.weight.dtype != torch.float32:
+            raise Unsupported("BatchNorm")
+        h = self.fa.alloc(4 * M * Cc)
+        self.emit(OP_BN_EVAL_DIRECT, n=(M,), i=(Cc, relu), f=(0.0, bn.eps),
+                  t=(x, self.ext(bn.weight), self.ext(bn.bias), self.ext(bn.running_mean), self.ext(bn.running_var), h))
+        return h
+
+    def coeffs(self, bn):
+        from models.network_blocks import BatchNormCL
+        off = self.bn_off.get(id(bn))
+        if off is None:
+            if type(bn) is not BatchNormCL or bn.weight.dtype != torch.float32:
+                raise Unsupported("BatchNorm")
+            off = self.bn_off[id(bn)] = self.aux_size
+            self.bn_recs.append((bn, off))
+            self.aux_size += _align(16 * bn.num_features)
+        return (S_AUX, off)
+
+    def stem_fwd(self, w, bn, x, d, srows, psh):
+        """The video stem: convolution, then BatchNorm + ReLU + max pool in one pass (no partial sums, no argmax)."""
+        B, T, H, W, Cc = d.B, d.To, d.Ho, d.Wo, d.Cout
+        n = B * psh[1] * psh[2] * psh[3] * Cc
+        y = self.fa.alloc(4 * B * T * H * W * Cc)
+        self.emit(OP_CONV_FWD, d=d, i=(0,), t=(x.ref, self.ext(w), None, None, None, y, None))
+        p = self.fa.alloc(4 * n)
+        if self.frozen(bn):                        # bn -> maxpool as the per-layer path runs them (its pool writes an argmax)
+            am = self.fa.alloc(n)
+            self.emit(OP_MAXPOOL_FWD, i=(B, T, H, W, Cc), t=(self.bn_direct(bn, y, B * T * H * W, Cc), p, am))
+        else:
+            self.emit(OP_BN_POOL_FWD_EVAL, i=(B, T, H, W, Cc), t=(y, self.coeffs(bn), p))
+        return None, p
+
+    def conv_bn_fwd(self, conv, bn, x, addend=None, next_conv=None):
+        """ReLU(bn_eval(conv(x) [+ addend])); returns {"h": Sym of the result} (``affine`` set: its only consumer applies the map)."""
+        w = conv.weight
+        d = self.desc(x.shape, w, conv.stride3, conv.padding3, conv.channel_first)[0]
+        ysh = (d.B, d.To, d.Ho, d.Wo, d.Cout)
+        M, Cc = d.B * d.To * d.Ho * d.Wo, d.Cout
+        xa = x.affine
+        if xa is not None and not d.in_affine:
+            raise Unsupported("a tensor with a pending BatchNorm reached a layer that cannot apply it")
+        iv = (0, 0, 0) if xa is None else (0, 2 if xa[1] else 1, xa[2])
+        t = [x.ref, self.ext(w), self.fwd_u(w, d), addend.ref if addend is not None else None, None]
+        xr = None if xa is None else xa[0]
+        if self.frozen(bn):                        # convolution, then the call the per-layer path makes: nothing fused
+            y = self.fa.alloc(4 * M * Cc)
+            self.emit(OP_CONV_FWD, d=d, i=iv, t=t + [y, None, xr])
+            return {"h": Sym(self.bn_direct(bn, y, M, Cc), ysh)}
+        c4 = self.coeffs(bn)
+        if d.out_affine:
+            h = self.fa.alloc(4 * M * Cc)
+            self.emit(OP_CONV_FWD, d=d, i=iv + (2,), t=t + [h, None, xr, c4])
+            return {"h": Sym(h, ysh)}
+        y = self.fa.alloc(4 * M * Cc)
+        self.emit(OP_CONV_FWD, d=d, i=iv, t=t + [y, None, xr])
+        if addend is None and self.applies_bn(next_conv, ysh):
+            return {"h": Sym(y, ysh, affine=(c4, 1, Cc))}
+        h = self.fa.alloc(4 * M * Cc)
+        self.emit(OP_BN_EVAL_APPLY, n=(M,), i=(Cc, 1), t=(y, c4, h))
+        return {"h": Sym(h, ysh)}
+
+    def r2p1d_block_fwd(self, blk, x):
+        """The strided 1x1x1 residual convolution is a record of its own in front of ``tmp_conv2``, which adds it: its output
+        lives for one record, which keeps the recycled arena small."""
+        h = self.conv_bn_fwd(blk.spt_conv1, blk.spt_bn1, x, next_conv=blk.tmp_conv1)["h"]
+        h = self.conv_bn_fwd(blk.tmp_conv1, blk.tmp_bn1, h)["h"]
+        h = self.conv_bn_fwd(blk.spt_conv2, blk.spt_bn2, h, next_conv=blk.tmp_conv2)["h"]
+        res = x
+        if blk.res:
+            rc = blk.res_conv
+            dr = self.desc(x.shape, rc.weight, rc.stride3, rc.padding3, False)[0]
+            yr = self.fa.alloc(4 * dr.B * dr.To * dr.Ho * dr.Wo * dr.Cout)
+            self.emit(OP_CONV_FWD, d=dr, i=(0,), t=(x.ref, self.ext(rc.weight), self.fwd_u(rc.weight, dr), None, None, yr, None))
+            res = Sym(yr, (dr.B, dr.To, dr.Ho, dr.Wo, dr.Cout))
+        return None, self.conv_bn_fwd(blk.tmp_conv2, blk.out_bn, h, addend=res)["h"]
+
+
 class Programs:
-    """A compiled pair of launch programs — forward and backward — over all of one model's parameters: what the two-tower
-    ``Plan`` and the classifier's ``ClsPlan`` share.  A subclass compiles its own graph between ``_open`` (the checks, the
-    forward's leading records), ``_backward_begins`` and ``_close`` (the backward's tail), and issues its own forward;
-    the backward program runs the same way for both (``backward``)."""
+    """Launch programs sealed and ready to run: the record arrays of what a ``Builder`` emitted, the aux buffer with the
+    weight-transform tables, the streams' workspaces, the slot table — and the per-run plumbing that fills them."""
 
-    adam_early = None        # gradient offset from which the optimizer may start before the backward program ends (Plan)
-
-    def _open(self, model, device, overlap_towers, trailing, group, frozen_ok=False):
-        """The Builder of the model's parameters and the forward's leading records: what the backward needs but the forward
-        does not — the gradient fill, the transposed / Winograd-transformed weights — runs on the trailing stream beside
-        the forward; the table is known only after the backward is compiled, so ``_finalize`` patches it in.
-        ``frozen_ok``: parameters without ``requires_grad`` are allowed (the linear probe's tower); the gradient buffer
-        then holds the trainable ones only, as ``parallel.FlatParams`` lays them out."""
-        params = [p for p in model.parameters()]
-        dry = device.type != "cuda"                  # (compile only: tests/test_plan_compile.py, no GPU)
-        if not all((p.requires_grad or frozen_ok) and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
-            raise Unsupported("frozen / non-fp32 parameters")
-        params = [p for p in params if p.requires_grad]
-        b = Builder(device, overlap_towers, trailing, group)
-        b.set_params(params)
-        self.device, self.params_fwd = device, params
-        b.cur = b.fwd
-        helper = ST_TRAIL if trailing else ST_MAIN
-        if trailing:
-            b.wait(helper, ST_MAIN)
-        self._zero_index = len(b.fwd)
-        b.emit(OP_MEMSET0, stream=helper, n=(4 * b.gnumel,), t=((S_GRAD, 0),))
-        self._wt_rec = b.emit(OP_WT_BATCH, stream=helper, i=(0,), n=(0,), t=((S_AUX, 0),))
-        b.S = ST_MAIN
-        return b
-
-    def _backward_begins(self, b):
-        """The forward program ends here; the backward starts once the transposed weights are complete."""
-        self.n_fwd = len(b.fwd)
-        b.cur = b.bwd
-        if b.trailing:
-            b.wait(ST_MAIN, ST_TRAIL)
-        b.S = ST_MAIN
-
-    def _close(self, b, *joined):
-        """The backward's last weight-gradient group, then the compute stream joins ``joined`` and every trailing stream."""
-        b.flush_group(ST_MAIN)
-        for S in joined + tuple(sorted(b.trail_used)):
-            b.wait(ST_MAIN, S)
-        self.n_bwd = len(b.bwd)
-        self._finalize(b)
-
-    def _finalize(self, b):
-        """The weight-transform table, the record arrays, the arenas' sizes and the streams' workspaces."""
-        # ------------------------------------------------------------------ the weight-transform table
-        self.aux_bytes = _align(b.aux_size) + 32 * len(b.wt_recs) + 256
-        self.table_off = _align(b.aux_size)
+    def _seal(self, b, *programs):
+        """Patch the weight-transform record (``self._wt_rec``) now that the table is known, then freeze each record list of
+        ``programs`` into an ``Instr`` array (returned, in order) and size the aux buffer and the streams' workspaces for all."""
         self.wt_recs = b.wt_recs
+        self.table_off = _align(b.aux_size)
+        self.aux_bytes = self._aux_layout(b)
         self._wt_rec.i[0] = len(b.wt_recs)
         self._wt_rec.n[0] = max([r[2] * r[3] * r[4] for r in b.wt_recs] + [1])
         self._wt_rec.t[0].off = self.table_off
         if not b.wt_recs:
             self._wt_rec.op = 0
-        self.fwd_prog = (Instr * max(1, self.n_fwd))(*b.fwd)
-        self.bwd_prog = (Instr * max(1, self.n_bwd))(*b.bwd)
-        self.fa_bytes, self.ba_bytes = max(b.fa.size, 256), max(b.ba.size, 256)
-        self.params, self.goff, self.gnumel = b.params, b.goff, b.gnumel
-        self.tensors = b.tensors
-        self.n_slots = S_FIRST_TENSOR + len(self.tensors)
-        self.grad_ready = b.grad_ready
-        self.n_streams = 4
-        need_f, need_b = (_sz * 4)(), (_sz * 4)()
-        lib.call("avid_program_workspace_bytes", self.fwd_prog, 0, self.n_fwd, 4, need_f)
-        lib.call("avid_program_workspace_bytes", self.bwd_prog, 0, self.n_bwd, 4, need_b)
-        self.ws_bytes = [max(int(need_f[k]), int(need_b[k]), 1 << 20) for k in range(4)]
+        progs = [(Instr * max(1, len(recs)))(*recs) for recs in programs]
+        self.ws_bytes = [1 << 20] * 4
+        for prog, recs in zip(progs, programs):
+            need = (_sz * 4)()
+            lib.call("avid_program_workspace_bytes", prog, 0, len(recs), 4, need)
+            self.ws_bytes = [max(have, int(n)) for have, n in zip(self.ws_bytes, need)]
         self.ws = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in self.ws_bytes]
         self.ws_arr = (StreamWs * 4)()
         for k in range(4):
             self.ws_arr[k].ptr, self.ws_arr[k].bytes = self.ws[k].data_ptr(), self.ws_bytes[k]
         self.aux = torch.empty(self.aux_bytes, dtype=torch.uint8, device=self.device)
         self._table_ptrs = None
+        self.tensors = b.tensors
+        self.n_slots = S_FIRST_TENSOR + len(self.tensors)
         self.slots = (_vp * self.n_slots)()
         self.streams = (_vp * 4)()
+        return progs
+
+    def _aux_layout(self, b):
+        """Bytes of the aux buffer: the builder's transformed weights, then the weight-transform table at ``table_off``."""
+        return self.table_off + 32 * len(b.wt_recs) + 256
 
     # ---- per-run plumbing ------------------------------------------------------------------------------------------
     def _fill_slots(self, fa, ba, grad, inputs):
@@ -658,6 +838,59 @@ class Programs:
         st[0], st[1], st[2], st[3] = ss.main.cuda_stream, ss.side.cuda_stream, ss.trail.cuda_stream, ss.comm.cuda_stream
         self.stream_objs = (ss.main, ss.side, ss.trail, ss.comm)
 
+    def _run(self, prog, begin, end):
+        """Issue records [begin, end) of ``prog`` with the slots and streams set."""
+        lib.call("avid_program_run", prog, begin, end, self.slots, self.n_slots, self.streams, self.ws_arr, 4)
+
+
+class TrainPrograms(Programs):
+    """A compiled pair of launch programs — forward and backward — over all of one model's parameters: what the two-tower
+    ``Plan``, the classifier's ``ClsPlan`` and the probe's ``ProbePlan`` share.  A subclass compiles its own graph between
+    ``_open`` (the checks, the forward's leading records), ``_backward_begins`` and ``_close`` (the backward's tail), and
+    issues its own forward; the backward program runs the same way for all (``backward``)."""
+
+    adam_early = None        # gradient offset from which the optimizer may start before the backward program ends (Plan)
+
+    def _open(self, model, device, overlap_towers, trailing, group, frozen_ok=False):
+        """The TrainBuilder of the model's parameters and the forward's leading records: what the backward needs but the forward
+        does not — the gradient fill, the transposed / Winograd-transformed weights — runs on the trailing stream beside
+        the forward; the table is known only after the backward is compiled, so ``_seal`` patches it in.
+        ``frozen_ok``: parameters without ``requires_grad`` are allowed (the linear probe's tower); the gradient buffer
+        then holds the trainable ones only, as ``parallel.FlatParams`` lays them out."""
+        params = [p for p in model.parameters()]
+        dry = device.type != "cuda"                  # (compile only: tests/test_plan_compile.py, no GPU)
+        if not all((p.requires_grad or frozen_ok) and (p.is_cuda or dry) and p.dtype == torch.float32 for p in params):
+            raise Unsupported("frozen / non-fp32 parameters")
+        params = [p for p in params if p.requires_grad]
+        b = TrainBuilder(device, overlap_towers, trailing, group)
+        b.set_params(params)
+        self.device, self.params_fwd = device, params
+        helper = ST_TRAIL if trailing else ST_MAIN
+        if trailing:
+            b.wait(helper, ST_MAIN)
+        self._zero_index = len(b.fwd)
+        b.emit(OP_MEMSET0, stream=helper, n=(4 * b.gnumel,), t=((S_GRAD, 0),))
+        self._wt_rec = b.emit(OP_WT_BATCH, stream=helper, i=(0,), n=(0,), t=((S_AUX, 0),))
+        b.S = ST_MAIN
+        return b
+
+    def _backward_begins(self, b):
+        """The forward program ends here; the backward starts once the transposed weights are complete."""
+        b.cur = b.bwd
+        if b.trailing:
+            b.wait(ST_MAIN, ST_TRAIL)
+        b.S = ST_MAIN
+
+    def _close(self, b, *joined):
+        """The backward's last weight-gradient group, then the compute stream joins ``joined`` and every trailing stream."""
+        b.flush_group(ST_MAIN)
+        for S in joined + tuple(sorted(b.trail_used)):
+            b.wait(ST_MAIN, S)
+        self.n_fwd, self.n_bwd = len(b.fwd), len(b.bwd)
+        self.fa_bytes, self.ba_bytes = max(b.fa.size, 256), max(b.ba.size, 256)
+        self.params, self.goff, self.gnumel, self.grad_ready = b.params, b.goff, b.gnumel, b.grad_ready
+        self.fwd_prog, self.bwd_prog = self._seal(b, b.fwd, b.bwd)
+
     def _forward_arena(self, grad_flat, zero_grad, inputs):
         """A run of the forward program set up: weight table, arena, slots, streams, gradient fill on or off.  Returns the arena."""
         self._refresh_table()
@@ -667,9 +900,10 @@ class Programs:
         self.fwd_prog[self._zero_index].op = OP_MEMSET0 if (zero_grad and grad_flat is not None) else 0
         return fa
 
-    def _run(self, prog, begin, end):
-        """Issue records [begin, end) of ``prog`` with the slots and streams set."""
-        lib.call("avid_program_run", prog, begin, end, self.slots, self.n_slots, self.streams, self.ws_arr, 4)
+    def _view(self, fa, lg):
+        """The tensor of a Sym (logits, embeddings) in the forward arena ``fa``."""
+        n = 4 * lg.numel
+        return fa[lg.ref[1]:lg.ref[1] + n].view(torch.float32).view(lg.shape)
 
     def backward(self, fa, inputs, grad_flat, begin=0, end=None, ba=None):
         """Issue records [begin, end) of the backward program (default: all of them) after the forward that returned ``fa``;
@@ -713,14 +947,13 @@ class Programs:
         return segs
 
 
-class Plan(Programs):
+class Plan(TrainPrograms):
     """The compiled forward / backward programs of one ``AV_Wrapper`` for one input geometry and stream arrangement."""
 
     def __init__(self, model, vshape, ashape, device, overlap_towers, trailing, group):
         if not model.use_linear_proj:
             raise Unsupported("no projection heads")
         b = self._open(model, device, overlap_towers, trailing, group)
-        self.key = (tuple(vshape), tuple(ashape), overlap_towers, trailing, group)
         self.vshape, self.ashape = tuple(vshape), tuple(ashape)
         video = Sym((S_VIDEO, 0), vshape)
         audio = Sym((S_AUDIO, 0), (ashape[0], ashape[1], 1, ashape[2], ashape[3]))   # [B,1,1,H,W]: T = kt = 1
@@ -780,11 +1013,7 @@ class Plan(Programs):
         """Issue the forward program; returns (v_emb, a_emb, arena)."""
         fa = self._forward_arena(grad_flat, zero_grad, (video, audio, None, None))
         self._run(self.fwd_prog, 0, self.n_fwd)
-        B = self.vshape[0]
-        D = self.vemb.shape[1]
-        ve = fa[self.vemb.ref[1]:self.vemb.ref[1] + 4 * B * D].view(torch.float32).view(B, D)
-        ae = fa[self.aemb.ref[1]:self.aemb.ref[1] + 4 * B * D].view(torch.float32).view(B, D)
-        return ve, ae, fa
+        return self._view(fa, self.vemb), self._view(fa, self.aemb), fa
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -837,6 +1066,17 @@ def _check_backward(ctx):
         raise RuntimeError("avid_hip.plan: a parameter was modified in place between the forward and the backward pass")
 
 
+def _autograd_backward(ctx, inputs, n_inputs):
+    """The backward program outside a step engine: into a fresh flat gradient buffer whose slices go to autograd as the
+    parameters' gradients, behind ``n_inputs`` Nones for the node's other inputs.  Releases the forward's arena."""
+    pl = ctx.pl
+    g = torch.empty(pl.gnumel, dtype=torch.float32, device=inputs[2].device)
+    pl.backward(ctx.fa, inputs, g)
+    ctx.fa = None
+    views = pl.grad_views(g)
+    return (None,) * n_inputs + tuple(views[id(p)] for p in ctx.params)
+
+
 class NetFn(torch.autograd.Function):
     """(video, audio) -> (video_emb, audio_emb): models/av_wrapper.py:50-61 with both towers, both heads and all of
     their backward as two launch programs."""
@@ -865,11 +1105,7 @@ class NetFn(torch.autograd.Function):
             eng._plan_backward(pl, ctx.fa, inputs)
             ctx.fa = None
             return (None, None, None) + (None,) * len(params)
-        g = torch.empty(pl.gnumel, dtype=torch.float32, device=dv.device)
-        pl.backward(ctx.fa, inputs, g)
-        ctx.fa = None
-        views = pl.grad_views(g)
-        return (None, None, None) + tuple(views[id(p)] for p in params)
+        return _autograd_backward(ctx, inputs, 3)
 
 
 def _cached(model, name, make):
@@ -880,26 +1116,28 @@ def _cached(model, name, make):
     return v
 
 
-def _tree_ok(model):
-    """Every module in training mode and none hooked (a hook on any of them sends the call to the per-layer path, where
-    each module's own ``__call__`` runs its hooks)."""
+def _tree_ok(model, training=True):
+    """No module hooked (a hook on any of them sends the call to the per-layer path, where each module's own ``__call__`` runs
+    its hooks) and, for a ``training`` call, every module in training mode."""
     for m in _cached(model, "_avid_modules", lambda: list(model.modules())):
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks or not m.training:
+        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks or (training and not m.training):
             return False
     return True
 
 
+def _inputs_ok(inputs):
+    """float32 GPU inputs — video [B,3,T,H,W], then audio [B,1,F,T] if there is one — and no graph being captured."""
+    if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == rank for x, rank in zip(inputs, (5, 4))):
+        return False
+    return not torch.cuda.is_current_stream_capturing()
+
+
 def eligible(model, *inputs, need_grad=True):
     """The launch-program path applies: a training call (gradients on, unless ``need_grad`` is False: ``FinetuneStep`` runs
-    the programs itself) on float32 GPU inputs — video [B,3,T,H,W], then audio [B,1,F,T] if the model has one — through
-    the stock module tree, nothing hooked, no graph being captured."""
+    the programs itself) on inputs the programs take (``_inputs_ok``) through the stock module tree, nothing hooked."""
     if not ENABLED or not model.training or (need_grad and not torch.is_grad_enabled()):
         return False
-    if not all(x.is_cuda and x.dtype == torch.float32 and x.dim() == rank for x, rank in zip(inputs, (5, 4))):
-        return False
-    if torch.cuda.is_current_stream_capturing():
-        return False
-    return _tree_ok(model)
+    return _inputs_ok(inputs) and _tree_ok(model)
 
 
 def _bn_identity(model):
@@ -953,14 +1191,6 @@ def run(model, video, audio):
     return NetFn.apply(video, audio, pl, *pl.params_fwd)
 
 
-_OP_NAMES = {0: "nop", 1: "wait", 2: "memset0", 3: "conv_fwd", 4: "conv_dgrad", 5: "conv_wgrad", 6: "wgrad_group", 7: "wgrad_item",
-             8: "bn_fwd", 9: "bn_bwd", 10: "bn_pool_fwd", 11: "bn_pool_bwd", 12: "gpool_fwd", 13: "gpool_bwd", 14: "relu_bwd",
-             15: "colsum", 16: "wt_batch", 17: "adam", 18: "dropout_fwd", 19: "dropout_bwd", 20: "cls_loss",
-             21: "cls_linear_fwd", 22: "cls_linear_bwd", 23: "adaptive_maxpool", 24: "bn1d_fwd", 25: "bn1d_bwd",
-             26: "probe_linear_fwd", 27: "probe_linear_bwd", 28: "bn_eval_coeffs", 29: "bn_eval_apply", 30: "bn_pool_fwd_eval",
-             31: "bn_eval_direct", 32: "maxpool_fwd"}
-
-
 def dump(prog, n):
     """Readable listing of a program (debugging / tests)."""
     lines = []
@@ -977,35 +1207,28 @@ def dump(prog, n):
 # ------------------------------------------------------------------------------------------------------------------
 # fine-tuning: models.classification.ClassificationWrapper (utils/eval_utils.py:193-214 of the reference)
 # ------------------------------------------------------------------------------------------------------------------
-S_LABELS, S_DLOGITS, S_OUT = S_AUDIO, S_DV, S_DA     # the classifier plan's use of the two-tower plan's input slots
-OUT_BYTES = 32                                       # S_OUT: loss (f32) at 0, hits (2 x i64) at 8
-
-
 def _i32(v):
     v &= 0xFFFFFFFF
     return v - (1 << 32) if v >= (1 << 31) else v
 
 
-class ClsPlan(Programs):
+class ClsPlan(TrainPrograms):
     """The compiled programs of one ``ClassificationWrapper`` around this package's ``R2Plus1D`` for one clip geometry.
 
-    Forward: the tower (``Builder.video_fwd``), dropout, the classifier (``avid_cls_linear_fwd``: any number of classes)
+    Forward: the tower (``Builder.video_fwd``), dropout, the classifier (``Builder.cls_linear_fwd``)
     — records [0, n_logits) — then ``AVID_OP_CLS_LOSS`` with ``dlogits`` (record n_logits, run by the step engine only).
     Backward, from ``dlogits``: the classifier's weight, bias and input gradients (one ``avid_cls_linear_bwd``), dropout's
-    backward, the tower's backward (``Builder.video_bwd`` / ``video_stem_bwd``).  ``classifier_only``: the reference's warm-up epochs — the
+    backward, the tower's backward (``TrainBuilder.video_bwd`` / ``video_stem_bwd``).  ``classifier_only``: the reference's warm-up epochs — the
     tower still runs in training mode (its BatchNorm running statistics move) but no tower backward is compiled, the
     classifier's input gradient neither, and only the classifier's slice of the gradient buffer is zeroed."""
 
     def __init__(self, model, vshape, device, trailing, group, classifier_only=False):
-        from models.classification import ClassificationWrapper, ClsLinear, HipDropout
-        if type(model) is not ClassificationWrapper or model.feat_name != "pool" or model.pooling is not None:
-            raise Unsupported("classification wrapper outside the compiled pattern")
-        cls = model.classifier
-        if type(cls) is not ClsLinear or (model.use_dropout and type(model.dropout) is not HipDropout):
+        from models.classification import HipDropout
+        cls = _classifier(model)
+        if model.use_dropout and type(model.dropout) is not HipDropout:
             raise Unsupported("classifier / dropout")
         b = self._open(model, device, False, trailing, group)
         self.classifier_only = classifier_only
-        self.key = (tuple(vshape), trailing, group, classifier_only)
         self.vshape, self.ashape = tuple(vshape), None
         self.p = float(model.dropout.p) if model.use_dropout else 0.0
         # (parameters in reverse order: the classifier's bias and weight lead the gradient buffer)
@@ -1022,15 +1245,10 @@ class ClsPlan(Programs):
             self.drop_index = len(b.fwd)
             b.emit(OP_DROPOUT_FWD, n=(B, 0), i=(Fd, 0, 0), f=(self.p,), t=(feat.ref, y, self.mask, None))
             feat = Sym(y, (B, Fd))
-        self.n_classes = C = cls.weight.shape[0]
-        if cls.weight.shape[1] != Fd or not cls.weight.is_contiguous():
-            raise Unsupported("classifier")
-        logits = b.fa.alloc(4 * B * C)
-        b.emit(OP_CLS_LINEAR_FWD, i=(B, Fd, C), t=(feat.ref, b.ext(cls.weight), b.ext(cls.bias), logits))
-        self.logits = Sym(logits, (B, C))
+        self.logits = b.cls_linear_fwd(cls, feat)
+        self.n_classes = C = self.logits.shape[1]
         self.n_logits = len(b.fwd)
-        b.emit(OP_CLS_LOSS, i=(B, 1, self.n_classes), f=(1.0,),
-               t=(self.logits.ref, (S_LABELS, 0), (S_OUT, 0), None, (S_OUT, 8), (S_DLOGITS, 0), self._err_ref(b, device)))
+        b.cls_loss(self.logits)
         # ------------------------------------------------------------------ backward
         self._backward_begins(b)
         dlog = (S_DLOGITS, 0)
@@ -1047,12 +1265,6 @@ class ClsPlan(Programs):
             b.video_stem_bwd(V, dh)
         self._close(b)
 
-    @staticmethod
-    def _err_ref(b, device):
-        """The device error word (ops.DeviceErrors) as an external tensor: a label outside [0, C) is reported there."""
-        flag = ops.DeviceErrors.get(device).flag if device.type == "cuda" else torch.zeros((), dtype=torch.int32)
-        return b.ext(flag)
-
     def forward(self, video, grad_flat, zero_grad, seed=0, offset=0, labels=None, out=None, dlogits=None, grad_scale=1.0):
         """Issue the forward program — with ``labels`` also the loss record, which writes ``out`` (OUT_BYTES: loss, hits)
         and ``dlogits``; returns (logits, arena)."""
@@ -1065,9 +1277,7 @@ class ClsPlan(Programs):
             self.fwd_prog[self.n_logits].f[0] = float(grad_scale)
             end = self.n_fwd
         self._run(self.fwd_prog, 0, end)
-        B, C = self.vshape[0], self.n_classes
-        off = self.logits.ref[1]
-        return fa[off:off + 4 * B * C].view(torch.float32).view(B, C), fa
+        return self._view(fa, self.logits), fa
 
 
 class ClsFn(torch.autograd.Function):
@@ -1084,12 +1294,7 @@ class ClsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         _check_backward(ctx)
-        pl, params = ctx.pl, ctx.params
-        g = torch.empty(pl.gnumel, dtype=torch.float32, device=dlogits.device)
-        pl.backward(ctx.fa, (ctx.video, None, dlogits.contiguous(), None), g)
-        ctx.fa = None
-        views = pl.grad_views(g)
-        return (None, None, None, None) + tuple(views[id(p)] for p in params)
+        return _autograd_backward(ctx, (ctx.video, None, dlogits.contiguous(), None), 4)
 
 
 def cls_plan(model, video, classifier_only=False, need_grad=True):
@@ -1117,89 +1322,49 @@ def run_cls(model, video):
 # ------------------------------------------------------------------------------------------------------------------
 # linear probe: models.linear_probe.MOSTModel (utils/eval_utils.py:217-242, 298-329 of the reference)
 # ------------------------------------------------------------------------------------------------------------------
-PROBE_OUT_BYTES = 32                                 # per tap in S_OUT: loss (f32) at 0, hits (2 x i64) at 8
-_PROBE_TAPS = ("conv2x", "conv3x", "conv4x", "conv5x")
-
-
-class ProbePlan(Programs):
+class ProbePlan(TrainPrograms):
     """The compiled programs of one ``MOSTModel`` in its stock form around this package's ``R2Plus1D`` for one clip geometry.
 
     Forward: the training-mode tower (``Builder.video_fwd``; the stage outputs it materialises anyway are the taps), then per
-    tap ``avid_adaptive_maxpool_fwd`` (channels-last tap -> the reference's flatten order), ``avid_bn1d_fwd_train`` and
-    ``avid_probe_linear_fwd`` — records [0, n_logits) — then one ``AVID_OP_CLS_LOSS`` with ``dlogits`` per tap (run by the step
+    tap ``Builder.probe_head_fwd`` — records [0, n_logits) — then one ``AVID_OP_CLS_LOSS`` with ``dlogits`` per tap (run by the step
     engine only).  Backward, from ``dlogits``, per tap: ``avid_probe_linear_bwd`` (weight, bias and input gradient),
     ``avid_bn1d_bwd`` (no input gradient: the pooled features are constants).  No tower record: the tower is frozen.  The
     gradient buffer holds the classifiers' parameters only (``FlatParams`` over the trainable ones)."""
 
     def __init__(self, model, vshape, device, trailing, group):
-        from models.linear_probe import MOSTModel, Classifier, ProbeBatchNorm1d, ProbeLinear
-        if type(model) is not MOSTModel or not len(model.classifiers):
-            raise Unsupported("linear probe outside the compiled pattern")
-        for c in model.classifiers:
-            if (type(c) is not Classifier or c.pool_size is None or c.use_dropout or c.l2_norm or not c.use_bn
-                    or type(c.pooling) is not torch.nn.AdaptiveMaxPool3d or c.feat_name not in _PROBE_TAPS
-                    or type(c.bn) is not ProbeBatchNorm1d or c.bn.momentum is None or not c.bn.affine
-                    or not c.bn.track_running_stats or type(c.classifier) is not ProbeLinear or c.classifier.bias is None):
-                raise Unsupported("probe head outside the compiled pattern")
+        classifiers = _probe_heads(model)
         if any(p.requires_grad for p in model.feature_extractor.parameters()):
             raise Unsupported("the probe's tower is not frozen")
-        if list(model.feat_names) != [c.feat_name for c in model.classifiers]:
-            raise Unsupported("feat_names")
         b = self._open(model, device, False, trailing, group, frozen_ok=True)
-        self.key = (tuple(vshape), trailing, group)
         self.vshape, self.ashape = tuple(vshape), None
-        self.n_taps = len(model.classifiers)
         # ------------------------------------------------------------------ forward
-        vm = model.feature_extractor
-        V, _ = b.video_fwd(vm, Sym((S_VIDEO, 0), vshape))
-        taps, k = {}, 0
-        for name in _PROBE_TAPS:
-            stage = getattr(vm, name)
-            k += len(stage) if isinstance(stage, torch.nn.Sequential) else 1
-            taps[name] = V["blocks"][k - 1][3]["h"]
+        V, _ = b.video_fwd(model.feature_extractor, Sym((S_VIDEO, 0), vshape))
         B = vshape[0]
-        self.n_classes = C = model.classifiers[0].classifier.weight.shape[0]
+        self.n_classes = C = classifiers[0].classifier.weight.shape[0]
         if C > 1024:
             raise Unsupported("more classes than avid_cls_loss takes")
-        heads, self.logits = [], []
-        for c in model.classifiers:
-            h = taps[c.feat_name]
+        if B < 2:
+            raise Unsupported("probe head geometry")          # (BatchNorm1d on batch statistics)
+        heads = []
+        for c in classifiers:
+            h = V["stages"][c.feat_name]
             if h.affine is not None:
                 raise Unsupported("tap not materialised")
-            _, T, H, W, Cc = h.shape
-            To, Ho, Wo = c.pool_size
-            Fd = Cc * To * Ho * Wo
-            bn, lin = c.bn, c.classifier
-            if (tuple(lin.weight.shape) != (C, Fd) or not lin.weight.is_contiguous() or bn.num_features != Fd or B < 2
-                    or B > 256 or Fd > 16384):
-                raise Unsupported("probe head geometry")
-            pooled, normed, save2 = b.fa.alloc(4 * B * Fd), b.fa.alloc(4 * B * Fd), b.fa.alloc(8 * Fd)
-            d = ConvDesc()
-            d.To, d.Ho, d.Wo = To, Ho, Wo
-            b.emit(OP_ADAPTIVE_MAXPOOL, d=d, i=(B, T, H, W, Cc), t=(h.ref, pooled))
-            b.emit(OP_BN1D_FWD, i=(B, Fd, 1), f=(bn.momentum, bn.eps),
-                   t=(pooled, b.ext(bn.weight), b.ext(bn.bias), b.ext(bn.running_mean), b.ext(bn.running_var), normed, save2,
-                      b.ext(bn.num_batches_tracked)))
-            logits = b.fa.alloc(4 * B * C)
-            b.emit(OP_PROBE_LINEAR_FWD, i=(B, Fd, C), t=(normed, b.ext(lin.weight), b.ext(lin.bias), logits))
-            self.logits.append(Sym(logits, (B, C)))
-            heads.append((c, Fd, pooled, normed, save2))
+            heads.append(b.probe_head_fwd(c, h, C, True))
+        self.logits = [hd["logits"] for hd in heads]
         self.n_logits = len(b.fwd)
-        err = ClsPlan._err_ref(b, device)
         for i, lg in enumerate(self.logits):
-            b.emit(OP_CLS_LOSS, i=(B, 1, C), f=(1.0,),
-                   t=(lg.ref, (S_LABELS, 0), (S_OUT, PROBE_OUT_BYTES * i), None, (S_OUT, PROBE_OUT_BYTES * i + 8),
-                      (S_DLOGITS, 4 * B * C * i), err))
+            b.cls_loss(lg, tap=i)
         # ------------------------------------------------------------------ backward
         self._backward_begins(b)
-        for i, (c, Fd, pooled, normed, save2) in enumerate(heads):
-            bn, lin = c.bn, c.classifier
+        for i, hd in enumerate(heads):
+            bn, lin, Fd = hd["c"].bn, hd["c"].classifier, hd["Fd"]
             dn = b.ba.alloc(4 * B * Fd)
             b.emit(OP_PROBE_LINEAR_BWD, i=(B, Fd, C),
-                   t=(normed, b.ext(lin.weight), (S_DLOGITS, 4 * B * C * i), dn, b.grad(lin.weight), b.grad(lin.bias)))
+                   t=(hd["normed"], b.ext(lin.weight), (S_DLOGITS, 4 * B * C * i), dn, b.grad(lin.weight), b.grad(lin.bias)))
             b._ready(b.S, lin.weight, lin.bias)
             b.emit(OP_BN1D_BWD, i=(B, Fd, 0), f=(0.0, bn.eps),
-                   t=(pooled, dn, b.ext(bn.weight), save2, None, b.grad(bn.weight), b.grad(bn.bias)))
+                   t=(hd["pooled"], dn, b.ext(bn.weight), hd["save2"], None, b.grad(bn.weight), b.grad(bn.bias)))
             b._ready(b.S, bn.weight, bn.bias)
         self._close(b)
 
@@ -1208,8 +1373,7 @@ class ProbePlan(Programs):
         loss, hits) and ``dlogits [n_taps, B, C]``; returns ([logits per tap], arena)."""
         fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out))
         self._run(self.fwd_prog, 0, self.n_fwd if labels is not None else self.n_logits)
-        B, C = self.vshape[0], self.n_classes
-        return [fa[lg.ref[1]:lg.ref[1] + 4 * B * C].view(torch.float32).view(B, C) for lg in self.logits], fa
+        return [self._view(fa, lg) for lg in self.logits], fa
 
 
 class ProbeFn(torch.autograd.Function):
@@ -1226,15 +1390,10 @@ class ProbeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dlogits):
         _check_backward(ctx)
-        pl, params = ctx.pl, ctx.params
-        B, C = pl.vshape[0], pl.n_classes
+        B, C = ctx.pl.vshape[0], ctx.pl.n_classes
         dl = torch.stack([d.contiguous() if d is not None else torch.zeros((B, C), dtype=torch.float32, device=ctx.video.device)
                           for d in dlogits])
-        g = torch.empty(pl.gnumel, dtype=torch.float32, device=dl.device)
-        pl.backward(ctx.fa, (ctx.video, None, dl, None), g)
-        ctx.fa = None
-        views = pl.grad_views(g)
-        return (None, None) + tuple(views[id(p)] for p in params)
+        return _autograd_backward(ctx, (ctx.video, None, dl, None), 2)
 
 
 def probe_plan(model, video, need_grad=True):
@@ -1261,183 +1420,19 @@ def run_probe(model, video):
 # ------------------------------------------------------------------------------------------------------------------
 # inference: eval-mode forward programs (parallel.Inference, the engines' evaluate())
 # ------------------------------------------------------------------------------------------------------------------
-class EvalArena:
-    """The activation arena of an inference program while it is compiled: ``alloc`` hands out VIRTUAL offsets that never
-    overlap; ``EvalPlan._recycle`` then maps every buffer to a physical offset, re-using the bytes of buffers whose last
-    reader has been emitted on the same stream (nothing runs backward, nothing trails on another stream)."""
-
-    def __init__(self, slot):
-        self.slot, self.size, self.bufs = slot, 0, []
-
-    def alloc(self, nbytes):
-        off, n = self.size, _align(max(int(nbytes), 4))
-        self.size += n
-        self.bufs.append((off, n))
-        return (self.slot, off)
-
-
-class EvalBuilder(Builder):
-    """The eval form of the forward emitters: BatchNorms use their running statistics — every coefficient vector comes out of ONE
-    launch at the head of the program (``AVID_OP_BN_EVAL_COEFFS``), a (3,1,1) layer of conv2x applies its own BatchNorm in its
-    epilogue (``d.out_affine``) and the one in front of it while staging (``d.in_affine``), everything else is a convolution
-    followed by ``AVID_OP_BN_EVAL_APPLY``; the stem's tail is one pass.  No statistics, no argmax of the stem's pool, no saved
-    vectors for a backward.  Each record is the call the per-layer path makes in eval mode with trainable BatchNorm parameters
-    (``avid_bn_fwd_eval`` with ``save4``: y = fma(x, scale, shift)) or a fusion that is bit-identical to it.
-    A BatchNorm whose weight and bias take NO gradient (the linear probe's frozen tower) is another case: the per-layer path then
-    calls ``avid_bn_fwd_eval`` without ``save4``, which evaluates ``(x - mean) * invstd * gamma + beta`` — other bits than the
-    fma.  Such a BatchNorm is never fused: it is one ``AVID_OP_BN_EVAL_DIRECT`` record (the same call), the stem's pool behind it
-    an ``AVID_OP_MAXPOOL_FWD`` record, and it has no entry in the coefficient table."""
-
-    def __init__(self, device):
-        super().__init__(device, False, False, False)
-        self.fa, self.oa = EvalArena(S_FWD), Arena(S_OUT)
-        self.bn_recs, self.bn_off = [], {}         # (BatchNorm module, aux offset of its [4][C] vectors)
-
-    @staticmethod
-    def frozen(bn):
-        """The per-layer path computes this BatchNorm without coefficient vectors (ops._BatchNormCL.forward: no gradient can flow)."""
-        return not (bn.weight.requires_grad or bn.bias.requires_grad)
-
-    def bn_direct(self, bn, x, M, Cc, relu=1):
-        """The unfused eval-mode BatchNorm (+ReLU) of a frozen BatchNorm: x -> a new tensor."""
-        from models.network_blocks import BatchNormCL
-        if type(bn) is not BatchNormCL or bn.weight.dtype != torch.float32:
-            raise Unsupported("BatchNorm")
-        h = self.fa.alloc(4 * M * Cc)
-        self.emit(OP_BN_EVAL_DIRECT, n=(M,), i=(Cc, relu), f=(0.0, bn.eps),
-                  t=(x, self.ext(bn.weight), self.ext(bn.bias), self.ext(bn.running_mean), self.ext(bn.running_var), h))
-        return h
-
-    def coeffs(self, bn):
-        from models.network_blocks import BatchNormCL
-        off = self.bn_off.get(id(bn))
-        if off is None:
-            if type(bn) is not BatchNormCL or bn.weight.dtype != torch.float32:
-                raise Unsupported("BatchNorm")
-            off = self.bn_off[id(bn)] = self.aux_size
-            self.bn_recs.append((bn, off))
-            self.aux_size += _align(16 * bn.num_features)
-        return (S_AUX, off)
-
-    def conv_bn_fwd(self, conv, bn, x, addend=None, next_conv=None):
-        """ReLU(bn_eval(conv(x) [+ addend])); returns the Sym of the result (``affine`` set: its only consumer applies the map)."""
-        w = conv.weight
-        d = self.desc(x.shape, w, conv.stride3, conv.padding3, conv.channel_first)[0]
-        ysh = (d.B, d.To, d.Ho, d.Wo, d.Cout)
-        M, Cc = d.B * d.To * d.Ho * d.Wo, d.Cout
-        xa = x.affine
-        if xa is not None and not d.in_affine:
-            raise Unsupported("a tensor with a pending BatchNorm reached a layer that cannot apply it")
-        iv = (0, 0, 0) if xa is None else (0, 2 if xa[1] else 1, xa[2])
-        t = [x.ref, self.ext(w), self.fwd_u(w, d), addend.ref if addend is not None else None, None]
-        xr = None if xa is None else xa[0]
-        if self.frozen(bn):                        # convolution, then the call the per-layer path makes: nothing fused
-            y = self.fa.alloc(4 * M * Cc)
-            self.emit(OP_CONV_FWD, d=d, i=iv, t=t + [y, None, xr])
-            return Sym(self.bn_direct(bn, y, M, Cc), ysh)
-        c4 = self.coeffs(bn)
-        if d.out_affine:
-            h = self.fa.alloc(4 * M * Cc)
-            self.emit(OP_CONV_FWD, d=d, i=iv + (2,), t=t + [h, None, xr, c4])
-            return Sym(h, ysh)
-        y = self.fa.alloc(4 * M * Cc)
-        self.emit(OP_CONV_FWD, d=d, i=iv, t=t + [y, None, xr])
-        if next_conv is not None and addend is None:
-            nw = next_conv.weight
-            if (ops.weight_layout_ok(nw) and nw.dtype == torch.float32 and nw.shape[1] == Cc and not next_conv.channel_first
-                    and self.desc(ysh, nw, next_conv.stride3, next_conv.padding3, False)[0].in_affine):
-                return Sym(y, ysh, affine=(c4, 1, Cc))
-        h = self.fa.alloc(4 * M * Cc)
-        self.emit(OP_BN_EVAL_APPLY, n=(M,), i=(Cc, 1), t=(y, c4, h))
-        return Sym(h, ysh)
-
-    def r2p1d_block_fwd(self, blk, x):
-        from models.network_blocks import BasicR2P1DBlock
-        if type(blk) is not BasicR2P1DBlock:
-            raise Unsupported(type(blk).__name__)
-        h = self.conv_bn_fwd(blk.spt_conv1, blk.spt_bn1, x, next_conv=blk.tmp_conv1)
-        h = self.conv_bn_fwd(blk.tmp_conv1, blk.tmp_bn1, h)
-        h = self.conv_bn_fwd(blk.spt_conv2, blk.spt_bn2, h, next_conv=blk.tmp_conv2)
-        res = x
-        if blk.res:                                # the 1x1x1 strided residual convolution: a record of its own
-            rc = blk.res_conv
-            dr = self.desc(x.shape, rc.weight, rc.stride3, rc.padding3, False)[0]
-            yr = self.fa.alloc(4 * dr.B * dr.To * dr.Ho * dr.Wo * dr.Cout)
-            self.emit(OP_CONV_FWD, d=dr, i=(0,), t=(x.ref, self.ext(rc.weight), self.fwd_u(rc.weight, dr), None, None, yr, None))
-            res = Sym(yr, (dr.B, dr.To, dr.Ho, dr.Wo, dr.Cout))
-        return None, self.conv_bn_fwd(blk.tmp_conv2, blk.out_bn, h, addend=res)
-
-    def video_fwd(self, vm, x, after_stem=None, arena=None):
-        """The tower; ``arena``: where the pooled output goes.  Returns ({stage name: Sym of its output}, pooled Sym)."""
-        from models.video import R2Plus1D
-        from models.network_blocks import BatchNormCL, ConvCL
-        if type(vm) is not R2Plus1D:
-            raise Unsupported(type(vm).__name__)
-        conv, bn = vm.conv1[0], vm.conv1[1]
-        if type(conv) is not ConvCL or type(bn) is not BatchNormCL:
-            raise Unsupported("video stem")
-        w = conv.weight
-        d = self.desc(x.shape, w, conv.stride3, conv.padding3, True)[0]
-        B, T, H, W, Cc = d.B, d.To, d.Ho, d.Wo, d.Cout
-        y = self.fa.alloc(4 * B * T * H * W * Cc)
-        self.emit(OP_CONV_FWD, d=d, i=(0,), t=(x.ref, self.ext(w), None, None, None, y, None))
-        Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
-        p = self.fa.alloc(4 * B * T * Ho * Wo * Cc)
-        if self.frozen(bn):                        # bn -> maxpool as the per-layer path runs them (its pool writes an argmax)
-            am = self.fa.alloc(B * T * Ho * Wo * Cc)
-            self.emit(OP_MAXPOOL_FWD, i=(B, T, H, W, Cc), t=(self.bn_direct(bn, y, B * T * H * W, Cc), p, am))
-        else:
-            self.emit(OP_BN_POOL_FWD_EVAL, i=(B, T, H, W, Cc), t=(y, self.coeffs(bn), p))
-        h = Sym(p, (B, T, Ho, Wo, Cc))
-        if after_stem is not None:
-            after_stem()
-        stages = {}
-        for name in ("conv2x", "conv3x", "conv4x", "conv5x"):
-            stage = getattr(vm, name)
-            for blk in (stage if isinstance(stage, torch.nn.Sequential) else [stage]):
-                _, h = self.r2p1d_block_fwd(blk, h)
-            stages[name] = h
-        return stages, self.gpool_fwd(h, arena=arena)["y"]
-
-    def audio_fwd(self, am, x):
-        from models.audio import Conv2D
-        from models.network_blocks import Basic2DBlock
-        if type(am) is not Conv2D:
-            raise Unsupported(type(am).__name__)
-        h = self.conv_bn_fwd(am.conv1[0], am.conv1[1], x)
-        for blk in (am.block1, am.block2, am.block3, am.block4):
-            if type(blk) is not Basic2DBlock:
-                raise Unsupported(type(blk).__name__)
-            h = self.conv_bn_fwd(blk.conv2, blk.bn2, self.conv_bn_fwd(blk.conv1, blk.bn1, h))
-        return None, self.gpool_fwd(h)["y"]
-
-    def head_fwd(self, head, x, arena=None):
-        """The projection head; ``arena``: where the LAST layer's output goes."""
-        from models.av_wrapper import Head, LinearCL
-        if type(head) is not Head:
-            raise Unsupported(type(head).__name__)
-        mods, k = list(head.projection), 0
-        while k < len(mods):
-            if type(mods[k]) is not LinearCL:
-                raise Unsupported("head")
-            relu = k + 1 < len(mods) and isinstance(mods[k + 1], torch.nn.ReLU)
-            k_next = k + (2 if relu else 1)
-            x = self.linear_fwd(mods[k], x, relu, arena=arena if k_next >= len(mods) else None)["y"]
-            k = k_next
-        return None, x
-
-
 class EvalPlan(Programs):
     """The compiled inference program of one model for one input geometry: ``R2Plus1D`` (pooled features), ``AV_Wrapper`` (the two
     embeddings; the audio tower on its own stream and its own buffers), ``ClassificationWrapper(R2Plus1D, feat_name='pool',
-    pooling_op=None)`` (logits; dropout is the identity in eval mode) or the stock ``MOSTModel`` (every tap's logits).  Record 0 is the batched BatchNorm-coefficient launch — it
+    pooling_op=None)`` (logits; dropout is the identity in eval mode) or the stock ``MOSTModel`` (every tap's logits:
+    ``Builder.probe_head_fwd`` with training = 0).  Record 0 is the batched BatchNorm-coefficient launch — it
     runs on every call, because running statistics move between evaluations — record 1 the weight-transform launch (the
     pre-split weights of the layers that read them).  Activations live in a RECYCLED arena (``_recycle``); what leaves the program
-    lives in a buffer of its own (slot ``S_OUT``), so the caller's results do not keep the arena alive."""
+    lives in a buffer of its own (slot ``S_OUT``), so the caller's results do not keep the arena alive.  There is no backward
+    program and no gradient buffer: this is ``Programs``, not ``TrainPrograms``."""
 
     def __init__(self, model, vshape, ashape, device):
         from models.av_wrapper import AV_Wrapper
-        from models.classification import ClassificationWrapper, ClsLinear
+        from models.classification import ClassificationWrapper
         from models.linear_probe import MOSTModel
         from models.video import R2Plus1D
         dry = device.type != "cuda"
@@ -1448,77 +1443,57 @@ class EvalPlan(Programs):
         self._coef_rec = b.emit(OP_BN_EVAL_COEFFS, i=(0,), t=((S_AUX, 0),))
         self._wt_rec = b.emit(OP_WT_BATCH, i=(0,), n=(0,), t=((S_AUX, 0),))
         video = Sym((S_VIDEO, 0), vshape)
-        B = vshape[0]
         if type(model) is R2Plus1D:
             _, feat = b.video_fwd(model, video, arena=b.oa)
-            self.outputs = [(feat.ref[1], (B, feat.shape[1], 1, 1, 1))]
+            outs = [Sym(feat.ref, feat.shape + (1, 1, 1))]       # [B, C, 1, 1, 1], as the module returns them
         elif type(model) is ClassificationWrapper:
-            cls = model.classifier
-            if model.feat_name != "pool" or model.pooling is not None or type(cls) is not ClsLinear:
-                raise Unsupported("classification wrapper outside the compiled pattern")
+            cls = _classifier(model)
             _, feat = b.video_fwd(model.feature_extractor, video)
-            Fd, Cn = feat.shape[1], cls.weight.shape[0]
-            if cls.weight.shape[1] != Fd or not cls.weight.is_contiguous():
-                raise Unsupported("classifier")
-            logits = b.oa.alloc(4 * B * Cn)
-            b.emit(OP_CLS_LINEAR_FWD, i=(B, Fd, Cn), t=(feat.ref, b.ext(cls.weight), b.ext(cls.bias), logits))
-            self.outputs = [(logits[1], (B, Cn))]
+            outs = [b.cls_linear_fwd(cls, feat, arena=b.oa)]
         elif type(model) is AV_Wrapper:
             if not model.use_linear_proj or ashape is None:
                 raise Unsupported("no projection heads")
             audio = Sym((S_AUDIO, 0), (ashape[0], ashape[1], 1, ashape[2], ashape[3]))
             A_S = ST_MAIN if lib.TIMING else ST_AUDIO
-            out = {}
+            outs = [None, None]
 
             def start_audio():                      # behind the video stem, as in training (models/av_wrapper.py AUDIO_AFTER)
                 b.wait(A_S, ST_MAIN)
                 b.S = A_S
                 _, afeat = b.audio_fwd(model.audio_model, audio)
-                out["a"] = b.head_fwd(model.audio_proj, afeat, arena=b.oa)[1]
+                outs[1] = b.head_fwd(model.audio_proj, afeat, arena=b.oa)[1]
                 b.S = ST_MAIN
             _, vfeat = b.video_fwd(model.video_model, video, after_stem=start_audio)
-            vemb = b.head_fwd(model.video_proj, vfeat, arena=b.oa)[1]
+            outs[0] = b.head_fwd(model.video_proj, vfeat, arena=b.oa)[1]
             b.wait(ST_MAIN, A_S)
-            self.outputs = [(vemb.ref[1], vemb.shape), (out["a"].ref[1], out["a"].shape)]
         elif type(model) is MOSTModel:
-            self._most(b, model, video)
+            heads = _probe_heads(model)
+            V, _ = b.video_fwd(model.feature_extractor, video)
+            Cn = heads[0].classifier.weight.shape[0]
+            self.out_names = list(model.feat_names)
+            outs = [b.probe_head_fwd(c, V["stages"][c.feat_name], Cn, False, arena=b.oa)["logits"] for c in heads]
         else:
             raise Unsupported(type(model).__name__)
-        self._finalize_eval(b)
+        self.outputs = [(o.ref[1], o.shape) for o in outs]
+        # ------------------------------------------------------------------ the arena, then the tables and the record array
+        self.n_fwd = len(b.fwd)
+        self.virtual_bytes = b.fa.size                       # what a bump allocator would take
+        self.fa_bytes, self.buffers = self._recycle(b.fwd, b.fa.bufs, S_FWD)
+        self.fa_bytes = max(self.fa_bytes, 256)
+        self.out_bytes = max(b.oa.size, 256)
+        (self.fwd_prog,) = self._seal(b, b.fwd)
+        self._bn_ptrs = None
 
-    def _most(self, b, model, video):
-        """The stock linear probe (``ProbePlan``'s pattern) in eval mode: the tower, then per tap ``AVID_OP_ADAPTIVE_MAXPOOL``,
-        ``AVID_OP_BN1D_FWD`` with training = 0 and ``AVID_OP_PROBE_LINEAR_FWD``; the logits of every tap leave the program."""
-        from models.linear_probe import Classifier, ProbeBatchNorm1d, ProbeLinear
-        if not len(model.classifiers) or list(model.feat_names) != [c.feat_name for c in model.classifiers]:
-            raise Unsupported("linear probe outside the compiled pattern")
-        for c in model.classifiers:
-            if (type(c) is not Classifier or c.pool_size is None or c.use_dropout or c.l2_norm or not c.use_bn
-                    or type(c.pooling) is not torch.nn.AdaptiveMaxPool3d or c.feat_name not in _PROBE_TAPS
-                    or type(c.bn) is not ProbeBatchNorm1d or c.bn.momentum is None or not c.bn.affine
-                    or not c.bn.track_running_stats or type(c.classifier) is not ProbeLinear or c.classifier.bias is None):
-                raise Unsupported("probe head outside the compiled pattern")
-        stages, _ = b.video_fwd(model.feature_extractor, video)
-        B = self.vshape[0]
-        Cn = model.classifiers[0].classifier.weight.shape[0]
-        self.outputs, self.out_names = [], list(model.feat_names)
-        for c in model.classifiers:
-            h = stages[c.feat_name]
-            _, T, H, W, Cc = h.shape
-            To, Ho, Wo = c.pool_size
-            Fd = Cc * To * Ho * Wo
-            bn, lin = c.bn, c.classifier
-            if tuple(lin.weight.shape) != (Cn, Fd) or not lin.weight.is_contiguous() or bn.num_features != Fd or B > 256 or Fd > 16384:
-                raise Unsupported("probe head geometry")
-            pooled, normed, save2 = b.fa.alloc(4 * B * Fd), b.fa.alloc(4 * B * Fd), b.fa.alloc(8 * Fd)
-            d = ConvDesc()
-            d.To, d.Ho, d.Wo = To, Ho, Wo
-            b.emit(OP_ADAPTIVE_MAXPOOL, d=d, i=(B, T, H, W, Cc), t=(h.ref, pooled))
-            b.emit(OP_BN1D_FWD, i=(B, Fd, 0), f=(bn.momentum, bn.eps),
-                   t=(pooled, b.ext(bn.weight), b.ext(bn.bias), b.ext(bn.running_mean), b.ext(bn.running_var), normed, save2, None))
-            logits = b.oa.alloc(4 * B * Cn)
-            b.emit(OP_PROBE_LINEAR_FWD, i=(B, Fd, Cn), t=(normed, b.ext(lin.weight), b.ext(lin.bias), logits))
-            self.outputs.append((logits[1], (B, Cn)))
+    def _aux_layout(self, b):
+        """aux: transformed weights | BatchNorm vectors (both at the builder's offsets) | weight-transform table | BatchNorm table,
+        which the coefficient record (record 0) reads."""
+        self.bn_recs = b.bn_recs
+        self.bn_table_off = self.table_off + _align(32 * len(b.wt_recs) + 32)
+        self._coef_rec.i[0] = len(b.bn_recs)
+        self._coef_rec.t[0].off = self.bn_table_off
+        if not b.bn_recs:
+            self._coef_rec.op = 0
+        return self.bn_table_off + C.sizeof(lib.BnEvalItem) * len(b.bn_recs) + 256
 
     @staticmethod
     def _recycle(recs, bufs, slot):
@@ -1559,41 +1534,6 @@ class EvalPlan(Programs):
                         free.setdefault((recs[k].stream, bufs[b2][1]), []).append(phys[b2])
         return top, [(phys[bi], bufs[bi][1], min(streams[bi]), first[bi], last[bi]) for bi in sorted(phys)]
 
-    def _finalize_eval(self, b):
-        self.n_fwd = len(b.fwd)
-        self.virtual_bytes = b.fa.size                       # what a bump allocator would take
-        self.fa_bytes, self.buffers = self._recycle(b.fwd, b.fa.bufs, S_FWD)
-        self.fa_bytes = max(self.fa_bytes, 256)
-        self.out_bytes = max(b.oa.size, 256)
-        # aux: transformed weights | BatchNorm vectors (both at the Builder's offsets) | weight-transform table | BatchNorm table
-        self.wt_recs, self.bn_recs = b.wt_recs, b.bn_recs
-        self.table_off = _align(b.aux_size)
-        self.bn_table_off = self.table_off + _align(32 * len(b.wt_recs) + 32)
-        self.aux_bytes = self.bn_table_off + C.sizeof(lib.BnEvalItem) * len(b.bn_recs) + 256
-        self._wt_rec.i[0] = len(b.wt_recs)
-        self._wt_rec.n[0] = max([r[2] * r[3] * r[4] for r in b.wt_recs] + [1])
-        self._wt_rec.t[0].off = self.table_off
-        if not b.wt_recs:
-            self._wt_rec.op = 0
-        self._coef_rec.i[0] = len(b.bn_recs)
-        self._coef_rec.t[0].off = self.bn_table_off
-        if not b.bn_recs:
-            self._coef_rec.op = 0
-        self.fwd_prog = (Instr * self.n_fwd)(*b.fwd)
-        self.tensors = b.tensors
-        self.n_slots = S_FIRST_TENSOR + len(self.tensors)
-        need = (_sz * 4)()
-        lib.call("avid_program_workspace_bytes", self.fwd_prog, 0, self.n_fwd, 4, need)
-        self.ws_bytes = [max(int(need[k]), 1 << 20) for k in range(4)]
-        self.ws = [torch.empty(n, dtype=torch.uint8, device=self.device) for n in self.ws_bytes]
-        self.ws_arr = (StreamWs * 4)()
-        for k in range(4):
-            self.ws_arr[k].ptr, self.ws_arr[k].bytes = self.ws[k].data_ptr(), self.ws_bytes[k]
-        self.aux = torch.empty(self.aux_bytes, dtype=torch.uint8, device=self.device)
-        self._table_ptrs = self._bn_ptrs = None
-        self.slots = (_vp * self.n_slots)()
-        self.streams = (_vp * 4)()
-
     def _refresh_bn_table(self):
         """The device table of the coefficient launch follows the BatchNorms' current parameter and buffer addresses."""
         ptrs = tuple(t.data_ptr() for bn, _ in self.bn_recs for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
@@ -1622,22 +1562,13 @@ class EvalPlan(Programs):
         return res
 
 
-def _unhooked(model):
-    for m in _cached(model, "_avid_modules", lambda: list(model.modules())):
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
-            return False
-    return True
-
-
 def eval_plan(model, *inputs):
     """The cached ``EvalPlan`` of this call, or None: the caller takes the per-layer path.  Staleness as the training plans'
     (``_plan_for``: dtype, device, which parameters take gradients, BatchNorm buffer identity, the dispatch epoch that
     ``ops.wino_configure`` / ``tconv_configure`` / ``set_cu_budget`` bump); the key's leading "eval" keeps it apart from theirs."""
     if not EVAL_ENABLED or not ENABLED or not inputs or len(inputs) > 2:
         return None
-    if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == rank for x, rank in zip(inputs, (5, 4))):
-        return None
-    if torch.cuda.is_current_stream_capturing() or not _unhooked(model):
+    if not _inputs_ok(inputs) or not _tree_ok(model, training=False):
         return None
     shapes = tuple(tuple(x.shape) for x in inputs)
     dev = inputs[0].device
