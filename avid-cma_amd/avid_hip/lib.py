@@ -219,6 +219,9 @@ SIGNATURES = {
     "avid_cma_negatives": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_cma_topk_workspace_bytes": (_sz, [_i64, _i, _i]),
     "avid_cma_topk": (_i, [_i64, _i, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "avid_knn_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "avid_knn_search": (_i, [_i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avid_knn_vote": (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "avid_adam_flat": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp]),
     "avid_probe_spin": (_i, [_i, _vp]),
     "avid_stream_wait": (_i, [_vp, _vp]),

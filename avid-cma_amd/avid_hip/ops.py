@@ -1789,3 +1789,100 @@ class _ProbeLinear(Function):
 def probe_linear(x, w, bias):
     """The probe's ``Linear(Fin, C)`` on the matrix pipe (avid_probe_linear_fwd / _bwd): B <= 256, Fin <= 16384, any C."""
     return _ProbeLinear.apply(x, w, bias)
+
+
+# ------------------------------------------------------------------------------------------------
+# k-nearest-neighbour search and vote (k-NN / retrieval evaluation of a frozen tower)
+# ------------------------------------------------------------------------------------------------
+def _knn_arg(name, t, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise AvidHipError(f"{name} must be a HIP device tensor — there is no CPU fallback")
+    if t.dtype != dtype:
+        raise AvidHipError(f"{name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise AvidHipError(f"{name} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise AvidHipError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def knn_search(gallery, queries, k, exclude=None, batch=128, fallbacks=None):
+    """The ``k`` gallery rows of largest dot product for every query: ``(idx int32 [Q, k], sim fp32 [Q, k])``, each row
+    ordered by (similarity descending, gallery index ascending).  ``gallery [N, D]``, ``queries [Q, D]``: fp32, contiguous,
+    on the device; ``D % 32 == 0``, ``N >= 64``, any ``Q >= 1``.  ``exclude`` (optional int32 ``[Q]``): a gallery row that
+    must not be returned for that query, -1 for none (``arange(N)`` = leave-one-out of the gallery against itself);
+    ``k + (exclude is not None) <= 64``.
+
+    Queries are processed ``batch`` at a time (a multiple of 64), so that the ``[N, batch]`` score slab stays
+    cache-resident.  The kernel wants full batches: the last batch is shifted back to end at ``Q`` (a few queries are
+    computed twice, to the same rows); fewer than 64 queries are padded to 64 with copies of the last one — zero rows would
+    tie every gallery row and send the batch through the exact fallback.  A row's result does not depend on the batch it
+    was computed in.  ``fallbacks`` (optional 0-d int32 device tensor) counts the batches that overflowed the threshold
+    filter and were redone by the exact scan (diagnostics; the result is exact either way).  No host synchronisation."""
+    for name, t in (("gallery", gallery), ("queries", queries)):
+        _knn_arg("knn_search: " + name, t, torch.float32)
+        if t.dim() != 2:
+            raise AvidHipError(f"knn_search: {name} must be [rows, D]")
+    N, D = gallery.shape
+    Q = queries.shape[0]
+    k = int(k)
+    if queries.shape[1] != D or Q < 1:
+        raise AvidHipError(f"knn_search: queries {tuple(queries.shape)} do not match the gallery {tuple(gallery.shape)}")
+    if batch < 64 or batch % 64:
+        raise AvidHipError("knn_search: batch must be a multiple of 64")
+    if exclude is not None:
+        _knn_arg("knn_search: exclude", exclude, torch.int32, (Q,))
+    if fallbacks is not None:
+        _knn_arg("knn_search: fallbacks", fallbacks, torch.int32, ())
+    dev = gallery.device
+    if Q < 64:
+        pad = 64 - Q
+        queries = torch.cat([queries, queries[-1:].expand(pad, D)], 0)
+        if exclude is not None:
+            exclude = torch.cat([exclude, exclude[-1:].expand(pad)], 0)
+    Qp = queries.shape[0]
+    batch = min(batch, (Qp // 64) * 64)
+    nb = lib.raw("avid_knn_workspace_bytes")(N, batch, k)
+    ws = workspace(dev, nb)
+    idx = torch.empty((Qp, k), dtype=torch.int32, device=dev)
+    sim = torch.empty((Qp, k), dtype=torch.float32, device=dev)
+    tail = Qp % batch != 0
+    tmp_i = torch.empty((batch, k), dtype=torch.int32, device=dev) if tail else None
+    tmp_s = torch.empty((batch, k), dtype=torch.float32, device=dev) if tail else None
+    st = _stream()
+    q = 0
+    while q < Qp:
+        start = min(q, Qp - batch)                      # a full batch that ends inside the queries
+        direct = start == q
+        oi, os_ = (idx[q:], sim[q:]) if direct else (tmp_i, tmp_s)
+        lib.call("avid_knn_search", N, D, _p(gallery), _p(queries[start:]), batch, k,
+                 _p(exclude[start:]) if exclude is not None else None, _p(oi), _p(os_), _p(fallbacks), _p(ws), ws.numel(), st)
+        if not direct:
+            idx[q:] = tmp_i[q - start:]
+            sim[q:] = tmp_s[q - start:]
+        q = start + batch
+    return (idx[:Q], sim[:Q]) if Qp != Q else (idx, sim)
+
+
+def knn_vote(idx, sim, gallery_labels, n_classes, T=0.07, query_labels=None):
+    """The similarity-weighted vote over the rows of ``knn_search``: ``(scores fp32 [Q, n_classes], pred5 int32 [Q, 5],
+    first_match int32 [Q] or None)``.  ``scores[q, c]`` = the sum over ranks ``j``, in rank order, of ``exp(sim[q, j] / T)``
+    with ``gallery_labels[idx[q, j]] == c``; ``pred5`` = the five best classes by (score descending, class ascending), padded
+    with -1 below five classes; with ``query_labels``, ``first_match[q]`` = the smallest rank whose gallery label is the
+    query's, ``k`` if none — recall@r is ``first_match < r``.  Labels: int32 in ``[0, n_classes)``, on the device."""
+    _knn_arg("knn_vote: idx", idx, torch.int32)
+    if idx.dim() != 2:
+        raise AvidHipError("knn_vote: idx must be [Q, k]")
+    Q, k = idx.shape
+    _knn_arg("knn_vote: sim", sim, torch.float32, (Q, k))
+    _knn_arg("knn_vote: gallery_labels", gallery_labels, torch.int32)
+    if gallery_labels.dim() != 1:
+        raise AvidHipError("knn_vote: gallery_labels must be [N]")
+    if query_labels is not None:
+        _knn_arg("knn_vote: query_labels", query_labels, torch.int32, (Q,))
+    dev = idx.device
+    scores = torch.empty((Q, int(n_classes)), dtype=torch.float32, device=dev)
+    pred5 = torch.empty((Q, 5), dtype=torch.int32, device=dev)
+    first = torch.empty(Q, dtype=torch.int32, device=dev) if query_labels is not None else None
+    lib.call("avid_knn_vote", Q, k, _p(idx), _p(sim), _p(gallery_labels), gallery_labels.numel(), int(n_classes), 1.0 / float(T),
+             _p(query_labels), _p(scores), _p(pred5), _p(first), _stream())
+    return scores, pred5, first

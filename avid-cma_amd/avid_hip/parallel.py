@@ -896,6 +896,122 @@ class Inference:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# k-nearest-neighbour / retrieval evaluation of a frozen tower
+# ---------------------------------------------------------------------------------------------------------------------
+class KNNEval:
+    """Weighted k-NN classification and retrieval recall over the embeddings of a frozen tower, without training anything:
+    embed a labelled gallery, then classify each query by the vote of its ``k`` nearest gallery embeddings, every neighbour
+    weighing ``exp(similarity / T)`` (``ops.knn_search`` / ``ops.knn_vote``; no ``[Q, N]`` matrix is ever held).
+
+    ``model``: anything ``Inference`` runs — ``R2Plus1D`` (its ``pool`` output, flattened to ``[B, 512]``), ``AV_Wrapper`` (the
+    video embedding; pass ``(video, audio)`` where a clip batch is expected) — or ``None`` to work on features the caller
+    extracted.  The forward is ``Inference(model)``'s and nothing else: frozen towers, hooks and so on take whatever path it
+    takes.  ``feat``: only ``"pool"``, the tower's output.  ``normalize``: L2-normalise the (clip-averaged) features, so that
+    the similarity is the cosine.  The feature width must be a multiple of 32, the gallery needs 64 rows, ``k <= 63``.
+
+    Clips arrive as ``[B * clips_per_sample, 3, T, H, W]`` in the reference's ``test_dense`` order (a sample's clips are
+    adjacent) or as ``[B, clips_per_sample, 3, T, H, W]``; a sample's clip features are averaged before the normalisation
+    (``view(B, clips, -1).mean(1)``).  Labels: integer ``[B]`` on the device, in ``[0, n_classes)``.
+
+    ``evaluate`` returns integer counts as device tensors and never synchronises.  Nothing here is distributed: with several
+    ranks the caller builds the same gallery on every rank, gives each rank its share of the queries and all-reduces the counts."""
+
+    def __init__(self, model=None, feat="pool", k=20, T=0.07, n_classes=None, normalize=True):
+        if feat != "pool":
+            raise ValueError(f"KNNEval: feat must be 'pool' (got {feat!r})")
+        if n_classes is None or int(n_classes) < 1:
+            raise ValueError("KNNEval: n_classes is required")
+        if not 1 <= int(k) <= 63:
+            raise ValueError(f"KNNEval: k must be in [1, 63] (got {k})")
+        self.model, self.k, self.T, self.n_classes, self.normalize = model, int(k), float(T), int(n_classes), bool(normalize)
+        self._infer = Inference(model) if model is not None else None
+        self._chunks, self._gallery = [], None
+
+    # ---- features
+    def _labels(self, labels, n):
+        if labels.is_floating_point() or labels.dtype == torch.bool or tuple(labels.shape) != (n,):
+            raise ValueError(f"KNNEval: labels must be an integer tensor [{n}] (got {labels.dtype} {tuple(labels.shape)})")
+        return labels.to(torch.int32).contiguous()
+
+    def _pooled(self, feats, clips):
+        """[B * clips, D] clip features -> [B, D]: the clips' mean, then the normalisation."""
+        from . import ops
+        feats = feats.flatten(1).float()
+        if clips > 1:
+            if feats.shape[0] % clips:
+                raise ValueError(f"KNNEval: {feats.shape[0]} clips are not a multiple of clips_per_sample = {clips}")
+            feats = feats.view(feats.shape[0] // clips, clips, -1).mean(1)
+        feats = feats.contiguous()
+        return ops.l2_normalize(feats) if self.normalize else feats
+
+    def _embed(self, video, clips):
+        if self._infer is None:
+            raise ValueError("KNNEval was built without a model: pass features")
+        inputs = tuple(video) if isinstance(video, (tuple, list)) else (video,)
+        inputs = tuple((x.flatten(0, 1) if x.dim() == 6 else x).contiguous() for x in inputs)
+        with torch.no_grad():
+            out = self._infer(*inputs)
+            if isinstance(out, (tuple, list)):
+                out = out[0]
+            return self._pooled(out, clips)
+
+    def _features(self, x, clips):
+        if isinstance(x, torch.Tensor) and x.dim() == 2:
+            with torch.no_grad():
+                return self._pooled(x, clips)
+        return self._embed(x, clips)
+
+    # ---- gallery
+    def add_gallery(self, video, labels, clips_per_sample=1):
+        """Embed a batch of gallery clips (``Inference(model)``) and keep the features and labels on the device."""
+        feats = self._embed(video, int(clips_per_sample))
+        self._chunks.append((feats, self._labels(labels, feats.shape[0])))
+        self._gallery = None
+
+    def add_gallery_features(self, feats, labels):
+        """Add features ``[B, D]`` the caller extracted (one row per sample)."""
+        if feats.dim() != 2:
+            raise ValueError("KNNEval.add_gallery_features: feats must be [B, D]")
+        with torch.no_grad():
+            feats = self._pooled(feats, 1)
+        self._chunks.append((feats, self._labels(labels, feats.shape[0])))
+        self._gallery = None
+
+    def gallery(self):
+        """``(features [N, D], labels int32 [N])``: the chunks, concatenated once."""
+        if self._gallery is None:
+            if not self._chunks:
+                raise ValueError("KNNEval: the gallery is empty")
+            self._gallery = (torch.cat([f for f, _ in self._chunks], 0).contiguous(), torch.cat([l for _, l in self._chunks], 0))
+            self._chunks = [self._gallery]
+        return self._gallery
+
+    # ---- evaluation
+    def evaluate(self, video_or_features=None, labels=None, clips_per_sample=1, recall_at=(1, 5, 10, 20, 50), leave_one_out=False):
+        """k-NN top-1 / top-5 and retrieval recall of a batch of queries (clips, or features ``[B * clips, D]``) against the
+        gallery.  Returns ``{"n", "top1_hits", "top5_hits", "recall_hits": {r: ...}}``: int64 device scalars — counts, so that
+        batches and ranks add up; accuracy = hits / n.  ``recall_hits[r]`` (for every ``r <= k`` of ``recall_at``) counts the
+        queries with a gallery row of their own label among the ``r`` nearest.  ``leave_one_out=True`` takes no queries: every
+        gallery row is evaluated against the others."""
+        from . import ops
+        gal, gal_labels = self.gallery()
+        if leave_one_out:
+            if video_or_features is not None or labels is not None:
+                raise ValueError("KNNEval.evaluate: leave_one_out evaluates the gallery itself, pass no queries")
+            q, q_labels = gal, gal_labels
+            exclude = torch.arange(gal.shape[0], dtype=torch.int32, device=gal.device)
+        else:
+            q = self._features(video_or_features, int(clips_per_sample))
+            q_labels, exclude = self._labels(labels, q.shape[0]), None
+        idx, sim = ops.knn_search(gal, q, self.k, exclude=exclude)
+        _, pred5, first = ops.knn_vote(idx, sim, gal_labels, self.n_classes, T=self.T, query_labels=q_labels)
+        return {"n": torch.full((), q.shape[0], dtype=torch.int64, device=q.device),
+                "top1_hits": (pred5[:, 0] == q_labels).sum(),
+                "top5_hits": (pred5 == q_labels[:, None]).any(1).sum(),
+                "recall_hits": {int(r): (first < int(r)).sum() for r in recall_at if int(r) <= self.k}}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Action-recognition fine-tuning (eval-action-recg.py: run_phase 'train' / 'test_dense', the warm-up epochs of the classifier)
 # ---------------------------------------------------------------------------------------------------------------------
 class FinetuneStep(AdamStep):

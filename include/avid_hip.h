@@ -563,6 +563,27 @@ int avid_cma_topk(int64_t N, int D, const float* view1, const float* view2, int6
                   int pos_k, int kind, int32_t* out, int32_t* fallbacks, void* ws, size_t ws_bytes,
                   avid_stream_t stream);
 
+/* k-nearest-neighbour search (k-NN / retrieval evaluation of a frozen tower): for nq query rows [nq][D] against a
+ * gallery [N][D] (fp32, row-major) the k gallery rows of largest dot product per query, ordered by (similarity
+ * descending, gallery index ascending) -> out_idx int32 [nq][k], out_sim fp32 [nq][k].
+ * exclude (nullable): int32 [nq], a gallery row that must not be returned for that query (-1: none) — leave-one-out
+ * when the queries are gallery rows: k + 1 rows are selected, the named one removed where it is among them, the last one
+ * otherwise.  Nothing is assumed to be "self".
+ * Limits: D % 32 == 0, nq % 64 == 0, 64 <= N < 2^31, 1 <= k, k + (exclude ? 1 : 0) <= 64 (AVID_E_UNSUPPORTED otherwise).
+ * fallbacks (nullable): as avid_cma_topk.  ws: avid_knn_workspace_bytes(N, nq, k) bytes (0 = unsupported arguments). */
+size_t avid_knn_workspace_bytes(int64_t N, int nq, int k);
+int avid_knn_search(int64_t N, int D, const float* gallery, const float* queries, int nq, int k, const int32_t* exclude,
+                    int32_t* out_idx, float* out_sim, int32_t* fallbacks, void* ws, size_t ws_bytes,
+                    avid_stream_t stream);
+/* Similarity-weighted vote over the rows of avid_knn_search: scores[q][c] = sum over ranks j, in rank order, of
+ * exp(sim[q][j] * inv_T) with gallery_labels[idx[q][j]] == c (fp32 [nq][n_classes]; a row or a label out of range takes no
+ * part); pred5 int32 [nq][5]: the five best classes by (score descending, class ascending), padded with -1 when
+ * n_classes < 5; with query_labels (nullable, int32 [nq]) first_match[q] = the smallest rank whose gallery label is the
+ * query's, k if none (recall@r = first_match < r).  1 <= k <= 64, 1 <= n_classes <= 8192; labels int32 [N]. */
+int avid_knn_vote(int nq, int k, const int32_t* idx, const float* sim, const int32_t* gallery_labels, int64_t N,
+                  int n_classes, float inv_T, const int32_t* query_labels, float* scores, int32_t* pred5,
+                  int32_t* first_match, avid_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: torch.optim.Adam semantics (L2 weight decay folded into the gradient; bias-corrected)
  * over one flat fp32 buffer — utils/main_utils.py:250-261.
