@@ -775,6 +775,12 @@ class EvalBuilder(Builder):
         return None, self.conv_bn_fwd(blk.tmp_conv2, blk.out_bn, h, addend=res)["h"]
 
 
+# Least size of a stream's workspace in a sealed program.  Every record that takes scratch is counted by
+# avid_program_workspace_bytes; the floor only keeps small programs from each holding an odd-sized allocation of its own.
+# The tests set it to 0, so that the size function alone decides what the records get.
+WS_FLOOR = 1 << 20
+
+
 class Programs:
     """Launch programs sealed and ready to run: the record arrays of what a ``Builder`` emitted, the aux buffer with the
     weight-transform tables, the streams' workspaces, the slot table — and the per-run plumbing that fills them."""
@@ -791,7 +797,7 @@ class Programs:
         if not b.wt_recs:
             self._wt_rec.op = 0
         progs = [(Instr * max(1, len(recs)))(*recs) for recs in programs]
-        self.ws_bytes = [1 << 20] * 4
+        self.ws_bytes = [int(WS_FLOOR)] * 4
         for prog, recs in zip(progs, programs):
             need = (_sz * 4)()
             lib.call("avid_program_workspace_bytes", prog, 0, len(recs), 4, need)
