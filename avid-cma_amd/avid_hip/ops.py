@@ -1590,6 +1590,14 @@ def adam_flat(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, step_
              float(eps), float(wd), int(step), _p(step_dev), _p(lr_dev), float(grad_scale), st)
 
 
+def sgd_flat(p, g, buf, lr, momentum, wd, nesterov=False, grad_scale=1.0, lr_dev=None):
+    """torch.optim.SGD's update (dampening 0) over one flat slice in one launch; ``buf``: the momentum buffer, None exactly
+    when ``momentum == 0``.  ``lr_dev`` as ``adam_flat``'s.  There is no step counter: a zero buffer is torch's first step."""
+    _need_cuda(p, g, buf)
+    lib.call("avid_sgd_flat", p.numel(), _p(p), _p(g), _p(buf), float(lr), float(momentum), float(wd), int(bool(nesterov)),
+             _p(lr_dev), float(grad_scale), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # fine-tuning head (classify.hip): dropout, softmax cross-entropy / clip-averaged confidence
 # ------------------------------------------------------------------------------------------------

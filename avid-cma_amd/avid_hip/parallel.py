@@ -17,6 +17,8 @@ What the reference does with ``DistributedDataParallel`` + ``torch.optim.Adam``
                      ends.  No optimizer, no criterion (``DistributedDataParallel``'s engine is this and little else).
 * ``AdamStep``     — the core + one fused flat-Adam launch; ``state_dict`` / ``load_state_dict`` in torch.optim.Adam's
                      format (the reference's CheckpointManager saves ``optimizer.state_dict()``, main-avid.py:115,127,138).
+                     ``optimizer="sgd"``: the other optimizer of ``build_optimizer`` (utils/main_utils.py:242-248) instead —
+                     one flat SGD launch, one momentum buffer, torch.optim.SGD's checkpoint format.
 * ``TrainStep``    — AdamStep for pretraining: fwd -> criterion -> bwd (+ overlapped all-reduce) -> Adam; hipGraph capture
                      (``FinetuneStep``: for action-recognition fine-tuning).
 
@@ -114,6 +116,17 @@ class FlatParams:
                 self.view(v, i).copy_(st["exp_avg_sq"])
                 step = max(step, int(float(st["step"])))
         return step
+
+    def load_momentum(self, buf, states):
+        """Fill the flat SGD momentum buffer ``buf`` from ``states``, pairs as above of a torch.optim.SGD ``state`` (an entry
+        without a buffer: zeros, which the update takes exactly as torch takes a missing one).  Returns whether any was there."""
+        buf.zero_()
+        found = False
+        for i, st in states:
+            if st and st.get("momentum_buffer") is not None:
+                self.view(buf, i).copy_(st["momentum_buffer"])
+                found = True
+        return found
 
 
 class FlatBuffers:
@@ -415,20 +428,56 @@ class EngineCore:
             ops.poll_device_errors(self.flat.flat.device)
 
 
+def _sgd_param_group(lr, momentum, weight_decay, nesterov):
+    """``param_groups[0]`` (without ``params``) as the installed torch.optim.SGD writes it for these hyper-parameters."""
+    probe = torch.optim.SGD([torch.zeros(1)], lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+    return {k: v for k, v in probe.state_dict()["param_groups"][0].items() if k != "params"}
+
+
+def _require_format(who, sd, want):
+    """``sd`` is a state dict of torch.optim.<want>'s format (``"Adam"`` / ``"SGD"``), told by its first parameter group."""
+    g = sd["param_groups"][0]
+    got = "Adam" if "betas" in g else "SGD" if "momentum" in g else None
+    if got != want:
+        given = f"torch.optim.{got}'s" if got else "neither"
+        raise ValueError(f"{who} loads torch.optim.{want}'s state dict format, the one given is {given} (torch.optim.Adam: "
+                         "param_groups with betas / eps, state step / exp_avg / exp_avg_sq; torch.optim.SGD: param_groups with "
+                         "momentum / dampening / nesterov, state momentum_buffer)")
+    if want == "SGD" and (g.get("dampening", 0) != 0 or g.get("maximize", False)):
+        raise NotImplementedError(f"{who}: dampening / maximize")
+    return g
+
+
 class AdamStep(EngineCore):
     """The core plus Adam over the flat buffers: one fused launch per step (or per slice of the buffers), moments ``m`` / ``v``,
-    the step count and learning rate in device memory as well (a captured graph reads them there)."""
+    the step count and learning rate in device memory as well (a captured graph reads them there).
 
-    def __init__(self, model, lr, betas, eps, weight_decay, **core):
+    ``optimizer="sgd"`` (with ``momentum``, ``nesterov``; ``betas`` / ``eps`` are ignored): torch.optim.SGD's update instead,
+    the same one launch per slice (``ops.sgd_flat``).  Its only state is ``momentum_buffer``, laid out like the flat
+    parameters (None without momentum); ``m`` / ``v`` / ``t_dev`` are None — the update needs no step count, a zero buffer
+    is torch's first step — and ``t`` just counts steps on the host.  ``state_dict`` is then torch.optim.SGD's."""
+
+    def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False, **core):
+        if optimizer not in ("adam", "sgd"):
+            raise ValueError("optimizer must be 'adam' or 'sgd'")
+        if optimizer == "sgd" and (momentum < 0 or (nesterov and momentum == 0)):
+            raise ValueError("SGD: momentum must be >= 0, and Nesterov momentum requires a momentum")
         super().__init__(model, **core)
+        self.optimizer = optimizer
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
-        self.m = torch.zeros_like(self.flat.flat)
-        self.v = torch.zeros_like(self.flat.flat)
+        self.momentum, self.nesterov = float(momentum), bool(nesterov)
         self.t = 0
         dev = self.flat.flat.device if self.flat.flat.is_cuda else None
-        self.t_dev = torch.zeros((), dtype=torch.int64, device=dev) if dev is not None else None
         # the learning rate lives in device memory as well: a captured graph freezes by-value arguments
         self.lr_dev = torch.full((), float(lr), dtype=torch.float32, device=dev) if dev is not None else None
+        self.m = self.v = self.t_dev = self.momentum_buffer = None
+        if optimizer == "sgd":
+            if self.momentum != 0:
+                self.momentum_buffer = torch.zeros_like(self.flat.flat)
+            return
+        self.m = torch.zeros_like(self.flat.flat)
+        self.v = torch.zeros_like(self.flat.flat)
+        self.t_dev = torch.zeros((), dtype=torch.int64, device=dev) if dev is not None else None
 
     def set_lr(self, lr):
         """Change the learning rate (an LR scheduler's hook; also reaches a captured graph)."""
@@ -436,18 +485,23 @@ class AdamStep(EngineCore):
         if self.lr_dev is not None:
             self.lr_dev.fill_(self.lr)
 
-    def _adam(self, begin=0, end=None, advance=True):
-        """One flat-Adam launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (step
-        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays)."""
+    def _update(self, begin=0, end=None, advance=True):
+        """One optimizer launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (Adam: step
+        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays.  SGD has no counter)."""
         from . import ops
         s = slice(begin, end)
+        if self.optimizer == "sgd":
+            buf = self.momentum_buffer
+            ops.sgd_flat(self.flat.flat[s], self.flat.grad[s], None if buf is None else buf[s], self.lr, self.momentum, self.wd,
+                         self.nesterov, grad_scale=1.0 / self.buckets.world, lr_dev=self.lr_dev)
+            return
         ops.adam_flat(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0], self.betas[1],
                       self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev,
                       lr_dev=self.lr_dev, advance=advance)
 
     def optimizer_step(self):
         self.t += 1
-        self._adam()
+        self._update()
 
     # ---- what the supervised steps (FinetuneStep, ProbeStep) share
     def _labelled(self, video, labels):
@@ -485,7 +539,31 @@ class AdamStep(EngineCore):
     def _slice(self, flat_tensor, i):
         return self.flat.view(flat_tensor, i)
 
+    def _sgd_state_dict(self):
+        """torch.optim.SGD's format: a ``momentum_buffer`` per trainable parameter once a step has run (none without momentum)."""
+        state = {}
+        if self.t > 0 and self.momentum_buffer is not None:
+            for k, i, _ in self._param_order():
+                state[k] = {"momentum_buffer": self._slice(self.momentum_buffer, i).detach().clone()}
+        group = _sgd_param_group(self.lr, self.momentum, self.wd, self.nesterov)
+        group["params"] = list(range(sum(1 for _ in self.model.parameters())))
+        return {"state": state, "param_groups": [group]}
+
+    def _load_sgd_state_dict(self, sd):
+        g = _require_format(type(self).__name__, sd, "SGD")
+        self.momentum, self.wd, self.nesterov = float(g["momentum"]), g["weight_decay"], bool(g["nesterov"])
+        self.set_lr(g["lr"])
+        if self.momentum == 0:
+            self.momentum_buffer, self.t = None, 0
+            return
+        if self.momentum_buffer is None:
+            self.momentum_buffer = torch.zeros_like(self.flat.flat)
+        self.t = int(self.flat.load_momentum(self.momentum_buffer, ((i, sd["state"].get(k, sd["state"].get(str(k))))
+                                                                    for k, i, _ in self._param_order())))
+
     def state_dict(self):
+        if self.optimizer == "sgd":
+            return self._sgd_state_dict()
         step = float(int(self.t_dev) if self.t_dev is not None else self.t)
         state = {}
         if step > 0:
@@ -500,7 +578,9 @@ class AdamStep(EngineCore):
                                   "params": list(range(nparams))}]}
 
     def load_state_dict(self, sd):
-        g = sd["param_groups"][0]
+        if self.optimizer == "sgd":
+            return self._load_sgd_state_dict(sd)
+        g = _require_format(type(self).__name__, sd, "Adam")
         self.betas, self.eps, self.wd = tuple(g["betas"]), g["eps"], g["weight_decay"]
         self.set_lr(g["lr"])
         self.t = self.flat.load_moments(self.m, self.v, ((i, sd["state"].get(k, sd["state"].get(str(k))))
@@ -517,9 +597,10 @@ class TrainStep(AdamStep):
     """
 
     def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
-                 bucket_bytes=16 << 20, broadcast_buffers="step"):
-        """``broadcast_buffers``: see ``EngineCore``."""
-        super().__init__(model, lr, betas, eps, weight_decay, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+                 bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False):
+        """``broadcast_buffers``: see ``EngineCore``.  ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``."""
+        super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
+                         bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.criterion = criterion
         self.graph = None
 
@@ -610,9 +691,9 @@ class TrainStep(AdamStep):
         self.t += 1
         main, fourth = torch.cuda.current_stream(), pl.stream_objs[3]
         with torch.cuda.stream(fourth):
-            self._adam(0, pl.adam_early)
+            self._update(0, pl.adam_early)
         main.wait_stream(fourth)
-        self._adam(pl.adam_early, advance=False)
+        self._update(pl.adam_early, advance=False)
 
     def _sampler(self):
         """The criterion's negative sampler (``nce_average.multinomial``), or None."""
@@ -858,6 +939,87 @@ class Adam(torch.optim.Optimizer):
             self._publish_state()
 
 
+class SGD(torch.optim.Optimizer):
+    """`torch.optim.SGD(params, lr, momentum, weight_decay, nesterov)` (utils/main_utils.py:242-248; L2 weight decay, dampening 0)
+    whose `step()` is ONE launch over the flat parameter / gradient / momentum buffers.  A `torch.optim.Optimizer`: `param_groups`
+    (MultiStepLR writes `lr` there, utils/main_utils.py:261), `state_dict()` / `load_state_dict()` in torch.optim.SGD's own format
+    (`state[i] = {momentum_buffer}`, nothing without momentum), so checkpoints written by either load into the other.
+
+    The parameters are used where they lie if they already are the views of one flat buffer (the model went through
+    `DistributedDataParallel` above or `TrainStep`), otherwise they are re-seated into one here.  One parameter group.
+
+    Differences from torch.optim.SGD, by construction of the one-launch step: `zero_grad()` always zero-fills (set_to_none is
+    accepted and ignored: `.grad` stays the view of the flat buffer), and `step()` updates EVERY parameter of the buffer — one
+    that received no gradient this step is stepped with a zero gradient (its momentum buffer decays and still moves it, L2
+    weight decay still applies), where torch.optim.SGD would skip a parameter whose `.grad` is None.  The reference freezes
+    nothing (main-avid.py:106)."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
+        if dampening != 0 or kw.get("maximize") or kw.get("differentiable"):
+            raise NotImplementedError("avid_hip.parallel.SGD: dampening / maximize / differentiable")
+        params = list(params)
+        # torch's own constructor checks the values (ValueError: Nesterov momentum requires a momentum) and names the keys
+        # this torch's SGD writes into a parameter group
+        defaults = dict(torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov, **kw).defaults)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise NotImplementedError("avid_hip.parallel.SGD: one parameter group")
+        ps = self.param_groups[0]["params"]
+        self.flat = flat_of(ps)
+        if self.flat is None:
+            # (see Adam above: a second flat buffer over parameters that live in an engine's would orphan the engine's)
+            owned = [p for p in ps if _FLAT_OF.get(id(p)) is not None and _FLAT_OF[id(p)]() is not None]
+            if owned:
+                raise ValueError("avid_hip.parallel.SGD: %d of the %d parameters already live in a flat buffer (DistributedDataParallel / "
+                                 "TrainStep) but the list is not exactly that buffer's parameter set (or they were moved after it was built); "
+                                 "pass exactly the wrapped model's parameters, or use torch.optim.SGD for a different set" % (len(owned), len(ps)))
+            self.flat = FlatParams(ps)
+        self.buf = None                                  # the flat momentum buffer: made when a step or a checkpoint needs it
+
+    def _buffer(self):
+        if self.buf is None:
+            self.buf = torch.zeros_like(self.flat.flat)
+        return self.buf
+
+    def _publish_state(self):
+        """`self.state` in torch.optim.SGD's shape: views of the flat momentum buffer."""
+        if self.state or self.buf is None:
+            return
+        for i, p in enumerate(self.flat.params):
+            self.state[p] = {"momentum_buffer": self.flat.view(self.buf, i)}
+
+    def zero_grad(self, set_to_none=True):
+        """One fill of the flat gradient buffer; `.grad` stays seated (a launch program writes the buffer, not the attribute)."""
+        self.flat.zero_grad()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        from . import ops
+        g = self.param_groups[0]
+        p0 = self.flat.params[0]
+        if p0.data_ptr() != self.flat.flat.data_ptr() + 4 * self.flat.offsets[0]:
+            raise RuntimeError("avid_hip.parallel.SGD: the parameters were moved after the optimizer was built (model.cuda() / a "
+                               "wrapper constructed later): build the optimizer last, as main-avid.py:95-108 does")
+        self.flat.seat_grads()
+        ops.sgd_flat(self.flat.flat, self.flat.grad, self._buffer() if g["momentum"] != 0 else None, g["lr"], g["momentum"],
+                     g["weight_decay"], g["nesterov"])
+        if g["momentum"] != 0:
+            self._publish_state()
+        return loss
+
+    def load_state_dict(self, state_dict):
+        _require_format("avid_hip.parallel.SGD", state_dict, "SGD")
+        super().load_state_dict(state_dict)              # (torch: casts, re-keys by parameter, replaces self.state)
+        found = self.flat.load_momentum(self._buffer(), ((i, self.state.get(p)) for i, p in enumerate(self.flat.params)))
+        self.state.clear()
+        if found:
+            self._publish_state()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Inference: an eval-mode forward as one launch program
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1029,10 +1191,12 @@ class FinetuneStep(AdamStep):
     ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``AdamStep``'s, shared with ``TrainStep``."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
-                 bucket_bytes=16 << 20, broadcast_buffers="step"):
+                 bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False):
         """``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
-        0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never."""
-        super().__init__(model, lr, betas, eps, weight_decay, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+        0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never.
+        ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``."""
+        super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
+                         bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
 
@@ -1068,7 +1232,7 @@ class FinetuneStep(AdamStep):
             if self.buckets.comm:
                 self.buckets.finish()
         self.t += 1
-        self._adam(0, self.n_cls if self.classifier_only else self.flat.numel)
+        self._update(0, self.n_cls if self.classifier_only else self.flat.numel)
         self._poll_errors()
         return out[0], out[2:6].view(torch.int64)
 
@@ -1106,10 +1270,13 @@ class ProbeStep(AdamStep):
     ``set_lr`` and ``state_dict`` / ``load_state_dict`` are ``AdamStep``'s — ``torch.optim.Adam(model.parameters())``'s format,
     the frozen tower parameters listed without state."""
 
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
+                 nesterov=False):
+        """``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``."""
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
-        super().__init__(model, lr, betas, eps, weight_decay, broadcast_buffers="off")
+        super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
+                         broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
 
     def _plan(self, video):
@@ -1131,7 +1298,7 @@ class ProbeStep(AdamStep):
         _, fa = pl.forward(video, self.flat.grad, True, labels=labels, out=out, dlogits=dlogits)
         self._plan_backward(pl, fa, (video, None, dlogits, None))
         self.t += 1
-        self._adam()
+        self._update()
         self._poll_errors()
         return out[:, 0], out[:, 2:6].view(torch.int64)
 

@@ -1,6 +1,7 @@
 // Flat fused Adam (torch.optim.Adam semantics: L2 weight decay folded into the gradient, bias
 // correction as in torch's single-tensor path) over ONE contiguous fp32 buffer holding every
 // parameter — replaces the 141 per-tensor optimizer launches of utils/main_utils.py:250-261.
+// Flat SGD with momentum (torch.optim.SGD semantics, utils/main_utils.py:242-248) over the same buffers: one state buffer.
 #include <math.h>
 
 #include "common.h"
@@ -50,6 +51,64 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, c
   }
 }
 
+// torch's single-tensor SGD (dampening 0) for one element, in torch's order, every product and every sum rounded to fp32 on
+// its own: hipcc contracts a * b + c into one fused multiply-add by default, torch's kernels (and the numpy restatement the
+// tests hold this against, bit for bit) do not.  A zero-initialised buffer makes the first step torch's ``buf = clone(d)``.
+__device__ __forceinline__ float sgd_element(float& p, float g, float* buf, float lr, float momentum, float wd, bool nesterov,
+                                             float grad_scale) {
+#pragma clang fp contract(off)
+  float d = g * grad_scale;
+  if (wd != 0.f) {
+    const float t = wd * p;
+    d = d + t;
+  }
+  float b = 0.f;
+  if (buf) {
+    const float t = momentum * *buf;
+    b = t + d;
+    if (nesterov) {
+      const float u = momentum * b;
+      d = d + u;
+    } else {
+      d = b;
+    }
+  }
+  const float s = lr * d;
+  p = p - s;
+  return b;
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ buf, long long n4, long long n, float lr,
+                                                       float momentum, float wd, int nesterov, float grad_scale,
+                                                       const float* __restrict__ lr_dev) {
+  if (lr_dev) lr = *lr_dev;   // graph-replay safe learning rate, as adam_flat_kernel's
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
+    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
+    floatx4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (buf) bv = reinterpret_cast<floatx4*>(buf)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], bj = bv[j];
+      bj = sgd_element(pj, gv[j], buf ? &bj : nullptr, lr, momentum, wd, nesterov != 0, grad_scale);
+      pv[j] = pj;
+      bv[j] = bj;
+    }
+    reinterpret_cast<floatx4*>(p)[i] = pv;
+    if (buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
+  }
+  // tail (n % 4) handled by block 0
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    float pi = p[i], bi = buf ? buf[i] : 0.f;
+    bi = sgd_element(pi, g[i], buf ? &bi : nullptr, lr, momentum, wd, nesterov != 0, grad_scale);
+    p[i] = pi;
+    if (buf) buf[i] = bi;
+  }
+}
+
 }  // namespace avid
 
 using namespace avid;
@@ -74,4 +133,21 @@ extern "C" int avid_adam_flat(int64_t n, float* p, const float* g, float* m, flo
                      (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
                      (const long long*)step_dev, lr_dev);
   return check_launch("adam_flat");
+}
+
+extern "C" int avid_sgd_flat(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
+                             int nesterov, const float* lr_dev, float grad_scale, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g, AVID_E_BADARG, "sgd_flat: bad argument");
+  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat: momentum needs its buffer");
+  if (momentum == 0.f) buf = nullptr;   // (the kernel takes the buffer as the switch)
+  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat: nesterov needs momentum");
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
+               "sgd_flat: buffers must be 16-byte aligned");
+  const long long n4 = n / 4;
+  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  ScopedTimer t((hipStream_t)stream, "sgd_flat_kernel", 0.0, (buf ? 20.0 : 12.0) * n);
+  hipLaunchKernelGGL(sgd_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, n4, (long long)n,
+                     lr, momentum, weight_decay, nesterov, grad_scale, lr_dev);
+  return check_launch("sgd_flat");
 }

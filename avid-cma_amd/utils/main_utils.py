@@ -13,6 +13,11 @@ proxy that forwards everything to torch except ``nn.parallel.DistributedDataPara
 parameter list that IS the wrapped model's flat-buffer set (main-avid.py's case); any other list (the evaluation scripts' bare models
 and parameter subsets) gets torch's own Adam.
 
+``build_optimizer``'s other branch, ``:242`` ``torch.optim.SGD(params, lr, momentum, weight_decay, nesterov)``, is forwarded the same
+way to ``avid_hip.parallel.SGD`` when ``AVID_DROPIN_SGD=1`` is set.  It is an opt-in because ``optim.SGD`` forwarding to torch
+unchanged under the default is pinned behaviour of this module (tests/test_host_logic.py); without the variable an ``sgd``
+config keeps torch's per-tensor optimizer, as before.
+
 Nothing of the reference is copied or edited; without a reference checkout on the path the import fails as it would have.
 ``AVID_DROPIN=0`` leaves ``torch`` alone (the reference's module as it is)."""
 import os as _os
@@ -72,6 +77,26 @@ def _adam_factory():
     return Adam
 
 
+def _sgd_factory():
+    """`torch.optim.SGD` as `build_optimizer` sees it (the reference's other optimizer: `name: sgd` with `momentum` / `nesterov`):
+    the flat-buffer SGD under the same condition as `_adam_factory()`'s, torch's own for every other parameter list and for
+    arguments the one-launch step does not reproduce (dampening, maximize, several groups)."""
+    import torch
+    from avid_hip import parallel
+
+    def SGD(params, *args, **kwargs):
+        ps = list(params)
+        plain = all(isinstance(p, torch.Tensor) for p in ps)
+        if plain and ps and parallel.flat_of([p for p in ps if p.requires_grad]) is not None:
+            try:
+                return parallel.SGD(ps, *args, **kwargs)
+            except (NotImplementedError, ValueError):
+                pass
+        return torch.optim.SGD(ps, *args, **kwargs)
+    SGD.__doc__ = parallel.SGD.__doc__
+    return SGD
+
+
 def _ddp_factory():
     """`torch.nn.parallel.DistributedDataParallel` as `distribute_model_to_cuda` sees it: this build's wrapper for this build's two-tower
     model (`models.av_wrapper`'s class), torch's own for any other module or for arguments the wrapper does not reproduce."""
@@ -93,7 +118,10 @@ def _torch_with_dropins():
     from avid_hip import parallel
     nn_parallel = _Forward(torch.nn.parallel, {"DistributedDataParallel": _ddp_factory()})
     nn = _Forward(torch.nn, {"parallel": nn_parallel})
-    optim = _Forward(torch.optim, {"Adam": _adam_factory()})
+    over = {"Adam": _adam_factory()}
+    if _os.environ.get("AVID_DROPIN_SGD", "0") == "1":
+        over["SGD"] = _sgd_factory()
+    optim = _Forward(torch.optim, over)
     return _Forward(torch, {"nn": nn, "optim": optim})
 
 

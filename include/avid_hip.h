@@ -593,6 +593,14 @@ int avid_knn_vote(int nq, int k, const int32_t* idx, const float* sim, const int
 int avid_adam_flat(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
                    const float* lr_dev, float grad_scale, avid_stream_t stream);
+/* torch.optim.SGD semantics (utils/main_utils.py:242-248; dampening 0, L2 weight decay folded into the gradient) over
+ * one flat fp32 buffer, in torch's single-tensor order with every product and sum rounded to fp32 on its own:
+ *   d = g * grad_scale;  if (weight_decay != 0) d += weight_decay * p;
+ *   if (momentum != 0) { buf = momentum * buf + d;  d = nesterov ? d + momentum * buf : buf; }   p -= lr * d
+ * A zero-filled buf makes the first step torch's buf = clone(d): there is no step counter.  buf may be NULL exactly when
+ * momentum == 0 (it is not touched then); nesterov needs momentum.  lr_dev as above.  Buffers 16-byte aligned. */
+int avid_sgd_flat(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
+                  int nesterov, const float* lr_dev, float grad_scale, avid_stream_t stream);
 
 /* Video clip front end: frames [B][T][H][W][3] uint8 (what the decoder / augmentation hands over)
  * -> out [B][3][T][H][W] fp32 = ((u / 255) - mean[c]) / std[c], the reference's ClipToTensor + Normalize
