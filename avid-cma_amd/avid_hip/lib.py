@@ -76,6 +76,11 @@ class AugDesc(C.Structure):
 AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE, AUG_CONTRAST = 0, 1, 2, 3
 
 
+class PcmDesc(C.Structure):
+    """Mirror of ``avid_pcm_desc`` (include/avid_hip.h): one clip of ``avid_audio_prep`` / ``avid_logspec_pcm``."""
+    _fields_ = [("samples", C.c_void_p), ("channels", C.c_int32), ("n", C.c_int32), ("gain", C.c_float)]
+
+
 class Ref(C.Structure):
     """Mirror of ``avid_ref``: (slot, byte offset); slot < 0 = NULL."""
     _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("off", C.c_int64)]
@@ -180,6 +185,10 @@ SIGNATURES = {
     "avid_logspec_basis": (_i, [_i, _vp, _vp]),
     "avid_logspec_workspace_bytes": (_sz, [_i, _i, _i]),
     "avid_logspec": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _sz, _vp]),
+    "avid_audio_prep_workspace_bytes": (_sz, [_i]),
+    "avid_audio_prep": (_i, [_i, C.POINTER(PcmDesc), _i, _vp, _vp, _sz, _vp]),
+    "avid_logspec_pcm_workspace_bytes": (_sz, [_i, _i, _i]),
+    "avid_logspec_pcm": (_i, [_i, C.POINTER(PcmDesc), _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _sz, _vp]),
     "avid_maxpool_hw3s2_fwd": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "avid_maxpool_hw3s2_bwd": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "avid_global_maxpool_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),

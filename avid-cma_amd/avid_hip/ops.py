@@ -1201,6 +1201,19 @@ def clip_augment(clips, descs, num_frames, out_size, mean=(0.485, 0.456, 0.406),
 _LOGSPEC_BASIS = {}
 
 
+def _logspec_basis(device, n_stft):
+    key = (device, int(n_stft))
+    basis = _LOGSPEC_BASIS.get(key)
+    if basis is None:
+        nfl = lib.raw("avid_logspec_basis_floats")(int(n_stft))
+        if nfl == 0:
+            raise AvidHipError(f"log_spectrogram: unsupported STFT size {n_stft}")
+        basis = torch.empty(nfl, dtype=torch.float32, device=device)
+        lib.call("avid_logspec_basis", int(n_stft), _p(basis), _stream())
+        _LOGSPEC_BASIS[key] = basis
+    return basis
+
+
 def log_spectrogram(sig, n_stft, hop, frames, mean=None, std=None, top_db=100.0):
     """``sig [B, L]`` mono fp32 on the GPU -> ``[B, 1, frames, n_stft/4 + 1]`` (avid_logspec; reference
     datasets/preprocessing.py:174-186 with librosa's stft / power_to_db defaults).  No gradient."""
@@ -1208,18 +1221,58 @@ def log_spectrogram(sig, n_stft, hop, frames, mean=None, std=None, top_db=100.0)
     if sig.dim() != 2 or sig.dtype != torch.float32 or not sig.is_contiguous():
         raise AvidHipError("log_spectrogram: sig must be a contiguous fp32 [B, L] tensor")
     B, L = sig.shape
-    key = (sig.device, int(n_stft))
-    basis = _LOGSPEC_BASIS.get(key)
-    if basis is None:
-        nfl = lib.raw("avid_logspec_basis_floats")(int(n_stft))
-        if nfl == 0:
-            raise AvidHipError(f"log_spectrogram: unsupported STFT size {n_stft}")
-        basis = torch.empty(nfl, dtype=torch.float32, device=sig.device)
-        lib.call("avid_logspec_basis", int(n_stft), _p(basis), _stream())
-        _LOGSPEC_BASIS[key] = basis
+    basis = _logspec_basis(sig.device, n_stft)
     out = torch.empty((B, 1, int(frames), n_stft // 4 + 1), dtype=torch.float32, device=sig.device)
     ws = workspace(sig.device, lib.raw("avid_logspec_workspace_bytes")(B, int(n_stft), int(frames)))
     lib.call("avid_logspec", B, L, _p(sig), int(n_stft), int(hop), int(frames), _p(basis), _p(mean), _p(std),
+             float(top_db), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def _pcm_descs(what, clips, gains):
+    """The ``avid_pcm_desc`` array of a list of int16 ``[C_b, n_b]`` GPU clips (an empty clip is a missing one) and its device."""
+    clips = list(clips)
+    _need_cuda(*clips)
+    gains = [1.0] * len(clips) if gains is None else list(gains)
+    if len(clips) == 0 or len(gains) != len(clips):
+        raise AvidHipError(f"{what}: {len(clips)} clips but {len(gains)} gains")
+    dev = clips[0].device
+    arr = (lib.PcmDesc * len(clips))()
+    for b, (c, g) in enumerate(zip(clips, gains)):
+        if c.dim() != 2 or c.dtype != torch.int16 or not c.is_contiguous() or c.device != dev:
+            raise AvidHipError(f"{what}: clip {b} must be a contiguous int16 [channels, samples] tensor on {dev}")
+        d = arr[b]
+        d.channels, d.n, d.gain = c.shape[0], c.shape[1], float(g)
+        d.samples = c.data_ptr() if c.numel() else None
+    return arr, dev, clips
+
+
+def audio_prep(clips, gains, length):
+    """The reference's ``AudioPrep`` (datasets/preprocessing.py:116-155) for a ragged batch in one call (avid_audio_prep, bit-
+    identical): ``clips``: a list of int16 ``[C_b, n_b]`` GPU tensors, the decoder's samples (``n_b`` = 0: a missing clip);
+    ``gains``: one volume factor per clip (None: no augmentation) -> fp32 ``[B, length]``: the channel mean of ``s / 32767``,
+    trimmed / zero-padded to ``length``, times the gain.  No gradient."""
+    arr, dev, clips = _pcm_descs("audio_prep", clips, gains)
+    if int(length) <= 0:
+        raise AvidHipError(f"audio_prep: length {length}")
+    out = torch.empty((len(clips), int(length)), dtype=torch.float32, device=dev)
+    ws = workspace(dev, lib.raw("avid_audio_prep_workspace_bytes")(len(clips)))
+    lib.call("avid_audio_prep", len(clips), arr, int(length), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def log_spectrogram_pcm(clips, gains, length, n_stft, hop, frames, mean=None, std=None, top_db=100.0):
+    """``log_spectrogram(audio_prep(clips, gains, length), ...)``, the same bits, without the waveform in between
+    (avid_logspec_pcm: the frame matrix is filled straight from the int16 clips) -> ``[B, 1, frames, n_stft/4 + 1]``."""
+    arr, dev, clips = _pcm_descs("log_spectrogram_pcm", clips, gains)
+    _need_cuda(mean, std)
+    if int(length) <= int(n_stft) // 2:
+        raise AvidHipError(f"log_spectrogram_pcm: length {length} does not exceed half the STFT size {n_stft}")
+    B = len(clips)
+    basis = _logspec_basis(dev, n_stft)
+    out = torch.empty((B, 1, int(frames), n_stft // 4 + 1), dtype=torch.float32, device=dev)
+    ws = workspace(dev, lib.raw("avid_logspec_pcm_workspace_bytes")(B, int(n_stft), int(frames)))
+    lib.call("avid_logspec_pcm", B, arr, int(length), int(n_stft), int(hop), int(frames), _p(basis), _p(mean), _p(std),
              float(top_db), _p(out), _p(ws), ws.numel(), _stream())
     return out
 

@@ -346,31 +346,6 @@ static AugLayout layout(int B, const avid_aug_desc* descs, int nf, int ch, int c
   return L;
 }
 
-// Pinned staging buffers, reused across calls: a buffer is taken again only once the copy that read it has completed (its
-// event), otherwise another one is allocated; the host never waits.
-struct Stage {
-  void* host = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-  bool used = false;
-};
-static std::mutex g_stage_mu;
-static std::vector<Stage> g_stages;
-
-static Stage* take_stage(size_t bytes) {
-  for (auto& s : g_stages)
-    if (s.bytes >= bytes && (!s.used || hipEventQuery(s.done) == hipSuccess)) return &s;
-  Stage s;
-  s.bytes = bytes < (1u << 20) ? (1u << 20) : bytes * 2;
-  if (hipHostMalloc(&s.host, s.bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-  if (hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipHostFree(s.host);
-    return nullptr;
-  }
-  g_stages.push_back(s);
-  return &g_stages.back();
-}
-
 }  // namespace avid
 
 using namespace avid;

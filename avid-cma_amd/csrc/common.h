@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <mutex>
+
 #include "../../include/avid_hip.h"
 
 namespace avid {
@@ -45,6 +47,19 @@ struct ScopedTimer {
   ScopedTimer(hipStream_t stream, const char* name, double flops, double bytes);
   ~ScopedTimer();
 };
+
+// Pinned staging buffers for tables the host builds per call (avid_clip_augment's coefficient tables, the descriptor tables of
+// the audio front end), reused across calls: a buffer is taken again only once the copy that read it has completed (its
+// event), otherwise another one is allocated; the host never waits.  The caller holds g_stage_mu from take_stage() until it
+// has recorded `done` behind its copy and set `used`.
+struct Stage {
+  void* host = nullptr;
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;
+  bool used = false;
+};
+extern std::mutex g_stage_mu;
+Stage* take_stage(size_t bytes);     // nullptr: the pinned allocation failed
 
 // conv.hip: C[M][N] = A[M][K].Bq[N][K]^T (op 0) / min(.,Cin) (1) / max(.,Cin) (2) on the MFMA igemm kernel
 int sim_gemm_nt(const float* A, const float* Bq, float* C, const float* Cin, int op, long long M, int N, int K,

@@ -50,6 +50,24 @@ ScopedTimer::~ScopedTimer() {
   if (slot >= 0) (void)hipEventRecord(g_recs[slot].e1, s);
 }
 
+// ---- pinned staging buffers (common.h)
+std::mutex g_stage_mu;
+static std::vector<Stage> g_stages;
+
+Stage* take_stage(size_t bytes) {
+  for (auto& s : g_stages)
+    if (s.bytes >= bytes && (!s.used || hipEventQuery(s.done) == hipSuccess)) return &s;
+  Stage s;
+  s.bytes = bytes < (1u << 20) ? (1u << 20) : bytes * 2;
+  if (hipHostMalloc(&s.host, s.bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+  if (hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) {
+    (void)hipHostFree(s.host);
+    return nullptr;
+  }
+  g_stages.push_back(s);
+  return &g_stages.back();
+}
+
 // ---- CU budget of the persistent kernels (include/avid_hip.h: avid_set_cu_budget)
 // -1: not configured (AVID_CU_RESERVE from the environment on first use); 0: every CU.  Read from the forward thread and from
 // autograd's backward thread: atomic (relaxed; both would initialise it to the same value)
@@ -134,7 +152,7 @@ extern "C" int avid_timing_report(char* buf, size_t len) {
 }
 
 extern "C" const char* avid_last_error(void) { return avid::g_err; }
-extern "C" int avid_version(void) { return 162; }
+extern "C" int avid_version(void) { return 163; }
 
 extern "C" int avid_device_info(int device, int* cu_count, int* lds_bytes, char* arch, int arch_len) {
   hipDeviceProp_t prop;

@@ -650,6 +650,32 @@ int avid_logspec(int B, int L, const float* sig, int n_stft, int hop, int T, con
                  const float* mean, const float* std, float top_db, float* out, void* ws, size_t ws_bytes,
                  avid_stream_t stream);
 
+/* The same front end from the decoder's samples: the reference's AudioPrep (datasets/preprocessing.py:116-155: downmix, trim /
+ * zero-pad to L samples, volume jitter) for a ragged batch of int16 clips, bit for bit.  One descriptor per clip; samples:
+ * DEVICE pointer to planar int16 [channels][n], 2-byte aligned (clips may be views into one packed upload); 1 <= channels <= 8;
+ * n == 0 is a missing clip (samples may then be NULL); gain: the float32 the waveform is multiplied by, 1.0f when not
+ * augmenting.  The prepared sample p of a clip, 0 <= p < L:
+ *     p <  n:  (float)((s[0][p] / 32767.0 + s[1][p] / 32767.0 + ...) / channels)   summed in channel order, in double
+ *     p >= n:  0.0f
+ *     then one float32 multiply by gain
+ * (numpy's arithmetic for  data / np.iinfo(int16).max -> .mean(0).astype(float32) -> np.pad -> sig *= float).
+ * descs: HOST array of B descriptors, checked before anything is launched (an error names the clip), then copied into ws on
+ * the stream through pinned staging (no host synchronisation).
+ * avid_audio_prep: out [B][L] fp32.  avid_logspec_pcm: avid_logspec of that waveform (same arguments and checks, bit-identical
+ * output) with the frame matrix filled straight from the clips: no waveform is written. */
+typedef struct avid_pcm_desc {
+  const int16_t* samples;
+  int32_t channels;
+  int32_t n;
+  float gain;
+} avid_pcm_desc;
+size_t avid_audio_prep_workspace_bytes(int B);
+int avid_audio_prep(int B, const avid_pcm_desc* descs, int L, float* out, void* ws, size_t ws_bytes, avid_stream_t stream);
+size_t avid_logspec_pcm_workspace_bytes(int B, int n_stft, int T);
+int avid_logspec_pcm(int B, const avid_pcm_desc* descs, int L, int n_stft, int hop, int T, const float* basis,
+                     const float* mean, const float* std, float top_db, float* out, void* ws, size_t ws_bytes,
+                     avid_stream_t stream);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Collectives: NOT part of this library.  SURVEY.md 8(b) sketched avid_comm_init / avid_allreduce_f32 /
