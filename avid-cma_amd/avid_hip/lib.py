@@ -233,6 +233,7 @@ SIGNATURES = {
     "avid_knn_vote": (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "avid_adam_flat": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp]),
     "avid_sgd_flat": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp]),
+    "avid_grad_accum_flat": (_i, [_i64, _vp, _vp, _vp, _vp]),
     "avid_probe_spin": (_i, [_i, _vp]),
     "avid_stream_wait": (_i, [_vp, _vp]),
     "avid_clock_probe": (_i, [_i, _vp, _vp]),

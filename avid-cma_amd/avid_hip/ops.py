@@ -1651,6 +1651,16 @@ def sgd_flat(p, g, buf, lr, momentum, wd, nesterov=False, grad_scale=1.0, lr_dev
              _p(lr_dev), float(grad_scale), _stream())
 
 
+def grad_accum_flat(dst, a, b):
+    """``dst = a + b`` over flat fp32 buffers of one size in one launch (``dst`` may be ``a`` or ``b`` themselves; any other
+    overlap raises): the sum of a virtual-rank step's shard gradients, left to right in rank order (parallel.TrainStep)."""
+    _need_cuda(dst, a, b)
+    if not (dst.dtype == a.dtype == b.dtype == torch.float32 and dst.numel() == a.numel() == b.numel()
+            and dst.is_contiguous() and a.is_contiguous() and b.is_contiguous()):
+        raise AvidHipError("grad_accum_flat: three contiguous fp32 buffers of one size")
+    lib.call("avid_grad_accum_flat", dst.numel(), _p(dst), _p(a), _p(b), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # fine-tuning head (classify.hip): dropout, softmax cross-entropy / clip-averaged confidence
 # ------------------------------------------------------------------------------------------------

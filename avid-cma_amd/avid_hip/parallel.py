@@ -35,6 +35,8 @@ from . import lib
 
 
 _FLAT_OF = {}           # id(parameter) -> weakref(FlatParams it is a view of)
+_U64 = 0xFFFFFFFFFFFFFFFF
+_RANK_SEED_STRIDE = 0x9E3779B97F4A7C15      # rank r's negative sampler: base seed + stride * r (criterions/avid.py)
 
 
 def flat_of(params):
@@ -391,6 +393,8 @@ class EngineCore:
             bucket_bytes = int(float(os.environ["AVID_BUCKET_MB"]) * (1 << 20))
         self.buckets = GradBuckets(self.flat, bucket_bytes, average=average, hooks=hooks)
         self._step_plan = None                           # the launch program the current step's backward ran through
+        self._grad_target = None                         # where the launch programs write gradients, if not flat.grad
+        self._share_tables, self._tables_of = False, None   # a virtual-rank step: the plan whose derived weight tables are current
         self.twt = self.slots = None
         if self.flat.flat.is_cuda:
             from . import ops
@@ -403,17 +407,30 @@ class EngineCore:
         evaluating the model or saving it on a rank other than 0."""
         self.flat_buffers.broadcast(0)
 
+    def grad_target(self):
+        """The flat buffer the launch programs zero and write this pass's gradients into: ``flat.grad``, unless a virtual-rank
+        step has pointed shard 0 at its accumulator (``TrainStep._virtual_forward_backward``)."""
+        return self.flat.grad if self._grad_target is None else self._grad_target
+
+    def rebuild_tables(self, pl):
+        """Whether a forward through ``pl`` has to rebuild the derived weight tables: always, except for the later passes of
+        a virtual-rank step (``_share_tables``), which run the program that built them a moment ago from the same weights."""
+        if not self._share_tables:
+            return True
+        fresh, self._tables_of = self._tables_of is not pl, pl
+        return fresh
+
     def _plan_backward(self, pl, fa, inputs):
         """A backward launch program into the flat gradient buffer (``pl.backward``'s ``fa`` / ``inputs``; called from the
         model's autograd node or by ``FinetuneStep``): in one piece, or — with gradient collectives — cut where a bucket
         becomes complete, so that its all-reduce starts under the rest of the pass."""
         self._step_plan = pl
         if not self.buckets.comm or self.buckets._capturing():
-            pl.backward(fa, inputs, self.flat.grad)
+            pl.backward(fa, inputs, self.grad_target())
             return
         ba, begin = None, 0
         for end, ready in pl.segments(self.buckets.bucket_of, self.buckets.counts):
-            ba = pl.backward(fa, inputs, self.flat.grad, begin, end, ba)
+            ba = pl.backward(fa, inputs, self.grad_target(), begin, end, ba)
             for i, st in ready:
                 self.buckets.ready(i, pl.stream_objs[st])
             begin = end
@@ -457,6 +474,8 @@ class AdamStep(EngineCore):
     parameters (None without momentum); ``m`` / ``v`` / ``t_dev`` are None — the update needs no step count, a zero buffer
     is torch's first step — and ``t`` just counts steps on the host.  ``state_dict`` is then torch.optim.SGD's."""
 
+    virtual_ranks = 1        # ranks whose gradients the buffer holds the SUM of, per process (TrainStep(virtual_ranks=R))
+
     def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False, **core):
         if optimizer not in ("adam", "sgd"):
             raise ValueError("optimizer must be 'adam' or 'sgd'")
@@ -493,10 +512,10 @@ class AdamStep(EngineCore):
         if self.optimizer == "sgd":
             buf = self.momentum_buffer
             ops.sgd_flat(self.flat.flat[s], self.flat.grad[s], None if buf is None else buf[s], self.lr, self.momentum, self.wd,
-                         self.nesterov, grad_scale=1.0 / self.buckets.world, lr_dev=self.lr_dev)
+                         self.nesterov, grad_scale=1.0 / (self.buckets.world * self.virtual_ranks), lr_dev=self.lr_dev)
             return
         ops.adam_flat(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0], self.betas[1],
-                      self.eps, self.wd, self.t, grad_scale=1.0 / self.buckets.world, step_dev=self.t_dev,
+                      self.eps, self.wd, self.t, grad_scale=1.0 / (self.buckets.world * self.virtual_ranks), step_dev=self.t_dev,
                       lr_dev=self.lr_dev, advance=advance)
 
     def optimizer_step(self):
@@ -597,12 +616,169 @@ class TrainStep(AdamStep):
     """
 
     def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
-                 bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False):
-        """``broadcast_buffers``: see ``EngineCore``.  ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``."""
+                 bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
+                 virtual_ranks=1):
+        """``broadcast_buffers``: see ``EngineCore``.  ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``.
+        ``virtual_ranks`` = R > 1: ``step`` takes the GLOBAL batch [R * b, ...] and is the step of an R-rank job of per-rank
+        batch b, run on this one GPU shard after shard (``_virtual_forward_backward``): per-shard BatchNorm statistics,
+        per-rank negatives, the first step's Z the mean of the ranks', the gradient their mean, one bank update with all
+        records in rank order, rank 0's running statistics.  One process only, ``broadcast_buffers="step"``, no ``capture()``."""
+        R = int(virtual_ranks)
+        if R < 1:
+            raise ValueError(f"TrainStep: virtual_ranks must be >= 1 (got {virtual_ranks})")
+        if R > 1:
+            if _dist_on():
+                raise ValueError(f"TrainStep(virtual_ranks={R}) emulates the ranks of a job inside ONE process: a process group of "
+                                 "more than one rank (or AVID_FORCE_DIST=1) is not supported with virtual_ranks > 1")
+            if broadcast_buffers != "step":
+                raise ValueError(f"TrainStep(virtual_ranks={R}) keeps rank 0's BatchNorm running statistics, which is "
+                                 f"broadcast_buffers='step'; broadcast_buffers={broadcast_buffers!r} is not supported with "
+                                 "virtual_ranks > 1")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.criterion = criterion
         self.graph = None
+        self.virtual_ranks = R
+        self.rank_losses = None      # [R] device tensor: the loss each rank of the emulated job logged in the last step
+        self._acc = self._bn_keep = self._nbt = None
+        self._rank_sampler = None    # per virtual rank: [seed, offset] of its negative-sampler stream
+        mult = self._sampler()
+        if R > 1 and mult is not None:                   # criterions/avid.py AVIDSimilarityMemoryBank.__init__'s per-rank formula
+            self._rank_sampler = [[(int(mult.seed) + _RANK_SEED_STRIDE * r) & _U64, int(mult.offset)] for r in range(R)]
+
+    def reseed(self, seeds, offset=0):
+        """Set the seed of every (virtual) rank's negative-sampler stream and the position all of them are at."""
+        seeds = [int(s) & _U64 for s in seeds]
+        mult = self._sampler()
+        if len(seeds) != self.virtual_ranks:
+            raise ValueError(f"TrainStep.reseed: {self.virtual_ranks} seed(s) expected, one per virtual rank (got {len(seeds)})")
+        if mult is None:
+            raise ValueError("TrainStep.reseed: the criterion has no negative sampler")
+        mult.reseed(seeds[0], offset)
+        if self.virtual_ranks > 1:
+            self._rank_sampler = [[s, int(offset)] for s in seeds]
+
+    def _partition_terms(self):
+        """The criterion's NCE terms: every module that freezes a partition constant Z on its first call (criterions/nce.py)."""
+        return [m for m in self.criterion.modules() if hasattr(m, "avg_exp_score") and hasattr(m, "z_ready")]
+
+    def _shard_forward(self, r, shard):
+        """Virtual rank r's forward through the launch programs and the criterion, with ITS sampler stream: (embeddings' loss
+        node, where the stream stands afterwards).  The programs are the only path: there is no per-layer form of this step."""
+        from . import plan
+        mult = self._sampler()
+        if mult is not None:
+            mult.reseed(*self._rank_sampler[r])
+        out = plan.run(self.model, shard[0], shard[1])
+        if out is None:
+            raise lib.AvidHipError("TrainStep(virtual_ranks > 1) runs through the compiled launch programs only; this model / "
+                                   "these inputs are outside them (hooked or frozen modules, non-fp32 or host tensors)")
+        return out, mult
+
+    def _partition_pass(self, shards, terms):
+        """The first step of an R-rank job: every rank estimates Z from ITS first batch and all take the mean over ranks
+        (criterions/nce.py:27-33) — so the R per-shard values are needed before any shard's loss.  A statistics pass: every
+        shard's forward and criterion (no backward), its Z noted, Z reset; then Z = ((z0 + z1) + ...) / R, frozen.  It leaves
+        no other trace: the BatchNorm buffers and ``num_batches_tracked`` are put back, the bank updates are dropped, the
+        samplers' positions are not stored (the real pass draws the same negatives again)."""
+        from . import plan
+        R = self.virtual_ranks
+        fb, bank = self.flat_buffers.flat, self.criterion.nce_average
+        saved = fb.clone() if fb is not None else None
+        zs = [[] for _ in terms]
+        bank.defer_updates()
+        try:
+            for r, shard in enumerate(shards):
+                for m in terms:
+                    m.avg_exp_score.fill_(-1.0)
+                    m._z_ready = False
+                with plan.engine(self):
+                    out, _ = self._shard_forward(r, shard)
+                    with torch.no_grad():
+                        self.criterion(out[0], out[1], shard[2])
+                for z, m in zip(zs, terms):
+                    z.append(m.avg_exp_score.clone())
+        finally:
+            bank.flush_updates(apply=False)
+        if saved is not None:
+            fb.copy_(saved)
+        if self._nbt:
+            torch._foreach_sub_(self._nbt, R)
+        for z, m in zip(zs, terms):
+            acc = z[0]
+            for other in z[1:]:
+                acc += other
+            acc /= R
+            m.avg_exp_score.copy_(acc)
+            m._z_ready = True
+
+    def _virtual_forward_backward(self, video, audio, index):
+        """forward_backward of an R-rank job on the global batch: the flat gradient buffer ends up holding the SUM over ranks,
+        left to right in rank order, ((g0 + g1) + g2) + ... — what the ranks' all-reduce leaves — ``rank_losses`` the ranks'
+        losses; returns their mean.  Shard 0's programs write straight into the accumulator, every later shard's into the
+        flat gradient buffer, followed by one ``ops.grad_accum_flat``: acc = acc + g, and for the last shard g = acc + g."""
+        from . import ops, plan
+        R = self.virtual_ranks
+        B = video.shape[0]
+        if B % R or audio.shape[0] != B or index.shape[0] != B:
+            raise ValueError(f"TrainStep(virtual_ranks={R}).step: the global batch must be R * b samples in video, audio and index "
+                             f"alike; virtual_ranks={R} does not divide {B} (audio {audio.shape[0]}, index {index.shape[0]})")
+        if not self.flat.grad.is_cuda:
+            raise lib.AvidHipError("TrainStep(virtual_ranks > 1) needs the model on a HIP device")
+        b = B // R
+        video, audio, index = video.contiguous(), audio.contiguous(), index.contiguous()
+        shards = [(video[r * b:(r + 1) * b], audio[r * b:(r + 1) * b], index[r * b:(r + 1) * b]) for r in range(R)]
+        fb, bank = self.flat_buffers.flat, self.criterion.nce_average
+        if self._acc is None:
+            self._acc = torch.empty_like(self.flat.grad)
+            self._bn_keep = torch.empty_like(fb) if fb is not None else None
+            self._nbt = [m.num_batches_tracked for m in self.model.modules() if getattr(m, "num_batches_tracked", None) is not None]
+        if self._rank_sampler is None and self._sampler() is not None:
+            raise ValueError("TrainStep(virtual_ranks > 1): the criterion's negative sampler appeared after the engine was built; "
+                             "call reseed() with one seed per virtual rank")
+        terms = self._partition_terms()
+        first = [m for m in terms if not m.z_ready()]
+        fused = ops.FUSED_CRITERION
+        self._share_tables, self._tables_of = True, None
+        losses = []
+        try:
+            if first:
+                self._partition_pass(shards, first)
+                # every rank of a real job runs its first step through the unfused criterion ops (Z is not frozen when it
+                # enters the criterion): so does every shard here — the same launches, the same bits
+                ops.FUSED_CRITERION = False
+            bank.defer_updates()
+            for r, shard in enumerate(shards):
+                last = r == R - 1
+                self._grad_target = self._acc if r == 0 else None
+                with plan.engine(self):
+                    out, mult = self._shard_forward(r, shard)
+                    # DDP broadcasts rank 0's buffers in front of every forward: what the step leaves is what shard 0's forward left
+                    if r == 0 and fb is not None:
+                        self._bn_keep.copy_(fb)
+                    if last:
+                        if fb is not None:
+                            fb.copy_(self._bn_keep)
+                        if self._nbt:
+                            torch._foreach_sub_(self._nbt, R - 1)
+                    loss, _ = self.criterion(out[0], out[1], shard[2])
+                    loss.backward()
+                self.buckets.finish()
+                if mult is not None:
+                    self._rank_sampler[r][1] = int(mult.offset)
+                losses.append(loss.detach())
+                if r > 0:
+                    ops.grad_accum_flat(self.flat.grad if last else self._acc, self._acc, self.flat.grad)
+        except BaseException:
+            bank.flush_updates(apply=False)
+            raise
+        finally:
+            ops.FUSED_CRITERION = fused
+            self._grad_target = None
+            self._share_tables, self._tables_of = False, None
+        bank.flush_updates()             # ONE bank update with the R * b records in global order
+        self.rank_losses = torch.stack(losses)
+        return self.rank_losses.mean()
 
     def _forward_backward_plan(self, video, audio, index):
         """The step through the compiled launch programs (avid_hip/plan.py); None if the model is outside them."""
@@ -619,6 +795,8 @@ class TrainStep(AdamStep):
         return loss
 
     def forward_backward(self, video, audio, index):
+        if self.virtual_ranks > 1:
+            return self._virtual_forward_backward(video, audio, index)
         if self.broadcast_buffers == "step":
             self.sync_buffers()
         loss = self._forward_backward_plan(video, audio, index)
@@ -705,19 +883,27 @@ class TrainStep(AdamStep):
         if mult is not None:       # the negative sampler's stream position (not part of the reference's checkpoint:
             off = int(mult.offset_dev) if getattr(mult, "offset_dev", None) is not None else int(mult.offset)
             sd["avid_sampler"] = {"seed": int(mult.seed), "offset": off}   # torch's global RNG is not saved either)
+            if self.virtual_ranks > 1:               # every virtual rank's stream: its seed; all stand at one position
+                sd["avid_sampler"] = {"seed": self._rank_sampler[0][0], "offset": self._rank_sampler[0][1],
+                                      "seeds": [s for s, _ in self._rank_sampler]}
         return sd
 
     def load_state_dict(self, sd):
         super().load_state_dict(sd)
         mult = self._sampler()
         if mult is not None and "avid_sampler" in sd:
-            mult.reseed(sd["avid_sampler"]["seed"], sd["avid_sampler"]["offset"])
+            saved = sd["avid_sampler"]
+            if self.virtual_ranks > 1:               # (a one-rank checkpoint: the other ranks' seeds by the per-rank formula)
+                seeds = saved.get("seeds") or [int(saved["seed"]) + _RANK_SEED_STRIDE * r for r in range(self.virtual_ranks)]
+                self.reseed(seeds, saved["offset"])
+            else:
+                mult.reseed(saved["seed"], saved["offset"])
 
     def step(self, video, audio, index):
         self._step_plan = None
         loss = self.forward_backward(video, audio, index)
         pl = self._step_plan
-        if pl is not None and pl.adam_early and not self.buckets.comm and not lib.TIMING:
+        if pl is not None and pl.adam_early and not self.buckets.comm and not lib.TIMING and self.virtual_ranks == 1:
             self._optimizer_step_overlapped(pl)
         else:
             self.optimizer_step()
@@ -728,6 +914,9 @@ class TrainStep(AdamStep):
     def capture(self, video, audio, index):
         """Capture one full step into a hipGraph.  Call after >= 2 eager warm-up steps (Z fixed, workspaces
         sized).  Inputs are copied into static buffers on every ``replay``."""
+        if self.virtual_ranks > 1:
+            raise NotImplementedError("TrainStep.capture: a hipGraph of a virtual-rank step (virtual_ranks > 1) is not supported — "
+                                      "the shards' sampler streams and the deferred bank update are driven from the host")
         self._sv, self._sa, self._si = video.clone(), audio.clone(), index.clone()
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()

@@ -876,6 +876,7 @@ class TrainPrograms(Programs):
             b.wait(helper, ST_MAIN)
         self._zero_index = len(b.fwd)
         b.emit(OP_MEMSET0, stream=helper, n=(4 * b.gnumel,), t=((S_GRAD, 0),))
+        self._wt_index = len(b.fwd)
         self._wt_rec = b.emit(OP_WT_BATCH, stream=helper, i=(0,), n=(0,), t=((S_AUX, 0),))
         b.S = ST_MAIN
         return b
@@ -896,10 +897,14 @@ class TrainPrograms(Programs):
         self.fa_bytes, self.ba_bytes = max(b.fa.size, 256), max(b.ba.size, 256)
         self.params, self.goff, self.gnumel, self.grad_ready = b.params, b.goff, b.gnumel, b.grad_ready
         self.fwd_prog, self.bwd_prog = self._seal(b, b.fwd, b.bwd)
+        self._wt_op = int(self.fwd_prog[self._wt_index].op)      # (0: the model has no weight in a derived form)
 
-    def _forward_arena(self, grad_flat, zero_grad, inputs):
-        """A run of the forward program set up: weight table, arena, slots, streams, gradient fill on or off.  Returns the arena."""
+    def _forward_arena(self, grad_flat, zero_grad, inputs, tables=True):
+        """A run of the forward program set up: weight table, arena, slots, streams, gradient fill on or off.  Returns the arena.
+        ``tables=False``: the derived weight tables in the aux buffer (transposed, Winograd-transformed, pre-split) are those
+        of an earlier run of THIS program with the same weights — a later shard of a virtual-rank step — and are not rebuilt."""
         self._refresh_table()
+        self.fwd_prog[self._wt_index].op = self._wt_op if tables else 0
         fa = torch.empty(self.fa_bytes, dtype=torch.uint8, device=self.device)
         self._fill_slots(fa, None, grad_flat, inputs)
         self._streams()
@@ -1015,9 +1020,9 @@ class Plan(TrainPrograms):
             b.S = S0
         return b.video_fwd(model.video_model, video, after_stem=start_audio)
 
-    def forward(self, video, audio, grad_flat, zero_grad):
-        """Issue the forward program; returns (v_emb, a_emb, arena)."""
-        fa = self._forward_arena(grad_flat, zero_grad, (video, audio, None, None))
+    def forward(self, video, audio, grad_flat, zero_grad, tables=True):
+        """Issue the forward program; returns (v_emb, a_emb, arena).  ``tables``: see ``_forward_arena``."""
+        fa = self._forward_arena(grad_flat, zero_grad, (video, audio, None, None), tables)
         self._run(self.fwd_prog, 0, self.n_fwd)
         return self._view(fa, self.vemb), self._view(fa, self.aemb), fa
 
@@ -1054,7 +1059,7 @@ def _engine_flat(eng, pl):
         same = (len(flat.params) == len(pl.params) and all(a is b for a, b in zip(flat.params, pl.params))
                 and list(flat.offsets) == list(pl.goff))
         pl._engine_ok = ok = (flat, same)
-    return flat.grad if ok[1] else None
+    return eng.grad_target() if ok[1] else None
 
 
 def _remember(ctx, pl, fa, params):
@@ -1091,7 +1096,7 @@ class NetFn(torch.autograd.Function):
     def forward(ctx, video, audio, pl, *params):
         eng = _ENGINE
         gflat = _engine_flat(eng, pl) if eng is not None else None
-        ve, ae, fa = pl.forward(video, audio, gflat, zero_grad=gflat is not None)
+        ve, ae, fa = pl.forward(video, audio, gflat, zero_grad=gflat is not None, tables=eng is None or eng.rebuild_tables(pl))
         _remember(ctx, pl, fa, params)
         ctx.video, ctx.audio = video, audio
         ctx.in_engine = gflat is not None

@@ -126,9 +126,28 @@ class AVIDSimilarityMemoryBank(nn.Module):
             dist.broadcast(self.view2_mem, 0)
             dist.barrier()
 
+    # ---- the seam of a virtual-rank step (avid_hip.parallel.TrainStep(virtual_ranks=R)): R shards score against the banks as
+    # the step found them, then ONE update with all their records in rank order — what the all-gather gives every rank
+    _pending = None
+
+    def defer_updates(self):
+        """From here on ``update_memory`` only notes its records; ``flush_updates`` applies them."""
+        self._pending = []
+
+    def flush_updates(self, apply=True):
+        """One ``update_memory`` with every record noted since ``defer_updates``, in the order they came (``apply=False``:
+        they are dropped); updates are immediate again."""
+        pending, self._pending = self._pending, None
+        if apply and pending:
+            v, a, y = (torch.cat([rec[k] for rec in pending]) for k in range(3))
+            self.update_memory(v, a, y)
+
     def update_memory(self, video_emb, audio_emb, y):
         """avid.py:103-129: EMA + renormalise the rows of every sample of the GLOBAL batch, both banks.
         Duplicate ids: last occurrence (highest global position) wins — the reference is unordered."""
+        if self._pending is not None:
+            self._pending.append((video_emb, audio_emb, y))
+            return
         video_mom = float(self.momentum[0])
         audio_mom = float(self.momentum[1])
         v_all, a_all, y_all = gather_update_records(video_emb, audio_emb, y)

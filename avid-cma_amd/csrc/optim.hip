@@ -2,6 +2,7 @@
 // correction as in torch's single-tensor path) over ONE contiguous fp32 buffer holding every
 // parameter — replaces the 141 per-tensor optimizer launches of utils/main_utils.py:250-261.
 // Flat SGD with momentum (torch.optim.SGD semantics, utils/main_utils.py:242-248) over the same buffers: one state buffer.
+// Flat gradient accumulation (dst = a + b) over the same buffers: what sums the shards of a virtual-rank step.
 #include <math.h>
 
 #include "common.h"
@@ -109,6 +110,23 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, co
   }
 }
 
+// dst[i] = a[i] + b[i]: one fp32 rounding per element, every element written by exactly one thread from the two values at
+// its own index — the result does not depend on the launch geometry, and dst may BE a or b (no __restrict__: an element is
+// read before it is written, by the thread that writes it).  vec: the three pointers are 16-byte aligned (n4 = n / 4
+// vectors, then the tail); otherwise n4 = 0 and the scalar loop takes all n elements.
+__global__ __launch_bounds__(256) void grad_accum_flat_kernel(float* dst, const float* a, const float* b, long long n4,
+                                                              long long n) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = tid; i < n4; i += stride) {
+    const floatx4 av = reinterpret_cast<const floatx4*>(a)[i];
+    const floatx4 bv = reinterpret_cast<const floatx4*>(b)[i];
+    reinterpret_cast<floatx4*>(dst)[i] = av + bv;
+  }
+  // scalar elements: the tail (n % 4) behind the vectors, or everything when the buffers are not 16-byte aligned
+  for (long long i = n4 * 4 + tid; i < n; i += stride) dst[i] = a[i] + b[i];
+}
+
 }  // namespace avid
 
 using namespace avid;
@@ -150,4 +168,23 @@ extern "C" int avid_sgd_flat(int64_t n, float* p, const float* g, float* buf, fl
   hipLaunchKernelGGL(sgd_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, n4, (long long)n,
                      lr, momentum, weight_decay, nesterov, grad_scale, lr_dev);
   return check_launch("sgd_flat");
+}
+
+extern "C" int avid_grad_accum_flat(int64_t n, float* dst, const float* a, const float* b, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && dst && a && b, AVID_E_BADARG, "grad_accum_flat: bad argument");
+  // dst is exactly a, exactly b, or disjoint from both: a partly overlapping dst would be read after it was written
+  const uintptr_t d0 = (uintptr_t)dst, bytes = (uintptr_t)n * 4;
+  const uintptr_t src[2] = {(uintptr_t)a, (uintptr_t)b};
+  for (int k = 0; k < 2; ++k)
+    AVID_REQUIRE(src[k] == d0 || src[k] + bytes <= d0 || d0 + bytes <= src[k], AVID_E_BADARG,
+                 "grad_accum_flat: dst overlaps an input without being that input");
+  const bool vec = ((d0 | src[0] | src[1]) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  const long long work = vec ? (n4 > 0 ? n4 : 1) : (long long)n;
+  long long grid = ceil_div(work, 256);
+  if (grid > 4096) grid = 4096;
+  ScopedTimer t((hipStream_t)stream, "grad_accum_flat_kernel", 0.0, 12.0 * n);
+  hipLaunchKernelGGL(grad_accum_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dst, a, b, n4,
+                     (long long)n);
+  return check_launch("grad_accum_flat");
 }

@@ -601,6 +601,12 @@ int avid_adam_flat(int64_t n, float* p, const float* g, float* m, float* v, floa
  * momentum == 0 (it is not touched then); nesterov needs momentum.  lr_dev as above.  Buffers 16-byte aligned. */
 int avid_sgd_flat(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
                   int nesterov, const float* lr_dev, float grad_scale, avid_stream_t stream);
+/* dst[i] = a[i] + b[i] in fp32 over one flat buffer of n elements: what accumulates the gradients of the shards of a
+ * virtual-rank step (parallel.TrainStep(virtual_ranks=R)) in rank order.  One rounding per element, no atomics, the same
+ * bits whatever the launch geometry; inf / nan propagate as IEEE addition has them.  dst may be exactly a or exactly b
+ * (in place); any other overlap of dst with an input, n <= 0 or a null pointer is AVID_E_BADARG.  16-byte vectors where
+ * all three pointers are 16-byte aligned, a scalar path otherwise: any 4-byte aligned addresses are taken. */
+int avid_grad_accum_flat(int64_t n, float* dst, const float* a, const float* b, avid_stream_t stream);
 
 /* Video clip front end: frames [B][T][H][W][3] uint8 (what the decoder / augmentation hands over)
  * -> out [B][3][T][H][W] fp32 = ((u / 255) - mean[c]) / std[c], the reference's ClipToTensor + Normalize
