@@ -1374,6 +1374,14 @@ class _BankScores(Function):
         idx = idx.contiguous()
         if idx.dtype != torch.int64 or not bank.is_contiguous():
             raise AvidHipError("bank_scores: idx must be int64 and the bank contiguous")
+        if emb.dim() != 2 or bank.dim() != 2 or idx.dim() != 2:
+            raise AvidHipError("bank_scores: emb [bs, D], bank [N, D] and idx [bs, R] must be 2-D")
+        if emb.dtype != torch.float32 or bank.dtype != torch.float32:
+            raise AvidHipError(f"bank_scores: emb and bank must be float32 (got {emb.dtype}, {bank.dtype})")
+        if bank.shape[1] != emb.shape[1]:
+            raise AvidHipError(f"bank_scores: embedding width {emb.shape[1]} != bank width {bank.shape[1]}")
+        if idx.shape[0] != emb.shape[0]:
+            raise AvidHipError(f"bank_scores: idx has {idx.shape[0]} rows, emb {emb.shape[0]}")
         bs, D = emb.shape
         R = idx.shape[1]
         s = torch.empty((bs, R), dtype=torch.float32, device=emb.device)
@@ -1521,8 +1529,23 @@ def alias_draw(n, K, prob, alias, uniform, seed, offset, y=None, per_row=1, devi
     return out
 
 
+def _check_bank_update(what, bank, y, emb):
+    """The kernels take the width from the bank and the row count from ``y``: everything else must agree with them."""
+    if bank.dim() != 2 or emb.dim() != 2 or y.dim() != 1:
+        raise AvidHipError(f"{what}: bank [N, D], emb [B, D] and y [B] expected")
+    if bank.dtype != torch.float32 or emb.dtype != torch.float32 or not bank.is_contiguous():
+        raise AvidHipError(f"{what}: bank and emb must be float32 and the bank contiguous (got {bank.dtype}, {emb.dtype})")
+    if y.dtype != torch.int64:
+        raise AvidHipError(f"{what}: y must be int64 (got {y.dtype})")
+    if emb.shape[1] != bank.shape[1]:
+        raise AvidHipError(f"{what}: embedding width {emb.shape[1]} != bank width {bank.shape[1]}")
+    if y.shape[0] != emb.shape[0]:
+        raise AvidHipError(f"{what}: y has {y.shape[0]} ids, emb {emb.shape[0]} rows")
+
+
 def bank_update(bank, y, emb, momentum):
     _need_cuda(bank, y, emb)
+    _check_bank_update("bank_update", bank, y, emb)
     lib.call("avid_bank_update", y.shape[0], bank.shape[1], bank.shape[0], _p(bank), _p(y.contiguous()),
              _p(emb.contiguous()), float(momentum), DeviceErrors.get(bank.device).ptr(), _stream())
 
@@ -1530,6 +1553,10 @@ def bank_update(bank, y, emb, momentum):
 def bank_update_pair(bank0, bank1, y, emb0, emb1, momentum0, momentum1):
     """``bank_update`` of both banks in one launch (criterions/avid.py:118-129), bit-identical to two calls."""
     _need_cuda(bank0, bank1, y, emb0, emb1)
+    if tuple(bank0.shape) != tuple(bank1.shape):
+        raise AvidHipError(f"bank_update_pair: the banks differ in shape ({tuple(bank0.shape)} and {tuple(bank1.shape)})")
+    _check_bank_update("bank_update_pair", bank0, y, emb0)
+    _check_bank_update("bank_update_pair", bank1, y, emb1)
     lib.call("avid_bank_update2", y.shape[0], bank0.shape[1], bank0.shape[0], _p(bank0), _p(bank1), _p(y.contiguous()),
              _p(emb0.contiguous()), _p(emb1.contiguous()), float(momentum0), float(momentum1),
              DeviceErrors.get(bank0.device).ptr(), _stream())

@@ -22,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _width_ref as W
 from _guards import FILLS, guarded
 from oracle import avid_oracle as O
 from oracle import detgen
@@ -371,6 +372,7 @@ def _l2norm(bs, D):
 
 case("crit:l2_normalize:7x128", backward=True)(_l2norm(7, 128))
 case("crit:l2_normalize:5x512", backward=True)(_l2norm(5, 512))
+case("crit:l2norm:D1000", backward=True)(_l2norm(5, 1000))       # 16 trips, the last one ragged (40 of 64 lanes)
 
 
 @case("crit:bank_scores+mean_exp", backward=True)
@@ -385,6 +387,24 @@ def _bank_scores(dev, P):
     z0, z1 = ops.mean_exp(s.detach() * 0.1), ops.mean_exp((s.detach() * 0.1)[:, 1:])
     s.backward(P(gen("uniform", "bs:g", (bs, R)).to(dev)))
     return {"s": s, "demb": ed.grad, "mean_exp": z0, "mean_exp_sliced": z1}
+
+
+def _bank_scores_width(D):
+    def fn(dev, P):
+        """test_bank_scores_widths at (3, 65): one row past a 64-row block; the snapshot [3, 65, D] is guarded at pitch D"""
+        from avid_hip import ops
+        bank, emb, idx, ds = W.score_inputs(D, 3, 65)
+        bank_d, idx_d = P(bank.to(dev)), P(idx.to(dev))
+        ed = P(emb.to(dev).requires_grad_(True))
+        s = ops.bank_scores(ed, bank_d, idx_d, W.INV_T)
+        s.backward(P(ds.to(dev)))
+        ops.check_device_errors(dev)
+        return {"s": s, "demb": ed.grad}
+    return fn
+
+
+case("crit:bank_scores:D64", backward=True)(_bank_scores_width(64))
+case("crit:bank_scores:D512", backward=True)(_bank_scores_width(512))
 
 
 def _nce(bs, Pn, K, joint=False):
@@ -433,6 +453,25 @@ def _bank_update(dev, P):
     ops.bank_update_pair(p1, p2, yd, emb, emb2, 0.5, 0.9)
     ops.check_device_errors(dev)
     return {"b1": b1, "b2": b2, "p1": p1, "p2": p2}
+
+
+def _bank_update_width(D):
+    def fn(dev, P):
+        """test_bank_update_widths at B = 5 (ragged against 4 samples per block, a triple duplicate): in place, single and pair"""
+        from avid_hip import ops
+        bank, emb0, emb1, y = W.update_inputs(D, 5)
+        e0, e1, yd = P(emb0.to(dev)), P(emb1.to(dev)), P(y.to(dev))
+        b0, b1, p0, p1 = (P(bank.to(dev)) for _ in range(4))
+        ops.bank_update(b0, yd, e0, 0.5)
+        ops.bank_update(b1, yd, e1, 0.9)
+        ops.bank_update_pair(p0, p1, yd, e0, e1, 0.5, 0.9)
+        ops.check_device_errors(dev)
+        return {"b0": b0, "b1": b1, "p0": p0, "p1": p1}
+    return fn
+
+
+case("crit:bank_update:D100")(_bank_update_width(100))
+case("crit:bank_update:D512")(_bank_update_width(512))
 
 
 def _fused_inputs(bs, K, N, P_=None):

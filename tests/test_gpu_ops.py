@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _fused_ref import cma_case, xmodal_case
 from oracle import avid_oracle as O
 from oracle import detgen
 
@@ -751,25 +752,8 @@ def test_xmodal_fused_vs_unfused_ops_and_fp64(bs, K, N, gpu_device):
     criterions/nce.py:38-58 with a frozen Z): losses 2e-6, gradients 2e-5 of their scale; normalised embeddings 1e-6;
     repeated calls bit-identical (fixed summation order, re-armed tickets); bank_update_pair == two bank_update."""
     from avid_hip import ops
-    gen = torch.Generator().manual_seed(bs * 1000 + K)
-    v1 = F.normalize(torch.randn(N, 128, generator=gen), dim=1)
-    v2 = F.normalize(torch.randn(N, 128, generator=gen), dim=1)
-    ve = torch.randn(bs, 128, generator=gen) * 2
-    ae = torch.randn(bs, 128, generator=gen) * 0.5
-    y = torch.randperm(N, generator=gen)[:bs]
-    idx = torch.randint(0, N - 1, (bs, K), generator=gen)
-    idx = idx + (idx >= y[:, None]).long()
-    Z, coeff, T_ = torch.tensor(0.83), 0.75, 0.07
-    # (b) float64
-    vr, ar = ve.double().requires_grad_(True), ae.double().requires_grad_(True)
-    vh, ah = F.normalize(vr, dim=1), F.normalize(ar, dim=1)
-    rows = torch.cat([y[:, None], idx], 1)
-    s_v2a = torch.bmm(v2.double()[rows], vh.unsqueeze(2)).squeeze(-1) / T_
-    s_a2v = torch.bmm(v1.double()[rows], ah.unsqueeze(2)).squeeze(-1) / T_
-    l1, _ = O.nce_loss(s_v2a[:, :1], s_v2a[:, 1:], Z.double())
-    l2, _ = O.nce_loss(s_a2v[:, :1], s_a2v[:, 1:], Z.double())
-    tot = (l1 / 2 + l2 / 2) * coeff
-    tot.backward()
+    c = xmodal_case(bs, K, N)                                        # (b) float64: tests/_fused_ref.py
+    v1, v2, ve, ae, y, idx, rows, Z, coeff, T_ = c.v1, c.v2, c.ve, c.ae, c.y, c.idx, c.rows, c.Z, c.coeff, c.T
     # (a) device
     b1, b2 = v1.to(gpu_device), v2.to(gpu_device)
     vd, ad = ve.to(gpu_device).requires_grad_(True), ae.to(gpu_device).requires_grad_(True)
@@ -779,9 +763,9 @@ def test_xmodal_fused_vs_unfused_ops_and_fp64(bs, K, N, gpu_device):
     total, losses, hats = outs[0]
     assert all(torch.equal(o[0], total) and torch.equal(o[1], losses) and torch.equal(o[2], hats) for o in outs[1:])
     (total * 2.0).backward()                                         # the upstream gradient scales the stored one
-    np.testing.assert_allclose(losses.cpu().numpy(), [float(l1), float(l2), float(l1 / 2 + l2 / 2), float(tot)], rtol=2e-6)
-    assert relerr(hats[0], vh.detach()) < 1e-6 and relerr(hats[1], ah.detach()) < 1e-6
-    assert relerr(vd.grad, 2.0 * vr.grad) < 2e-5 and relerr(ad.grad, 2.0 * ar.grad) < 2e-5
+    np.testing.assert_allclose(losses.cpu().numpy(), c.losses, rtol=2e-6)
+    assert relerr(hats[0], c.vh) < 1e-6 and relerr(hats[1], c.ah) < 1e-6
+    assert relerr(vd.grad, 2.0 * c.gv) < 2e-5 and relerr(ad.grad, 2.0 * c.ga) < 2e-5
     # unfused chain on the device
     vu, au = ve.to(gpu_device).requires_grad_(True), ae.to(gpu_device).requires_grad_(True)
     vhu, ahu = ops.l2_normalize(vu), ops.l2_normalize(au)
@@ -811,27 +795,8 @@ def test_cma_fused_vs_fp64_and_the_criterion_it_replaces(bs, P, K, Kw, N, gpu_de
     group means and the total 2e-6, gradients 2e-5 of their scale, normalised embeddings 1e-6, repeated calls
     bit-identical — and, through criterions.AVID_CMA, against the chain of unfused ops (AVID_FUSED_CRITERION=0)."""
     from avid_hip import ops
-    gen = torch.Generator().manual_seed(bs * 1000 + K + P)
-    v1 = F.normalize(torch.randn(N, 128, generator=gen), dim=1)
-    v2 = F.normalize(torch.randn(N, 128, generator=gen), dim=1)
-    ve = torch.randn(bs, 128, generator=gen) * 2
-    ae = torch.randn(bs, 128, generator=gen) * 0.5
-    y = torch.randperm(N, generator=gen)[:bs]
-    pos = torch.randint(0, N, (bs, P), generator=gen)
-    idx = torch.randint(0, N, (bs, K), generator=gen)
-    Z, cI, cP, T_ = torch.tensor(0.83), 0.4, 0.6, 0.07
-    vr, ar = ve.double().requires_grad_(True), ae.double().requires_grad_(True)
-    vh, ah = F.normalize(vr, dim=1), F.normalize(ar, dim=1)
-    rows = torch.cat([y[:, None], pos, idx], 1)
-    sc = lambda bank, e: torch.bmm(bank.double()[rows], e.unsqueeze(2)).squeeze(-1) / T_
-    s_v2a, s_a2v, s_v2v, s_a2a = sc(v2, vh), sc(v1, ah), sc(v1, vh), sc(v2, ah)
-    neg = slice(1 + P, None)
-    wneg = slice(1 + P, 1 + P + Kw)
-    l = [O.nce_loss(s_v2a[:, :1], s_v2a[:, neg], Z.double())[0], O.nce_loss(s_a2v[:, :1], s_a2v[:, neg], Z.double())[0],
-         O.nce_loss(s_v2v[:, 1:1 + P], s_v2v[:, wneg], Z.double())[0], O.nce_loss(s_a2a[:, 1:1 + P], s_a2a[:, wneg], Z.double())[0]]
-    gi, gp = l[0] / 2 + l[1] / 2, l[2] / 2 + l[3] / 2
-    tot = gi * cI + gp * cP
-    tot.backward()
+    c = cma_case(bs, P, K, Kw, N)                                    # float64: tests/_fused_ref.py
+    v1, v2, ve, ae, y, pos, idx, Z, cI, cP, T_ = c.v1, c.v2, c.ve, c.ae, c.y, c.pos, c.idx, c.Z, c.cI, c.cP, c.T
     b1, b2 = v1.to(gpu_device), v2.to(gpu_device)
     vd, ad = ve.to(gpu_device).requires_grad_(True), ae.to(gpu_device).requires_grad_(True)
     ws = ops.cma_fused_workspace(gpu_device, bs, P, K)
@@ -840,9 +805,9 @@ def test_cma_fused_vs_fp64_and_the_criterion_it_replaces(bs, P, K, Kw, N, gpu_de
     total, losses, hats = outs[0]
     assert all(torch.equal(o[0], total) and torch.equal(o[1][:7], losses[:7]) and torch.equal(o[2], hats) for o in outs[1:])
     (total * 2.0).backward()
-    np.testing.assert_allclose(losses[:7].cpu().numpy(), [float(v) for v in l] + [float(gi), float(gp), float(tot)], rtol=2e-6)
-    assert relerr(hats[0], vh.detach()) < 1e-6 and relerr(hats[1], ah.detach()) < 1e-6
-    assert relerr(vd.grad, 2.0 * vr.grad) < 2e-5 and relerr(ad.grad, 2.0 * ar.grad) < 2e-5
+    np.testing.assert_allclose(losses[:7].cpu().numpy(), c.losses, rtol=2e-6)
+    assert relerr(hats[0], c.vh) < 1e-6 and relerr(hats[1], c.ah) < 1e-6
+    assert relerr(vd.grad, 2.0 * c.gv) < 2e-5 and relerr(ad.grad, 2.0 * c.ga) < 2e-5
     ops.check_device_errors(gpu_device)
 
 
