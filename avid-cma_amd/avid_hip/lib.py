@@ -81,6 +81,12 @@ class PcmDesc(C.Structure):
     _fields_ = [("samples", C.c_void_p), ("channels", C.c_int32), ("n", C.c_int32), ("gain", C.c_float)]
 
 
+class StepGuard(C.Structure):
+    """Mirror of ``avid_step_guard`` (include/avid_hip.h): the 32-byte device record of the step guard."""
+    _fields_ = [("grad_norm", C.c_float), ("clip_coef", C.c_float), ("skip", C.c_int32), ("reserved", C.c_int32),
+                ("skipped_total", C.c_int64), ("steps_total", C.c_int64)]
+
+
 class Ref(C.Structure):
     """Mirror of ``avid_ref``: (slot, byte offset); slot < 0 = NULL."""
     _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("off", C.c_int64)]
@@ -234,6 +240,13 @@ SIGNATURES = {
     "avid_adam_flat": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp]),
     "avid_sgd_flat": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp]),
     "avid_grad_accum_flat": (_i, [_i64, _vp, _vp, _vp, _vp]),
+    "avid_grad_guard_workspace_bytes": (_sz, [_i64]),
+    "avid_grad_guard": (_i, [_i64, _vp, _f, _f, _i, _vp, _vp, _sz, _vp]),
+    "avid_guard_nonfinite": (_i, [_i64, _vp, _vp, _vp]),
+    "avid_adam_flat_guarded": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp, _vp]),
+    "avid_sgd_flat_guarded": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp, _vp]),
+    "avid_counter_add_unless": (_i, [_vp, _u64, _vp, _vp]),
+    "avid_guard_restore": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "avid_probe_spin": (_i, [_i, _vp]),
     "avid_stream_wait": (_i, [_vp, _vp]),
     "avid_clock_probe": (_i, [_i, _vp, _vp]),

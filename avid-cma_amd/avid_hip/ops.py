@@ -1688,6 +1688,80 @@ def grad_accum_flat(dst, a, b):
     lib.call("avid_grad_accum_flat", dst.numel(), _p(dst), _p(a), _p(b), _stream())
 
 
+class StepGuard:
+    """The device record of the step guard (``avid_step_guard``, include/avid_hip.h), zeroed, and its fields as 0-d device
+    tensors that are views of it — reading one (``float(...)``, ``int(...)``) is the caller's synchronisation:
+    ``grad_norm`` (the norm of the averaged gradient the last judged step had; inf / nan when not finite), ``clip_coef``
+    (the factor its optimizer applied), ``skipped`` (1: it was skipped), ``skipped_total``, ``steps_total``."""
+
+    def __init__(self, device):
+        self.record = torch.zeros(8, dtype=torch.int32, device=device)
+        f, q = self.record.view(torch.float32), self.record.view(torch.int64)
+        self.grad_norm, self.clip_coef = f[0], f[1]
+        self.skipped = self.record[2]
+        self.skipped_total, self.steps_total = q[2], q[3]
+
+
+def grad_guard(g, guard, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False):
+    """Judge the flat fp32 gradient ``g`` (any contiguous 1-d slice) into ``guard`` (a ``StepGuard``): ``avid_grad_guard``.
+    ``max_norm`` 0: no clipping."""
+    _need_cuda(g, guard.record)
+    if g.dtype != torch.float32 or g.dim() != 1 or not g.is_contiguous():
+        raise AvidHipError("grad_guard: one contiguous flat fp32 buffer")
+    need = int(lib.raw("avid_grad_guard_workspace_bytes")(g.numel()))
+    ws = workspace(g.device, need)
+    lib.call("avid_grad_guard", g.numel(), _p(g), float(grad_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
+             _p(guard.record), _p(ws), ws.numel(), _stream())
+
+
+def guard_nonfinite(x, guard):
+    """``guard`` becomes a skip if any element of the (small, contiguous fp32) buffer ``x`` is not finite: ``avid_guard_nonfinite``."""
+    _need_cuda(x, guard.record)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise AvidHipError("guard_nonfinite: one contiguous fp32 buffer")
+    if x.numel():
+        lib.call("avid_guard_nonfinite", x.numel(), _p(x), _p(guard.record), _stream())
+
+
+def adam_flat_guarded(p, g, m, v, lr, beta1, beta2, eps, wd, step, guard, grad_scale=1.0, step_dev=None, lr_dev=None,
+                      advance=True):
+    """``adam_flat`` under ``guard``: a skipped step writes nothing and leaves ``step_dev`` where it is; otherwise the
+    gradient is scaled by ``guard.clip_coef`` on the way in."""
+    _need_cuda(p, g, m, v, guard.record)
+    st = _stream()
+    if step_dev is not None and advance:
+        lib.call("avid_counter_add_unless", _p(step_dev), 1, _p(guard.record), st)
+    lib.call("avid_adam_flat_guarded", p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
+             float(eps), float(wd), int(step), _p(step_dev), _p(lr_dev), float(grad_scale), _p(guard.record), st)
+
+
+def sgd_flat_guarded(p, g, buf, lr, momentum, wd, guard, nesterov=False, grad_scale=1.0, lr_dev=None):
+    """``sgd_flat`` under ``guard`` (as ``adam_flat_guarded``)."""
+    _need_cuda(p, g, buf, guard.record)
+    lib.call("avid_sgd_flat_guarded", p.numel(), _p(p), _p(g), _p(buf), float(lr), float(momentum), float(wd),
+             int(bool(nesterov)), _p(lr_dev), float(grad_scale), _p(guard.record), _stream())
+
+
+def guard_restore(dst, idx, saved, guard):
+    """When ``guard`` says skip: ``dst[idx[r]] = saved[r]`` for every row of ``saved`` ([rows, D], ``dst`` [N, D]; ``idx`` int64
+    [rows] with every id a row of ``dst``), or ``dst.copy_(saved)`` with ``idx`` None (same shape); nothing otherwise."""
+    _need_cuda(dst, idx, saved, guard.record)
+    if dst.dtype != torch.float32 or saved.dtype != torch.float32 or not dst.is_contiguous() or not saved.is_contiguous():
+        raise AvidHipError("guard_restore: contiguous fp32 tensors")
+    if idx is None:
+        if dst.numel() != saved.numel():
+            raise AvidHipError("guard_restore: a flat restore needs dst and saved of one size")
+        rows, D = 1, saved.numel()
+    else:
+        if (idx.dtype != torch.int64 or not idx.is_contiguous() or saved.dim() != 2 or dst.dim() != 2
+                or idx.numel() != saved.shape[0] or saved.shape[1] != dst.shape[1]):
+            raise AvidHipError("guard_restore: dst [N, D], idx int64 [rows], saved [rows, D]")
+        rows, D = saved.shape
+    if rows * D == 0:
+        return
+    lib.call("avid_guard_restore", rows, D, _p(dst), _p(idx), _p(saved), _p(guard.record), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # fine-tuning head (classify.hip): dropout, softmax cross-entropy / clip-averaged confidence
 # ------------------------------------------------------------------------------------------------

@@ -27,6 +27,7 @@ kernel needs the GPU.  BatchNorm statistics stay per-rank — the reference has 
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 import torch
@@ -472,16 +473,39 @@ class AdamStep(EngineCore):
     ``optimizer="sgd"`` (with ``momentum``, ``nesterov``; ``betas`` / ``eps`` are ignored): torch.optim.SGD's update instead,
     the same one launch per slice (``ops.sgd_flat``).  Its only state is ``momentum_buffer``, laid out like the flat
     parameters (None without momentum); ``m`` / ``v`` / ``t_dev`` are None — the update needs no step count, a zero buffer
-    is torch's first step — and ``t`` just counts steps on the host.  ``state_dict`` is then torch.optim.SGD's."""
+    is torch's first step — and ``t`` just counts steps on the host.  ``state_dict`` is then torch.optim.SGD's.
+
+    The step guard, off by default (``guard`` is None and nothing below is launched).  ``max_grad_norm`` (> 0, finite):
+    ``torch.nn.utils.clip_grad_norm_``'s rule on the norm of the averaged flat gradient; ``skip_nonfinite=True``: a step whose
+    gradient is not finite leaves no trace.  Either one puts ``ops.grad_guard`` behind the backward pass — one fixed-order pass
+    over the flat gradient that fills a 32-byte device record, ``guard`` (``ops.StepGuard``: ``grad_norm``, ``clip_coef``,
+    ``skipped``, ``skipped_total``, ``steps_total`` as 0-d device tensors; reading one is the caller's synchronisation) — and
+    runs the optimizer in one piece through the guarded kernels, which read the record: nothing synchronises the host, a
+    captured graph replays it.  In one process ``skip_nonfinite`` also skips a step whose BatchNorm running statistics went
+    non-finite (``ops.guard_nonfinite``: a ReLU can keep a NaN channel out of the gradient).  A skipped step leaves the parameters, the optimizer state, ``t_dev``, the BatchNorm running
+    statistics, ``num_batches_tracked`` (and ``TrainStep``: both memory banks) exactly as it found them; what still advances
+    is the host's ``t`` (it counts ATTEMPTED steps: ``t - int(t_dev) == int(guard.skipped_total)`` for Adam; ``state_dict``
+    saves ``t_dev``), the negative sampler's position and the dropout offset — the next step draws fresh ones."""
 
     virtual_ranks = 1        # ranks whose gradients the buffer holds the SUM of, per process (TrainStep(virtual_ranks=R))
 
-    def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False, **core):
+    def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False,
+                 max_grad_norm=None, skip_nonfinite=False, **core):
         if optimizer not in ("adam", "sgd"):
             raise ValueError("optimizer must be 'adam' or 'sgd'")
         if optimizer == "sgd" and (momentum < 0 or (nesterov and momentum == 0)):
             raise ValueError("SGD: momentum must be >= 0, and Nesterov momentum requires a momentum")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (max_grad_norm > 0 and math.isfinite(max_grad_norm)):
+                raise ValueError(f"max_grad_norm must be a finite number > 0, or None for no clipping (got {max_grad_norm})")
         super().__init__(model, **core)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self.guard = None
+        self._fb_saved = self._guard_nbt = None
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            from . import ops
+            self.guard = ops.StepGuard(self.flat.flat.device)
         self.optimizer = optimizer
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.momentum, self.nesterov = float(momentum), bool(nesterov)
@@ -504,11 +528,59 @@ class AdamStep(EngineCore):
         if self.lr_dev is not None:
             self.lr_dev.fill_(self.lr)
 
+    def _grad_scale(self):
+        return 1.0 / (self.buckets.world * self.virtual_ranks)
+
+    def _guard_begin(self):
+        """In front of a guarded step's forward: the snapshot a skipped step is put back from (``skip_nonfinite``) — the flat
+        buffer of BatchNorm running statistics, one 78 KB copy."""
+        if not self.skip_nonfinite:
+            return
+        fb = self.flat_buffers.flat
+        if fb is not None:
+            if self._fb_saved is None or self._fb_saved.shape != fb.shape or self._fb_saved.device != fb.device:
+                self._fb_saved = torch.empty_like(fb)
+            self._fb_saved.copy_(fb)
+        if self._guard_nbt is None:
+            self._guard_nbt = [m.num_batches_tracked for m in self.model.modules()
+                               if getattr(m, "num_batches_tracked", None) is not None]
+
+    def _guard_judge(self, begin=0, end=None):
+        """Behind a guarded step's backward pass (all gradient collectives finished): judge elements [begin, end) of the flat
+        gradient into the record, then — ``skip_nonfinite`` — the launches that put the snapshot back if the record says skip
+        (``num_batches_tracked`` goes back by the record's skip word).  All on the device."""
+        from . import ops
+        ops.grad_guard(self.flat.grad[begin:end], self.guard, grad_scale=self._grad_scale(),
+                       max_norm=self.max_grad_norm or 0.0, skip_nonfinite=self.skip_nonfinite)
+        if not self.skip_nonfinite:
+            return
+        fb = self.flat_buffers.flat
+        if fb is not None:
+            # the running statistics are a second witness: a non-finite activation poisons them even where a ReLU (max(NaN, 0)
+            # = 0) keeps it out of the gradient — a frozen tower's heads (ProbeStep) never see it.  One process only: they are
+            # per-rank, and with gradient collectives every rank must reach the verdict of the all-reduced gradient.
+            if not self.buckets.comm:
+                ops.guard_nonfinite(fb, self.guard)
+            ops.guard_restore(fb, None, self._fb_saved, self.guard)
+        if self._guard_nbt:
+            torch._foreach_sub_(self._guard_nbt, [self.guard.skipped.to(torch.int64)] * len(self._guard_nbt))
+
     def _update(self, begin=0, end=None, advance=True):
         """One optimizer launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (Adam: step
-        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays.  SGD has no counter)."""
+        ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays.  SGD has no counter).
+        With the step guard on: the guarded kernels, which obey the record ``_guard_judge`` filled."""
         from . import ops
         s = slice(begin, end)
+        if self.guard is not None:
+            if self.optimizer == "sgd":
+                buf = self.momentum_buffer
+                ops.sgd_flat_guarded(self.flat.flat[s], self.flat.grad[s], None if buf is None else buf[s], self.lr, self.momentum,
+                                     self.wd, self.guard, self.nesterov, grad_scale=self._grad_scale(), lr_dev=self.lr_dev)
+                return
+            ops.adam_flat_guarded(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0],
+                                  self.betas[1], self.eps, self.wd, self.t, self.guard, grad_scale=self._grad_scale(),
+                                  step_dev=self.t_dev, lr_dev=self.lr_dev, advance=advance)
+            return
         if self.optimizer == "sgd":
             buf = self.momentum_buffer
             ops.sgd_flat(self.flat.flat[s], self.flat.grad[s], None if buf is None else buf[s], self.lr, self.momentum, self.wd,
@@ -581,6 +653,8 @@ class AdamStep(EngineCore):
                                                                     for k, i, _ in self._param_order())))
 
     def state_dict(self):
+        """torch.optim.Adam's (SGD's) format.  Adam's ``step`` is the device counter ``t_dev``: the steps APPLIED — with the step
+        guard on it lags the host's ``t`` (attempted steps) by ``guard.skipped_total``."""
         if self.optimizer == "sgd":
             return self._sgd_state_dict()
         step = float(int(self.t_dev) if self.t_dev is not None else self.t)
@@ -617,8 +691,11 @@ class TrainStep(AdamStep):
 
     def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 virtual_ranks=1):
+                 virtual_ranks=1, max_grad_norm=None, skip_nonfinite=False):
         """``broadcast_buffers``: see ``EngineCore``.  ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``.
+        ``max_grad_norm`` / ``skip_nonfinite``: the step guard, see ``AdamStep``.  Here a skipped step also puts back the bank
+        rows it updated, the optimizer gives up its overlapped early slice (it would run before the norm is known), and the
+        step that freezes Z reads the skip word back (the one host synchronisation: a skipped first step estimates Z again).
         ``virtual_ranks`` = R > 1: ``step`` takes the GLOBAL batch [R * b, ...] and is the step of an R-rank job of per-rank
         batch b, run on this one GPU shard after shard (``_virtual_forward_backward``): per-shard BatchNorm statistics,
         per-rank negatives, the first step's Z the mean of the ranks', the gradient their mean, one bank update with all
@@ -635,6 +712,7 @@ class TrainStep(AdamStep):
                                  f"broadcast_buffers='step'; broadcast_buffers={broadcast_buffers!r} is not supported with "
                                  "virtual_ranks > 1")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.criterion = criterion
         self.graph = None
@@ -794,7 +872,43 @@ class TrainStep(AdamStep):
         self.buckets.finish()
         return loss
 
+    def _bank(self):
+        """The criterion's memory banks (``nce_average``) if they can note the rows an update writes, or None."""
+        bank = getattr(self.criterion, "nce_average", None)
+        return bank if hasattr(bank, "kept_rows") else None
+
+    def _guard_begin(self):
+        super()._guard_begin()
+        bank = self._bank()
+        if self.skip_nonfinite and bank is not None:      # (criterions/avid.py: update_memory notes the rows it writes)
+            bank.keep_rows, bank.kept_rows = True, None
+
+    def _guard_judge(self, begin=0, end=None):
+        from . import ops
+        super()._guard_judge(begin, end)
+        bank = self._bank()
+        if self.skip_nonfinite and bank is not None:
+            kept, bank.keep_rows, bank.kept_rows = bank.kept_rows, False, None
+            if kept is not None:
+                ops.guard_restore(bank.view1_mem, kept[0], kept[1], self.guard)
+                ops.guard_restore(bank.view2_mem, kept[0], kept[2], self.guard)
+
     def forward_backward(self, video, audio, index):
+        """Forward, criterion, backward, gradient collectives.  With the step guard on also its judgement (``guard`` is filled
+        when this returns, ``optimizer_step()`` obeys it) and, ``skip_nonfinite``, the restoring launches of a skipped step."""
+        if self.guard is None:
+            return self._forward_backward(video, audio, index)
+        unfrozen = [m for m in self._partition_terms() if not m.z_ready()] if self.skip_nonfinite else []
+        self._guard_begin()
+        loss = self._forward_backward(video, audio, index)
+        self._guard_judge()
+        if unfrozen and int(self.guard.skipped):     # the step that froze Z was skipped: the next one estimates it again
+            for m in unfrozen:
+                m.avg_exp_score.fill_(-1.0)
+                m._z_ready = False
+        return loss
+
+    def _forward_backward(self, video, audio, index):
         if self.virtual_ranks > 1:
             return self._virtual_forward_backward(video, audio, index)
         if self.broadcast_buffers == "step":
@@ -903,7 +1017,8 @@ class TrainStep(AdamStep):
         self._step_plan = None
         loss = self.forward_backward(video, audio, index)
         pl = self._step_plan
-        if pl is not None and pl.adam_early and not self.buckets.comm and not lib.TIMING and self.virtual_ranks == 1:
+        if (pl is not None and pl.adam_early and not self.buckets.comm and not lib.TIMING and self.virtual_ranks == 1
+                and self.guard is None):
             self._optimizer_step_overlapped(pl)
         else:
             self.optimizer_step()
@@ -1380,11 +1495,14 @@ class FinetuneStep(AdamStep):
     ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``AdamStep``'s, shared with ``TrainStep``."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
-                 bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False):
+                 bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
+                 max_grad_norm=None, skip_nonfinite=False):
         """``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
         0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never.
-        ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``."""
+        ``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard; it judges the slice
+        the optimizer updates): see ``AdamStep``."""
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
@@ -1405,6 +1523,8 @@ class FinetuneStep(AdamStep):
         if self.broadcast_buffers == "step":
             self.sync_buffers()
         pl = self._plan(video)
+        if self.guard is not None:
+            self._guard_begin()
         drop = self.model.dropout if pl.drop_index is not None else None
         seed, offset = (drop.seed, drop.next_offset()) if drop is not None else (0, 0)
         out = torch.empty(8, dtype=torch.float32, device=video.device)          # plan.OUT_BYTES
@@ -1421,7 +1541,10 @@ class FinetuneStep(AdamStep):
             if self.buckets.comm:
                 self.buckets.finish()
         self.t += 1
-        self._update(0, self.n_cls if self.classifier_only else self.flat.numel)
+        end = self.n_cls if self.classifier_only else self.flat.numel
+        if self.guard is not None:
+            self._guard_judge(0, end)
+        self._update(0, end)
         self._poll_errors()
         return out[0], out[2:6].view(torch.int64)
 
@@ -1460,12 +1583,12 @@ class ProbeStep(AdamStep):
     the frozen tower parameters listed without state."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
-                 nesterov=False):
-        """``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``."""
+                 nesterov=False, max_grad_norm=None, skip_nonfinite=False):
+        """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``."""
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
-                         broadcast_buffers="off")
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
 
     def _plan(self, video):
@@ -1482,11 +1605,15 @@ class ProbeStep(AdamStep):
         video, labels = self._labelled(video, labels)
         B = video.shape[0]
         pl = self._plan(video)
+        if self.guard is not None:
+            self._guard_begin()
         out = torch.empty((self.n_taps, 8), dtype=torch.float32, device=video.device)     # plan.PROBE_OUT_BYTES per tap
         dlogits = torch.empty((self.n_taps, B, pl.n_classes), dtype=torch.float32, device=video.device)
         _, fa = pl.forward(video, self.flat.grad, True, labels=labels, out=out, dlogits=dlogits)
         self._plan_backward(pl, fa, (video, None, dlogits, None))
         self.t += 1
+        if self.guard is not None:
+            self._guard_judge()
         self._update()
         self._poll_errors()
         return out[:, 0], out[:, 2:6].view(torch.int64)

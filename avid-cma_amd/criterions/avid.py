@@ -142,6 +142,12 @@ class AVIDSimilarityMemoryBank(nn.Module):
             v, a, y = (torch.cat([rec[k] for rec in pending]) for k in range(3))
             self.update_memory(v, a, y)
 
+    # ---- the seam of the step guard (avid_hip.parallel: ``skip_nonfinite``): with ``keep_rows`` on, an update first notes the
+    # rows it is about to write — (ids, view1 rows, view2 rows), ids clamped into the bank as the update kernel stays inside it —
+    # so that a step found non-finite afterwards can put them back (``ops.guard_restore``)
+    keep_rows = False
+    kept_rows = None
+
     def update_memory(self, video_emb, audio_emb, y):
         """avid.py:103-129: EMA + renormalise the rows of every sample of the GLOBAL batch, both banks.
         Duplicate ids: last occurrence (highest global position) wins — the reference is unordered."""
@@ -151,6 +157,10 @@ class AVIDSimilarityMemoryBank(nn.Module):
         video_mom = float(self.momentum[0])
         audio_mom = float(self.momentum[1])
         v_all, a_all, y_all = gather_update_records(video_emb, audio_emb, y)
+        if self.keep_rows:
+            with torch.no_grad():
+                ids = y_all.clamp(0, self.view1_mem.shape[0] - 1)
+                self.kept_rows = (ids, self.view1_mem.index_select(0, ids), self.view2_mem.index_select(0, ids))
         with torch.no_grad():
             if self.view1_mem.is_cuda and self.view1_mem.shape[1] <= 512:
                 ops.bank_update_pair(self.view1_mem, self.view2_mem, y_all, v_all, a_all, video_mom, audio_mom)

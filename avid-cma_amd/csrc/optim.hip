@@ -3,6 +3,8 @@
 // parameter — replaces the 141 per-tensor optimizer launches of utils/main_utils.py:250-261.
 // Flat SGD with momentum (torch.optim.SGD semantics, utils/main_utils.py:242-248) over the same buffers: one state buffer.
 // Flat gradient accumulation (dst = a + b) over the same buffers: what sums the shards of a virtual-rank step.
+// The step guard (avid_grad_guard): one deterministic pass over the flat gradient -> norm, clip coefficient, skip word in a
+// device record; guarded forms of the two optimizers and of the counter that obey it, and the row restore of a skipped step.
 #include <math.h>
 
 #include "common.h"
@@ -127,6 +129,246 @@ __global__ __launch_bounds__(256) void grad_accum_flat_kernel(float* dst, const 
   for (long long i = n4 * 4 + tid; i < n; i += stride) dst[i] = a[i] + b[i];
 }
 
+// ---- the step guard ---------------------------------------------------------------------------------------------------
+// Sum of squares of g[0, n) in a FIXED order, whatever the scheduling: grid-stride 16-byte vectors into four double
+// accumulators per thread (the product of two floats is exact in double), the up to three scalar elements in front of the
+// first 16-byte boundary and the up to three behind the last vector added by threads of block 0, (a0 + a1) + (a2 + a3), the
+// xor butterfly over the wave, the four waves left to right: one double per block.  No atomics.
+constexpr int GUARD_THREADS = 256;
+constexpr int GUARD_MAX_BLOCKS = 1024;
+
+__device__ __forceinline__ double guard_block_sum(double s, double* lds) {
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+__global__ __launch_bounds__(GUARD_THREADS) void grad_sumsq_kernel(const float* __restrict__ g, long long n, int head,
+                                                                   long long n4, double* __restrict__ partials) {
+  __shared__ double lds[GUARD_THREADS / 64];
+  const floatx4* body = reinterpret_cast<const floatx4*>(g + head);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const floatx4 v = body[i];
+    a0 += (double)v[0] * (double)v[0];
+    a1 += (double)v[1] * (double)v[1];
+    a2 += (double)v[2] * (double)v[2];
+    a3 += (double)v[3] * (double)v[3];
+  }
+  if (blockIdx.x == 0) {   // scalar head (threads 0 .. head-1) and tail (the threads behind them)
+    const int tail = (int)(n - head - n4 * 4), t = threadIdx.x;
+    if (t < head) {
+      a0 += (double)g[t] * (double)g[t];
+    } else if (t < head + tail) {
+      const float x = g[head + n4 * 4 + (t - head)];
+      a0 += (double)x * (double)x;
+    }
+  }
+  const double s = guard_block_sum((a0 + a1) + (a2 + a3), lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// One block: thread t sums partials t, t + 256, ... in that order, then the same block sum; thread 0 judges and writes the
+// record (plain stores).  The sum is judged as the float it would have been: a double sum above FLT_MAX is an overflow.
+__global__ __launch_bounds__(GUARD_THREADS) void grad_guard_finish_kernel(const double* __restrict__ partials, int nparts,
+                                                                          float grad_scale, float max_norm, int skip_nonfinite,
+                                                                          avid_step_guard* __restrict__ guard) {
+  __shared__ double lds[GUARD_THREADS / 64];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += GUARD_THREADS) a += partials[i];
+  const double sum = guard_block_sum(a, lds);
+  if (threadIdx.x != 0) return;
+  const float sum_f = (float)sum;
+  const bool finite = sum_f - sum_f == 0.f;
+  const float norm = (float)(sqrt(finite ? sum : (double)sum_f) * (double)grad_scale);
+  float coef = 1.f;
+  if (max_norm > 0.f) {   // torch.nn.utils.clip_grad_norm_: min(1, max_norm / (total_norm + 1e-6)), rounded once
+    const double c = (double)max_norm / ((double)norm + (double)1e-6f);
+    if (c < 1.0) coef = (float)c;
+  }
+  const int skip = (skip_nonfinite && !finite) ? 1 : 0;
+  guard->grad_norm = norm;
+  guard->clip_coef = skip ? 1.f : coef;
+  guard->skip = skip;
+  guard->reserved = 0;
+  guard->skipped_total += skip;
+  guard->steps_total += 1;
+}
+
+// adam_flat_kernel under a guard record: nothing is written when guard->skip; the gradient term is (g * grad_scale) *
+// clip_coef, the two products rounded one after the other — and, with clip_coef == 1.0f, what adam_flat_kernel computes, so
+// that an unclipped step has its bits.  adam_flat_kernel's `g * grad_scale + wd * p` is compiled (vector loop and tail) as
+// fma(g, grad_scale, round(wd * p)); left to the compiler the same expression came out here as fma(wd, p, round(g *
+// grad_scale)) — both are contractions it may choose — so the form is spelled out (tests/test_gpu_guard.py holds the two
+// kernels together bit for bit).
+template <bool CLIP>
+__device__ __forceinline__ float adam_grad_term(float g, float p, float grad_scale, float wd, float coef) {
+  if (!CLIP) {
+    const float t = wd * p;
+    return __builtin_fmaf(g, grad_scale, t);
+  }
+  float t;
+  {
+#pragma clang fp contract(off)
+    t = g * grad_scale;
+    t = t * coef;
+  }
+  return t + wd * p;
+}
+
+template <bool CLIP>
+__device__ __forceinline__ void adam_guarded_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, long long n4, long long n, float b1, float b2,
+                                                  float eps, float wd, float step_size, float inv_sqrt_bc2, float grad_scale,
+                                                  float coef) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
+    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
+    floatx4 mv = reinterpret_cast<floatx4*>(m)[i];
+    floatx4 vv = reinterpret_cast<floatx4*>(v)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gg = adam_grad_term<CLIP>(gv[j], pv[j], grad_scale, wd, coef);
+      mv[j] = b1 * mv[j] + (1.f - b1) * gg;
+      vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
+      const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
+      pv[j] -= step_size * (mv[j] / denom);
+    }
+    reinterpret_cast<floatx4*>(p)[i] = pv;
+    reinterpret_cast<floatx4*>(m)[i] = mv;
+    reinterpret_cast<floatx4*>(v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    const float gg = adam_grad_term<CLIP>(g[i], p[i], grad_scale, wd, coef);
+    m[i] = b1 * m[i] + (1.f - b1) * gg;
+    v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
+    p[i] -= step_size * (m[i] / (sqrtf(v[i]) * inv_sqrt_bc2 + eps));
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_flat_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v, long long n4,
+                                                                long long n, float b1, float b2, float eps, float wd,
+                                                                float step_size, double inv_bc1, float inv_sqrt_bc2,
+                                                                float grad_scale, float lr,
+                                                                const long long* __restrict__ step_dev,
+                                                                const float* __restrict__ lr_dev,
+                                                                const avid_step_guard* __restrict__ guard) {
+  if (guard->skip) return;
+  const float coef = guard->clip_coef;
+  if (lr_dev) {   // as adam_flat_kernel
+    lr = *lr_dev;
+    step_size = (float)((double)lr * inv_bc1);
+  }
+  if (step_dev) {
+    const double t = (double)*step_dev;
+    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
+  }
+  if (coef == 1.f)
+    adam_guarded_span<false>(p, g, m, v, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef);
+  else
+    adam_guarded_span<true>(p, g, m, v, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef);
+}
+
+// sgd_flat_kernel under a guard record: sgd_element's arithmetic, operation for operation, on d = (g * grad_scale) * clip_coef —
+// each product rounded on its own; times 1.0f is exact, so an unclipped step has sgd_flat_kernel's bits.  (Its own copy
+// of the element: the momentum value travels by reference, so nothing of it lives in a private segment.)
+__device__ __forceinline__ void sgd_element_clipped(float& p, float g, float& b, bool has_buf, float lr, float momentum, float wd,
+                                                    bool nesterov, float grad_scale, float coef) {
+#pragma clang fp contract(off)
+  float d = g * grad_scale;
+  d = d * coef;
+  if (wd != 0.f) {
+    const float t = wd * p;
+    d = d + t;
+  }
+  if (has_buf) {
+    const float t = momentum * b;
+    b = t + d;
+    if (nesterov) {
+      const float u = momentum * b;
+      d = d + u;
+    } else {
+      d = b;
+    }
+  }
+  const float s = lr * d;
+  p = p - s;
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ buf, long long n4, long long n, float lr,
+                                                               float momentum, float wd, int nesterov, float grad_scale,
+                                                               const float* __restrict__ lr_dev,
+                                                               const avid_step_guard* __restrict__ guard) {
+  if (guard->skip) return;
+  const float coef = guard->clip_coef;
+  if (lr_dev) lr = *lr_dev;
+  const bool has_buf = buf != nullptr;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
+    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
+    floatx4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (has_buf) bv = reinterpret_cast<floatx4*>(buf)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], bj = bv[j];
+      sgd_element_clipped(pj, gv[j], bj, has_buf, lr, momentum, wd, nesterov != 0, grad_scale, coef);
+      pv[j] = pj;
+      bv[j] = bj;
+    }
+    reinterpret_cast<floatx4*>(p)[i] = pv;
+    if (has_buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    float pi = p[i], bi = has_buf ? buf[i] : 0.f;
+    sgd_element_clipped(pi, g[i], bi, has_buf, lr, momentum, wd, nesterov != 0, grad_scale, coef);
+    p[i] = pi;
+    if (has_buf) buf[i] = bi;
+  }
+}
+
+// One block over a SMALL buffer (the 78 KB of BatchNorm running statistics): any element that is not finite turns the record
+// into a skip — clip_coef 1.0f, skipped_total advanced unless the gradient's verdict was a skip already.
+__global__ __launch_bounds__(256) void guard_nonfinite_kernel(const float* __restrict__ x, long long n,
+                                                              avid_step_guard* __restrict__ guard) {
+  int bad = 0;
+  for (long long i = threadIdx.x; i < n; i += blockDim.x) {
+    const float v = x[i];
+    bad |= (v - v == 0.f) ? 0 : 1;
+  }
+  const int any = __syncthreads_or(bad);
+  if (threadIdx.x == 0 && any && !guard->skip) {
+    guard->skip = 1;
+    guard->clip_coef = 1.f;
+    guard->skipped_total += 1;
+  }
+}
+
+__global__ void counter_add_unless_kernel(unsigned long long* ctr, unsigned long long inc, const avid_step_guard* guard) {
+  if (!guard->skip) *ctr += inc;
+}
+
+// dst[idx[r]][0, D) = saved[r][0, D) for every row when guard->skip (idx == nullptr: row r itself); nothing otherwise.
+// Duplicate ids carry identical saved rows: the writes race on equal values.
+__global__ __launch_bounds__(256) void guard_restore_kernel(long long rows, long long D, float* __restrict__ dst,
+                                                            const long long* __restrict__ idx, const float* __restrict__ saved,
+                                                            const avid_step_guard* __restrict__ guard) {
+  if (!guard->skip) return;
+  const long long total = rows * D, stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const long long r = i / D, c = i - r * D;
+    dst[(idx ? idx[r] : r) * D + c] = saved[i];
+  }
+}
+
 }  // namespace avid
 
 using namespace avid;
@@ -187,4 +429,102 @@ extern "C" int avid_grad_accum_flat(int64_t n, float* dst, const float* a, const
   hipLaunchKernelGGL(grad_accum_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, dst, a, b, n4,
                      (long long)n);
   return check_launch("grad_accum_flat");
+}
+
+// ---- the step guard
+static long long guard_blocks(int64_t n) {
+  long long b = ceil_div(n, GUARD_THREADS * 4);
+  return b < 1 ? 1 : (b > GUARD_MAX_BLOCKS ? GUARD_MAX_BLOCKS : b);
+}
+
+extern "C" size_t avid_grad_guard_workspace_bytes(int64_t n) { return n > 0 ? (size_t)guard_blocks(n) * sizeof(double) : 0; }
+
+extern "C" int avid_grad_guard(int64_t n, const float* g, float grad_scale, float max_norm, int skip_nonfinite,
+                               avid_step_guard* guard_dev, void* ws, size_t ws_bytes, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && g && guard_dev && ws, AVID_E_BADARG, "grad_guard: bad argument");
+  AVID_REQUIRE(ws_bytes >= avid_grad_guard_workspace_bytes(n), AVID_E_BADARG, "grad_guard: workspace too small");
+  AVID_REQUIRE(((uintptr_t)g & 3) == 0 && (((uintptr_t)guard_dev | (uintptr_t)ws) & 7) == 0, AVID_E_BADARG,
+               "grad_guard: the gradient must be 4-byte, the record and the workspace 8-byte aligned");
+  long long head = (long long)(((16 - ((uintptr_t)g & 15)) & 15) / 4);   // scalar elements in front of the first 16-byte boundary
+  if (head > n) head = n;
+  const long long n4 = (n - head) / 4;
+  const int blocks = (int)guard_blocks(n);
+  {
+    ScopedTimer t((hipStream_t)stream, "grad_sumsq_kernel", 2.0 * n, 4.0 * n);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)blocks), dim3(GUARD_THREADS), 0, (hipStream_t)stream, g, (long long)n,
+                       (int)head, n4, (double*)ws);
+  }
+  int rc = check_launch("grad_guard");
+  if (rc != AVID_OK) return rc;
+  ScopedTimer t((hipStream_t)stream, "grad_guard_finish_kernel", 0.0, 8.0 * blocks);
+  hipLaunchKernelGGL(grad_guard_finish_kernel, dim3(1), dim3(GUARD_THREADS), 0, (hipStream_t)stream, (const double*)ws, blocks,
+                     grad_scale, max_norm, skip_nonfinite, guard_dev);
+  return check_launch("grad_guard");
+}
+
+extern "C" int avid_guard_nonfinite(int64_t n, const float* x, avid_step_guard* guard, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && x && guard, AVID_E_BADARG, "guard_nonfinite: bad argument");
+  AVID_REQUIRE(((uintptr_t)x & 3) == 0 && ((uintptr_t)guard & 7) == 0, AVID_E_BADARG, "guard_nonfinite: misaligned pointer");
+  ScopedTimer t((hipStream_t)stream, "guard_nonfinite_kernel", 0.0, 4.0 * n);
+  hipLaunchKernelGGL(guard_nonfinite_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, (long long)n, guard);
+  return check_launch("guard_nonfinite");
+}
+
+extern "C" int avid_adam_flat_guarded(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
+                                      float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
+                                      const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                                      avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g && m && v && guard && (step >= 1 || step_dev), AVID_E_BADARG, "adam_flat_guarded: bad argument");
+  if (step < 1) step = 1;
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
+               "adam_flat_guarded: buffers must be 16-byte aligned");
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float step_size = (float)((double)lr / bc1);
+  const double inv_bc1 = 1.0 / bc1;
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const long long n4 = n / 4;
+  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  ScopedTimer t((hipStream_t)stream, "adam_flat_guarded_kernel", 0.0, 28.0 * n);
+  hipLaunchKernelGGL(adam_flat_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4,
+                     (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
+                     (const long long*)step_dev, lr_dev, guard);
+  return check_launch("adam_flat_guarded");
+}
+
+extern "C" int avid_sgd_flat_guarded(int64_t n, float* p, const float* g, float* buf, float lr, float momentum,
+                                     float weight_decay, int nesterov, const float* lr_dev, float grad_scale,
+                                     const avid_step_guard* guard, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g && guard, AVID_E_BADARG, "sgd_flat_guarded: bad argument");
+  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat_guarded: momentum needs its buffer");
+  if (momentum == 0.f) buf = nullptr;
+  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat_guarded: nesterov needs momentum");
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
+               "sgd_flat_guarded: buffers must be 16-byte aligned");
+  const long long n4 = n / 4;
+  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  ScopedTimer t((hipStream_t)stream, "sgd_flat_guarded_kernel", 0.0, (buf ? 20.0 : 12.0) * n);
+  hipLaunchKernelGGL(sgd_flat_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, n4,
+                     (long long)n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev, guard);
+  return check_launch("sgd_flat_guarded");
+}
+
+extern "C" int avid_counter_add_unless(uint64_t* counter, uint64_t inc, const avid_step_guard* guard, avid_stream_t stream) {
+  AVID_REQUIRE(counter && guard, AVID_E_BADARG, "counter_add_unless: null pointer");
+  hipLaunchKernelGGL(counter_add_unless_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long*)counter,
+                     (unsigned long long)inc, guard);
+  return check_launch("counter_add_unless");
+}
+
+extern "C" int avid_guard_restore(int64_t rows, int64_t D, float* dst, const int64_t* idx, const float* saved,
+                                  const avid_step_guard* guard, avid_stream_t stream) {
+  AVID_REQUIRE(rows > 0 && D > 0 && dst && saved && guard, AVID_E_BADARG, "guard_restore: bad argument");
+  long long grid = ceil_div(rows * D, 256);
+  if (grid > 1024) grid = 1024;
+  ScopedTimer t((hipStream_t)stream, "guard_restore_kernel", 0.0, 0.0);
+  hipLaunchKernelGGL(guard_restore_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (long long)rows,
+                     (long long)D, dst, (const long long*)idx, saved, guard);
+  return check_launch("guard_restore");
 }

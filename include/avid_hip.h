@@ -608,6 +608,58 @@ int avid_sgd_flat(int64_t n, float* p, const float* g, float* buf, float lr, flo
  * all three pointers are 16-byte aligned, a scalar path otherwise: any 4-byte aligned addresses are taken. */
 int avid_grad_accum_flat(int64_t n, float* dst, const float* a, const float* b, avid_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Step guard: skip a non-finite step, clip the gradient norm — decided on the device, obeyed by the
+ * launches behind it without a host synchronisation (avid_hip/parallel.py: AdamStep(max_grad_norm=,
+ * skip_nonfinite=)).  One 32-byte record in device memory per engine; zero it once.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct avid_step_guard {
+    float   grad_norm;      /* grad_scale * sqrt(sum g^2): the norm of the AVERAGED gradient; inf / nan when not finite */
+    float   clip_coef;      /* factor the optimizer applies; exactly 1.0f when nothing is clipped */
+    int32_t skip;           /* 1: this step must leave no trace */
+    int32_t reserved;
+    int64_t skipped_total;  /* steps skipped since the record was zeroed */
+    int64_t steps_total;    /* steps the record has judged */
+} avid_step_guard;
+
+/* Judge the flat gradient g[0, n): sum of squares in a fixed order (no floating-point atomics: the same bits run to run,
+ * whatever the block scheduling), accumulated in double — the product of two floats is exact there, subnormal gradients
+ * count — then the record is filled:
+ *   grad_norm = (float)(sqrt(sum) * grad_scale)
+ *   clip_coef = max_norm > 0 ? min(1, max_norm / (grad_norm + 1e-6f)) : 1.0f   (torch.nn.utils.clip_grad_norm_'s rule,
+ *               evaluated in double from the stored grad_norm and rounded once)
+ *   skip      = skip_nonfinite && !isfinite((float)sum);  on a skip clip_coef = 1.0f
+ *   skipped_total += skip;  steps_total += 1
+ * The sum is judged as a float: one that exceeds FLT_MAX from finite gradients (a single 3e19) counts as non-finite and
+ * grad_norm is inf — torch's fp32 norm is inf there too.  With skip_nonfinite == 0 a non-finite gradient gives skip == 0
+ * and an inf / nan grad_norm.  16-byte vector loads between a scalar head and tail: any 4-byte aligned g.  ws: device
+ * scratch of avid_grad_guard_workspace_bytes(n) bytes, 8-byte aligned (so guard_dev).  n <= 0, a null pointer or a short
+ * workspace is AVID_E_BADARG, before anything is launched. */
+size_t avid_grad_guard_workspace_bytes(int64_t n);
+int avid_grad_guard(int64_t n, const float* g, float grad_scale, float max_norm, int skip_nonfinite,
+                    avid_step_guard* guard_dev, void* ws, size_t ws_bytes, avid_stream_t stream);
+/* A second witness for the same record, behind avid_grad_guard: if any of x[0, n) is not finite, the record becomes a skip
+ * (skip = 1, clip_coef = 1.0f, skipped_total advanced unless it was a skip already); a finite x changes nothing.  One block:
+ * meant for a small buffer — the BatchNorm running statistics, which a non-finite activation poisons even where a ReLU
+ * (max(NaN, 0) = 0) keeps it out of the gradient.  n <= 0 or a null pointer: AVID_E_BADARG. */
+int avid_guard_nonfinite(int64_t n, const float* x, avid_step_guard* guard, avid_stream_t stream);
+/* avid_adam_flat / avid_sgd_flat under a record: with guard->skip nothing is written (p, m, v, buf untouched); otherwise
+ * the gradient term is (g * grad_scale) * guard->clip_coef, the two products rounded to fp32 one after the other, in that
+ * order.  With clip_coef == 1.0f the results are the unguarded kernels', bit for bit. */
+int avid_adam_flat_guarded(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
+                           const float* lr_dev, float grad_scale, const avid_step_guard* guard, avid_stream_t stream);
+int avid_sgd_flat_guarded(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
+                          int nesterov, const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                          avid_stream_t stream);
+/* avid_counter_add unless guard->skip: Adam's device step counter stands still on a skipped step. */
+int avid_counter_add_unless(uint64_t* counter, uint64_t inc, const avid_step_guard* guard, avid_stream_t stream);
+/* When guard->skip: dst[idx[r]][0, D) = saved[r][0, D) for r in [0, rows) (idx == NULL: row r itself, a flat copy);
+ * nothing is written otherwise.  Every idx[r] must be a row of dst (the kernel does not know its height); duplicates
+ * must carry the same saved row, as rows saved before one update do. */
+int avid_guard_restore(int64_t rows, int64_t D, float* dst, const int64_t* idx, const float* saved,
+                       const avid_step_guard* guard, avid_stream_t stream);
+
 /* Video clip front end: frames [B][T][H][W][3] uint8 (what the decoder / augmentation hands over)
  * -> out [B][3][T][H][W] fp32 = ((u / 255) - mean[c]) / std[c], the reference's ClipToTensor + Normalize
  * (utils/videotransforms/volume_transforms.py:14-66, tensor_transforms.py:13-37; datasets/preprocessing.py:45-48)
