@@ -410,7 +410,7 @@ class EngineCore:
 
     def grad_target(self):
         """The flat buffer the launch programs zero and write this pass's gradients into: ``flat.grad``, unless a virtual-rank
-        step has pointed shard 0 at its accumulator (``TrainStep._virtual_forward_backward``)."""
+        step has pointed shard 0 at its accumulator (``AdamStep._virtual_pass``, ``TrainStep._virtual_forward_backward``)."""
         return self.flat.grad if self._grad_target is None else self._grad_target
 
     def rebuild_tables(self, pl):
@@ -444,6 +444,23 @@ class EngineCore:
         if self.flat.flat.is_cuda:
             from . import ops
             ops.poll_device_errors(self.flat.flat.device)
+
+
+def _virtual_ranks_arg(who, virtual_ranks, broadcast_buffers="step"):
+    """An engine's ``virtual_ranks`` argument as R >= 1, or the ValueError that names it: R > 1 emulates the ranks (replicas) of a
+    job inside one process and keeps rank 0's BatchNorm running statistics.  Raised before anything is broadcast or flattened."""
+    R = int(virtual_ranks)
+    if R < 1:
+        raise ValueError(f"{who}: virtual_ranks must be >= 1 (got {virtual_ranks})")
+    if R > 1:
+        if _dist_on():
+            raise ValueError(f"{who}(virtual_ranks={R}) emulates the ranks of a job inside ONE process: a process group of "
+                             "more than one rank (or AVID_FORCE_DIST=1) is not supported with virtual_ranks > 1")
+        if broadcast_buffers != "step":
+            raise ValueError(f"{who}(virtual_ranks={R}) keeps rank 0's BatchNorm running statistics, which is "
+                             f"broadcast_buffers='step'; broadcast_buffers={broadcast_buffers!r} is not supported with "
+                             "virtual_ranks > 1")
+    return R
 
 
 def _sgd_param_group(lr, momentum, weight_decay, nesterov):
@@ -487,7 +504,7 @@ class AdamStep(EngineCore):
     is the host's ``t`` (it counts ATTEMPTED steps: ``t - int(t_dev) == int(guard.skipped_total)`` for Adam; ``state_dict``
     saves ``t_dev``), the negative sampler's position and the dropout offset — the next step draws fresh ones."""
 
-    virtual_ranks = 1        # ranks whose gradients the buffer holds the SUM of, per process (TrainStep(virtual_ranks=R))
+    virtual_ranks = 1        # ranks whose gradients the buffer holds the SUM of, per process (the step engines' virtual_ranks=R)
 
     def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False,
                  max_grad_norm=None, skip_nonfinite=False, **core):
@@ -503,6 +520,8 @@ class AdamStep(EngineCore):
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self.guard = None
         self._fb_saved = self._guard_nbt = None
+        self._acc = self._bn_keep = self._nbt = None     # a virtual-rank step's accumulator and rank 0's statistics (_virtual_buffers)
+        self._bn_seen = None                             # ... and, skip_nonfinite, what witnesses the later shards' statistics
         if self.max_grad_norm is not None or self.skip_nonfinite:
             from . import ops
             self.guard = ops.StepGuard(self.flat.flat.device)
@@ -561,6 +580,8 @@ class AdamStep(EngineCore):
             # per-rank, and with gradient collectives every rank must reach the verdict of the all-reduced gradient.
             if not self.buckets.comm:
                 ops.guard_nonfinite(fb, self.guard)
+                if self._bn_seen is not None:        # (the later shards' statistics of a virtual-rank step: _virtual_pass)
+                    ops.guard_nonfinite(self._bn_seen, self.guard)
             ops.guard_restore(fb, None, self._fb_saved, self.guard)
         if self._guard_nbt:
             torch._foreach_sub_(self._guard_nbt, [self.guard.skipped.to(torch.int64)] * len(self._guard_nbt))
@@ -593,6 +614,73 @@ class AdamStep(EngineCore):
     def optimizer_step(self):
         self.t += 1
         self._update()
+
+    # ---- a virtual-rank step (``virtual_ranks`` = R > 1): the ranks of an R-rank job, shard after shard on this one GPU
+    def _virtual_buffers(self):
+        """What a virtual-rank step needs beside the engine's own buffers, made at the first one: the gradient accumulator
+        (the size of the flat gradient buffer), room for rank 0's BatchNorm running statistics, the ``num_batches_tracked``."""
+        if self._acc is None:
+            fb = self.flat_buffers.flat
+            self._acc = torch.empty_like(self.flat.grad)
+            self._bn_keep = torch.empty_like(fb) if fb is not None else None
+            self._nbt = [m.num_batches_tracked for m in self.model.modules() if getattr(m, "num_batches_tracked", None) is not None]
+
+    def _virtual_pass(self, shards, run_shard, end=None):
+        """Forward, loss and backward of every rank's shard, in rank order: ``run_shard(r, shard)`` runs them for rank r through
+        ONE launch program, writing the parameter gradients into ``grad_target()`` and asking ``rebuild_tables(pl)`` whether
+        its forward rebuilds the derived weight tables (the first shard's does, the weights do not change in between).
+        Shard 0 writes into the accumulator, every later shard into the flat gradient buffer, followed by one
+        ``ops.grad_accum_flat`` over elements [0, end): acc = acc + g, and for the last shard g = acc + g — the flat gradient
+        buffer ends up holding the SUM over ranks, ((g0 + g1) + g2) + ..., which the optimizer takes with 1 / R
+        (``_grad_scale``).  The BatchNorm running statistics the pass leaves are those shard 0's forward left (a replica other
+        than the first never keeps its own; DistributedDataParallel broadcasts rank 0's), ``num_batches_tracked`` has advanced
+        by one.  Two 78 KB copies, R - 1 accumulations; nothing synchronises the host."""
+        from . import ops
+        R = len(shards)
+        self._virtual_buffers()
+        fb = self.flat_buffers.flat
+        acc, grad = self._acc[:end], self.flat.grad[:end]
+        # skip_nonfinite: the running statistics are the step guard's second witness (``_guard_judge``), and those of a later
+        # shard are not kept — a NaN in its clips that a ReLU hides from the gradient would go unseen.  Their sum goes with them
+        # to the guard (one more 78 KB pass per later shard): it is not finite if any of them was not.
+        witness = self.skip_nonfinite and fb is not None
+        if witness and self._bn_seen is None:
+            self._bn_seen = torch.empty_like(fb)
+        self._share_tables, self._tables_of = True, None
+        try:
+            for r, shard in enumerate(shards):
+                self._grad_target = self._acc if r == 0 else None
+                run_shard(r, shard)
+                if r == 0 and fb is not None:
+                    self._bn_keep.copy_(fb)
+                if r > 0:
+                    ops.grad_accum_flat(grad if r == R - 1 else acc, acc, grad)
+                    if witness and r == 1:
+                        self._bn_seen.copy_(fb)
+                    elif witness:
+                        self._bn_seen.add_(fb)
+        finally:
+            self._grad_target = None
+            self._share_tables, self._tables_of = False, None
+        if fb is not None:
+            fb.copy_(self._bn_keep)
+        if self._nbt:
+            torch._foreach_sub_(self._nbt, R - 1)
+
+    def _virtual_shards(self, video, labels):
+        """The global batch [R * b, ...] of a supervised virtual-rank step as (b, [(video, labels) of rank r]): rank r holds
+        rows [r * b, (r + 1) * b) — DataParallel's scatter of a divisible batch, DistributedDataParallel's per-rank batch."""
+        R, B = self.virtual_ranks, video.shape[0]
+        if B % R or labels.shape[0] != B:
+            raise ValueError(f"{type(self).__name__}(virtual_ranks={R}).step: the global batch must be R * b samples in video and "
+                             f"labels alike; virtual_ranks={R} does not divide {B} (labels {labels.shape[0]})")
+        video, labels = self._labelled(video, labels)
+        b = B // R
+        clips = [video[r * b:(r + 1) * b] for r in range(R)]
+        # (a shard is a view of the global batch; one that does not start on a 16-byte boundary — an odd clip size — is copied:
+        #  the kernels read their input as the allocator hands tensors out)
+        clips = [c.clone() if c.data_ptr() % 16 else c for c in clips]
+        return b, [(c, labels[r * b:(r + 1) * b]) for r, c in enumerate(clips)]
 
     # ---- what the supervised steps (FinetuneStep, ProbeStep) share
     def _labelled(self, video, labels):
@@ -700,17 +788,7 @@ class TrainStep(AdamStep):
         batch b, run on this one GPU shard after shard (``_virtual_forward_backward``): per-shard BatchNorm statistics,
         per-rank negatives, the first step's Z the mean of the ranks', the gradient their mean, one bank update with all
         records in rank order, rank 0's running statistics.  One process only, ``broadcast_buffers="step"``, no ``capture()``."""
-        R = int(virtual_ranks)
-        if R < 1:
-            raise ValueError(f"TrainStep: virtual_ranks must be >= 1 (got {virtual_ranks})")
-        if R > 1:
-            if _dist_on():
-                raise ValueError(f"TrainStep(virtual_ranks={R}) emulates the ranks of a job inside ONE process: a process group of "
-                                 "more than one rank (or AVID_FORCE_DIST=1) is not supported with virtual_ranks > 1")
-            if broadcast_buffers != "step":
-                raise ValueError(f"TrainStep(virtual_ranks={R}) keeps rank 0's BatchNorm running statistics, which is "
-                                 f"broadcast_buffers='step'; broadcast_buffers={broadcast_buffers!r} is not supported with "
-                                 "virtual_ranks > 1")
+        R = _virtual_ranks_arg("TrainStep", virtual_ranks, broadcast_buffers)
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
@@ -718,7 +796,6 @@ class TrainStep(AdamStep):
         self.graph = None
         self.virtual_ranks = R
         self.rank_losses = None      # [R] device tensor: the loss each rank of the emulated job logged in the last step
-        self._acc = self._bn_keep = self._nbt = None
         self._rank_sampler = None    # per virtual rank: [seed, offset] of its negative-sampler stream
         mult = self._sampler()
         if R > 1 and mult is not None:                   # criterions/avid.py AVIDSimilarityMemoryBank.__init__'s per-rank formula
@@ -807,10 +884,7 @@ class TrainStep(AdamStep):
         video, audio, index = video.contiguous(), audio.contiguous(), index.contiguous()
         shards = [(video[r * b:(r + 1) * b], audio[r * b:(r + 1) * b], index[r * b:(r + 1) * b]) for r in range(R)]
         fb, bank = self.flat_buffers.flat, self.criterion.nce_average
-        if self._acc is None:
-            self._acc = torch.empty_like(self.flat.grad)
-            self._bn_keep = torch.empty_like(fb) if fb is not None else None
-            self._nbt = [m.num_batches_tracked for m in self.model.modules() if getattr(m, "num_batches_tracked", None) is not None]
+        self._virtual_buffers()
         if self._rank_sampler is None and self._sampler() is not None:
             raise ValueError("TrainStep(virtual_ranks > 1): the criterion's negative sampler appeared after the engine was built; "
                              "call reseed() with one seed per virtual rank")
@@ -1492,20 +1566,61 @@ class FinetuneStep(AdamStep):
     With more than one rank, gradients are averaged as DistributedDataParallel does: through ``GradBuckets`` (the full
     step), or one collective over the classifier's slice (``classifier_only``); Adam's ``grad_scale`` takes the 1 / world.
     Rank 0's BatchNorm running statistics are broadcast before every step (``broadcast_buffers="step"``, DDP's default).
-    ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``AdamStep``'s, shared with ``TrainStep``."""
+    ``set_lr`` and ``state_dict`` / ``load_state_dict`` (torch.optim.Adam's format) are ``AdamStep``'s, shared with ``TrainStep``.
+
+    ``virtual_ranks`` = R > 1: the step of an R-replica job — the shipped fine-tuning configs are eight-GPU ``nn.DataParallel``
+    jobs of batch 64 — on this one GPU.  ``step`` takes the GLOBAL batch [R * b, ...] and runs it shard after shard through one
+    ``ClsPlan`` of the shard geometry (``AdamStep._virtual_pass``): every BatchNorm normalises with its replica's b clips,
+    every replica draws its own dropout mask (``dropout_seeds``), the flat gradient buffer ends up holding the replicas' sum in
+    rank order, the optimizer takes it with 1 / R — the gradient of the cross-entropy over the gathered R * b logits, and the
+    all-reduced mean of an R-rank DistributedDataParallel job — the running statistics left are replica 0's.  ``rank_losses``
+    [R] / ``rank_hits`` [R, 2] hold every replica's own (None before the first such step).  One process,
+    ``broadcast_buffers="step"``, the compiled programs only; ``virtual_ranks`` is not part of a checkpoint."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1):
         """``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
         0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never.
         ``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard; it judges the slice
-        the optimizer updates): see ``AdamStep``."""
+        the optimizer updates — with ``virtual_ranks`` the accumulated gradient, a skipped step puts back the running
+        statistics from before shard 0's forward): see ``AdamStep``.  ``virtual_ranks``: see the class."""
+        R = _virtual_ranks_arg("FinetuneStep", virtual_ranks, broadcast_buffers)
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
+        self.virtual_ranks = R
+        self.rank_losses = self.rank_hits = None     # [R] float32 / [R, 2] int64 device tensors of the last virtual-rank step
+        self._dropout_seeds = None                   # reseed_dropout()'s, while the model's own seed is still the first of them
+
+    @property
+    def dropout_seeds(self):
+        """The seed of every (virtual) rank's dropout stream, or None for a model without dropout: rank 0's is the model's own
+        (``model.dropout.seed``), rank r's follows by the per-rank formula of the negative samplers unless ``reseed_dropout``
+        set it.  All ranks stand at one offset, ``model.dropout.offset``."""
+        drop = getattr(self.model, "dropout", None)
+        if not hasattr(drop, "seed"):
+            return None
+        base = int(drop.seed) & _U64
+        if self._dropout_seeds is not None and self._dropout_seeds[0] == base:
+            return list(self._dropout_seeds)
+        return [(base + _RANK_SEED_STRIDE * r) & _U64 for r in range(self.virtual_ranks)]
+
+    def reseed_dropout(self, seeds, offset=None):
+        """Set the seed of every (virtual) rank's dropout stream, and with ``offset`` the position all of them are at."""
+        seeds = [int(s) & _U64 for s in seeds]
+        if len(seeds) != self.virtual_ranks:
+            raise ValueError(f"FinetuneStep.reseed_dropout: {self.virtual_ranks} seed(s) expected, one per virtual rank "
+                             f"(got {len(seeds)})")
+        drop = getattr(self.model, "dropout", None)
+        if not hasattr(drop, "seed"):
+            raise ValueError("FinetuneStep.reseed_dropout: the model has no dropout")
+        drop.seed = seeds[0]
+        if offset is not None:
+            drop.offset = int(offset)
+        self._dropout_seeds = seeds
 
     def _plan(self, video):
         from . import plan
@@ -1517,7 +1632,10 @@ class FinetuneStep(AdamStep):
         return pl
 
     def step(self, video, labels):
-        """(loss [], hits [2] int64: top-1 / top-5 hits of the batch) as device tensors."""
+        """(loss [], hits [2] int64: top-1 / top-5 hits of the batch) as device tensors.  ``virtual_ranks`` > 1: the mean of the
+        ranks' losses and the sum of their hits, over the global batch [R * b, ...]."""
+        if self.virtual_ranks > 1:
+            return self._virtual_step(video, labels)
         video, labels = self._labelled(video, labels)
         B = video.shape[0]
         if self.broadcast_buffers == "step":
@@ -1548,9 +1666,38 @@ class FinetuneStep(AdamStep):
         self._poll_errors()
         return out[0], out[2:6].view(torch.int64)
 
+    def _virtual_step(self, video, labels):
+        """The step of ``virtual_ranks`` replicas (see the class): per shard the forward program with that replica's dropout
+        seed, ``avid_cls_loss`` over its b logits (mean over b) and the backward program; then ONE guard and optimizer pass over
+        the accumulated slice — all parameters, or the classifier's [:n_cls] (``classifier_only``: the tower's slice of the
+        gradient buffer and of the accumulator is neither written nor read)."""
+        b, shards = self._virtual_shards(video, labels)
+        pl = self._plan(shards[0][0])
+        if self.guard is not None:
+            self._guard_begin()                      # (the snapshot a skipped step is put back from: before shard 0's forward)
+        drop = self.model.dropout if pl.drop_index is not None else None
+        seeds, offset = (self.dropout_seeds, drop.next_offset()) if drop is not None else ([0] * len(shards), 0)
+        dev = video.device
+        out = torch.empty((len(shards), 8), dtype=torch.float32, device=dev)    # plan.OUT_BYTES per rank
+        dlogits = torch.empty((b, pl.n_classes), dtype=torch.float32, device=dev)
+
+        def run_shard(r, shard):
+            _, fa = pl.forward(shard[0], self.grad_target(), True, seeds[r], offset, labels=shard[1], out=out[r], dlogits=dlogits,
+                               tables=self.rebuild_tables(pl))
+            self._plan_backward(pl, fa, (shard[0], None, dlogits, None))
+        end = self.n_cls if self.classifier_only else self.flat.numel
+        self._virtual_pass(shards, run_shard, end)
+        self.t += 1
+        if self.guard is not None:
+            self._guard_judge(0, end)
+        self._update(0, end)
+        self._poll_errors()
+        self.rank_losses, self.rank_hits = out[:, 0], out[:, 2:6].view(torch.int64)
+        return self.rank_losses.mean(), self.rank_hits.sum(0)
+
     def _param_order(self):
         order = super()._param_order()
-        if self.classifier_only:            # the warm-up optimizer holds the classifier's parameters only
+        if self.classifier_only:           # the warm-up optimizer holds the classifier's parameters only
             cls = {id(p) for p in self.model.classifier.parameters()}
             order = [(k, i, p) for k, (_, i, p) in enumerate(o for o in order if id(o[2]) in cls)]
         return order
@@ -1580,16 +1727,27 @@ class ProbeStep(AdamStep):
     (its BatchNorm running statistics still move: the reference trains the probe with the tower in training mode).  Nothing
     synchronises the host.  Single process: the shipped config is not distributed.
     ``set_lr`` and ``state_dict`` / ``load_state_dict`` are ``AdamStep``'s — ``torch.optim.Adam(model.parameters())``'s format,
-    the frozen tower parameters listed without state."""
+    the frozen tower parameters listed without state.
+
+    ``virtual_ranks`` = R > 1: the step of an R-replica ``nn.DataParallel`` job (the shipped probe config: eight GPUs, batch
+    128) on this one GPU, as ``FinetuneStep``'s: ``step`` takes the global batch [R * b, ...], b in the programs' 2..256, and
+    runs it shard after shard through one ``ProbePlan`` of the shard geometry — the tower's BatchNorm3d AND the heads'
+    BatchNorm1d normalise with their replica's b rows — the classifiers' gradients are summed in rank order and applied with
+    1 / R, the running statistics left (tower and heads) are replica 0's.  ``rank_losses`` [R, n_taps] / ``rank_hits``
+    [R, n_taps, 2] hold every replica's own (None before the first such step)."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
-                 nesterov=False, max_grad_norm=None, skip_nonfinite=False):
-        """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``."""
+                 nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1):
+        """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``.
+        ``virtual_ranks``: see the class."""
+        R = _virtual_ranks_arg("ProbeStep", virtual_ranks)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
+        self.virtual_ranks = R
+        self.rank_losses = self.rank_hits = None     # [R, n_taps] float32 / [R, n_taps, 2] int64 of the last virtual-rank step
 
     def _plan(self, video):
         from . import plan
@@ -1601,7 +1759,10 @@ class ProbeStep(AdamStep):
         return pl
 
     def step(self, video, labels):
-        """(losses [n_taps], hits [n_taps, 2] int64: top-1 / top-5 hits of the batch per tap) as device tensors."""
+        """(losses [n_taps], hits [n_taps, 2] int64: top-1 / top-5 hits of the batch per tap) as device tensors.
+        ``virtual_ranks`` > 1: per tap the mean of the ranks' losses and the sum of their hits, over the global batch."""
+        if self.virtual_ranks > 1:
+            return self._virtual_step(video, labels)
         video, labels = self._labelled(video, labels)
         B = video.shape[0]
         pl = self._plan(video)
@@ -1617,6 +1778,34 @@ class ProbeStep(AdamStep):
         self._update()
         self._poll_errors()
         return out[:, 0], out[:, 2:6].view(torch.int64)
+
+    def _virtual_step(self, video, labels):
+        """The step of ``virtual_ranks`` replicas (see the class): per shard the forward program (tower, pools, heads, one
+        ``avid_cls_loss`` per tap over the shard's b rows) and the heads' backward; then ONE guard and optimizer pass."""
+        b, shards = self._virtual_shards(video, labels)
+        if not 2 <= b <= 256:
+            raise ValueError(f"ProbeStep(virtual_ranks={self.virtual_ranks}).step: the per-rank batch must be 2..256 clips "
+                             f"(BatchNorm1d on the rank's own rows; the probe programs' limit): a global batch of "
+                             f"{video.shape[0]} with virtual_ranks={self.virtual_ranks} leaves {b}")
+        pl = self._plan(shards[0][0])
+        if self.guard is not None:
+            self._guard_begin()
+        dev = video.device
+        out = torch.empty((len(shards), self.n_taps, 8), dtype=torch.float32, device=dev)   # plan.PROBE_OUT_BYTES per rank and tap
+        dlogits = torch.empty((self.n_taps, b, pl.n_classes), dtype=torch.float32, device=dev)
+
+        def run_shard(r, shard):
+            _, fa = pl.forward(shard[0], self.grad_target(), True, labels=shard[1], out=out[r], dlogits=dlogits,
+                               tables=self.rebuild_tables(pl))
+            self._plan_backward(pl, fa, (shard[0], None, dlogits, None))
+        self._virtual_pass(shards, run_shard)
+        self.t += 1
+        if self.guard is not None:
+            self._guard_judge()
+        self._update()
+        self._poll_errors()
+        self.rank_losses, self.rank_hits = out[:, :, 0], out[:, :, 2:6].view(torch.int64)
+        return self.rank_losses.mean(0), self.rank_hits.sum(0)
 
     def evaluate(self, video, labels, batch):
         """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] in eval mode, fed through the model ``batch`` clips at a

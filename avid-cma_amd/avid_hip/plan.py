@@ -1276,10 +1276,11 @@ class ClsPlan(TrainPrograms):
             b.video_stem_bwd(V, dh)
         self._close(b)
 
-    def forward(self, video, grad_flat, zero_grad, seed=0, offset=0, labels=None, out=None, dlogits=None, grad_scale=1.0):
+    def forward(self, video, grad_flat, zero_grad, seed=0, offset=0, labels=None, out=None, dlogits=None, grad_scale=1.0,
+                tables=True):
         """Issue the forward program — with ``labels`` also the loss record, which writes ``out`` (OUT_BYTES: loss, hits)
-        and ``dlogits``; returns (logits, arena)."""
-        fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out))
+        and ``dlogits``; returns (logits, arena).  ``tables``: see ``_forward_arena``."""
+        fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out), tables)
         if self.drop_index is not None:
             r = self.fwd_prog[self.drop_index]
             r.i[1], r.i[2], r.n[1] = _i32(seed), _i32(seed >> 32), int(offset)
@@ -1379,10 +1380,10 @@ class ProbePlan(TrainPrograms):
             b._ready(b.S, bn.weight, bn.bias)
         self._close(b)
 
-    def forward(self, video, grad_flat, zero_grad, labels=None, out=None, dlogits=None):
+    def forward(self, video, grad_flat, zero_grad, labels=None, out=None, dlogits=None, tables=True):
         """Issue the forward program — with ``labels`` also the loss records, which write ``out`` ([n_taps] x PROBE_OUT_BYTES:
-        loss, hits) and ``dlogits [n_taps, B, C]``; returns ([logits per tap], arena)."""
-        fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out))
+        loss, hits) and ``dlogits [n_taps, B, C]``; returns ([logits per tap], arena).  ``tables``: see ``_forward_arena``."""
+        fa = self._forward_arena(grad_flat, zero_grad, (video, labels, dlogits, out), tables)
         self._run(self.fwd_prog, 0, self.n_fwd if labels is not None else self.n_logits)
         return [self._view(fa, lg) for lg in self.logits], fa
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Fine-tuning throughput on one GPU (not bench.py: the flagship workload stays the pretraining step).  One JSON line:
 
-    python tools/finetune_bench.py [--steps 10] [--warmup 3]
+    python tools/finetune_bench.py [--steps 10] [--warmup 3] [--virtual-ranks R] [--batch-scale K]
 
 Per-GPU shapes are the shipped benchmark configs (configs/benchmark/{ucf,hmdb51}/*.yaml) split over 8 GPUs: 8 x 3x8x224^2
 (``8at16``, global batch 64) and 4 x 3x32x224^2 (``32at16``, global batch 32), R(2+1)D-18 + dropout 0.5 + Linear(512, 101).
@@ -12,7 +12,12 @@ For each shape, clips/s and ms/step of
       torch ``Dropout``, ``Linear``, ``cross_entropy`` and ``torch.optim.Adam``
   (d) ``FinetuneStep.evaluate`` at 10 clips per video
 plus ``mcycles_per_step`` (ms per step x the mean shader clock during the timed steps, bench.py's definition) and the
-kernels that served the 32-frame step (launch log of one timed step)."""
+kernels that served the 32-frame step (launch log of one timed step).
+
+``--virtual-ranks R`` (default 1): (a) and (b) run ``FinetuneStep(virtual_ranks=R)`` on the GLOBAL batch of R per-GPU batches —
+R = 8 is the shipped eight-replica job on one GPU; (c) and (d) take that batch whole.  ``--batch-scale K`` (default 1): every
+per-GPU batch times K (K = 8, R = 1: the shipped global batch as ONE whole-batch step, what the virtual step is compared with).
+With the defaults the output is what it was; otherwise it also says ``virtual_ranks`` and ``batch_scale``."""
 import argparse
 import json
 import os
@@ -62,7 +67,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--classes", type=int, default=101)
+    ap.add_argument("--virtual-ranks", type=int, default=1)
+    ap.add_argument("--batch-scale", type=int, default=1)
     args = ap.parse_args()
+    R, K = args.virtual_ranks, args.batch_scale
     import models
     from avid_hip import lib, parallel
     from bench import ClockSampler
@@ -70,6 +78,7 @@ def main():
     torch.cuda.set_device(dev)
     out = {"metric": "fine-tuning clips/s (R(2+1)D-18 + dropout + linear, 1 GPU)", "unit": "clips/s", "shapes": {}}
     for name, shape in (("8at16", (8, 3, 8, 224, 224)), ("32at16", (4, 3, 32, 224, 224))):
+        shape = (shape[0] * K * R,) + shape[1:]
         B = shape[0]
         g = torch.Generator().manual_seed(0)
         video = torch.randn(shape, generator=g).to(dev)
@@ -81,7 +90,7 @@ def main():
             return models.ClassificationWrapper(models.R2Plus1D(18), args.classes, "pool", 512, use_dropout=True,
                                                 dropout=0.5).to(dev).train()
         for tag, co in (("a_finetune_step", False), ("b_classifier_only", True)):
-            eng = parallel.FinetuneStep(wrapper(), classifier_only=co)
+            eng = parallel.FinetuneStep(wrapper(), classifier_only=co, **({"virtual_ranks": R} if R != 1 else {}))
             ms, ghz = _time(lambda: eng.step(video, labels), args.steps, args.warmup, ClockSampler, dev)
             res[tag] = {"ms_per_step": round(ms, 3), "clips_per_s": round(B / ms * 1e3, 2),
                         "mcycles_per_step": None if ghz is None else round(ms * ghz, 2)}
@@ -117,7 +126,9 @@ def main():
         res["a_over_c"] = round(res["c_per_layer_torch_head"]["ms_per_step"] / res["a_finetune_step"]["ms_per_step"], 3)
         del ref, opt
         torch.cuda.empty_cache()
-        out["shapes"][name] = {"per_gpu_batch": B, "clip": list(shape[1:]), **res}
+        out["shapes"][name] = {"per_gpu_batch": B // R, "clip": list(shape[1:]), **res}
+    if (R, K) != (1, 1):
+        out["virtual_ranks"], out["batch_scale"] = R, K
     print(json.dumps(out))
 
 

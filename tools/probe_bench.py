@@ -2,7 +2,7 @@
 """Linear-probe training throughput on one GPU at the shipped config (configs/benchmark/kinetics/8x224x224-linear.yaml:
 clips 3x8x224x224, 400 classes, four AdaptiveMaxPool3d heads with BatchNorm1d).  One JSON line:
 
-    python tools/probe_bench.py [--steps 6] [--warmup 2] [--rounds 3]
+    python tools/probe_bench.py [--steps 6] [--warmup 2] [--rounds 3] [--virtual-ranks R]
 
 The batch is the largest of 128 (the shipped one), 64, 32 that both paths run without exhausting memory (``batch``).
   ``probe_step``      clips/s of ``parallel.ProbeStep`` (the launch programs + flat Adam)
@@ -13,7 +13,11 @@ The batch is the largest of 128 (the shipped one), 64, 32 that both paths run wi
                       heads, the summed ``CrossEntropyLoss`` and ``torch.optim.Adam``
 The two paths alternate (``rounds`` times ``steps`` steps each, same process, same box); the rates are the medians over the
 rounds.  ``linear_128x9216x400_ms``: forward + backward of one head's Linear on ``avid_probe_linear_*``, on the fine-tuning
-classifier's ``avid_cls_linear_*`` and on torch's ``F.linear``."""
+classifier's ``avid_cls_linear_*`` and on torch's ``F.linear``.
+
+``--virtual-ranks R`` (default 1, the output is then what it was): ``probe_step`` is ``ProbeStep(virtual_ranks=R)`` on the same
+global batch — R = 8 at batch 128 is the shipped eight-replica job, 16 rows per BatchNorm1d; the baseline stays the whole-batch
+step.  The output then also says ``virtual_ranks``."""
 import argparse
 import json
 import os
@@ -108,7 +112,7 @@ def _run(B, args, dev):
     labels = torch.randint(0, ARGS["n_classes"], (B,), generator=g).to(dev)
     torch.manual_seed(0)
     model = models.MOSTModel(models.R2Plus1D(18), **ARGS).to(dev).train()
-    eng = parallel.ProbeStep(model, lr=1e-4)
+    eng = parallel.ProbeStep(model, lr=1e-4, **({"virtual_ranks": args.virtual_ranks} if args.virtual_ranks != 1 else {}))
     torch.manual_seed(0)
     base = _TorchProbe(models.R2Plus1D(18)).to(dev).train()
     opt = torch.optim.Adam(base.parameters(), lr=1e-4, weight_decay=0)
@@ -158,6 +162,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--batches", default="128,64,32")
+    ap.add_argument("--virtual-ranks", type=int, default=1)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -174,6 +179,8 @@ def main():
         raise SystemExit(f"no batch fits: {skipped}")
     out.update(res)
     out["batches_skipped"] = skipped
+    if args.virtual_ranks != 1:
+        out["virtual_ranks"] = args.virtual_ranks
     out["linear_128x9216x400_ms"] = _linear_compare(dev)
     print(json.dumps(out))
 
