@@ -3169,7 +3169,8 @@ static int plan_pk_order(const PkPlan& pk, long long M, int Cd, int nk, int cpt,
   // (an unsplit tail leaves its BatchNorm partial sums in the workgroups' rows: another order of the units would add them in
   //  another order — the model only re-orders K-split tails, whose sums come out of the reduce; outputs stay bit-identical)
   if (pk.f == 1) return 0;
-  struct Entry { long long M; int Cd, nk, cpt, presplit, grid, f, rot, cus, ws; };
+  // (the memo holds the decision alone, keyed by everything pk_order_bytes reads; the M-tile count handed back is this call's)
+  struct Entry { long long M; int Cd, nk, cpt, presplit, grid, f, rot, cus, tile, kps, paired; bool stationary; };
   static Entry cache[64];
   static std::atomic_flag lock = ATOMIC_FLAG_INIT;
   const unsigned h = (unsigned)((M * 2654435761ull + (unsigned)Cd * 40503u + (unsigned)nk * 97u + (unsigned)cpt * 7u + (presplit ? 1 : 0) +
@@ -3178,14 +3179,14 @@ static int plan_pk_order(const PkPlan& pk, long long M, int Cd, int nk, int cpt,
   Entry& e = cache[h];
   const int cus = device_cus();
   if (!(e.cus == cus && e.M == M && e.Cd == Cd && e.nk == nk && e.cpt == cpt && e.presplit == (presplit ? 1 : 0) && e.grid == pk.grid &&
-        e.f == pk.f && e.rot == pk.rot)) {
+        e.f == pk.f && e.rot == pk.rot && e.tile == pk.tile && e.kps == pk.kps && e.paired == (pk.paired ? 1 : 0))) {
     const double wb = presplit ? 6.0 : 4.0;
     const double tile_major = pk_order_bytes(pk, ntn, mtt, nk, cpt, wb, false), stationary = pk_order_bytes(pk, ntn, mtt, nk, cpt, wb, true);
-    e = Entry{M, Cd, nk, cpt, presplit ? 1 : 0, pk.grid, pk.f, pk.rot, cus, stationary * 1.2 < tile_major ? mtt : 0};
+    e = Entry{M, Cd, nk, cpt, presplit ? 1 : 0, pk.grid, pk.f, pk.rot, cus, pk.tile, pk.kps, pk.paired ? 1 : 0, stationary * 1.2 < tile_major};
   }
-  const int ws = e.ws;
+  const bool stationary = e.stationary;
   lock.clear(std::memory_order_release);
-  return ws;
+  return stationary ? mtt : 0;
 }
 
 // n / d == (n * magic) >> shift for every n < 2^31 (d >= 1)

@@ -71,22 +71,33 @@ def case(name, backward=False, ws=False, in_place=False):
 
 
 # ------------------------------------------------------------------------------------------------------------ convolutions
-def _conv(name, cin, cout, k, stride, pad, shp, tag="conv", wino2=False, bn_stats=False):
+def _conv(name, cin, cout, k, stride, pad, shp, tag="conv", wino2=False, bn_stats=False, budget=0):
+    """``budget``: the CUs the persistent kernels plan for while the case runs (ops.set_cu_budget; set before, restored in
+    ``finally``): the guarded runs size every workspace under that budget too, so a size function that plans for another
+    budget than the launch shows as a changed guard byte."""
     def fn(dev, P):
         from avid_hip import ops
         B, Ti, Hi, Wi = shp
         To, Ho, Wo = [(n + 2 * p - kk) // s + 1 for n, p, kk, s in zip((Ti, Hi, Wi), pad, k, stride)]
         x = cl(gen("normalish", f"{tag}:{name}:x", (B, cin, Ti, Hi, Wi)))
         gy = cl(gen("uniform", f"{tag}:{name}:gy", (B, cout, To, Ho, Wo)))
+        if budget:
+            full = torch.cuda.get_device_properties(dev).multi_processor_count
+            if budget >= full:
+                pytest.skip(f"a budget of {budget} CUs is no reduction on a device of {full}")
         if wino2:
             ops.wino2_configure(0)
         try:
+            if budget:
+                assert ops.set_cu_budget(budget) == budget
             xd = P(x.to(dev).requires_grad_(True))
             wd = P(weight(dev, f"{tag}:{name}:w.weight", cout, cin, *k).requires_grad_(True))
             out = ops.conv_cl(xd, wd, stride, pad, bn_stats=bn_stats)
             y, part = out if bn_stats else (out, None)
             y.backward(P(gy.to(dev)))
         finally:
+            if budget:
+                ops.set_cu_budget(0)
             if wino2:
                 ops.wino2_configure(-1)
         res = {"y": y, "dx": xd.grad, "dw": wd.grad}
@@ -115,6 +126,17 @@ def _register_convs():
         nm = "x".join(map(str, shp))
         case(f"conv:bn_stats:{nm}", backward=True)(
             _conv(f"bnstats{nm}", 64, 64, (1, 3, 3), (1, 1, 1), (0, 1, 1), shp, tag="cbp", bn_stats=True))
+    # under a reduced CU budget (tests/_budget_ref.py, inputs of tests/test_gpu_cu_budget.py): whole rounds + an unsplit tail,
+    # whole rounds + a K-split tail (slabs of the rows >= tail_row0 only), a weight-stationary tail, three column blocks (its
+    # input gradient weight-stationary), a Winograd grid of 8 CUs, and the K-split layer with the BatchNorm-statistics epilogue
+    import _budget_ref as R
+    rows = {R.row_id(r): r for r in R.ROWS}
+    for rid, ws, stats in (("s64@24", False, False), ("s64@16", ("forward", "backward"), False), ("s64_small@16", ("forward", "backward"), False),
+                           ("s64_192@16", ("backward",), False), ("wino256@8", ("forward", "backward"), False),
+                           ("s64@16", ("forward", "backward"), True)):
+        layer, budget = rows[rid][:2]
+        case(f"conv:budget:{rid}" + (":bn_stats" if stats else ""), backward=True, ws=ws)(
+            _conv(layer, *R.LAYERS[layer], tag="budget", bn_stats=stats, budget=budget))
 
 
 _register_convs()
@@ -887,7 +909,7 @@ def test_no_write_outside_and_no_read_of_unwritten_memory(name, gpu_device):
         pytest.fail(f"not run: the earlier case {_DEVICE_ERROR[0]} ended in a device error")
     try:
         _run_case(name, gpu_device)
-    except AssertionError:
+    except (AssertionError, pytest.skip.Exception):       # (a skip: a CU budget that is no reduction on this device)
         raise
     except BaseException:
         _DEVICE_ERROR.append(name)

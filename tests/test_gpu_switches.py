@@ -59,7 +59,10 @@ def test_arrangement_switches_are_bit_identical(default_run, env):
 
 @pytest.mark.parametrize("env", CLOSE, ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
 def test_kernel_switches_agree_to_summation_noise(default_run, env):
-    got = _probe(env)
+    _assert_close(_probe(env), default_run, env)
+
+
+def _assert_close(got, default_run, env):
     # same weights at step 1; later steps drift apart: Adam's first updates are +-lr whatever the gradient's size, so a
     # gradient that differs in the last bits near zero (or one flipped ReLU / max-pool tie) moves a weight the other way
     for a, b, tol in zip(got["losses"], default_run["losses"], (3e-6, 2e-3, 1e-2)):
@@ -93,6 +96,24 @@ def test_cu_budget_is_deterministic_and_reported(gpu_device):
         assert ops.set_cu_budget(10 * full) == full
     finally:
         assert ops.set_cu_budget(0) == full == torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def test_arrangement_switches_stay_bit_identical_at_a_64_cu_budget(default_run, gpu_device):
+    """Three bs-4 probes planning for 64 CUs (a quarter of the chip: whole rounds + K-split tails at this batch): alone, with
+    the per-layer path instead of the launch programs, and with every K-split tail dealt tile-major.  Bit-identical among the
+    three — launch programs == per-layer path and weight-stationary == tile-major order hold under a budget too — and the first
+    within the CLOSE rule for AVID_CU_RESERVE of the default run."""
+    import torch
+    full = torch.cuda.get_device_properties(0).multi_processor_count
+    if full <= 64:
+        pytest.skip(f"a budget of 64 CUs is no reduction on a device of {full}")
+    reserve = {"AVID_CU_RESERVE": str(full - 64)}
+    alone = _probe(reserve)
+    for extra in ({"AVID_PLAN": "0"}, {"AVID_PK_WS": "0"}):
+        got = _probe({**reserve, **extra})
+        assert got["losses"] == alone["losses"], extra
+        assert got["grad_sha"] == alone["grad_sha"], extra
+    _assert_close(alone, default_run, reserve)
 
 
 def test_batchnorm_applied_by_its_consumer_is_bit_identical_at_batch_64(gpu_device):
