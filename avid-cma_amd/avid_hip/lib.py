@@ -87,6 +87,17 @@ class StepGuard(C.Structure):
                 ("skipped_total", C.c_int64), ("steps_total", C.c_int64)]
 
 
+class CritDesc(C.Structure):
+    """Mirror of ``avid_crit_desc`` (include/avid_hip.h): one call of ``avid_crit_fused``."""
+    _fields_ = [(n, C.c_int32) for n in ("bs", "P", "K", "Kw", "D", "mask")] + [("N", C.c_int64)] + \
+        [(n, C.c_void_p) for n in ("v_emb", "a_emb", "y", "pos", "idx", "bank_v", "bank_a", "Z")] + \
+        [("inv_T", C.c_float), ("coeff", C.c_float * 4), ("reserved", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("v_hat", "a_hat", "losses", "dv", "da")]
+
+
+CRIT_X_INST, CRIT_W_INST, CRIT_X_POS, CRIT_W_POS = 1, 2, 4, 8     # AVID_CRIT_* (include/avid_hip.h)
+
+
 class Ref(C.Structure):
     """Mirror of ``avid_ref``: (slot, byte offset); slot < 0 = NULL."""
     _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("off", C.c_int64)]
@@ -230,6 +241,8 @@ SIGNATURES = {
     "avid_cma_fused_workspace_bytes": (_sz, [_i, _i, _i]),
     "avid_cma_fused": (_i, [_i, _i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _vp,
                             _vp, _vp, _sz, _vp, _vp]),
+    "avid_crit_fused_workspace_bytes": (_sz, [_i, _i, _i]),
+    "avid_crit_fused": (_i, [C.POINTER(CritDesc), _vp, _sz, _vp, _vp]),
     "avid_bank_update2": (_i, [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp]),
     "avid_cma_negatives": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_cma_topk_workspace_bytes": (_sz, [_i64, _i, _i]),

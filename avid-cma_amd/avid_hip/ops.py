@@ -1646,6 +1646,77 @@ def cma_fused(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, coeff_ins
     return _CMAFused.apply(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, coeff_inst, coeff_pos, ws)
 
 
+CRIT_X_INST, CRIT_W_INST, CRIT_X_POS, CRIT_W_POS = lib.CRIT_X_INST, lib.CRIT_W_INST, lib.CRIT_X_POS, lib.CRIT_W_POS
+# losses[16] of ``crit_fused``: the eight terms in group order, the four group means, the total
+CRIT_TERMS = ("inst-v2a", "inst-a2v", "inst-v2v", "inst-a2a", "pos-v2a", "pos-a2v", "pos-v2v", "pos-a2a")
+CRIT_GROUP_MEAN, CRIT_TOTAL = 8, 12
+
+
+class _CritFused(Function):
+    """Any term set of the AVID / AVID+CMA criterion of a steady-state step in one kernel (``avid_crit_fused``): returns
+    (total loss, losses[16], hats); as ``_CMAFused`` the gradient with respect to both raw embeddings is formed in the
+    forward pass and only scaled in backward.  ``pos`` is None (or [bs][0]) for a term set without positives."""
+
+    @staticmethod
+    def forward(ctx, v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, mask, coeffs, ws):
+        if pos is not None and pos.shape[1] == 0:
+            pos = None
+        _need_cuda(*[t for t in (v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, ws) if t is not None])
+        v_emb, a_emb, y, idx = v_emb.contiguous(), a_emb.contiguous(), y.contiguous(), idx.contiguous()
+        pos = None if pos is None else pos.contiguous()
+        mask, Kw, coeffs = int(mask), int(Kw), [float(c) for c in coeffs]
+        if v_emb.dim() != 2 or a_emb.shape != v_emb.shape or idx.dim() != 2 or y.shape[0] != v_emb.shape[0] \
+                or idx.shape[0] != v_emb.shape[0] or (pos is not None and (pos.dim() != 2 or pos.shape[0] != v_emb.shape[0])):
+            raise AvidHipError("crit_fused: v_emb / a_emb [bs][D], y [bs], pos [bs][P], idx [bs][K] disagree in shape")
+        bs, D = v_emb.shape
+        P, K = (0 if pos is None else pos.shape[1]), idx.shape[1]
+        if any(t.dtype != torch.int64 for t in (y, idx) + (() if pos is None else (pos,))) or not bank_v.is_contiguous() \
+                or not bank_a.is_contiguous():
+            raise AvidHipError("crit_fused: y / pos / idx must be int64 and the banks contiguous")
+        if any(t.dtype != torch.float32 for t in (v_emb, a_emb, bank_v, bank_a, Z)):
+            raise AvidHipError("crit_fused: embeddings, banks and Z must be float32")
+        if tuple(bank_v.shape) != tuple(bank_a.shape) or bank_v.dim() != 2 or bank_v.shape[1] != D:
+            raise AvidHipError(f"crit_fused: banks {tuple(bank_v.shape)} / {tuple(bank_a.shape)} do not fit embeddings of width {D}")
+        if not 1 <= mask <= 15:
+            raise AvidHipError(f"crit_fused: mask {mask} names no term")
+        if len(coeffs) != 4:
+            raise AvidHipError("crit_fused: four coefficients (X_INST, W_INST, X_POS, W_POS)")
+        if mask & (CRIT_X_POS | CRIT_W_POS) and P < 1:
+            raise AvidHipError("crit_fused: a positive-set term needs pos [bs][P >= 1]")
+        if not 1 <= Kw <= K:
+            raise AvidHipError(f"crit_fused: Kw={Kw} outside 1..K={K}")
+        dev = v_emb.device
+        hats = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
+        grads = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
+        losses = torch.empty(16, dtype=torch.float32, device=dev)
+        a = lambda t: None if t is None else t.data_ptr()       # noqa: E731  (structure fields take the address itself)
+        d = lib.CritDesc(bs=bs, P=P, K=K, Kw=Kw, D=D, mask=mask, N=bank_v.shape[0], v_emb=a(v_emb), a_emb=a(a_emb), y=a(y),
+                         pos=a(pos), idx=a(idx), bank_v=a(bank_v), bank_a=a(bank_a), Z=a(Z), inv_T=float(inv_T),
+                         coeff=(C.c_float * 4)(*coeffs), v_hat=a(hats[0]), a_hat=a(hats[1]), losses=a(losses),
+                         dv=a(grads[0]), da=a(grads[1]))
+        lib.call("avid_crit_fused", C.byref(d), _p(ws), ws.numel(), DeviceErrors.get(dev).ptr(), _stream())
+        ctx.save_for_backward(grads)
+        total = losses[CRIT_TOTAL]
+        ctx.mark_non_differentiable(losses, hats)
+        return total, losses, hats
+
+    @staticmethod
+    def backward(ctx, dtotal, _dl, _dh):
+        (grads,) = ctx.saved_tensors
+        g = grads * dtotal
+        return (g[0], g[1]) + (None,) * 11
+
+
+def crit_fused_workspace(device, bs, P, K):
+    """Zero-filled scratch of ``avid_crit_fused`` (its device ticket re-arms itself): one per criterion object."""
+    return torch.zeros(int(lib.raw("avid_crit_fused_workspace_bytes")(int(bs), int(P), int(K))), dtype=torch.uint8, device=device)
+
+
+def crit_fused(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, mask, coeffs, ws):
+    """``mask``: CRIT_X_INST | CRIT_W_INST | CRIT_X_POS | CRIT_W_POS; ``coeffs``: the four groups' coefficients in that order."""
+    return _CritFused.apply(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, mask, tuple(coeffs), ws)
+
+
 def cma_negatives(positive_set, y, rand_idx):
     _need_cuda(positive_set, y, rand_idx)
     bs, K = rand_idx.shape

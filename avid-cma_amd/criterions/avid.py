@@ -83,26 +83,35 @@ class AVIDSimilarityMemoryBank(nn.Module):
         return scores
 
     def fused_ok(self, video_emb, audio_emb):
-        """The one-kernel steady-state path (ops.xmodal_fused): cross-modal scores only, 128-d embeddings on the GPU."""
-        return (ops.FUSED_CRITERION and self.xModal and not self.wModal and video_emb.is_cuda and video_emb.dim() == 2
+        """The one-kernel steady-state path: any term set (cross-modal only: ops.xmodal_fused; with within-modal terms:
+        ops.crit_fused) on 128-d fp32 embeddings on the GPU."""
+        return (ops.FUSED_CRITERION and (self.xModal or self.wModal) and video_emb.is_cuda and video_emb.dim() == 2
                 and video_emb.shape[1] == 128 and self.view1_mem.shape[1] == 128
                 and video_emb.dtype == torch.float32 and audio_emb.dtype == torch.float32)
 
-    def forward_fused(self, video_emb, audio_emb, y, Z, coeff):
-        """avid.py:47-80 + nce.py:38-58 for both cross-modal score sets with the partition constant ``Z`` frozen: one
+    def forward_fused(self, video_emb, audio_emb, y, Z, coeff, coeff_w=0.):
+        """avid.py:47-80 + nce.py:38-58 for every score set of the term set with the partition constant ``Z`` frozen: one
         kernel for normalize -> gather (both banks, shared indices) -> scores / T -> NCE terms AND their gradient with
-        respect to the embeddings, then ONE bank-update launch.  Returns (total loss, losses[4])."""
+        respect to the embeddings, then ONE bank-update launch.  Returns (total loss, losses): cross-modal terms only —
+        losses[4] of ops.xmodal_fused; with within-modal terms (Self-AVID, Joint-AVID) — losses[16] of ops.crit_fused."""
         K = int(self.num_negatives)
         ops.poll_device_errors(y.device)
         with torch.no_grad():
             idx = self.sample_negatives(y, K)
+        stock = self.xModal and not self.wModal
         ws = getattr(self, "_fused_ws", None)
-        key = (y.shape[0], K, video_emb.device)
+        key = (y.shape[0], K, video_emb.device, stock)
         if ws is None or self._fused_key != key:
-            ws = self._fused_ws = ops.xmodal_fused_workspace(video_emb.device, y.shape[0], K)
+            ws = self._fused_ws = (ops.xmodal_fused_workspace(video_emb.device, y.shape[0], K) if stock else
+                                   ops.crit_fused_workspace(video_emb.device, y.shape[0], 0, K))
             self._fused_key = key
-        total, losses, hats = ops.xmodal_fused(video_emb, audio_emb, y, idx, self.view1_mem, self.view2_mem, Z,
-                                               1.0 / self.temperature, coeff, ws)
+        if stock:
+            total, losses, hats = ops.xmodal_fused(video_emb, audio_emb, y, idx, self.view1_mem, self.view2_mem, Z,
+                                                   1.0 / self.temperature, coeff, ws)
+        else:
+            mask = (ops.CRIT_X_INST if self.xModal else 0) | ops.CRIT_W_INST
+            total, losses, hats = ops.crit_fused(video_emb, audio_emb, y, None, idx, self.view1_mem, self.view2_mem, Z,
+                                                 1.0 / self.temperature, K, mask, (coeff, coeff_w, 0., 0.), ws)
         self.update_memory(hats[0], hats[1], y)
         ops.poll_device_errors(y.device)
         return total, losses
@@ -244,13 +253,22 @@ class AVID(nn.Module):
 
     def forward(self, emb1, emb2, target):
         tb_log = {}
-        # steady state (Z frozen after the first batch, nce.py:22-24) with cross-modal scores only: one fused kernel
-        if self.nce_average.fused_ok(emb1, emb2) and self.criterion.z_ready():
-            total_loss, losses = self.nce_average.forward_fused(emb1, emb2, target, self.criterion.avg_exp_score,
-                                                                self.xModal_coeff)
-            tb_log['Loss/v2a'], tb_log['Loss/a2v'] = losses[0], losses[1]
-            tb_log['Loss/xModal'] = losses[2]
-            tb_log['Loss/wModal'] = 0
+        # steady state (Z frozen after the first batch, nce.py:22-24): one fused kernel, whatever the term set
+        bank = self.nce_average
+        if bank.fused_ok(emb1, emb2) and self.criterion.z_ready():
+            total_loss, losses = bank.forward_fused(emb1, emb2, target, self.criterion.avg_exp_score, self.xModal_coeff,
+                                                    self.wModal_coeff)
+            if not bank.wModal:
+                tb_log['Loss/v2a'], tb_log['Loss/a2v'] = losses[0], losses[1]
+                tb_log['Loss/xModal'] = losses[2]
+                tb_log['Loss/wModal'] = 0
+                return total_loss, tb_log
+            # the keys and their order as the unfused path below leaves them (combine_losses)
+            if bank.xModal:
+                tb_log['Loss/v2a'], tb_log['Loss/a2v'] = losses[0], losses[1]
+            tb_log['Loss/v2v'], tb_log['Loss/a2a'] = losses[2], losses[3]
+            tb_log['Loss/xModal'] = losses[ops.CRIT_GROUP_MEAN] if bank.xModal else 0.
+            tb_log['Loss/wModal'] = losses[ops.CRIT_GROUP_MEAN + 1]
             return total_loss, tb_log
         scores = self.nce_average(emb1, emb2, target)
         terms = {k: self.criterion(*pair) for k, pair in scores.items()}   # one shared NCECriterion: Z comes from 'v2a'

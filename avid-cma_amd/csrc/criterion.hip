@@ -712,6 +712,302 @@ __global__ __launch_bounds__(256) void xmodal_finish_kernel(const XModalArgs p) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The general fused criterion (avid_crit_fused): the CMA form of xmodal_fused_kernel with the term set as a template
+// parameter.  Rows = self | P positives (P may be 0) | K negatives, cut into blocks of 64 as there; a row pair's four dot
+// products are formed only if a term of MASK reads them, and every term adds its dL/ds (times its group's coefficient) to
+// the weight of the row it was scored against — a negative's v2a score under X_INST | X_POS carries both.
+//   terms (part_l / losses order): 0 inst-v2a  1 inst-a2v | 2 inst-v2v  3 inst-a2a | 4 pos-v2a  5 pos-a2v | 6 pos-v2v  7 pos-a2a
+// Same lane layout, same fold, same two launches (crit_finish_kernel = xmodal_finish_kernel with eight terms).
+// ---------------------------------------------------------------------------------------------
+constexpr int CRIT_X_INST = 1, CRIT_W_INST = 2, CRIT_X_POS = 4, CRIT_W_POS = 8, CRIT_NL = 8;
+
+struct CritArgs {
+  const float* v_emb; const float* a_emb;          // raw embeddings [bs][128]
+  const long long* y; const long long* pos; const long long* idx;   // [bs], [bs][P], [bs][K]
+  const float* bank_v; const float* bank_a;
+  const float* Z;
+  float* v_hat; float* a_hat;
+  float* losses;                                   // [16]
+  float* dv; float* da;
+  float* part_g;                                   // [bs][S][2][128]
+  double* part_l;                                  // [bs][S][8]
+  double* samp_l;                                  // [bs][8]
+  unsigned* tickets;                               // [bs + 1]
+  float* norms;                                    // [2][bs]
+  int* err;
+  long long N;
+  int bs, P, K, Kw, S;
+  float inv_T;
+  float c[4];                                      // group coefficients: X_INST, W_INST, X_POS, W_POS
+};
+
+// Four waves per SIMD (<= 128 registers), as the stock forms run: every term set the criterions can ask for fits without a
+// spill; W_INST together with W_POS (both within-modal chains on one score pair: reachable through the C-ABI only) does not,
+// and runs at three.
+template <int MASK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MASK & 10) == 10 ? 3 : 4, 4)))
+void crit_fused_kernel(const CritArgs p) {
+  constexpr int D = 128, RB = 64, RPW = RB / 4, NU = RPW / 4;
+  constexpr bool XI = (MASK & CRIT_X_INST) != 0, WI = (MASK & CRIT_W_INST) != 0;
+  constexpr bool XP = (MASK & CRIT_X_POS) != 0, WP = (MASK & CRIT_W_POS) != 0;
+  constexpr bool XS = XI || XP, WS = WI || WP;      // cross-modal / within-modal dot products needed
+  __shared__ float sh_g[4][2][D];
+  __shared__ double sh_l[4][CRIT_NL];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & 15, grp = lane >> 4;
+  const int b = blockIdx.y, split = blockIdx.x, PP = p.P, R = PP + p.K + 1;
+  auto group_sum = [](float v) {
+    v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
+    return v;
+  };
+  float ev[8], ea[8], nv, na;
+  {
+    const floatx4 v0 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8);
+    const floatx4 v1 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8 + 4);
+    const floatx4 a0 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8);
+    const floatx4 a1 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8 + 4);
+    float sv = 0.f, sa = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      ev[k] = v0[k]; ev[4 + k] = v1[k]; ea[k] = a0[k]; ea[4 + k] = a1[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sv = fmaf(ev[k], ev[k], sv); sa = fmaf(ea[k], ea[k], sa); }
+    nv = fmaxf(sqrtf(group_sum(sv)), 1e-12f);
+    na = fmaxf(sqrtf(group_sum(sa)), 1e-12f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { ev[k] /= nv; ea[k] /= na; }
+    if (split == 0 && wave == 0 && grp == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        p.v_hat[(long long)b * D + sub * 8 + k] = ev[k];
+        p.a_hat[(long long)b * D + sub * 8 + k] = ea[k];
+      }
+      if (sub == 0) { p.norms[b] = nv; p.norms[p.bs + b] = na; }
+    }
+  }
+  const float KZ = (float)p.K * p.Z[0];
+  const float KZw = (float)p.Kw * p.Z[0];
+  const float invP = (XP || WP) ? 1.f / (float)PP : 0.f;
+  const int j0 = split * RB, j1 = min(j0 + RB, R);
+  const int jw = j0 + wave * RPW;
+  // row j = 0: the sample's own row y; rows 1..P: the positives pos[b][j - 1]; then the negatives
+  long long mine = 0;
+  if (lane < RPW && jw + lane < j1) {
+    const int jj = jw + lane;
+    mine = jj == 0 ? p.y[b] : (jj <= PP ? p.pos[(long long)b * PP + jj - 1] : p.idx[(long long)b * p.K + jj - 1 - PP]);
+    if (mine < 0 || mine >= p.N) {
+      if (p.err) atomicOr(p.err, AVID_DEVERR_BANK_INDEX);
+      mine = mine < 0 ? 0 : p.N - 1;
+    }
+  }
+  floatx4 ra[NU][2], rv[NU][2];          // audio-bank rows and video-bank rows (rows past j1 re-read row 0: discarded below)
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const long long row = __shfl(mine, u * 4 + grp, 64);
+    const float* pa = p.bank_a + row * D + sub * 8;
+    const float* pv = p.bank_v + row * D + sub * 8;
+    ra[u][0] = *reinterpret_cast<const floatx4*>(pa); ra[u][1] = *reinterpret_cast<const floatx4*>(pa + 4);
+    rv[u][0] = *reinterpret_cast<const floatx4*>(pv); rv[u][1] = *reinterpret_cast<const floatx4*>(pv + 4);
+  }
+  float gv[8], ga[8];                    // d total / d v_hat, d total / d a_hat (x T, x 2 bs): this group's rows
+#pragma unroll
+  for (int k = 0; k < 8; ++k) gv[k] = ga[k] = 0.f;
+  // a lane's loss terms: at most NU = 4 per term, summed in fp32 here (each is an fp32 logf) and in fp64 from the fold on —
+  // eight fp64 accumulators live across the row loop cost the fourth wave per SIMD
+  float Lf[CRIT_NL];
+#pragma unroll
+  for (int q = 0; q < CRIT_NL; ++q) Lf[q] = 0.f;
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const int j = jw + u * 4 + grp;
+    float d1 = 0.f, d2 = 0.f, d3 = 0.f, d4 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (XS) {
+        d1 = fmaf(ra[u][0][k], ev[k], d1); d1 = fmaf(ra[u][1][k], ev[4 + k], d1);
+        d2 = fmaf(rv[u][0][k], ea[k], d2); d2 = fmaf(rv[u][1][k], ea[4 + k], d2);
+      }
+      if (WS) {
+        d3 = fmaf(rv[u][0][k], ev[k], d3); d3 = fmaf(rv[u][1][k], ev[4 + k], d3);
+        d4 = fmaf(ra[u][0][k], ea[k], d4); d4 = fmaf(ra[u][1][k], ea[4 + k], d4);
+      }
+    }
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    if (XS) { s1 = group_sum(d1) * p.inv_T; s2 = group_sum(d2) * p.inv_T; }    // v2a, a2v
+    if (WS) { s3 = group_sum(d3) * p.inv_T; s4 = group_sum(d4) * p.inv_T; }    // v2v, a2a
+    if (j < j1) {
+      const int n = j - 1 - PP;             // index among the negatives (< 0: self / positive)
+      const bool self = j == 0, neg = n >= 0;
+      float g1 = 0.f, g2 = 0.f, g3 = 0.f, g4 = 0.f;
+      if (XS && (neg || (self ? XI : XP))) {
+        const float e1 = expf(s1), e2 = expf(s2);
+        if (neg) {                          // -log(KZ / (e + KZ));  d / ds = e / (e + KZ)
+          const float q1 = e1 / (e1 + KZ), q2 = e2 / (e2 + KZ);
+          if (sub == 0) {
+            const float t1 = -logf(KZ / (e1 + KZ)), t2 = -logf(KZ / (e2 + KZ));
+            if (XI) { Lf[0] += t1; Lf[1] += t2; }
+            if (XP) { Lf[4] += t1; Lf[5] += t2; }
+          }
+          if (XI) { g1 = q1 * p.c[0]; g2 = q2 * p.c[0]; }
+          if (XP) { g1 = fmaf(q1, p.c[2], g1); g2 = fmaf(q2, p.c[2], g2); }
+        } else if (self) {                  // -log(e / (e + KZ));  d / ds = -KZ / (e + KZ)
+          if (sub == 0) { Lf[0] += -logf(e1 / (e1 + KZ)); Lf[1] += -logf(e2 / (e2 + KZ)); }
+          g1 = -(KZ / (e1 + KZ)) * p.c[0]; g2 = -(KZ / (e2 + KZ)) * p.c[0];
+        } else {                            // one of the P positives: 1 / P of the positive term
+          if (sub == 0) { Lf[4] += -logf(e1 / (e1 + KZ)) * invP; Lf[5] += -logf(e2 / (e2 + KZ)) * invP; }
+          g1 = -(KZ / (e1 + KZ)) * invP * p.c[2]; g2 = -(KZ / (e2 + KZ)) * invP * p.c[2];
+        }
+      }
+      if (WS && (neg ? (WI || n < p.Kw) : (self ? WI : WP))) {
+        const float e3 = expf(s3), e4 = expf(s4);
+        if (neg) {
+          if (WI) {                         // every negative, K Z
+            if (sub == 0) { Lf[2] += -logf(KZ / (e3 + KZ)); Lf[3] += -logf(KZ / (e4 + KZ)); }
+            g3 = e3 / (e3 + KZ) * p.c[1]; g4 = e4 / (e4 + KZ) * p.c[1];
+          }
+          if (WP && n < p.Kw) {             // the first Kw negatives, Kw Z
+            if (sub == 0) { Lf[6] += -logf(KZw / (e3 + KZw)); Lf[7] += -logf(KZw / (e4 + KZw)); }
+            g3 = fmaf(e3 / (e3 + KZw), p.c[3], g3); g4 = fmaf(e4 / (e4 + KZw), p.c[3], g4);
+          }
+        } else if (self) {
+          if (sub == 0) { Lf[2] += -logf(e3 / (e3 + KZ)); Lf[3] += -logf(e4 / (e4 + KZ)); }
+          g3 = -(KZ / (e3 + KZ)) * p.c[1]; g4 = -(KZ / (e4 + KZ)) * p.c[1];
+        } else {
+          if (sub == 0) { Lf[6] += -logf(e3 / (e3 + KZw)) * invP; Lf[7] += -logf(e4 / (e4 + KZw)) * invP; }
+          g3 = -(KZw / (e3 + KZw)) * invP * p.c[3]; g4 = -(KZw / (e4 + KZw)) * invP * p.c[3];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (XS) {
+          gv[k] = fmaf(g1, ra[u][0][k], gv[k]); gv[4 + k] = fmaf(g1, ra[u][1][k], gv[4 + k]);
+          ga[k] = fmaf(g2, rv[u][0][k], ga[k]); ga[4 + k] = fmaf(g2, rv[u][1][k], ga[4 + k]);
+        }
+        if (WS) {
+          gv[k] = fmaf(g3, rv[u][0][k], gv[k]); gv[4 + k] = fmaf(g3, rv[u][1][k], gv[4 + k]);
+          ga[k] = fmaf(g4, ra[u][0][k], ga[k]); ga[4 + k] = fmaf(g4, ra[u][1][k], ga[4 + k]);
+        }
+      }
+    }
+  }
+  // fold the four row groups of the wave (fixed order: (g0 + g1) + (g2 + g3)), then the four waves through LDS
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    gv[k] += __shfl_xor(gv[k], 16, 64); gv[k] += __shfl_xor(gv[k], 32, 64);
+    ga[k] += __shfl_xor(ga[k], 16, 64); ga[k] += __shfl_xor(ga[k], 32, 64);
+  }
+  double L[CRIT_NL];
+#pragma unroll
+  for (int q = 0; q < CRIT_NL; ++q) {
+    L[q] = (double)Lf[q];
+    if ((MASK >> (q >> 1)) & 1) { L[q] += __shfl_xor(L[q], 16, 64); L[q] += __shfl_xor(L[q], 32, 64); }
+  }
+  if (grp == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sh_g[wave][0][sub * 8 + k] = gv[k]; sh_g[wave][1][sub * 8 + k] = ga[k]; }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < CRIT_NL; ++q) sh_l[wave][q] = L[q];          // (a term that is off: 0)
+  }
+  __syncthreads();
+  float* pg = p.part_g + ((long long)b * p.S + split) * 2 * D;
+  {
+    const int t = threadIdx.x;                       // 256 threads = 2 x 128 gradient components
+    pg[t] = ((&sh_g[0][0][0])[t] + (&sh_g[1][0][0])[t]) + ((&sh_g[2][0][0])[t] + (&sh_g[3][0][0])[t]);
+  }
+  if (threadIdx.x < CRIT_NL) {
+    double* pl = p.part_l + ((long long)b * p.S + split) * CRIT_NL;
+    const int q = threadIdx.x;
+    pl[q] = (sh_l[0][q] + sh_l[1][q]) + (sh_l[2][q] + sh_l[3][q]);
+  }
+}
+
+// second launch: xmodal_finish_kernel for eight terms and four groups
+__global__ __launch_bounds__(256) void crit_finish_kernel(const CritArgs p) {
+  constexpr int D = 128, NL = CRIT_NL;
+  __shared__ float sh_dot[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, which = t >> 7, d = t & 127;
+  const int b = blockIdx.x;
+  const float eh = (which == 0 ? p.v_hat : p.a_hat)[(long long)b * D + d];
+  const float nrm = p.norms[which * p.bs + b];
+  const float* pg = p.part_g + (long long)b * p.S * 2 * D + t;
+  float g = 0.f;
+  int sidx = 0;
+  for (; sidx + 4 <= p.S; sidx += 4) {               // four independent loads per trip, summed in split order
+    const float g0 = pg[(long long)sidx * 2 * D], g1 = pg[(long long)(sidx + 1) * 2 * D];
+    const float g2 = pg[(long long)(sidx + 2) * 2 * D], g3 = pg[(long long)(sidx + 3) * 2 * D];
+    g += g0; g += g1; g += g2; g += g3;
+  }
+  for (; sidx < p.S; ++sidx) g += pg[(long long)sidx * 2 * D];
+  // d total / d score = coeff_g * 1/2 * 1/bs * dL/ds (the coefficient is already in);  d emb_hat = that * row / T
+  g *= 0.5f / (float)p.bs * p.inv_T;
+  const float dot = wave_sum(g * eh);
+  if (lane == 0) sh_dot[wave] = dot;
+  __syncthreads();
+  const float full = sh_dot[which * 2] + sh_dot[which * 2 + 1];
+  (which == 0 ? p.dv : p.da)[(long long)b * D + d] = (g - eh * full) / nrm;
+  if (wave != 0) return;
+  double l[NL];
+  {
+    const double* pl = p.part_l + (long long)b * p.S * NL;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) l[q] = 0;
+    for (int base = 0; base < p.S; base += 64) {
+      const int i = base + lane;
+      double v[NL];
+#pragma unroll
+      for (int q = 0; q < NL; ++q) v[q] = i < p.S ? pl[NL * i + q] : 0.0;
+      for (int k = 0; k < 64 && base + k < p.S; ++k) {
+#pragma unroll
+        for (int q = 0; q < NL; ++q) l[q] += __shfl(v[q], k, 64);
+      }
+    }
+  }
+  unsigned last = 0;
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) __hip_atomic_store(p.samp_l + NL * b + q, l[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    last = atomicAdd(&p.tickets[0], 1u) == (unsigned)p.bs - 1 ? 1u : 0u;
+  }
+  last = __shfl(last, 0, 64);
+  if (!last) return;
+  __threadfence();
+  double tot[NL];
+#pragma unroll
+  for (int q = 0; q < NL; ++q) tot[q] = 0;
+  for (int base = 0; base < p.bs; base += 64) {      // 64 samples per trip in flight, summed in sample order
+    const int i = base + lane;
+    double v[NL];
+#pragma unroll
+    for (int q = 0; q < NL; ++q) v[q] = i < p.bs ? __hip_atomic_load(p.samp_l + NL * i + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    for (int k = 0; k < 64 && base + k < p.bs; ++k) {
+#pragma unroll
+      for (int q = 0; q < NL; ++q) tot[q] += __shfl(v[q], k, 64);
+    }
+  }
+  if (lane == 0) {
+    // criterions/avid.py:216-232, criterions/avid_cma.py:338-358: every group the mean of its two directions, the total
+    // their weighted sum in group order (a group that is off: 0)
+    float total = 0.f;
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const float la = (float)(tot[2 * g4] / (double)p.bs), lb = (float)(tot[2 * g4 + 1] / (double)p.bs);
+      const float gm = la / 2.f + lb / 2.f;
+      p.losses[2 * g4] = la;
+      p.losses[2 * g4 + 1] = lb;
+      p.losses[8 + g4] = gm;
+      total = g4 == 0 ? gm * p.c[0] : total + gm * p.c[g4];
+    }
+    p.losses[12] = total;
+    p.losses[13] = p.losses[14] = p.losses[15] = 0.f;
+    __hip_atomic_store(&p.tickets[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // re-arm
+  }
+}
+
 // both banks in one launch (criterions/avid.py:118-129): blockIdx.y picks the bank
 __global__ __launch_bounds__(256) void bank_update2_kernel(float* __restrict__ bank0, float* __restrict__ bank1,
                                                            const long long* __restrict__ y, const float* __restrict__ emb0,
@@ -971,6 +1267,53 @@ extern "C" int avid_cma_fused(int bs, int P, int K, int Kw, int D, int64_t N, co
   a.err = err; a.N = N; a.bs = bs; a.K = K; a.inv_T = inv_T; a.coeff = 1.f;
   a.pos = (const long long*)pos; a.P = P; a.Kw = Kw; a.cI = coeff_inst; a.cP = coeff_pos;
   return fused_launch<true>(a, 1 + P + K, ws, (hipStream_t)stream);
+}
+
+extern "C" size_t avid_crit_fused_workspace_bytes(int bs, int P, int K) {
+  if (bs <= 0 || P < 0 || K <= 0) return 0;
+  return fused_ws_bytes(bs, 1 + P + K, CRIT_NL);
+}
+
+extern "C" int avid_crit_fused(const avid_crit_desc* d, void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream) {
+  AVID_REQUIRE(d, AVID_E_BADARG, "crit_fused: null descriptor");
+  AVID_REQUIRE(d->mask >= 1 && d->mask <= 15, AVID_E_BADARG, "crit_fused: mask %d names no term (1..15)", d->mask);
+  AVID_REQUIRE(d->bs > 0 && d->K > 0 && d->P >= 0 && d->N > 0, AVID_E_BADARG, "crit_fused: bad bs / P / K / N");
+  AVID_REQUIRE(d->Kw >= 1 && d->Kw <= d->K, AVID_E_BADARG, "crit_fused: Kw=%d outside 1..K=%d", d->Kw, d->K);
+  AVID_REQUIRE(d->P >= 1 || !(d->mask & (CRIT_X_POS | CRIT_W_POS)), AVID_E_BADARG,
+               "crit_fused: a positive-set term (mask %d) needs P >= 1", d->mask);
+  AVID_REQUIRE(d->D == 128, AVID_E_UNSUPPORTED, "crit_fused: D=%d unsupported (128 only; use the unfused ops)", d->D);
+  AVID_REQUIRE(d->v_emb && d->a_emb && d->y && d->idx && (d->pos || d->P == 0) && d->bank_v && d->bank_a && d->Z && d->v_hat &&
+                   d->a_hat && d->losses && d->dv && d->da && ws, AVID_E_BADARG, "crit_fused: null pointer");
+  AVID_REQUIRE(ws_bytes >= avid_crit_fused_workspace_bytes(d->bs, d->P, d->K), AVID_E_BADARG, "crit_fused: workspace too small");
+  CritArgs a;
+  a.v_emb = d->v_emb; a.a_emb = d->a_emb; a.y = (const long long*)d->y; a.pos = (const long long*)d->pos;
+  a.idx = (const long long*)d->idx; a.bank_v = d->bank_v; a.bank_a = d->bank_a; a.Z = d->Z; a.v_hat = d->v_hat; a.a_hat = d->a_hat;
+  a.losses = d->losses; a.dv = d->dv; a.da = d->da; a.err = err; a.N = d->N; a.bs = d->bs; a.P = d->P; a.K = d->K; a.Kw = d->Kw;
+  a.inv_T = d->inv_T;
+  for (int g = 0; g < 4; ++g) a.c[g] = d->coeff[g];
+  const int rows = 1 + d->P + d->K;
+  a.S = (int)ceil_div(rows, 64);
+  char* w = static_cast<char*>(ws);                 // (zero-filled once by the caller: the ticket re-arms itself)
+  a.part_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * a.S * CRIT_NL * 8;
+  a.samp_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * CRIT_NL * 8;
+  a.part_g = reinterpret_cast<float*>(w); w += (size_t)a.bs * a.S * 2 * 128 * 4;
+  a.tickets = reinterpret_cast<unsigned*>(w); w += ((size_t)a.bs + 1) * 4;
+  a.norms = reinterpret_cast<float*>(w);
+  hipStream_t s = (hipStream_t)stream;
+  const int pairs = ((d->mask & (CRIT_X_INST | CRIT_X_POS)) ? 1 : 0) + ((d->mask & (CRIT_W_INST | CRIT_W_POS)) ? 1 : 0);
+  ScopedTimer t(s, "crit_fused_kernel", pairs * 2.0 * 2.0 * 2.0 * a.bs * rows * 128, 2.0 * 4.0 * a.bs * rows * 128.0);
+  const dim3 grid((unsigned)a.S, (unsigned)a.bs);
+  switch (d->mask) {
+#define AVID_CRIT_CASE(M) case M: hipLaunchKernelGGL(crit_fused_kernel<M>, grid, dim3(256), 0, s, a); break;
+    AVID_CRIT_CASE(1) AVID_CRIT_CASE(2) AVID_CRIT_CASE(3) AVID_CRIT_CASE(4) AVID_CRIT_CASE(5)
+    AVID_CRIT_CASE(6) AVID_CRIT_CASE(7) AVID_CRIT_CASE(8) AVID_CRIT_CASE(9) AVID_CRIT_CASE(10)
+    AVID_CRIT_CASE(11) AVID_CRIT_CASE(12) AVID_CRIT_CASE(13) AVID_CRIT_CASE(14) default: AVID_CRIT_CASE(15)
+#undef AVID_CRIT_CASE
+  }
+  int rc = check_launch("crit_fused");
+  if (rc) return rc;
+  hipLaunchKernelGGL(crit_finish_kernel, dim3((unsigned)a.bs), dim3(256), 0, s, a);
+  return check_launch("crit_finish");
 }
 
 extern "C" int avid_bank_update2(int B, int D, int64_t N, float* bank0, float* bank1, const int64_t* y, const float* emb0,

@@ -543,6 +543,49 @@ int avid_cma_fused(int bs, int P, int K, int Kw, int D, int64_t N, const float* 
                    const int64_t* pos, const int64_t* idx, const float* bank_v, const float* bank_a, float inv_T,
                    const float* Z, float coeff_inst, float coeff_pos, float* v_hat, float* a_hat, float* losses, float* dv,
                    float* da, void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream);
+/* The general form of the two entry points above: ANY term set of criterions/avid.py and criterions/avid_cma.py with Z
+ * frozen, in the same two launches.  Rows gathered once from both banks = the sample's own row y | its P positives
+ * pos[bs][P] (P may be 0) | the K negatives idx[bs][K]; a row pair gives four dot products (v_hat . bank_a row,
+ * a_hat . bank_v row, v_hat . bank_v row, a_hat . bank_a row) and `mask` says which NCE terms they enter:
+ *   AVID_CRIT_X_INST  v2a / a2v: positive = row y, negatives = all K        (avid.py xModal; avid_cma.py xModalInst / wModalInst)
+ *   AVID_CRIT_W_INST  v2v / a2a: positive = row y, negatives = all K        (avid.py wModal)
+ *   AVID_CRIT_X_POS   pos-v2a / pos-a2v: the P positives (mean over P, nce.py:44), negatives = all K       (xModalPos)
+ *   AVID_CRIT_W_POS   pos-v2v / pos-a2a: the P positives, negatives = the first Kw                           (wModalPos)
+ *   total = sum over the groups g of the mask, in the order above, of coeff[g] * (L_g,first / 2 + L_g,second / 2)
+ * A score that serves two terms (a negative's v2a score under X_INST | X_POS) carries the sum of both dL/ds.  A set bit
+ * with coeff 0 reports its losses and contributes no gradient.
+ *   losses [16], every element written: [0..7] the term losses in the order X_INST (v2a, a2v), W_INST (v2v, a2a), X_POS,
+ *   W_POS — 0 for a term that is off; [8..11] the four group means; [12] the total; [13..15] 0.
+ *   v_hat, a_hat, dv, da, err, Z: as avid_xmodal_fused.  pos may be NULL when P = 0.
+ * Limits: D = 128 (AVID_E_UNSUPPORTED otherwise); mask in 1..15, bs, K > 0, P >= 0 and P >= 1 with a *_POS bit,
+ * 1 <= Kw <= K, ws_bytes >= avid_crit_fused_workspace_bytes(bs, P, K) (ws zero-filled once by the caller, then owned by
+ * this op), no null pointer: AVID_E_BADARG otherwise, before anything is launched. */
+#define AVID_CRIT_X_INST 1
+#define AVID_CRIT_W_INST 2
+#define AVID_CRIT_X_POS 4
+#define AVID_CRIT_W_POS 8
+typedef struct avid_crit_desc {
+  int32_t bs, P, K, Kw, D, mask;
+  int64_t N;
+  const float* v_emb;
+  const float* a_emb;
+  const int64_t* y;
+  const int64_t* pos;
+  const int64_t* idx;
+  const float* bank_v;
+  const float* bank_a;
+  const float* Z;
+  float inv_T;
+  float coeff[4];
+  int32_t reserved;
+  float* v_hat;
+  float* a_hat;
+  float* losses;
+  float* dv;
+  float* da;
+} avid_crit_desc;
+size_t avid_crit_fused_workspace_bytes(int bs, int P, int K);
+int avid_crit_fused(const avid_crit_desc* d, void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream);
 /* avid_bank_update for both banks in one launch (criterions/avid.py:118-129): bank0 <- emb0 (momentum0), bank1 <- emb1; bit-identical to two avid_bank_update calls. */
 int avid_bank_update2(int B, int D, int64_t N, float* bank0, float* bank1, const int64_t* y, const float* emb0,
                       const float* emb1, float momentum0, float momentum1, int32_t* err, avid_stream_t stream);

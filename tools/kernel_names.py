@@ -23,6 +23,7 @@ KEEP = {
     "wgrad_kernel": 2,
     "xmodal_fused_kernel": 0,      # <CMA,ROWS,NT>: CMA = true is timed as cma_fused_kernel
     "xmodal_finish_kernel": 0,
+    "crit_fused_kernel": 0,        # <MASK>: the term set of avid_crit_fused
     "bank_scores_fwd_kernel": 0,   # <rows per wave>
     "bank_scores_bwd_kernel": 0,
     "splitk_reduce_cls_kernel": 0,
