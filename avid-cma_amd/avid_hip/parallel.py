@@ -693,7 +693,8 @@ class AdamStep(EngineCore):
         return video, labels
 
     def _evaluate(self, video, batch, finish):
-        """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] through the model in eval mode, ``batch`` clips at a time (the
+        """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] (an audio tower: spectrograms [V, clips, 1, T, F]) through the
+        model in eval mode, ``batch`` clips at a time (the
         reference's BatchWrapper; ``Inference``: one program per distinct chunk size, cached on the model).  Returns
         ``finish([the chunks' outputs])``, evaluated before the model's mode is restored."""
         x = video.flatten(0, 1)
@@ -1403,10 +1404,12 @@ class SGD(torch.optim.Optimizer):
 # ---------------------------------------------------------------------------------------------------------------------
 class Inference:
     """``Inference(model)(*inputs)`` returns what ``model.eval()(*inputs)`` returns under ``torch.no_grad()`` — a tensor for
-    ``R2Plus1D`` and ``ClassificationWrapper``, the tuple of embeddings for ``AV_Wrapper``, whatever the model returns otherwise —
+    ``R2Plus1D``, ``Conv2D`` and ``ClassificationWrapper``, the tuple of embeddings for ``AV_Wrapper``, the dict of logits for
+    ``MOSTModel``, whatever the model returns otherwise —
     bit for bit, without touching the modules' ``training`` flags and without synchronising the host.
 
-    Models the inference compiler knows (``plan.EvalPlan``) run as ONE launch program per input geometry: the eval-mode
+    Models the inference compiler knows (``plan.EvalPlan``: the towers, and the two wrappers around either tower — clips
+    [B, 3, T, H, W] for ``R2Plus1D``, spectrograms [B, 1, T, F] for ``Conv2D``) run as ONE launch program per input geometry: the eval-mode
     BatchNorms' coefficients from one launch, conv2x's BatchNorms inside the temporal convolutions, the stem's tail in one
     pass, activations in a recycled arena.  Anything else — hooks on a module, frozen BatchNorm parameters, another model,
     CPU or non-fp32 tensors, a stream capture, ``AVID_EVAL_PLAN=0`` — takes the per-layer path.  ``used_programs`` says which
@@ -1443,9 +1446,10 @@ class KNNEval:
     embed a labelled gallery, then classify each query by the vote of its ``k`` nearest gallery embeddings, every neighbour
     weighing ``exp(similarity / T)`` (``ops.knn_search`` / ``ops.knn_vote``; no ``[Q, N]`` matrix is ever held).
 
-    ``model``: anything ``Inference`` runs — ``R2Plus1D`` (its ``pool`` output, flattened to ``[B, 512]``), ``AV_Wrapper`` (the
-    video embedding; pass ``(video, audio)`` where a clip batch is expected) — or ``None`` to work on features the caller
-    extracted.  The forward is ``Inference(model)``'s and nothing else: frozen towers, hooks and so on take whatever path it
+    ``model``: anything ``Inference`` runs — ``R2Plus1D`` (its ``pool`` output, flattened to ``[B, 512]``), ``Conv2D`` (the audio
+    tower: the same on spectrograms ``[B * clips_per_sample, 1, T, F]``, a sample's clips adjacent — the flat form only; nothing
+    here is specific to it, the forward is ``Inference``'s inference program), ``AV_Wrapper`` (the video embedding; pass ``(video, audio)`` where a clip batch is
+    expected) — or ``None`` to work on features the caller extracted.  The forward is ``Inference(model)``'s and nothing else: frozen towers, hooks and so on take whatever path it
     takes.  ``feat``: only ``"pool"``, the tower's output.  ``normalize``: L2-normalise the (clip-averaged) features, so that
     the similarity is the cosine.  The feature width must be a multiple of 32, the gallery needs 64 rows, ``k <= 63``.
 
@@ -1563,6 +1567,8 @@ class FinetuneStep(AdamStep):
     ``classifier_only=True``: the reference's warm-up (an optimizer over the classifier's parameters only).  The tower
     still runs in training mode and updates its BatchNorm running statistics; no tower backward is compiled, because the
     reference never applies those gradients; Adam touches only the classifier's slice of the flat buffer.
+    The tower may also be this package's ``Conv2D`` (sound classification): ``step`` and ``evaluate`` then take spectrograms
+    [B, 1, T, F] / [V, clips, 1, T, F] where they take clips; optimizers, the step guard, checkpoints and ``virtual_ranks`` alike.
     With more than one rank, gradients are averaged as DistributedDataParallel does: through ``GradBuckets`` (the full
     step), or one collective over the classifier's slice (``classifier_only``); Adam's ``grad_scale`` takes the 1 / world.
     Rank 0's BatchNorm running statistics are broadcast before every step (``broadcast_buffers="step"``, DDP's default).
@@ -1726,6 +1732,8 @@ class ProbeStep(AdamStep):
     Adam launch.  The tower is frozen: the flat parameter, gradient and moment buffers hold the classifiers' parameters only
     (its BatchNorm running statistics still move: the reference trains the probe with the tower in training mode).  Nothing
     synchronises the host.  Single process: the shipped config is not distributed.
+    The tower may also be this package's ``Conv2D`` with ``AdaptiveMaxPool2d((h, w))`` heads (sound classification): ``step`` and
+    ``evaluate`` then take spectrograms [B, 1, T, F] / [V, clips, 1, T, F] where they take clips, everything else alike.
     ``set_lr`` and ``state_dict`` / ``load_state_dict`` are ``AdamStep``'s — ``torch.optim.Adam(model.parameters())``'s format,
     the frozen tower parameters listed without state.
 

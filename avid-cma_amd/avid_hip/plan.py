@@ -142,14 +142,34 @@ def _classifier(model):
     return model.classifier
 
 
+def _audio_tower(model):
+    """The model's single tower — the model itself, or the ``feature_extractor`` of a wrapper — is this package's ``Conv2D``: its
+    input is a spectrogram batch [B, 1, T, F] (in slot ``S_VIDEO``, as every single-tower plan's input), its taps are 2-D."""
+    from models.audio import Conv2D
+    return type(getattr(model, "feature_extractor", model)) is Conv2D
+
+
+def _tower_input(tower_is_audio, shape):
+    """The Sym of a single-tower plan's input in slot ``S_VIDEO``: a clip batch [B, 3, T, H, W] as it is, a spectrogram batch
+    [B, 1, T, F] as [B, 1, 1, T, F] (a 2-D convolution is a 3-D one with T = kt = 1, as the two-tower plan builds it)."""
+    if len(shape) != (4 if tower_is_audio else 5):
+        raise Unsupported("input rank")
+    if not tower_is_audio:
+        return Sym((S_VIDEO, 0), shape)
+    return Sym((S_VIDEO, 0), (shape[0], shape[1], 1, shape[2], shape[3]))
+
+
 def _probe_heads(model):
-    """The heads of a ``MOSTModel`` in its stock form: per tap AdaptiveMaxPool3d -> BatchNorm1d -> Linear, no dropout, no l2 norm."""
+    """The heads of a ``MOSTModel`` in its stock form: per tap adaptive max pool -> BatchNorm1d -> Linear, no dropout, no l2 norm.
+    The pool is an ``AdaptiveMaxPool3d((t, h, w))`` on an ``R2Plus1D`` tower and an ``AdaptiveMaxPool2d((h, w))`` on a ``Conv2D``
+    tower (``pool_size`` (1, h, w)); the other pairing — whose torch module would refuse the tap's rank — is not compiled."""
     from models.linear_probe import MOSTModel, Classifier, ProbeBatchNorm1d, ProbeLinear
     if type(model) is not MOSTModel or not len(model.classifiers):
         raise Unsupported("linear probe outside the compiled pattern")
+    pool_type = torch.nn.AdaptiveMaxPool2d if _audio_tower(model) else torch.nn.AdaptiveMaxPool3d
     for c in model.classifiers:
         if (type(c) is not Classifier or c.pool_size is None or c.use_dropout or c.l2_norm or not c.use_bn
-                or type(c.pooling) is not torch.nn.AdaptiveMaxPool3d or c.feat_name not in _STAGES
+                or type(c.pooling) is not pool_type or c.feat_name not in _STAGES
                 or type(c.bn) is not ProbeBatchNorm1d or c.bn.momentum is None or not c.bn.affine
                 or not c.bn.track_running_stats or type(c.classifier) is not ProbeLinear or c.classifier.bias is None):
             raise Unsupported("probe head outside the compiled pattern")
@@ -363,19 +383,34 @@ class Builder:
         pool = self.gpool_fwd(h, arena=arena)
         return {"stem": stem, "blocks": blocks, "stages": stages, "pool": pool}, pool["y"]
 
-    def audio_fwd(self, am, x):
+    def audio_fwd(self, am, x, arena=None):
+        """The audio tower on x [B, 1, 1, T, F]; ``arena``: where the pooled output goes (default: the forward arena).  Returns
+        ({"layers": the layer records, "stages": {stage name: Sym of block1..block4's output — the names ``Conv2D.forward`` gives
+        them under ``return_embs``}, "pool"}, Sym of the pooled features)."""
         from models.audio import Conv2D
-        from models.network_blocks import Basic2DBlock
+        from models.network_blocks import Basic2DBlock, BatchNormCL, ConvCL
         if type(am) is not Conv2D:
             raise Unsupported(type(am).__name__)
+        if type(am.conv1[0]) is not ConvCL or type(am.conv1[1]) is not BatchNormCL:
+            raise Unsupported("audio stem")
         Ls = [self.conv_bn_fwd(am.conv1[0], am.conv1[1], x)]
-        for blk in (am.block1, am.block2, am.block3, am.block4):
+        stages = {}
+        for name, blk in zip(_STAGES, (am.block1, am.block2, am.block3, am.block4)):
             if type(blk) is not Basic2DBlock:
                 raise Unsupported(type(blk).__name__)
             for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2)):
                 Ls.append(self.conv_bn_fwd(conv, bn, Ls[-1]["h"]))
-        pool = self.gpool_fwd(Ls[-1]["h"])
-        return {"layers": Ls, "pool": pool}, pool["y"]
+            stages[name] = Ls[-1]["h"]
+        pool = self.gpool_fwd(Ls[-1]["h"], arena=arena)
+        return {"layers": Ls, "stages": stages, "pool": pool}, pool["y"]
+
+    def tower_fwd(self, tower, shape, arena=None):
+        """The single tower of a fine-tuning, probe or inference plan on the input of slot ``S_VIDEO``: ``video_fwd`` for an
+        ``R2Plus1D`` on clips [B, 3, T, H, W], ``audio_fwd`` for a ``Conv2D`` on spectrograms [B, 1, T, F]; anything else is
+        ``video_fwd``'s refusal.  Returns (the walker's record with "stages" and "pool", Sym of the pooled features)."""
+        if _audio_tower(tower):
+            return self.audio_fwd(tower, _tower_input(True, shape), arena=arena)
+        return self.video_fwd(tower, _tower_input(False, shape), arena=arena)
 
     def head_fwd(self, head, x, arena=None):
         """The projection head; ``arena``: where the LAST layer's output goes (default: the forward arena)."""
@@ -665,6 +700,15 @@ class TrainBuilder(Builder):
         Ls = A["layers"]
         for k in range(len(Ls) - 1, -1, -1):
             _, dh = self.conv_bn_bwd(Ls[k], dh, need_dx=k > 0)
+
+    def tower_bwd(self, V, dy):
+        """The backward of ``tower_fwd``'s record from the pooled features' gradient: ``audio_bwd``, or ``video_bwd`` with the
+        stem behind the queued weight-gradient group."""
+        if "layers" in V:
+            return self.audio_bwd(V, dy)
+        dh = self.video_bwd(V, dy)
+        self.flush_group(ST_MAIN)
+        self.video_stem_bwd(V, dh)
 
     def head_bwd(self, Ls, dy):
         for L in reversed(Ls):
@@ -1136,9 +1180,12 @@ def _tree_ok(model, training=True):
     return True
 
 
-def _inputs_ok(inputs):
-    """float32 GPU inputs — video [B,3,T,H,W], then audio [B,1,F,T] if there is one — and no graph being captured."""
-    if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == rank for x, rank in zip(inputs, (5, 4))):
+def _inputs_ok(inputs, audio_tower=False):
+    """float32 GPU inputs — video [B,3,T,H,W], then audio [B,1,F,T] if there is one; the one spectrogram batch [B,1,T,F] of a
+    single ``Conv2D`` tower (``audio_tower``) — and no graph being captured."""
+    ranks = (4,) if audio_tower else (5, 4)
+    if len(inputs) > len(ranks) or not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == rank
+                                           for x, rank in zip(inputs, ranks)):
         return False
     return not torch.cuda.is_current_stream_capturing()
 
@@ -1148,7 +1195,7 @@ def eligible(model, *inputs, need_grad=True):
     the programs itself) on inputs the programs take (``_inputs_ok``) through the stock module tree, nothing hooked."""
     if not ENABLED or not model.training or (need_grad and not torch.is_grad_enabled()):
         return False
-    return _inputs_ok(inputs) and _tree_ok(model)
+    return _inputs_ok(inputs, _audio_tower(model)) and _tree_ok(model)
 
 
 def _bn_identity(model):
@@ -1224,12 +1271,14 @@ def _i32(v):
 
 
 class ClsPlan(TrainPrograms):
-    """The compiled programs of one ``ClassificationWrapper`` around this package's ``R2Plus1D`` for one clip geometry.
+    """The compiled programs of one ``ClassificationWrapper`` around this package's ``R2Plus1D`` for one clip geometry, or around
+    its ``Conv2D`` for one spectrogram geometry [B, 1, T, F] (``Builder.tower_fwd``; the input stays in slot ``S_VIDEO``, because
+    the labels alias ``S_AUDIO``).
 
-    Forward: the tower (``Builder.video_fwd``), dropout, the classifier (``Builder.cls_linear_fwd``)
+    Forward: the tower (``Builder.video_fwd`` / ``audio_fwd``), dropout, the classifier (``Builder.cls_linear_fwd``)
     — records [0, n_logits) — then ``AVID_OP_CLS_LOSS`` with ``dlogits`` (record n_logits, run by the step engine only).
     Backward, from ``dlogits``: the classifier's weight, bias and input gradients (one ``avid_cls_linear_bwd``), dropout's
-    backward, the tower's backward (``TrainBuilder.video_bwd`` / ``video_stem_bwd``).  ``classifier_only``: the reference's warm-up epochs — the
+    backward, the tower's backward (``TrainBuilder.tower_bwd``: ``video_bwd`` / ``video_stem_bwd``, or ``audio_bwd``).  ``classifier_only``: the reference's warm-up epochs — the
     tower still runs in training mode (its BatchNorm running statistics move) but no tower backward is compiled, the
     classifier's input gradient neither, and only the classifier's slice of the gradient buffer is zeroed."""
 
@@ -1247,7 +1296,7 @@ class ClsPlan(TrainPrograms):
         if classifier_only:
             b.fwd[self._zero_index].n[0] = 4 * self.n_cls
         # ------------------------------------------------------------------ forward
-        V, feat = b.video_fwd(model.feature_extractor, Sym((S_VIDEO, 0), vshape))
+        V, feat = b.tower_fwd(model.feature_extractor, self.vshape)
         B, Fd = feat.shape
         self.drop_index = None
         if self.p > 0.0:
@@ -1271,9 +1320,7 @@ class ClsPlan(TrainPrograms):
                 df = b.ba.alloc(4 * B * Fd)
                 b.emit(OP_DROPOUT_BWD, n=(B * Fd,), f=(self.p,), t=(self.mask, dx, df))
                 dx = df
-            dh = b.video_bwd(V, dx)
-            b.flush_group(ST_MAIN)
-            b.video_stem_bwd(V, dh)
+            b.tower_bwd(V, dx)
         self._close(b)
 
     def forward(self, video, grad_flat, zero_grad, seed=0, offset=0, labels=None, out=None, dlogits=None, grad_scale=1.0,
@@ -1335,9 +1382,11 @@ def run_cls(model, video):
 # linear probe: models.linear_probe.MOSTModel (utils/eval_utils.py:217-242, 298-329 of the reference)
 # ------------------------------------------------------------------------------------------------------------------
 class ProbePlan(TrainPrograms):
-    """The compiled programs of one ``MOSTModel`` in its stock form around this package's ``R2Plus1D`` for one clip geometry.
+    """The compiled programs of one ``MOSTModel`` in its stock form around this package's ``R2Plus1D`` for one clip geometry, or
+    around its ``Conv2D`` for one spectrogram geometry (``AdaptiveMaxPool2d((h, w))`` heads: the taps are [B, 1, H, W, C] and pool
+    with T = To = 1 into the reference's (C, h, w) flatten order).
 
-    Forward: the training-mode tower (``Builder.video_fwd``; the stage outputs it materialises anyway are the taps), then per
+    Forward: the training-mode tower (``Builder.tower_fwd``; the stage outputs it materialises anyway are the taps), then per
     tap ``Builder.probe_head_fwd`` — records [0, n_logits) — then one ``AVID_OP_CLS_LOSS`` with ``dlogits`` per tap (run by the step
     engine only).  Backward, from ``dlogits``, per tap: ``avid_probe_linear_bwd`` (weight, bias and input gradient),
     ``avid_bn1d_bwd`` (no input gradient: the pooled features are constants).  No tower record: the tower is frozen.  The
@@ -1350,7 +1399,7 @@ class ProbePlan(TrainPrograms):
         b = self._open(model, device, False, trailing, group, frozen_ok=True)
         self.vshape, self.ashape = tuple(vshape), None
         # ------------------------------------------------------------------ forward
-        V, _ = b.video_fwd(model.feature_extractor, Sym((S_VIDEO, 0), vshape))
+        V, _ = b.tower_fwd(model.feature_extractor, self.vshape)
         B = vshape[0]
         self.n_classes = C = classifiers[0].classifier.weight.shape[0]
         if C > 1024:
@@ -1433,7 +1482,8 @@ def run_probe(model, video):
 # inference: eval-mode forward programs (parallel.Inference, the engines' evaluate())
 # ------------------------------------------------------------------------------------------------------------------
 class EvalPlan(Programs):
-    """The compiled inference program of one model for one input geometry: ``R2Plus1D`` (pooled features), ``AV_Wrapper`` (the two
+    """The compiled inference program of one model for one input geometry: ``R2Plus1D`` or ``Conv2D`` (pooled features; wherever
+    ``R2Plus1D`` stands as a wrapper's tower below, ``Conv2D`` on spectrograms [B, 1, T, F] is compiled too), ``AV_Wrapper`` (the two
     embeddings; the audio tower on its own stream and its own buffers), ``ClassificationWrapper(R2Plus1D, feat_name='pool',
     pooling_op=None)`` (logits; dropout is the identity in eval mode) or the stock ``MOSTModel`` (every tap's logits:
     ``Builder.probe_head_fwd`` with training = 0).  Record 0 is the batched BatchNorm-coefficient launch — it
@@ -1446,6 +1496,7 @@ class EvalPlan(Programs):
         from models.av_wrapper import AV_Wrapper
         from models.classification import ClassificationWrapper
         from models.linear_probe import MOSTModel
+        from models.audio import Conv2D
         from models.video import R2Plus1D
         dry = device.type != "cuda"
         if not all((p.is_cuda or dry) and p.dtype == torch.float32 for p in model.parameters()):
@@ -1455,12 +1506,13 @@ class EvalPlan(Programs):
         self._coef_rec = b.emit(OP_BN_EVAL_COEFFS, i=(0,), t=((S_AUX, 0),))
         self._wt_rec = b.emit(OP_WT_BATCH, i=(0,), n=(0,), t=((S_AUX, 0),))
         video = Sym((S_VIDEO, 0), vshape)
-        if type(model) is R2Plus1D:
-            _, feat = b.video_fwd(model, video, arena=b.oa)
-            outs = [Sym(feat.ref, feat.shape + (1, 1, 1))]       # [B, C, 1, 1, 1], as the module returns them
+        if type(model) in (R2Plus1D, Conv2D):
+            _, feat = b.tower_fwd(model, self.vshape, arena=b.oa)
+            # [B, C, 1, 1, 1] (R2Plus1D) / [B, C, 1, 1] (Conv2D), as the module returns them
+            outs = [Sym(feat.ref, feat.shape + ((1, 1) if type(model) is Conv2D else (1, 1, 1)))]
         elif type(model) is ClassificationWrapper:
             cls = _classifier(model)
-            _, feat = b.video_fwd(model.feature_extractor, video)
+            _, feat = b.tower_fwd(model.feature_extractor, self.vshape)
             outs = [b.cls_linear_fwd(cls, feat, arena=b.oa)]
         elif type(model) is AV_Wrapper:
             if not model.use_linear_proj or ashape is None:
@@ -1480,7 +1532,7 @@ class EvalPlan(Programs):
             b.wait(ST_MAIN, A_S)
         elif type(model) is MOSTModel:
             heads = _probe_heads(model)
-            V, _ = b.video_fwd(model.feature_extractor, video)
+            V, _ = b.tower_fwd(model.feature_extractor, self.vshape)
             Cn = heads[0].classifier.weight.shape[0]
             self.out_names = list(model.feat_names)
             outs = [b.probe_head_fwd(c, V["stages"][c.feat_name], Cn, False, arena=b.oa)["logits"] for c in heads]
@@ -1580,7 +1632,7 @@ def eval_plan(model, *inputs):
     ``ops.wino_configure`` / ``tconv_configure`` / ``set_cu_budget`` bump); the key's leading "eval" keeps it apart from theirs."""
     if not EVAL_ENABLED or not ENABLED or not inputs or len(inputs) > 2:
         return None
-    if not _inputs_ok(inputs) or not _tree_ok(model, training=False):
+    if not _inputs_ok(inputs, _audio_tower(model)) or not _tree_ok(model, training=False):
         return None
     shapes = tuple(tuple(x.shape) for x in inputs)
     dev = inputs[0].device
@@ -1589,7 +1641,7 @@ def eval_plan(model, *inputs):
 
 
 def run_eval(model, *inputs):
-    """``model.eval()(*inputs)`` under ``torch.no_grad()`` through an inference program: the output tensor (``R2Plus1D``,
+    """``model.eval()(*inputs)`` under ``torch.no_grad()`` through an inference program: the output tensor (``R2Plus1D``, ``Conv2D``,
     ``ClassificationWrapper``), the tuple of embeddings (``AV_Wrapper``) or the dict of logits (``MOSTModel``); None when the model / call is outside what the
     compiler knows.  Reached only from ``parallel.Inference``: ``model(x)`` in eval mode stays on the per-layer path."""
     pl = eval_plan(model, *inputs)

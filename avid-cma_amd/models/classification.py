@@ -4,9 +4,10 @@
 has the reference's constructor, ``state_dict`` keys and shapes (``feature_extractor.*``, ``classifier.weight``,
 ``classifier.bias``) and ``forward(video) -> logits [B, n_classes]``.
 
-* A training call on the GPU through the stock tree (``feat_name="pool"``, no pooling op, this package's ``R2Plus1D``,
-  fp32 trainable parameters, nothing hooked) runs as two launch programs: the tower, dropout and the classifier forward,
-  and their mirror image backward (``avid_hip.plan.ClsPlan``), one autograd node.
+* A training call on the GPU through the stock tree (``feat_name="pool"``, no pooling op, this package's ``R2Plus1D`` on
+  clips or its ``Conv2D`` on spectrograms ``[B, 1, T, F]``, fp32 trainable parameters, nothing hooked) runs as two launch
+  programs: the tower, dropout and the classifier forward, and their mirror image backward (``avid_hip.plan.ClsPlan``), one
+  autograd node.
 * The classifier is a ``ClsLinear`` (``nn.Linear``'s keys and initialisation) computed by ``avid_cls_linear_fwd`` / ``_bwd``,
   which take any number of classes (the heads' igemm takes multiples of 64; UCF-101 and HMDB-51 have 101 and 51).
 * Everything else takes the per-layer path with the HIP ops: evaluation, other ``feat_name`` values (the tower is asked

@@ -13,8 +13,10 @@ and move their running statistics.  That quirk is the published protocol; ``trai
   copy of the tap), then ``avid_bn1d_*`` and ``avid_probe_linear_*`` (matrix pipe, any number of classes).
 * A training call of that stock model around this package's ``R2Plus1D`` — every module in training mode, nothing hooked,
   gradients on — runs the tower, the pools and the heads as one forward launch program and the heads' backward as another
-  (``avid_hip.plan.ProbePlan``); ``avid_hip.parallel.ProbeStep`` adds the four losses and Adam.  Every other call (eval, a
-  hook, a tower put in eval mode by hand) walks the modules, the tower with ``return_embs``.
+  (``avid_hip.plan.ProbePlan``); so does one around this package's ``Conv2D`` on spectrograms ``[B, 1, T, F]`` whose pooling
+  ops are ``AdaptiveMaxPool2d((h, w))`` strings (sound classification: the taps are 2-D); ``avid_hip.parallel.ProbeStep``
+  adds the four losses and Adam.  Every other call (eval, a hook, a tower put in eval mode by hand) walks the modules, the
+  tower with ``return_embs``.
 * Any other pooling string, ``l2_norm``, ``use_dropout`` or ``use_bn=False`` takes the torch ops exactly as the reference
   builds them (correct, not fast), and so do CPU tensors; the BatchNorm1d and Linear of a GPU batch still run on the
   kernels above.
@@ -29,6 +31,19 @@ from avid_hip import ops
 __all__ = ["MOSTModel", "Classifier", "ProbeBatchNorm1d", "ProbeLinear"]
 
 _ADAPTIVE = re.compile(r"^\s*AdaptiveMaxPool3d\(\s*\(\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\)\s*\)\s*$")
+_ADAPTIVE_2D = re.compile(r"^\s*AdaptiveMaxPool2d\(\s*\(\s*(\d+)\s*,\s*(\d+)\s*\)\s*\)\s*$")
+
+
+def _pool_size(pooling):
+    """(t, h, w) of an ``AdaptiveMaxPool3d((t, h, w))`` string, (1, h, w) of an ``AdaptiveMaxPool2d((h, w))`` string (the audio
+    tower's taps have no time axis of their own), None for anything else."""
+    if not isinstance(pooling, str):
+        return None
+    m = _ADAPTIVE.match(pooling)
+    if m:
+        return tuple(int(v) for v in m.groups())
+    m = _ADAPTIVE_2D.match(pooling)
+    return (1,) + tuple(int(v) for v in m.groups()) if m else None
 
 
 class ProbeBatchNorm1d(nn.BatchNorm1d):
@@ -59,8 +74,7 @@ class Classifier(nn.Module):
         self.use_bn = use_bn
         self.feat_name = feat_name
         self.pooling = eval("nn." + pooling, {"nn": nn, "torch": torch}) if pooling is not None else None
-        m = _ADAPTIVE.match(pooling) if isinstance(pooling, str) else None
-        self.pool_size = tuple(int(v) for v in m.groups()) if m else None
+        self.pool_size = _pool_size(pooling)
         self.l2_norm = l2_norm
         if use_bn:
             self.bn = ProbeBatchNorm1d(feat_dim)
