@@ -308,7 +308,7 @@ def _desc_cached(xs, cin, cout, k, stride, pad, channel_first):
     if hit is None:
         d = _desc(xs, cin, cout, k, stride, pad, channel_first)
         hit = (d, lib.raw("avid_conv_fwd_workspace_bytes")(C.byref(d)),
-               0 if channel_first else lib.raw("avid_conv_dgrad_workspace_bytes")(C.byref(d)),
+               lib.raw("avid_conv_dgrad_workspace_bytes")(C.byref(d)),       # (0 for a channel-first stem)
                lib.raw("avid_conv_wgrad_workspace_bytes")(C.byref(d)),
                lib.raw("avid_conv_fwd_stats_rows")(C.byref(d)))
         d.bn_bwd_rows = 0 if channel_first else lib.raw("avid_conv_dgrad_bn_rows")(C.byref(d))
@@ -775,8 +775,6 @@ class _ConvCL(Function):
             dy = g
         dx = dw = dadd = dbias = None
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if need_dx and ctx.channel_first:
-            raise AvidHipError("conv: input gradient of a channel-first stem is not implemented (never needed)")
 
         def run_wgrad():
             ws = workspace(x.device, ctx.nb_wgrad)
@@ -853,7 +851,14 @@ class _ConvCL(Function):
                         d_res.record_stream(trail)
                 else:
                     dw_res = run_wgrad_res()
-        if need_dx:
+        if need_dx and ctx.channel_first:
+            # a stem: dx channel-first like x (saliency maps, adversarial probes, derivative checks) — stem_dgrad_kernel reads
+            # the parameter as it is and needs no workspace; any other channel-first geometry raises here (AVID_E_UNSUPPORTED)
+            if d_tap is not None:
+                raise AvidHipError("conv: a channel-first stem has no tap to fold into its input gradient")
+            dx = torch.empty_like(x)
+            lib.call("avid_conv_dgrad", C.byref(d), _p(dy), _p(w), None, None, None, None, _p(dx), None, None, 0, st)
+        elif need_dx:
             ws = workspace(x.device, ctx.nb_dgrad)
             dx = torch.empty_like(x)
             fuse = None

@@ -1192,8 +1192,12 @@ def _inputs_ok(inputs, audio_tower=False):
 
 def eligible(model, *inputs, need_grad=True):
     """The launch-program path applies: a training call (gradients on, unless ``need_grad`` is False: ``FinetuneStep`` runs
-    the programs itself) on inputs the programs take (``_inputs_ok``) through the stock module tree, nothing hooked."""
+    the programs itself) on inputs the programs take (``_inputs_ok``) through the stock module tree, nothing hooked.  An
+    input that requires a gradient sends the call to the per-layer path: the backward programs stop at the stems' weight
+    gradients, ``ops._ConvCL.backward`` goes on to the clip / the spectrogram (``stem_dgrad_kernel``)."""
     if not ENABLED or not model.training or (need_grad and not torch.is_grad_enabled()):
+        return False
+    if need_grad and any(torch.is_tensor(x) and x.requires_grad for x in inputs):
         return False
     return _inputs_ok(inputs, _audio_tower(model)) and _tree_ok(model)
 

@@ -4058,6 +4058,7 @@ static size_t dgrad_compact_bytes(const avid_conv_desc* d) {
 
 extern "C" size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d) {
   if (!d || validate(d)) return 0;
+  if (d->x_channel_first) return 0;            // the stems (stem_dgrad_kernel) need none; no other channel-first layer has a dgrad
   if (dgrad_compactable(d)) {
     const avid_conv_desc c = dgrad_compact_desc(d);
     return dgrad_compact_bytes(d) + avid_conv_dgrad_workspace_bytes(&c);
@@ -4127,6 +4128,14 @@ extern "C" int avid_conv_dgrad(const avid_conv_desc* d, const float* dy, const f
                                void* ws, size_t ws_bytes, avid_stream_t stream) {
   int rc = validate(d);
   if (rc) return rc;
+  if (d->x_channel_first) {                    // the stems: dx channel-first like x, straight from w, no workspace
+    AVID_REQUIRE(stem_dgrad_supported(d), AVID_E_UNSUPPORTED,
+                 "conv_dgrad: the only channel-first layers with an input gradient are the (3,7,7) / (1,7,7) stride-(1,2,2) stems");
+    AVID_REQUIRE(dy && w && dx, AVID_E_BADARG, "conv_dgrad: null pointer");
+    AVID_REQUIRE(!wt_in && !u && !addend && !addend_stride && !bn, AVID_E_BADARG,
+                 "conv_dgrad: a channel-first stem takes no wt / u / addend / addend_stride / bn");
+    return stem_dgrad(d, dy, w, dx, (hipStream_t)stream);
+  }
   AVID_REQUIRE(dy && w && dx && ws, AVID_E_BADARG, "conv_dgrad: null pointer");
   bool sparse_add = false;
   if (addend && addend_stride) {
@@ -4666,7 +4675,10 @@ extern "C" int avid_conv_kernel_name(const avid_conv_desc* d, int which, char* b
   } else if (which == 1) {
     const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
     const bool strided = d->st > 1 || d->sh > 1 || d->sw > 1;
-    if (wino_supported(d, 1)) {
+    if (d->x_channel_first) {
+      AVID_REQUIRE(stem_dgrad_supported(d), AVID_E_UNSUPPORTED, "conv_kernel_name: this channel-first layer has no input gradient");
+      snprintf(buf, len, "stem_dgrad_kernel<%d,%d>", d->Cin, d->kt);
+    } else if (wino_supported(d, 1)) {
       snprintf(buf, len, "wino_kernel<1> grid=%d", wino_grid(d, 1));
     } else if (strided && dgrad_compactable(d)) {
       snprintf(buf, len, "igemm_pk_kernel over the sub-sampled grid + dx_scatter_strided_kernel");

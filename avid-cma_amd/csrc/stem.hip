@@ -1514,6 +1514,138 @@ int stem_wgrad(const avid_conv_desc* d, const float* x, const float* dy, float* 
   return d->Cin == 3 ? stem_wgrad_launch<3, 3>(d, x, dy, dw, ws, s) : stem_wgrad_launch<1, 1>(d, x, dy, dw, ws, s);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Input gradient of the two stems (stem_dgrad_kernel): dx[b][c][t][h][w], channel-first like the x the forward reads.
+//
+// A thread owns one QUAD of input pixels (h = 2i + ph, w = 2j + pw: the four stride-parity classes) of one (b, t) frame and all
+// CIN channels of it.  Tap kh of pixel row h pairs with output row ho = (h + 3 - kh) / 2, so with a = ho - (i - 1) in 0..3 the
+// tap is kh = ph + 5 - 2a (ph = 0: taps 5, 3, 1 of a = 0, 1, 2; ph = 1: taps 6, 4, 2, 0), the same along w: the quad reads the
+// 4 x 4 dy positions around it and every one of the 49 taps meets exactly one (position, pixel) pair — no tap is tested at run
+// time, the loops unroll into 49 * CIN multiply-adds per dy value.  A workgroup (256 threads) owns 8 x 32 quads (16 x 64
+// input pixels) and stages the 11 x 35 dy positions they reach in LDS, 16 of the 64 channels per stage (pitch 17 floats:
+// the lanes of a quad row read disjoint banks), zero where the position is outside the frame.  The
+// weights are read straight from the parameter [64][KT][7][7][CIN] with wave-uniform indices (scalar loads).
+//
+// Every dx element is the sum one thread makes in one fixed order — frames kt, channel stages, positions, taps — whatever the
+// grid: the same bits on every run and under every CU budget, no atomics, no workspace.  Plain fp32 multiply-adds (no matrix
+// pipe); each (frame, 16-channel stage) is summed on its own (<= 256 terms) and then added to the total, so the rounding
+// error grows with sqrt(256 + 12) rather than sqrt(3072) terms.
+constexpr int SD_QH = 8, SD_QW = 32;                   // quads per workgroup tile
+constexpr int SD_PH = SD_QH + 3, SD_PW = SD_QW + 3;    // dy positions the tile's taps reach
+constexpr int SD_CC = 16;                              // dy channels per LDS stage
+constexpr int SD_LD = SD_CC + 1;                       // floats per staged position (odd: the lanes of a row read disjoint banks)
+
+template <int CIN, int KT>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                         float* __restrict__ dx, int Ti, int Hi, int Wi, int Ho, int Wo,
+                                                         int tiles_h, int tiles_w, int ntiles) {
+  __shared__ float S[SD_PH * SD_PW * SD_LD];
+  const int tid = threadIdx.x;
+  const int qi = tid >> 5, qj = tid & 31;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    int r = tile;
+    const int tw = r % tiles_w; r /= tiles_w;
+    const int th = r % tiles_h; r /= tiles_h;
+    const int t = r % Ti, b = r / Ti;
+    const int i0 = th * SD_QH, j0 = tw * SD_QW;
+    const int h0 = 2 * (i0 + qi), w0 = 2 * (j0 + qj);
+    const bool active = h0 < Hi && w0 < Wi;
+    float acc[2][2][CIN];
+#pragma unroll
+    for (int e = 0; e < 4 * CIN; ++e) (&acc[0][0][0])[e] = 0.f;
+    for (int kt = 0; kt < KT; ++kt) {
+      const int to = t + KT / 2 - kt;                  // (pt = KT / 2, st = 1, To == Ti: stem_match)
+      if ((unsigned)to >= (unsigned)Ti) continue;      // the same for the whole workgroup
+      // (offsets inside one frame of dy fit 32 bits: validate() bounds a batch item's span)
+      const float* __restrict__ dyf = dy + ((long long)b * Ti + to) * Ho * Wo * 64;
+      for (int cc = 0; cc < 64 / SD_CC; ++cc) {
+        __syncthreads();
+        for (int e = tid; e < SD_PH * SD_PW * (SD_CC / 4); e += 256) {
+          const int c4 = e & (SD_CC / 4 - 1), pos = e / (SD_CC / 4);
+          const int pr = pos / SD_PW, pc = pos - pr * SD_PW;
+          const int ho = i0 - 1 + pr, wo = j0 - 1 + pc;
+          floatx4 v = {0.f, 0.f, 0.f, 0.f};
+          if ((unsigned)ho < (unsigned)Ho && (unsigned)wo < (unsigned)Wo)
+            v = *reinterpret_cast<const floatx4*>(dyf + (ho * Wo + wo) * 64 + cc * SD_CC + c4 * 4);
+          float* o = S + pos * SD_LD + c4 * 4;
+          o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+        }
+        __syncthreads();
+        if (!active) continue;
+        float part[2][2][CIN];
+#pragma unroll
+        for (int e = 0; e < 4 * CIN; ++e) (&part[0][0][0])[e] = 0.f;
+        const float* __restrict__ wc = w + ((cc * SD_CC) * KT + kt) * (49 * CIN);
+#pragma unroll 1
+        for (int k = 0; k < SD_CC; ++k) {
+          float v[4][4];
+#pragma unroll
+          for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int bb = 0; bb < 4; ++bb) v[a][bb] = S[((qi + a) * SD_PW + qj + bb) * SD_LD + k];
+          const float* __restrict__ wk = wc + k * (KT * 49 * CIN);
+#pragma unroll
+          for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int ph = 0; ph < 2; ++ph) {
+              const int kh = ph + 5 - 2 * a;
+              if (kh < 0 || kh > 6) continue;
+#pragma unroll
+              for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+                for (int pw = 0; pw < 2; ++pw) {
+                  const int kw = pw + 5 - 2 * bb;
+                  if (kw < 0 || kw > 6) continue;
+#pragma unroll
+                  for (int c = 0; c < CIN; ++c)
+                    part[ph][pw][c] = fmaf(v[a][bb], wk[(kh * 7 + kw) * CIN + c], part[ph][pw][c]);
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4 * CIN; ++e) (&acc[0][0][0])[e] += (&part[0][0][0])[e];
+      }
+    }
+    if (active) {
+#pragma unroll
+      for (int c = 0; c < CIN; ++c)
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph) {
+          if (h0 + ph >= Hi) continue;
+          float* o = dx + ((((long long)b * CIN + c) * Ti + t) * Hi + (h0 + ph)) * Wi + w0;
+          if ((Wi & 1) == 0) {                         // (even rows: w0 + 1 < Wi and the pair is 8-byte aligned)
+            const floatx2_t v2 = {acc[ph][0][c], acc[ph][1][c]};
+            *reinterpret_cast<floatx2_t*>(o) = v2;
+          } else {
+            o[0] = acc[ph][0][c];
+            if (w0 + 1 < Wi) o[1] = acc[ph][1][c];
+          }
+        }
+    }
+  }
+}
+
+bool stem_dgrad_supported(const avid_conv_desc* d) { return stem_match(d); }
+
+template <int CIN, int KT>
+static int stem_dgrad_launch(const avid_conv_desc* d, const float* dy, const float* w, float* dx, hipStream_t s) {
+  const int tiles_h = ((d->Hi + 1) / 2 + SD_QH - 1) / SD_QH, tiles_w = ((d->Wi + 1) / 2 + SD_QW - 1) / SD_QW;
+  const long long ntiles = (long long)d->B * d->Ti * tiles_h * tiles_w;
+  AVID_REQUIRE(ntiles < (1ll << 31), AVID_E_UNSUPPORTED, "conv_dgrad: more than 2^31 tiles");
+  const long long slots = 4ll * device_cus();          // workgroups resident on the CUs (registers: four waves per SIMD)
+  const int grid = (int)(ntiles < slots ? ntiles : slots);
+  const double M = (double)d->B * d->To * d->Ho * d->Wo, K = (double)CIN * KT * 49;
+  ScopedTimer t(s, CIN == 3 ? "stem_dgrad_kernel<3,3>" : "stem_dgrad_kernel<1,1>", 2.0 * M * 64 * K,
+                4.0 * ((double)d->B * CIN * d->Ti * d->Hi * d->Wi + 64 * K + M * 64));
+  hipLaunchKernelGGL((stem_dgrad_kernel<CIN, KT>), dim3(grid), dim3(256), 0, s, dy, w, dx, d->Ti, d->Hi, d->Wi, d->Ho, d->Wo,
+                     tiles_h, tiles_w, (int)ntiles);
+  return check_launch("stem_dgrad");
+}
+
+int stem_dgrad(const avid_conv_desc* d, const float* dy, const float* w, float* dx, hipStream_t s) {
+  return d->Cin == 3 ? stem_dgrad_launch<3, 3>(d, dy, w, dx, s) : stem_dgrad_launch<1, 1>(d, dy, w, dx, s);
+}
+
 }  // namespace avid
 
 extern "C" int avid_stem_fwd_pre_configure(int on) {

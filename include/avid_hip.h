@@ -67,7 +67,7 @@ typedef struct avid_conv_desc {
   int32_t kt, kh, kw;         /* kernel extent */
   int32_t st, sh, sw;         /* stride */
   int32_t pt, ph, pw;         /* zero padding */
-  int32_t x_channel_first;    /* 1: x is [B,Cin,Ti,Hi,Wi] (stems only; Cin in {1,3}) */
+  int32_t x_channel_first;    /* 1: x (and the dx of avid_conv_dgrad) is [B,Cin,Ti,Hi,Wi] (stems only; Cin in {1,3}) */
 } avid_conv_desc;
 
 /* y = conv(x, w) [+ addend] [+ bias] [relu].  addend: [B,To,Ho,Wo,Cout] or NULL (residual add of
@@ -140,7 +140,14 @@ long long avid_debug_out_affine_launches(void);
  * avid_weight_transpose_batched; NULL = transform inside the call.  Each pointer is read only by the path it belongs
  * to: a Winograd-eligible layer that falls through to the implicit GEMM (compact addend) reads wt, never u.
  * A layer with avid_conv_uses_split(d, 1) != 0 (version >= 120) takes its mode-6 table as u and then reads neither wt
- * nor the repack scratch. */
+ * nor the repack scratch.
+ * x_channel_first = 1 (version >= 166): the input gradient of the two stems — Cin 3, kernel (3,7,7), padding (1,3,3) and
+ * Cin 1, kernel (1,7,7), padding (0,3,3), both Cout 64 and stride (1,2,2), any input size.  dy is channels-last
+ * [B,To,Ho,Wo,64], w the parameter's memory, dx channel-first [B,Cin,Ti,Hi,Wi] like the x the forward read
+ * (stem_dgrad_kernel: plain fp32 multiply-adds in one fixed order per element — the same bits on every run and under
+ * every CU budget).  wt, u, addend, addend_stride and bn must be NULL (AVID_E_BADARG otherwise); no workspace
+ * (avid_conv_dgrad_workspace_bytes == 0, ws may be NULL) and avid_conv_dgrad_bn_rows == 0.  Any other channel-first
+ * geometry: AVID_E_UNSUPPORTED before anything is launched. */
 size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d);
 /* bn (or NULL): dx is the COMPLETE gradient of the output of a training-mode BatchNorm(+ReLU) whose input was
  * bn->x (shape of dx) — the usual conv <- ReLU <- BN chain of models/network_blocks.py:30-60.  The dgrad epilogue
