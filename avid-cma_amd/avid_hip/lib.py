@@ -219,6 +219,7 @@ SIGNATURES = {
     "avid_dropout_fwd": (_i, [_i64, _i64, _f, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "avid_dropout_bwd": (_i, [_i64, _f, _vp, _vp, _vp, _vp]),
     "avid_cls_loss": (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avid_mlabel_loss": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_cls_linear_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avid_cls_linear_bwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_adaptive_maxpool_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
@@ -250,6 +251,8 @@ SIGNATURES = {
     "avid_knn_workspace_bytes": (_sz, [_i64, _i, _i]),
     "avid_knn_search": (_i, [_i64, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avid_knn_vote": (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "avid_rank_metrics_workspace_bytes": (_sz, [_i64, _i]),
+    "avid_rank_metrics": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "avid_adam_flat": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp]),
     "avid_sgd_flat": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp]),
     "avid_grad_accum_flat": (_i, [_i64, _vp, _vp, _vp, _vp]),

@@ -211,6 +211,14 @@ class LabelError(AvidHipError, IndexError):
     """A classification label outside [0, n_classes) reached ``avid_cls_loss`` (where the reference's cross-entropy raises)."""
 
 
+class TargetError(AvidHipError, ValueError):
+    """A multi-label target outside [0, 1] or not finite reached ``avid_mlabel_loss`` (where torch's binary_cross_entropy raises)."""
+
+
+class ScoreError(AvidHipError, ValueError):
+    """A NaN score reached ``avid_rank_metrics`` (where scikit-learn's metrics raise)."""
+
+
 class DeviceErrors:
     """One int32 error word per device that the gather / scatter kernels OR a code into when they meet an id
     outside [0, N) — where the reference's indexing raises (criterions/avid.py:57-62,124; avid_cma.py:199).
@@ -223,7 +231,9 @@ class DeviceErrors:
     _MSG = {1: "bank_scores: negative / positive index outside [0, num_data)",
             2: "update_memory: sample index outside [0, num_data)",
             4: "memory_sampling: sample index outside [0, num_data) (positive_set lookup)",
-            8: "cls_loss: label outside [0, n_classes)"}
+            8: "cls_loss: label outside [0, n_classes)",
+            16: "mlabel_loss: target outside [0, 1] or not finite",
+            32: "rank_metrics: NaN score"}
     _inst = {}
 
     def __init__(self, device):
@@ -246,8 +256,9 @@ class DeviceErrors:
         self.host.zero_()
         self.event = None
         what = "; ".join(m for b, m in self._MSG.items() if code & b) or f"code {code}"
-        cls = LabelError if code & 8 else IndexError
-        raise cls(f"avid_hip: index out of range in a device kernel — {what}")
+        cls = LabelError if code & 8 else IndexError if code & 7 else TargetError if code & 16 else ScoreError if code & 32 else IndexError
+        kind = "index out of range" if code & 15 else "value out of range"
+        raise cls(f"avid_hip: {kind} in a device kernel — {what}")
 
     def poll(self):
         if torch.cuda.is_current_stream_capturing():
@@ -1902,6 +1913,107 @@ def cls_loss(logits, labels, clips=1, grad_scale=None):
              float(grad_scale if grad_scale is not None else 0.0), _p(out), _p(conf), _p(hits), _p(dl), errs.ptr(), _stream())
     errs.poll()
     return out[0], conf, hits, dl
+
+
+def _mlabel_args(logits, targets, clips, pos_weight):
+    """The checked arguments of ``mlabel_loss``: (logits, targets, pos_weight) contiguous, V, C.  Refuses before any launch."""
+    for name, t in (("logits", logits), ("targets", targets), ("pos_weight", pos_weight)):
+        if t is None and name == "pos_weight":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise AvidHipError(f"mlabel_loss: {name} must be a HIP device tensor — there is no CPU fallback")
+        if t.dtype != torch.float32:
+            raise AvidHipError(f"mlabel_loss: {name} must be float32, got {t.dtype}")
+        if t.device != logits.device:
+            raise AvidHipError(f"mlabel_loss: {name} is on {t.device}, the logits on {logits.device}")
+    clips = int(clips)
+    if logits.dim() != 2 or targets.dim() != 2 or clips < 1:
+        raise AvidHipError("mlabel_loss: logits [V * clips, C], targets [V, C], clips >= 1 expected")
+    R, C = logits.shape
+    V = targets.shape[0]
+    if V < 1 or V * clips != R or targets.shape[1] != C:
+        raise AvidHipError(f"mlabel_loss: logits {tuple(logits.shape)} do not match targets {tuple(targets.shape)} x {clips} clips")
+    if not 1 <= C <= 1024:
+        raise AvidHipError(f"mlabel_loss: {C} classes outside [1, 1024]")
+    if pos_weight is not None and tuple(pos_weight.shape) != (C,):
+        raise AvidHipError(f"mlabel_loss: pos_weight must be [{C}], got {tuple(pos_weight.shape)}")
+    return logits.contiguous(), targets.contiguous(), None if pos_weight is None else pos_weight.contiguous(), V, C
+
+
+def _mlabel_launch(logits, targets, clips, pos_weight, V, C, grad_scale):
+    dev = logits.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    conf = torch.empty((V, C), dtype=torch.float32, device=dev)
+    hits = torch.empty(2, dtype=torch.int64, device=dev)
+    dl = torch.empty_like(logits) if grad_scale is not None else None
+    errs = DeviceErrors.get(dev)
+    lib.call("avid_mlabel_loss", V, int(clips), C, _p(logits), _p(targets), _p(pos_weight),
+             float(grad_scale if grad_scale is not None else 0.0), _p(out), _p(conf), _p(hits), _p(dl), errs.ptr(), _stream())
+    errs.poll()
+    return out[0], conf, hits, dl
+
+
+class _MlabelLoss(Function):
+    """logits -> loss: the launch writes ``dlogits`` with the forward, the backward scales it by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, clips, pos_weight, V, C, grad_scale):
+        loss, conf, hits, dl = _mlabel_launch(logits, targets, clips, pos_weight, V, C, grad_scale)
+        ctx.save_for_backward(dl)
+        ctx.gs = float(grad_scale)
+        ctx.mark_non_differentiable(conf, hits, dl)
+        return loss, conf, hits, dl
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (dl,) = ctx.saved_tensors
+        return dl * (g if ctx.gs == 1.0 else g / ctx.gs), None, None, None, None, None, None
+
+
+def mlabel_loss(logits, targets, clips=1, pos_weight=None, grad_scale=None):
+    """Binary cross-entropy with logits (``torch.nn.functional.binary_cross_entropy_with_logits``, mean reduction) of
+    ``logits [V * clips, C]`` against ``targets [V, C]`` in [0, 1] (a video's clips share its targets), ``pos_weight [C]``
+    optional — ``avid_mlabel_loss``, no host synchronisation.  Returns device tensors ``(loss [], confidence [V, C], hits [2]
+    int64, dlogits)`` as ``cls_loss`` does: the confidence is the clips' mean SIGMOID; a class is positive iff its target is
+    >= 0.5; ``hits[0]`` counts the videos whose highest-confidence class (ties: the lower index) is positive, ``hits[1]`` the
+    (video, class) pairs on the right side of 0.5; ``dlogits`` = d(loss * grad_scale) / d(logits), or None when ``grad_scale``
+    is None.  When the logits require a gradient the loss is also a node of the autograd graph (``loss.backward()``).  A target
+    outside [0, 1] or not finite raises ``TargetError`` at the next poll of the device error word."""
+    logits_c, targets, pos_weight, V, C = _mlabel_args(logits, targets, clips, pos_weight)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        loss, conf, hits, dl = _MlabelLoss.apply(logits_c, targets, int(clips), pos_weight, V, C,
+                                                 1.0 if grad_scale is None else float(grad_scale))
+        return loss, conf, hits, (dl if grad_scale is not None else None)
+    return _mlabel_launch(logits_c, targets, clips, pos_weight, V, C, grad_scale)
+
+
+def rank_metrics(scores, targets):
+    """Per-class average precision and ROC-AUC of ``scores [N, C]`` against ``targets [N, C]`` (float32, positive iff >= 0.5)
+    on the device — ``avid_rank_metrics``: scikit-learn's ``average_precision_score`` / ``roc_auc_score`` per column, ties
+    handled, no sort and no host synchronisation.  Returns ``(ap float64 [C], auc float64 [C], n_pos int64 [C])``; ``ap`` is
+    NaN for a class without positives, ``auc`` also for one without negatives.  A NaN score makes its class NaN and raises
+    ``ScoreError`` at the next poll of the device error word."""
+    for name, t in (("scores", scores), ("targets", targets)):
+        _knn_arg("rank_metrics: " + name, t, torch.float32)
+        if t.dim() != 2:
+            raise AvidHipError(f"rank_metrics: {name} must be [N, C]")
+    if scores.shape != targets.shape or scores.device != targets.device or scores.numel() == 0:
+        raise AvidHipError(f"rank_metrics: scores {tuple(scores.shape)} on {scores.device} do not match targets "
+                           f"{tuple(targets.shape)} on {targets.device}")
+    N, C = scores.shape
+    need = int(lib.raw("avid_rank_metrics_workspace_bytes")(N, C))
+    if need == 0:
+        raise AvidHipError(f"rank_metrics: N = {N} / C = {C} beyond the kernels' index range")
+    dev = scores.device
+    ws = workspace(dev, need)
+    ap = torch.empty(C, dtype=torch.float64, device=dev)
+    auc = torch.empty(C, dtype=torch.float64, device=dev)
+    n_pos = torch.empty(C, dtype=torch.int64, device=dev)
+    errs = DeviceErrors.get(dev)
+    lib.call("avid_rank_metrics", N, C, _p(scores), _p(targets), _p(ap), _p(auc), _p(n_pos), _p(ws), ws.numel(), errs.ptr(),
+             _stream())
+    errs.poll()
+    return ap, auc, n_pos
 
 
 class _ClsLinear(Function):

@@ -683,14 +683,52 @@ class AdamStep(EngineCore):
         return b, [(c, labels[r * b:(r + 1) * b]) for r, c in enumerate(clips)]
 
     # ---- what the supervised steps (FinetuneStep, ProbeStep) share
+    def _set_loss(self, loss, pos_weight, n_classes):
+        """The loss kind of a supervised engine: ``"ce"`` (softmax cross-entropy against int64 labels [B], ``avid_cls_loss``) or
+        ``"bce"`` (binary cross-entropy with logits against float32 targets [B, C], ``avid_mlabel_loss``; ``pos_weight``: [C]
+        values, kept as one float32 device tensor that the compiled programs reference)."""
+        from . import plan
+        try:
+            self.n_classes = int(n_classes() if callable(n_classes) else n_classes)
+        except (AttributeError, StopIteration, TypeError):
+            self.n_classes = None            # (a model outside the compiled patterns: step() says so)
+        if loss == "bce" and self.n_classes is None:
+            raise ValueError(f"{type(self).__name__}: loss='bce' needs a model whose classifier says how many classes there are")
+        if pos_weight is not None:
+            if loss != "bce":
+                raise ValueError(f"{type(self).__name__}: pos_weight belongs to loss='bce'")
+            pos_weight = torch.as_tensor(pos_weight).detach().to(device=self.flat.flat.device, dtype=torch.float32).contiguous()
+            if tuple(pos_weight.shape) != (self.n_classes,):
+                raise ValueError(f"{type(self).__name__}: pos_weight must hold {self.n_classes} values (one per class), got "
+                                 f"{tuple(pos_weight.shape)}")
+        self.loss, self.pos_weight = plan._loss_kind(loss, pos_weight, self.n_classes), pos_weight
+
     def _labelled(self, video, labels):
-        """A supervised step's inputs, contiguous, the labels checked: int64 [B] on the video's device."""
+        """A supervised step's inputs, contiguous, the labels checked: int64 [B] on the video's device — under ``loss="bce"``
+        targets [B, C], float32 (bool / uint8 are converted)."""
         video, labels = video.contiguous(), labels.contiguous()
         B = video.shape[0]
+        if getattr(self, "loss", "ce") == "bce":
+            if labels.dtype in (torch.bool, torch.uint8):
+                labels = labels.to(torch.float32)
+            if labels.dtype != torch.float32 or tuple(labels.shape) != (B, self.n_classes) or labels.device != video.device:
+                raise ValueError(f"{type(self).__name__}.step (loss='bce'): targets must be float32 (or bool / uint8) "
+                                 f"[{B}, {self.n_classes}] on {video.device} (got {labels.dtype} {tuple(labels.shape)} on "
+                                 f"{labels.device})")
+            return video, labels
         if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
             raise ValueError(f"{type(self).__name__}.step: labels must be int64 [{B}] on {video.device} "
                              f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
         return video, labels
+
+    def _eval_loss(self, logits, labels, clips):
+        """``ops.cls_loss`` / ``ops.mlabel_loss`` (the engine's loss kind) over the V * clips logits of a dense evaluation."""
+        from . import ops
+        if self.loss == "bce":
+            if labels.dtype in (torch.bool, torch.uint8):
+                labels = labels.to(torch.float32)
+            return ops.mlabel_loss(logits, labels, clips, self.pos_weight)
+        return ops.cls_loss(logits, labels, clips)
 
     def _evaluate(self, video, batch, finish):
         """``run_phase('test_dense')``: video [V, clips, 3, T, H, W] (an audio tower: spectrograms [V, clips, 1, T, F]) through the
@@ -1556,6 +1594,59 @@ class KNNEval:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Multi-label evaluation: the numbers tagging sets (AudioSet, Charades) are reported in
+# ---------------------------------------------------------------------------------------------------------------------
+class MultiLabelEval:
+    """Accumulates the confidences of a multi-label evaluation — what ``FinetuneStep(loss="bce").evaluate`` returns per batch —
+    and computes mAP, mean ROC-AUC and d' over the whole set on the device (``ops.rank_metrics``: scikit-learn's
+    ``average_precision_score`` / ``roc_auc_score`` per class, ties handled, no sort, no ``[N, C]`` copy to the host).
+
+    ``add(conf, targets)``: ``[n, n_classes]`` each, on one device; float32 confidences, targets float32 / bool / uint8
+    (positive iff >= 0.5).  The tensors are kept as they are; nothing is launched and nothing synchronises.
+    ``compute()`` returns device tensors: ``ap`` / ``auc`` float64 [C] (NaN where undefined: a class without positives, for
+    ``auc`` also one without negatives), ``n_pos`` int64 [C], and over the classes with a defined value ``mAP``, ``mAUC``,
+    ``d_prime`` = sqrt(2) * ndtri(mAUC) (float64 scalars) and ``n_valid`` (int64 [2]: classes behind mAP, behind mAUC).
+    Nothing here is distributed: with several ranks the caller gathers the confidences first."""
+
+    def __init__(self, n_classes):
+        if int(n_classes) < 1:
+            raise ValueError("MultiLabelEval: n_classes must be >= 1")
+        self.n_classes = int(n_classes)
+        self._chunks = []
+
+    def add(self, conf, targets):
+        shape = (conf.shape[0] if conf.dim() == 2 else -1, self.n_classes)
+        if (conf.dim() != 2 or tuple(conf.shape) != shape or tuple(targets.shape) != shape or conf.dtype != torch.float32
+                or targets.dtype not in (torch.float32, torch.bool, torch.uint8) or conf.device != targets.device
+                or not conf.is_cuda or conf.shape[0] < 1):
+            raise ValueError(f"MultiLabelEval.add: conf float32 [n, {self.n_classes}] and targets float32 / bool / uint8 of the "
+                             f"same shape on one HIP device expected (got {conf.dtype} {tuple(conf.shape)} on {conf.device}, "
+                             f"{targets.dtype} {tuple(targets.shape)} on {targets.device})")
+        if self._chunks and self._chunks[0][0].device != conf.device:
+            raise ValueError("MultiLabelEval.add: every chunk must be on the same device")
+        self._chunks.append((conf.detach(), targets.detach()))
+
+    def reset(self):
+        self._chunks = []
+
+    def compute(self):
+        from . import ops
+        if not self._chunks:
+            raise ValueError("MultiLabelEval.compute: nothing was added")
+        conf = torch.cat([c for c, _ in self._chunks], 0).contiguous()
+        targets = torch.cat([t.to(torch.float32) for _, t in self._chunks], 0).contiguous()
+        self._chunks = [(conf, targets)]
+        ap, auc, n_pos = ops.rank_metrics(conf, targets)
+        ok_ap, ok_auc = ~torch.isnan(ap), ~torch.isnan(auc)
+        zero = torch.zeros((), dtype=torch.float64, device=ap.device)
+        # (the mean over no class is NaN: 0 / 0)
+        m_ap = torch.where(ok_ap, ap, zero).sum() / ok_ap.sum()
+        m_auc = torch.where(ok_auc, auc, zero).sum() / ok_auc.sum()
+        return {"ap": ap, "auc": auc, "n_pos": n_pos, "mAP": m_ap, "mAUC": m_auc,
+                "d_prime": math.sqrt(2.0) * torch.special.ndtri(m_auc), "n_valid": torch.stack([ok_ap.sum(), ok_auc.sum()])}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Action-recognition fine-tuning (eval-action-recg.py: run_phase 'train' / 'test_dense', the warm-up epochs of the classifier)
 # ---------------------------------------------------------------------------------------------------------------------
 class FinetuneStep(AdamStep):
@@ -1585,8 +1676,12 @@ class FinetuneStep(AdamStep):
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1):
-        """``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
+                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None):
+        """``loss``: ``"ce"`` (default) or ``"bce"`` — multi-label fine-tuning: ``step(x, targets)`` takes float32 targets [B, C]
+        in [0, 1] (bool / uint8 are converted), the forward program ends in ``avid_mlabel_loss`` (``pos_weight``: [C], optional),
+        ``hits`` are (videos whose highest-confidence class is positive, (video, class) pairs on the right side of 0.5), and
+        ``evaluate`` returns the clip-mean sigmoid as its confidence; everything else as for ``"ce"``.
+        ``broadcast_buffers``: as ``TrainStep``'s — ``"step"`` (default, DistributedDataParallel's behaviour) broadcasts rank
         0's BatchNorm running statistics before every step, ``"lazy"`` only at ``sync_buffers()``, ``"off"`` never.
         ``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard; it judges the slice
         the optimizer updates — with ``virtual_ranks`` the accumulated gradient, a skipped step puts back the running
@@ -1597,6 +1692,7 @@ class FinetuneStep(AdamStep):
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
+        self._set_loss(loss, pos_weight, lambda: model.classifier.weight.shape[0])
         self.virtual_ranks = R
         self.rank_losses = self.rank_hits = None     # [R] float32 / [R, 2] int64 device tensors of the last virtual-rank step
         self._dropout_seeds = None                   # reseed_dropout()'s, while the model's own seed is still the first of them
@@ -1630,7 +1726,7 @@ class FinetuneStep(AdamStep):
 
     def _plan(self, video):
         from . import plan
-        pl = plan.cls_plan(self.model, video, self.classifier_only, need_grad=False)
+        pl = plan.cls_plan(self.model, video, self.classifier_only, need_grad=False, loss=self.loss, pos_weight=self.pos_weight)
         if pl is None or plan._engine_flat(self, pl) is None:
             raise NotImplementedError("FinetuneStep: the model is outside the compiled fine-tuning programs (plan.ClsPlan: "
                                       "ClassificationWrapper(R2Plus1D, feat_name='pool', pooling_op=None), fp32 CUDA "
@@ -1720,7 +1816,7 @@ class FinetuneStep(AdamStep):
         (confidence [V, C], loss [], hits [2] int64)."""
         from . import ops
         clips = video.shape[1]
-        loss, conf, hits, _ = self._evaluate(video, batch, lambda outs: ops.cls_loss(torch.cat(outs, 0), labels, clips))
+        loss, conf, hits, _ = self._evaluate(video, batch, lambda outs: self._eval_loss(torch.cat(outs, 0), labels, clips))
         return conf, loss, hits
 
 
@@ -1745,21 +1841,23 @@ class ProbeStep(AdamStep):
     [R, n_taps, 2] hold every replica's own (None before the first such step)."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
-                 nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1):
+                 nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None):
         """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``.
-        ``virtual_ranks``: see the class."""
+        ``virtual_ranks``: see the class.  ``loss`` / ``pos_weight``: as ``FinetuneStep``'s — ``"bce"`` ends every tap in
+        ``avid_mlabel_loss`` against float32 targets [B, C]."""
         R = _virtual_ranks_arg("ProbeStep", virtual_ranks)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
+        self._set_loss(loss, pos_weight, lambda: next(iter(model.classifiers)).classifier.weight.shape[0])
         self.virtual_ranks = R
         self.rank_losses = self.rank_hits = None     # [R, n_taps] float32 / [R, n_taps, 2] int64 of the last virtual-rank step
 
     def _plan(self, video):
         from . import plan
-        pl = plan.probe_plan(self.model, video, need_grad=False)
+        pl = plan.probe_plan(self.model, video, need_grad=False, loss=self.loss, pos_weight=self.pos_weight)
         if pl is None or plan._engine_flat(self, pl) is None:
             raise NotImplementedError("ProbeStep: the model is outside the compiled probe programs (plan.ProbePlan: MOSTModel("
                                       "R2Plus1D, AdaptiveMaxPool3d heads on conv2x..conv5x, use_bn, no l2_norm / dropout), fp32 "
@@ -1821,6 +1919,6 @@ class ProbeStep(AdamStep):
         (confidence [n_taps, V, C], losses [n_taps], hits [n_taps, 2] int64)."""
         from . import ops
         clips = video.shape[1]
-        res = self._evaluate(video, batch, lambda outs: [ops.cls_loss(torch.cat([o[ft] for o in outs], 0), labels, clips)
+        res = self._evaluate(video, batch, lambda outs: [self._eval_loss(torch.cat([o[ft] for o in outs], 0), labels, clips)
                                                          for ft in self.model.feat_names])
         return (torch.stack([r[1] for r in res]), torch.stack([r[0] for r in res]), torch.stack([r[2] for r in res]))

@@ -1,10 +1,13 @@
-// Action-recognition fine-tuning head: dropout and the classifier's softmax cross-entropy / clip-averaged confidence.
+// Action-recognition fine-tuning head: dropout and the classifier's softmax cross-entropy / clip-averaged confidence, and its
+// multi-label sibling (binary cross-entropy with logits: the reference has no multi-label code; torch's expression is the contract).
 //
 // Reference ops replaced: utils/eval_utils.py:203-213 (torch.nn.Dropout inside ClassificationWrapper),
 // eval-action-recg.py:150-165 (CrossEntropyLoss, Softmax, .view(V, clips, -1).mean(1), metrics_utils.accuracy top-1 / top-5).
 // The classifier Linear(F, C) has kernels of its own below: the heads' igemm (avid_conv_fwd) takes C in multiples of 64 only.
 // No MFMA: the head is a few MFLOP per step; what matters is that it costs few launches and no host synchronisation.
 #include <math.h>
+
+#include <atomic>
 
 #include "common.h"
 
@@ -141,6 +144,157 @@ __global__ __launch_bounds__(CLS_WAVES * 64) void cls_loss_kernel(int V, int cli
 }
 
 // ---------------------------------------------------------------------------------------------
+// Multi-label loss: binary cross-entropy with logits over logits [V * clips][C] (C <= 1024) against targets [V][C], torch's
+// expression l = (1 - t) x + w (log1p(exp(-|x|)) + max(-x, 0)), w = 1 + (pos_weight_c - 1) t.  A dense evaluation hands
+// this kernel 10^7 elements, so it is a grid: workgroup g takes the videos g, g + G, ... (G = min(V, ML_MAX_GRID), a
+// function of V alone), thread i the columns i, i + 256, ... of each and all of that video's clips (the clip sum of the
+// sigmoids stays in a register).  A thread sums its elements' losses in double, in the order it meets them; the workgroup
+// sums its threads' (wave butterfly, then the waves in order) into one MlPart; mlabel_final_kernel sums the G parts in
+// index order.  No floating-point atomics, nothing depends on the CU count: the same bits on every run.
+// Both tails of the sigmoid come from e = exp(-|x|): 1 / (1 + e) and e / (1 + e), so 1 - sigmoid(x) does not cancel.
+// The parts live in one of ML_RING slabs of device memory owned by the library, drawn round-robin per call (the event
+// pool's contract, program.hip): a slab is written again after ML_RING further calls on the same device.
+// ---------------------------------------------------------------------------------------------
+constexpr int ML_THREADS = 256;
+constexpr int ML_COLS = CLS_MAX_C / ML_THREADS;
+constexpr int ML_MAX_GRID = 1024;
+constexpr int ML_RING = 16;
+
+struct MlPart {
+  double loss;
+  long long top, pairs, pad;
+};
+__device__ MlPart g_ml_part[ML_RING][ML_MAX_GRID];
+
+__global__ __launch_bounds__(ML_THREADS) void mlabel_loss_kernel(int V, int clips, int C, const float* __restrict__ logits,
+                                                                 const float* __restrict__ targets,
+                                                                 const float* __restrict__ pos_weight, float grad_scale,
+                                                                 float* __restrict__ conf, float* __restrict__ dlogits,
+                                                                 int* __restrict__ err, MlPart* __restrict__ part) {
+  __shared__ float s_bv[ML_THREADS / 64];
+  __shared__ int s_bi[ML_THREADS / 64], s_bt[ML_THREADS / 64];
+  __shared__ double s_loss[ML_THREADS / 64];
+  __shared__ long long s_pairs[ML_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float dscale = grad_scale / (float)((long long)V * clips * C);
+  double tloss = 0.0;
+  long long tpairs = 0, top = 0;      // (top: thread 0's)
+  bool bad = false;
+  for (int v = blockIdx.x; v < V; v += gridDim.x) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff, bt = 0;
+#pragma unroll
+    for (int j = 0; j < ML_COLS; ++j) {
+      const int c = tid + j * ML_THREADS;
+      if (c >= C) break;
+      const float t = targets[(long long)v * C + c];
+      bad = bad || !(t >= 0.f && t <= 1.f);
+      const float w = 1.f + ((pos_weight ? pos_weight[c] : 1.f) - 1.f) * t, a = 1.f - t;
+      float acc = 0.f;
+      for (int k = 0; k < clips; ++k) {
+        const long long o = ((long long)v * clips + k) * C + c;
+        const float x = logits[o];
+        const float e = expf(-fabsf(x));
+        tloss += (double)(a * x + w * (log1pf(e) + fmaxf(-x, 0.f)));
+        const float r = 1.f / (1.f + e), er = e * r;
+        acc += x >= 0.f ? r : er;
+        if (dlogits) dlogits[o] = (a - w * (x >= 0.f ? er : r)) * dscale;
+      }
+      const float cf = acc / (float)clips;
+      if (conf) conf[(long long)v * C + c] = cf;
+      const int tp = t >= 0.5f ? 1 : 0;
+      tpairs += ((cf >= 0.5f ? 1 : 0) == tp) ? 1 : 0;
+      if (cf > bv) {                  // (a thread meets its columns in ascending order: strict > keeps the lower index)
+        bv = cf;
+        bi = c;
+        bt = tp;
+      }
+    }
+    // the video's highest-confidence class, ties to the lower index: lanes, then the waves in order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64), ot = __shfl_xor(bt, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+        bt = ot;
+      }
+    }
+    if (lane == 0) {
+      s_bv[wave] = bv;
+      s_bi[wave] = bi;
+      s_bt[wave] = bt;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w2 = 1; w2 < ML_THREADS / 64; ++w2)
+        if (s_bv[w2] > bv || (s_bv[w2] == bv && s_bi[w2] < bi)) {
+          bv = s_bv[w2];
+          bi = s_bi[w2];
+          bt = s_bt[w2];
+        }
+      top += bt;
+    }
+    __syncthreads();
+  }
+  if (bad && err) atomicOr(err, AVID_DEVERR_MLABEL_TARGET);
+  tloss = wave_sum_d(tloss);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tpairs += __shfl_xor(tpairs, o, 64);
+  if (lane == 0) {
+    s_loss[wave] = tloss;
+    s_pairs[wave] = tpairs;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double l = 0.0;
+    long long p = 0;
+    for (int w2 = 0; w2 < ML_THREADS / 64; ++w2) {
+      l += s_loss[w2];
+      p += s_pairs[w2];
+    }
+    part[blockIdx.x].loss = l;
+    part[blockIdx.x].top = top;
+    part[blockIdx.x].pairs = p;
+  }
+}
+
+// The G parts in index order: lane i sums the parts [16 i, 16 i + 16) in order, lane 0 the lanes' sums in order.
+__global__ __launch_bounds__(64) void mlabel_final_kernel(int G, const MlPart* __restrict__ part, double elems,
+                                                          float* __restrict__ loss, long long* __restrict__ hits) {
+  __shared__ double s_l[64];
+  __shared__ long long s_h[2][64];
+  constexpr int PER = ML_MAX_GRID / 64;
+  const int lane = threadIdx.x;
+  double l = 0.0;
+  long long h0 = 0, h1 = 0;
+  for (int g = lane * PER; g < min(G, lane * PER + PER); ++g) {
+    l += part[g].loss;
+    h0 += part[g].top;
+    h1 += part[g].pairs;
+  }
+  s_l[lane] = l;
+  s_h[0][lane] = h0;
+  s_h[1][lane] = h1;
+  __syncthreads();
+  if (lane == 0) {
+    l = 0.0;
+    h0 = h1 = 0;
+    for (int i = 0; i < 64; ++i) {
+      l += s_l[i];
+      h0 += s_h[0][i];
+      h1 += s_h[1][i];
+    }
+    if (loss) loss[0] = (float)(l / elems);
+    if (hits) {
+      hits[0] = h0;
+      hits[1] = h1;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The classifier Linear(F, C) for any C (the heads' igemm takes C in multiples of 64; 101 / 51 classes are not).
 // Forward: one wave per output (b, c), a dot product over F.  Backward: one thread per dW / db / dx element, each a sum
 // over the batch (dW, db) or over the classes (dx) in index order.  Deterministic; a few MFLOP per step.
@@ -250,4 +404,32 @@ extern "C" int avid_cls_loss(int V, int clips, int C, const float* logits, const
   hipLaunchKernelGGL(cls_loss_kernel, dim3(1), dim3(CLS_WAVES * 64), 0, s, V, clips, C, logits, (const long long*)labels,
                      grad_scale, loss, conf, (long long*)hits, dlogits, err);
   return check_launch("cls_loss");
+}
+
+extern "C" int avid_mlabel_loss(int V, int clips, int C, const float* logits, const float* targets, const float* pos_weight,
+                                float grad_scale, float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err,
+                                avid_stream_t stream) {
+  AVID_REQUIRE(V > 0 && clips > 0 && C > 0 && C <= CLS_MAX_C && logits && targets && loss, AVID_E_BADARG,
+               "mlabel_loss: bad arguments (V %d, clips %d, C %d: C must be in [1, %d])", V, clips, C, CLS_MAX_C);
+  static std::atomic<unsigned> ring{0};
+  MlPart* slabs = nullptr;
+  hipError_t he = hipGetSymbolAddress(reinterpret_cast<void**>(&slabs), HIP_SYMBOL(g_ml_part));
+  if (he != hipSuccess) {
+    set_error("mlabel_loss: %s", hipGetErrorString(he));
+    return AVID_E_HIP;
+  }
+  MlPart* part = slabs + (size_t)(ring.fetch_add(1) % ML_RING) * ML_MAX_GRID;
+  hipStream_t s = (hipStream_t)stream;
+  const int G = V < ML_MAX_GRID ? V : ML_MAX_GRID;
+  const double elems = (double)V * clips * C;
+  {
+    ScopedTimer t(s, "mlabel_loss_kernel", 0.0, elems * (dlogits ? 8.0 : 4.0) + 4.0 * (double)V * C * (conf ? 2.0 : 1.0));
+    hipLaunchKernelGGL(mlabel_loss_kernel, dim3(G), dim3(ML_THREADS), 0, s, V, clips, C, logits, targets, pos_weight, grad_scale,
+                       conf, dlogits, err, part);
+  }
+  int rc = check_launch("mlabel_loss");
+  if (rc != AVID_OK) return rc;
+  ScopedTimer t(s, "mlabel_final_kernel", 0.0, 32.0 * G);
+  hipLaunchKernelGGL(mlabel_final_kernel, dim3(1), dim3(64), 0, s, G, part, elems, loss, (long long*)hits);
+  return check_launch("mlabel_loss (final)");
 }

@@ -412,6 +412,8 @@ int avid_counter_add(uint64_t* counter, uint64_t inc, avid_stream_t stream);
 #define AVID_DEVERR_UPDATE_INDEX 2 /* avid_bank_update: y outside [0, N) */
 #define AVID_DEVERR_CMA_INDEX 4    /* avid_cma_negatives: y outside [0, N) */
 #define AVID_DEVERR_CLS_LABEL 8    /* avid_cls_loss: label outside [0, C) */
+#define AVID_DEVERR_MLABEL_TARGET 16 /* avid_mlabel_loss: target outside [0, 1] or not finite */
+#define AVID_DEVERR_RANK_SCORE 32  /* avid_rank_metrics: NaN score */
 
 /* Action-recognition fine-tuning head (utils/eval_utils.py:193-214, eval-action-recg.py:150-165) — classify.hip.
  *
@@ -435,6 +437,24 @@ int avid_dropout_bwd(int64_t n, float p, const uint8_t* mask, const float* dy, f
  * is bit-reproducible from run to run. */
 int avid_cls_loss(int V, int clips, int C, const float* logits, const int64_t* labels, float grad_scale, float* loss,
                   float* conf, int64_t* hits, float* dlogits, int32_t* err, avid_stream_t stream);
+/* Multi-label sibling of avid_cls_loss (version >= 167): binary cross-entropy with logits, torch's
+ * binary_cross_entropy_with_logits, of logits [V * clips][C] (1 <= C <= 1024) against targets [V][C] in [0, 1] (a video's
+ * clips share its targets); pos_weight [C] nullable (all ones).  Per element, with w = 1 + (pos_weight[c] - 1) t:
+ *   l           = (1 - t) x + w (log1p(exp(-|x|)) + max(-x, 0))             (the stable softplus is part of the contract)
+ *   loss[0]     = mean of l over all V * clips * C elements
+ *   dlogits     = ((1 - t) - w (1 - sigmoid(x))) * grad_scale / (V * clips * C)   (nullable)
+ *   conf [V][C] = mean over each video's clips of sigmoid(x) — not the sigmoid of the mean   (nullable)
+ *   hits[2]     (nullable; a class is positive iff t >= 0.5): hits[0] = videos whose highest-confidence class is positive
+ *                (ties to the lower class index, avid_cls_loss's rank rule), hits[1] = (video, class) pairs with
+ *                (conf >= 0.5) == (t >= 0.5)
+ * A target outside [0, 1] or not finite ORs AVID_DEVERR_MLABEL_TARGET into err (nullable).  A grid over the videos
+ * (min(V, 1024) workgroups), a partial sum per workgroup, the partial sums added in index order by a second small launch:
+ * no floating-point atomics, every output has the same bits on every run and under every avid_set_cu_budget.  The partial
+ * sums live in device memory the library owns: 16 slabs per device drawn round-robin per call, so a call's slab is written
+ * again by the 16th later call on that device (the contract of the event pool below). */
+int avid_mlabel_loss(int V, int clips, int C, const float* logits, const float* targets, const float* pos_weight,
+                     float grad_scale, float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err,
+                     avid_stream_t stream);
 /* The classifier Linear(Fin, C) for any C (avid_conv_fwd's igemm takes Cout in multiples of 64):
  * y [B][C] = x [B][Fin] . w [C][Fin]^T + bias (bias nullable).  Backward: dw = dy^T . x, db = column sums of dy (nullable),
  * dx = dy . w (nullable).  Each output is one sum in index order: deterministic. */
@@ -633,6 +653,22 @@ int avid_knn_search(int64_t N, int D, const float* gallery, const float* queries
 int avid_knn_vote(int nq, int k, const int32_t* idx, const float* sim, const int32_t* gallery_labels, int64_t N,
                   int n_classes, float inv_T, const int32_t* query_labels, float* scores, int32_t* pred5,
                   int32_t* first_match, avid_stream_t stream);
+
+/* Multi-label ranking metrics (version >= 167) — rank_metrics.hip: per class c of scores [N][C] against targets [N][C]
+ * (fp32, row-major; positive iff t >= 0.5; P positives, Nn negatives), scikit-learn's average_precision_score and
+ * roc_auc_score in their counting forms — ties handled, no sort:
+ *   ap[c]  = (1 / P) sum over positives i of TP_i / (TP_i + FP_i), TP_i / FP_i = the positives / negatives with score >=
+ *            score_i; the sum runs in ascending sample index in double (a class with more than 256 positives: 256 at
+ *            a time, those sums then in order)
+ *   auc[c] = U2 / (2 P Nn), U2 = sum over positives of 2 #{neg < s_i} + #{neg == s_i} as int64, then one double division
+ *   n_pos[c] = P (nullable)
+ * ap = NaN if P == 0; auc = NaN if P == 0 or Nn == 0.  A NaN score ORs AVID_DEVERR_RANK_SCORE into err (nullable) and makes
+ * that class's ap and auc NaN.  Plain float comparisons: -0.0 == +0.0, +-inf are scores like any other.  Any N >= 1, C >= 1
+ * (N < 2^31 - 1024).  Work: P x N compares per class.  No atomics on any result: the same bits on every run.
+ * ws: avid_rank_metrics_workspace_bytes(N, C) bytes, 8-byte aligned (0 = unsupported arguments). */
+size_t avid_rank_metrics_workspace_bytes(int64_t N, int C);
+int avid_rank_metrics(int64_t N, int C, const float* scores, const float* targets, double* ap, double* auc, int64_t* n_pos,
+                      void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: torch.optim.Adam semantics (L2 weight decay folded into the gradient; bias-corrected)
@@ -865,6 +901,8 @@ enum {
                                     what the per-layer path calls for a BatchNorm whose parameters take no gradient (another expression
                                     than fma(x, scale, shift): such a BatchNorm is never fused) */
   AVID_OP_MAXPOOL_FWD = 32,      /* i0..4 B T H W C; t: x y argmax: avid_maxpool_hw3s2_fwd (the stem's pool behind such a BatchNorm) */
+  /* multi-label fine-tuning / probing (version >= 167) */
+  AVID_OP_MLABEL_LOSS = 33,      /* i0 V, i1 clips, i2 C; f0 grad_scale; t: logits targets pos_weight loss conf hits dlogits err */
   AVID_OP_COUNT_
 };
 
