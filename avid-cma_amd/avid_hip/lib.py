@@ -220,6 +220,8 @@ SIGNATURES = {
     "avid_dropout_bwd": (_i, [_i64, _f, _vp, _vp, _vp, _vp]),
     "avid_cls_loss": (_i, [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_mlabel_loss": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avid_soft_ce_loss": (_i, [_i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "avid_batch_mix": (_i, [_i, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "avid_cls_linear_fwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "avid_cls_linear_bwd": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_adaptive_maxpool_fwd": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

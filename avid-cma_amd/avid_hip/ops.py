@@ -212,7 +212,8 @@ class LabelError(AvidHipError, IndexError):
 
 
 class TargetError(AvidHipError, ValueError):
-    """A multi-label target outside [0, 1] or not finite reached ``avid_mlabel_loss`` (where torch's binary_cross_entropy raises)."""
+    """A multi-label target outside [0, 1] or not finite reached ``avid_mlabel_loss`` (where torch's binary_cross_entropy raises),
+    or a negative or non-finite class probability ``avid_soft_ce_loss``."""
 
 
 class ScoreError(AvidHipError, ValueError):
@@ -233,7 +234,9 @@ class DeviceErrors:
             4: "memory_sampling: sample index outside [0, num_data) (positive_set lookup)",
             8: "cls_loss: label outside [0, n_classes)",
             16: "mlabel_loss: target outside [0, 1] or not finite",
-            32: "rank_metrics: NaN score"}
+            32: "rank_metrics: NaN score",
+            64: "soft_ce_loss: target negative or not finite",
+            128: "batch_mix: partner index outside [0, batch)"}
     _inst = {}
 
     def __init__(self, device):
@@ -256,8 +259,9 @@ class DeviceErrors:
         self.host.zero_()
         self.event = None
         what = "; ".join(m for b, m in self._MSG.items() if code & b) or f"code {code}"
-        cls = LabelError if code & 8 else IndexError if code & 7 else TargetError if code & 16 else ScoreError if code & 32 else IndexError
-        kind = "index out of range" if code & 15 else "value out of range"
+        cls = (LabelError if code & 8 else IndexError if code & 7 else TargetError if code & 16 else ScoreError if code & 32
+               else TargetError if code & 64 else IndexError)
+        kind = "index out of range" if code & (15 | 128) else "value out of range"
         raise cls(f"avid_hip: {kind} in a device kernel — {what}")
 
     def poll(self):
@@ -2014,6 +2018,162 @@ def rank_metrics(scores, targets):
              _stream())
     errs.poll()
     return ap, auc, n_pos
+
+
+def _soft_ce_args(logits, targets, clips, label_smoothing):
+    """The checked arguments of ``soft_ce_loss``: (logits, targets) contiguous, V, C, eps.  Refuses before any launch."""
+    for name, t in (("logits", logits), ("targets", targets)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise AvidHipError(f"soft_ce_loss: {name} must be a HIP device tensor — there is no CPU fallback")
+        if t.dtype != torch.float32:
+            raise AvidHipError(f"soft_ce_loss: {name} must be float32, got {t.dtype}")
+        if t.device != logits.device:
+            raise AvidHipError(f"soft_ce_loss: {name} is on {t.device}, the logits on {logits.device}")
+    clips, eps = int(clips), float(label_smoothing)
+    if not 0.0 <= eps < 1.0:                         # (NaN fails both comparisons)
+        raise AvidHipError(f"soft_ce_loss: label_smoothing = {label_smoothing!r} outside [0, 1)")
+    if logits.dim() != 2 or targets.dim() != 2 or clips < 1:
+        raise AvidHipError("soft_ce_loss: logits [V * clips, C], targets [V, C], clips >= 1 expected")
+    R, C = logits.shape
+    V = targets.shape[0]
+    if V < 1 or V * clips != R or targets.shape[1] != C:
+        raise AvidHipError(f"soft_ce_loss: logits {tuple(logits.shape)} do not match targets {tuple(targets.shape)} x {clips} clips")
+    if not 1 <= C <= 1024:
+        raise AvidHipError(f"soft_ce_loss: {C} classes outside [1, 1024]")
+    return logits.contiguous(), targets.contiguous(), V, C, eps
+
+
+def _soft_ce_launch(logits, targets, clips, eps, V, C, grad_scale):
+    dev = logits.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    conf = torch.empty((V, C), dtype=torch.float32, device=dev)
+    hits = torch.empty(2, dtype=torch.int64, device=dev)
+    dl = torch.empty_like(logits) if grad_scale is not None else None
+    errs = DeviceErrors.get(dev)
+    lib.call("avid_soft_ce_loss", V, int(clips), C, _p(logits), _p(targets), float(eps),
+             float(grad_scale if grad_scale is not None else 0.0), _p(out), _p(conf), _p(hits), _p(dl), errs.ptr(), _stream())
+    errs.poll()
+    return out[0], conf, hits, dl
+
+
+class _SoftCeLoss(Function):
+    """logits -> loss: the launch writes ``dlogits`` with the forward, the backward scales it by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, clips, eps, V, C, grad_scale):
+        loss, conf, hits, dl = _soft_ce_launch(logits, targets, clips, eps, V, C, grad_scale)
+        ctx.save_for_backward(dl)
+        ctx.gs = float(grad_scale)
+        ctx.mark_non_differentiable(conf, hits, dl)
+        return loss, conf, hits, dl
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (dl,) = ctx.saved_tensors
+        return dl * (g if ctx.gs == 1.0 else g / ctx.gs), None, None, None, None, None, None
+
+
+def soft_ce_loss(logits, targets, clips=1, label_smoothing=0.0, grad_scale=None):
+    """Softmax cross-entropy against a distribution — ``torch.nn.functional.cross_entropy(logits, target_probs,
+    label_smoothing=...)``, mean reduction — of ``logits [V * clips, C]`` against ``targets [V, C]`` float32 (a video's clips
+    share its targets; not renormalised, as torch does not): ``avid_soft_ce_loss``, no host synchronisation.  Returns device
+    tensors ``(loss [], confidence [V, C], hits [2] int64, dlogits)`` as ``cls_loss`` does: the confidence is the clips' mean
+    softmax, the hits are top-1 / top-5 against the argmax of each target row (ties: the lower index); ``dlogits`` =
+    d(loss * grad_scale) / d(logits), or None when ``grad_scale`` is None.  When the logits require a gradient the loss is also
+    a node of the autograd graph (``loss.backward()``).  A negative or non-finite target raises ``TargetError`` at the next poll
+    of the device error word."""
+    logits_c, targets, V, C, eps = _soft_ce_args(logits, targets, clips, label_smoothing)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        loss, conf, hits, dl = _SoftCeLoss.apply(logits_c, targets, int(clips), eps, V, C,
+                                                 1.0 if grad_scale is None else float(grad_scale))
+        return loss, conf, hits, (dl if grad_scale is not None else None)
+    return _soft_ce_launch(logits_c, targets, clips, eps, V, C, grad_scale)
+
+
+MIX_MIXUP, MIX_CUTMIX = 0, 1
+
+
+def _batch_mix_args(x, perm, lam, box, labels, targets, n_classes):
+    """The checked arguments of ``batch_mix``: (mode, geometry (B, Cin, T, H, W), n_classes or 0).  Refuses before any launch."""
+    def need(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise AvidHipError(f"batch_mix: {name} must be a HIP device tensor — there is no CPU fallback")
+        if t.dtype != dtype:
+            raise AvidHipError(f"batch_mix: {name} must be {dtype}, got {t.dtype}")
+        if t.device != x.device:
+            raise AvidHipError(f"batch_mix: {name} is on {t.device}, x on {x.device}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise AvidHipError(f"batch_mix: {name} must be {list(shape)}, got {list(t.shape)}")
+    need("x", x, torch.float32, None)
+    if x.dim() not in (4, 5) or x.numel() == 0:
+        raise AvidHipError(f"batch_mix: x must be clips [B, C, T, H, W] or spectrograms [B, 1, T, F], got {tuple(x.shape)}")
+    B = x.shape[0]
+    geom = tuple(x.shape) if x.dim() == 5 else (B, x.shape[1], 1, x.shape[2], x.shape[3])
+    need("perm", perm, torch.int64, (B,))
+    need("lam", lam, torch.float32, (B,))
+    if box is not None:
+        need("box", box, torch.int32, (B, 4))
+    if labels is not None and targets is not None:
+        raise AvidHipError("batch_mix: labels or targets, not both")
+    C = 0
+    if labels is not None:
+        need("labels", labels, torch.int64, (B,))
+        if n_classes is None or int(n_classes) < 1:
+            raise AvidHipError("batch_mix: labels need n_classes >= 1")
+        C = int(n_classes)
+    elif targets is not None:
+        need("targets", targets, torch.float32, None)
+        if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or (n_classes is not None and int(n_classes) != targets.shape[1]):
+            raise AvidHipError(f"batch_mix: targets must be [{B}, n_classes], got {tuple(targets.shape)} (n_classes {n_classes})")
+        C = targets.shape[1]
+    return (MIX_MIXUP if box is None else MIX_CUTMIX), geom, C
+
+
+def batch_mix(x, perm, lam, box=None, labels=None, targets=None, n_classes=None, out=None):
+    """Mixup (``box`` None) or CutMix of a batch on the device in one launch — ``avid_batch_mix``, no host synchronisation, no
+    gradient.  ``x``: clips [B, C, T, H, W] or spectrograms [B, 1, T, F], float32; ``perm`` int64 [B] (every sample's partner),
+    ``lam`` float32 [B] in [0, 1]; ``box`` int32 [B, 4] = (h0, h1, w0, w1), half-open, over the last two dimensions.
+    Returns ``(y, t_out)``: ``y = lam * x + (1 - lam) * x[perm]`` in torch's float32 arithmetic bit for bit (mixup), or ``x`` with
+    the box taken from ``x[perm]`` (CutMix: an exact copy); ``t_out [B, n_classes] = lam * t + (1 - lam) * t[perm]`` for ``t`` =
+    ``targets`` [B, n_classes] float32 or the one-hot rows of ``labels`` int64 [B] (``n_classes`` required), None without either.
+    ``out``: the tensor to write ``y`` into (it must not share memory with ``x``).  A partner outside [0, B) raises ``IndexError``
+    at the next poll of the device error word (that sample is copied unmixed), a label outside [0, n_classes) ``LabelError``."""
+    mode, geom, C = _batch_mix_args(x, perm, lam, box, labels, targets, n_classes)
+    x = x.contiguous()
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        y = out
+        if (not isinstance(y, torch.Tensor) or y.dtype != x.dtype or y.shape != x.shape or y.device != x.device
+                or not y.is_contiguous()):
+            raise AvidHipError("batch_mix: out must be a contiguous tensor of x's dtype, shape and device")
+        lo, hi = y.data_ptr(), y.data_ptr() + 4 * y.numel()
+        if lo < x.data_ptr() + 4 * x.numel() and x.data_ptr() < hi:
+            raise AvidHipError("batch_mix: out must not share memory with x")
+    dev = x.device
+    t_out = torch.empty((geom[0], C), dtype=torch.float32, device=dev) if C else None
+    t_in = None if targets is None else targets.contiguous()
+    errs = DeviceErrors.get(dev)
+    lib.call("avid_batch_mix", mode, *geom, _p(x), _p(perm.contiguous()), _p(lam.contiguous()),
+             _p(None if box is None else box.contiguous()), _p(y), C, _p(t_in), _p(None if labels is None else labels.contiguous()),
+             _p(t_out), errs.ptr(), _stream())
+    errs.poll()
+    return y, t_out
+
+
+def one_hot(labels, n_classes):
+    """The one-hot rows float32 [B, n_classes] of ``labels`` int64 [B] on the device (``avid_batch_mix``'s targets alone: no
+    data, the identity permutation).  A label outside [0, n_classes) is a zero row and raises ``LabelError`` at the next poll."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int64 or labels.dim() != 1 \
+            or labels.numel() == 0 or int(n_classes) < 1:
+        raise AvidHipError("one_hot: labels must be a non-empty int64 [B] HIP device tensor, n_classes >= 1")
+    B, C = labels.shape[0], int(n_classes)
+    t_out = torch.empty((B, C), dtype=torch.float32, device=labels.device)
+    errs = DeviceErrors.get(labels.device)
+    lib.call("avid_batch_mix", MIX_MIXUP, B, 0, 0, 0, 0, None, None, None, None, None, C, None, _p(labels.contiguous()), _p(t_out),
+             errs.ptr(), _stream())
+    errs.poll()
+    return t_out
 
 
 class _ClsLinear(Function):

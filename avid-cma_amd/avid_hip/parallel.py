@@ -683,17 +683,19 @@ class AdamStep(EngineCore):
         return b, [(c, labels[r * b:(r + 1) * b]) for r, c in enumerate(clips)]
 
     # ---- what the supervised steps (FinetuneStep, ProbeStep) share
-    def _set_loss(self, loss, pos_weight, n_classes):
-        """The loss kind of a supervised engine: ``"ce"`` (softmax cross-entropy against int64 labels [B], ``avid_cls_loss``) or
+    def _set_loss(self, loss, pos_weight, n_classes, label_smoothing=0.0):
+        """The loss kind of a supervised engine: ``"ce"`` (softmax cross-entropy against int64 labels [B], ``avid_cls_loss``),
         ``"bce"`` (binary cross-entropy with logits against float32 targets [B, C], ``avid_mlabel_loss``; ``pos_weight``: [C]
-        values, kept as one float32 device tensor that the compiled programs reference)."""
+        values, kept as one float32 device tensor that the compiled programs reference) or ``"soft_ce"`` (softmax cross-entropy
+        against float32 distributions [B, C] — or int64 labels [B], made one-hot on the device — ``avid_soft_ce_loss`` with
+        ``label_smoothing``)."""
         from . import plan
         try:
             self.n_classes = int(n_classes() if callable(n_classes) else n_classes)
         except (AttributeError, StopIteration, TypeError):
             self.n_classes = None            # (a model outside the compiled patterns: step() says so)
-        if loss == "bce" and self.n_classes is None:
-            raise ValueError(f"{type(self).__name__}: loss='bce' needs a model whose classifier says how many classes there are")
+        if loss in ("bce", "soft_ce") and self.n_classes is None:
+            raise ValueError(f"{type(self).__name__}: loss={loss!r} needs a model whose classifier says how many classes there are")
         if pos_weight is not None:
             if loss != "bce":
                 raise ValueError(f"{type(self).__name__}: pos_weight belongs to loss='bce'")
@@ -701,11 +703,13 @@ class AdamStep(EngineCore):
             if tuple(pos_weight.shape) != (self.n_classes,):
                 raise ValueError(f"{type(self).__name__}: pos_weight must hold {self.n_classes} values (one per class), got "
                                  f"{tuple(pos_weight.shape)}")
-        self.loss, self.pos_weight = plan._loss_kind(loss, pos_weight, self.n_classes), pos_weight
+        self.loss, self.pos_weight = plan._loss_kind(loss, pos_weight, self.n_classes, label_smoothing), pos_weight
+        self.label_smoothing = float(label_smoothing)
 
     def _labelled(self, video, labels):
         """A supervised step's inputs, contiguous, the labels checked: int64 [B] on the video's device — under ``loss="bce"``
-        targets [B, C], float32 (bool / uint8 are converted)."""
+        targets [B, C], float32 (bool / uint8 are converted), under ``loss="soft_ce"`` float32 targets [B, C] or int64 labels
+        [B], which become one-hot rows."""
         video, labels = video.contiguous(), labels.contiguous()
         B = video.shape[0]
         if getattr(self, "loss", "ce") == "bce":
@@ -716,14 +720,26 @@ class AdamStep(EngineCore):
                                  f"[{B}, {self.n_classes}] on {video.device} (got {labels.dtype} {tuple(labels.shape)} on "
                                  f"{labels.device})")
             return video, labels
+        if getattr(self, "loss", "ce") == "soft_ce":
+            if labels.dtype == torch.int64 and tuple(labels.shape) == (B,) and labels.device == video.device:
+                from . import ops
+                return video, ops.one_hot(labels, self.n_classes)   # (on the device; a label out of range: LabelError at the poll)
+            if labels.dtype != torch.float32 or tuple(labels.shape) != (B, self.n_classes) or labels.device != video.device:
+                raise ValueError(f"{type(self).__name__}.step (loss='soft_ce'): targets must be float32 [{B}, {self.n_classes}] or "
+                                 f"labels int64 [{B}] on {video.device} (got {labels.dtype} {tuple(labels.shape)} on "
+                                 f"{labels.device})")
+            return video, labels
         if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or labels.device != video.device:
             raise ValueError(f"{type(self).__name__}.step: labels must be int64 [{B}] on {video.device} "
                              f"(got {labels.dtype} {tuple(labels.shape)} on {labels.device})")
         return video, labels
 
     def _eval_loss(self, logits, labels, clips):
-        """``ops.cls_loss`` / ``ops.mlabel_loss`` (the engine's loss kind) over the V * clips logits of a dense evaluation."""
+        """``ops.cls_loss`` / ``ops.mlabel_loss`` (the engine's loss kind) over the V * clips logits of a dense evaluation;
+        ``"soft_ce"``: ``ops.cls_loss`` for int64 labels [V], ``ops.soft_ce_loss`` for float32 targets [V, C] — never smoothed."""
         from . import ops
+        if self.loss == "soft_ce" and labels.dtype != torch.int64:
+            return ops.soft_ce_loss(logits, labels, clips, 0.0)
         if self.loss == "bce":
             if labels.dtype in (torch.bool, torch.uint8):
                 labels = labels.to(torch.float32)
@@ -1676,8 +1692,13 @@ class FinetuneStep(AdamStep):
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None):
-        """``loss``: ``"ce"`` (default) or ``"bce"`` — multi-label fine-tuning: ``step(x, targets)`` takes float32 targets [B, C]
+                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None, label_smoothing=0.0):
+        """``loss``: ``"ce"`` (default), ``"soft_ce"`` or ``"bce"``.  ``"soft_ce"``: softmax cross-entropy against a distribution
+        (mixup / CutMix targets from ``datasets.gpu_mix.GpuBatchMix``, a teacher's probabilities) with ``label_smoothing`` in
+        [0, 1): ``step(x, targets)`` takes float32 targets [B, C], ``step(x, labels)`` int64 labels [B] (made one-hot on the
+        device, so smoothing alone works with ordinary labels); the forward program ends in ``avid_soft_ce_loss``, ``hits`` are
+        top-1 / top-5 against the argmax of each target row; ``evaluate`` is never smoothed (int64 labels: ``avid_cls_loss``,
+        float32 targets: ``avid_soft_ce_loss``).  ``"bce"`` — multi-label fine-tuning: ``step(x, targets)`` takes float32 targets [B, C]
         in [0, 1] (bool / uint8 are converted), the forward program ends in ``avid_mlabel_loss`` (``pos_weight``: [C], optional),
         ``hits`` are (videos whose highest-confidence class is positive, (video, class) pairs on the right side of 0.5), and
         ``evaluate`` returns the clip-mean sigmoid as its confidence; everything else as for ``"ce"``.
@@ -1692,7 +1713,7 @@ class FinetuneStep(AdamStep):
                          bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
-        self._set_loss(loss, pos_weight, lambda: model.classifier.weight.shape[0])
+        self._set_loss(loss, pos_weight, lambda: model.classifier.weight.shape[0], label_smoothing)
         self.virtual_ranks = R
         self.rank_losses = self.rank_hits = None     # [R] float32 / [R, 2] int64 device tensors of the last virtual-rank step
         self._dropout_seeds = None                   # reseed_dropout()'s, while the model's own seed is still the first of them
@@ -1726,7 +1747,8 @@ class FinetuneStep(AdamStep):
 
     def _plan(self, video):
         from . import plan
-        pl = plan.cls_plan(self.model, video, self.classifier_only, need_grad=False, loss=self.loss, pos_weight=self.pos_weight)
+        pl = plan.cls_plan(self.model, video, self.classifier_only, need_grad=False, loss=self.loss, pos_weight=self.pos_weight,
+                           label_smoothing=self.label_smoothing)
         if pl is None or plan._engine_flat(self, pl) is None:
             raise NotImplementedError("FinetuneStep: the model is outside the compiled fine-tuning programs (plan.ClsPlan: "
                                       "ClassificationWrapper(R2Plus1D, feat_name='pool', pooling_op=None), fp32 CUDA "
@@ -1841,23 +1863,26 @@ class ProbeStep(AdamStep):
     [R, n_taps, 2] hold every replica's own (None before the first such step)."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
-                 nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None):
+                 nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None,
+                 label_smoothing=0.0):
         """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``.
-        ``virtual_ranks``: see the class.  ``loss`` / ``pos_weight``: as ``FinetuneStep``'s — ``"bce"`` ends every tap in
-        ``avid_mlabel_loss`` against float32 targets [B, C]."""
+        ``virtual_ranks``: see the class.  ``loss`` / ``pos_weight`` / ``label_smoothing``: as ``FinetuneStep``'s — ``"bce"`` ends
+        every tap in ``avid_mlabel_loss`` against float32 targets [B, C], ``"soft_ce"`` in ``avid_soft_ce_loss`` against float32
+        distributions [B, C] (or int64 labels [B], made one-hot on the device)."""
         R = _virtual_ranks_arg("ProbeStep", virtual_ranks)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
-        self._set_loss(loss, pos_weight, lambda: next(iter(model.classifiers)).classifier.weight.shape[0])
+        self._set_loss(loss, pos_weight, lambda: next(iter(model.classifiers)).classifier.weight.shape[0], label_smoothing)
         self.virtual_ranks = R
         self.rank_losses = self.rank_hits = None     # [R, n_taps] float32 / [R, n_taps, 2] int64 of the last virtual-rank step
 
     def _plan(self, video):
         from . import plan
-        pl = plan.probe_plan(self.model, video, need_grad=False, loss=self.loss, pos_weight=self.pos_weight)
+        pl = plan.probe_plan(self.model, video, need_grad=False, loss=self.loss, pos_weight=self.pos_weight,
+                             label_smoothing=self.label_smoothing)
         if pl is None or plan._engine_flat(self, pl) is None:
             raise NotImplementedError("ProbeStep: the model is outside the compiled probe programs (plan.ProbePlan: MOSTModel("
                                       "R2Plus1D, AdaptiveMaxPool3d heads on conv2x..conv5x, use_bn, no l2_norm / dropout), fp32 "

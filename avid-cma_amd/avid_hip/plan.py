@@ -45,6 +45,7 @@ OP_DROPOUT_FWD, OP_DROPOUT_BWD, OP_CLS_LOSS, OP_CLS_LINEAR_FWD, OP_CLS_LINEAR_BW
 OP_ADAPTIVE_MAXPOOL, OP_BN1D_FWD, OP_BN1D_BWD, OP_PROBE_LINEAR_FWD, OP_PROBE_LINEAR_BWD = 23, 24, 25, 26, 27
 OP_BN_EVAL_COEFFS, OP_BN_EVAL_APPLY, OP_BN_POOL_FWD_EVAL, OP_BN_EVAL_DIRECT, OP_MAXPOOL_FWD = 28, 29, 30, 31, 32   # inference programs only
 OP_MLABEL_LOSS = 33                                  # the "bce" plans' loss record
+OP_SOFT_CE_LOSS = 34                                 # the "soft_ce" plans' loss record
 _OP_NAMES = {0: "nop", **{v: k[3:].lower() for k, v in list(globals().items()) if k.startswith("OP_")}}   # (``dump``)
 NREF = lib.INSTR_REFS
 Ref, Instr, StreamWs = lib.Ref, lib.Instr, lib.StreamWs
@@ -562,10 +563,25 @@ class TrainBuilder(Builder):
                   t=(logits.ref, (S_LABELS, 0), None if pos_weight is None else self.ext(pos_weight), (S_OUT, OUT_BYTES * tap), None,
                      (S_OUT, OUT_BYTES * tap + 8), (S_DLOGITS, 4 * B * Cn * tap), self._err))
 
-    def loss(self, kind, logits, tap=0, pos_weight=None):
-        """The loss record of a supervised plan: ``"ce"`` (``cls_loss``) or ``"bce"`` (``mlabel_loss``)."""
+    def soft_ce_loss(self, logits, tap=0, label_smoothing=0.0):
+        """``AVID_OP_SOFT_CE_LOSS`` of head ``tap`` (run by the step engine only), ``cls_loss`` against a distribution: the label
+        slot holds float32 targets [B, C]; ``label_smoothing`` is the record's f1; a negative or non-finite target is reported
+        in the device error word."""
+        B, Cn = logits.shape
+        if self._err is None:
+            dry = self.device.type != "cuda"
+            self._err = self.ext(torch.zeros((), dtype=torch.int32) if dry else ops.DeviceErrors.get(self.device).flag)
+        self.emit(OP_SOFT_CE_LOSS, i=(B, 1, Cn), f=(1.0, float(label_smoothing)),
+                  t=(logits.ref, (S_LABELS, 0), (S_OUT, OUT_BYTES * tap), None, (S_OUT, OUT_BYTES * tap + 8),
+                     (S_DLOGITS, 4 * B * Cn * tap), self._err))
+
+    def loss(self, kind, logits, tap=0, pos_weight=None, label_smoothing=0.0):
+        """The loss record of a supervised plan: ``"ce"`` (``cls_loss``), ``"bce"`` (``mlabel_loss``) or ``"soft_ce"``
+        (``soft_ce_loss``)."""
         if kind == "ce":
             self.cls_loss(logits, tap=tap)
+        elif kind == "soft_ce":
+            self.soft_ce_loss(logits, tap=tap, label_smoothing=label_smoothing)
         else:
             self.mlabel_loss(logits, tap=tap, pos_weight=pos_weight)
 
@@ -1306,10 +1322,12 @@ class ClsPlan(TrainPrograms):
     tower still runs in training mode (its BatchNorm running statistics move) but no tower backward is compiled, the
     classifier's input gradient neither, and only the classifier's slice of the gradient buffer is zeroed."""
 
-    def __init__(self, model, vshape, device, trailing, group, classifier_only=False, loss="ce", pos_weight=None):
+    def __init__(self, model, vshape, device, trailing, group, classifier_only=False, loss="ce", pos_weight=None,
+                 label_smoothing=0.0):
         from models.classification import HipDropout
         cls = _classifier(model)
-        self.loss, self.pos_weight = _loss_kind(loss, pos_weight, cls.weight.shape[0]), pos_weight
+        self.loss, self.pos_weight = _loss_kind(loss, pos_weight, cls.weight.shape[0], label_smoothing), pos_weight
+        self.label_smoothing = float(label_smoothing)
         if model.use_dropout and type(model.dropout) is not HipDropout:
             raise Unsupported("classifier / dropout")
         b = self._open(model, device, False, trailing, group)
@@ -1333,7 +1351,7 @@ class ClsPlan(TrainPrograms):
         self.logits = b.cls_linear_fwd(cls, feat)
         self.n_classes = C = self.logits.shape[1]
         self.n_logits = len(b.fwd)
-        b.loss(self.loss, self.logits, pos_weight=pos_weight)
+        b.loss(self.loss, self.logits, pos_weight=pos_weight, label_smoothing=label_smoothing)
         # ------------------------------------------------------------------ backward
         self._backward_begins(b)
         dlog = (S_DLOGITS, 0)
@@ -1381,11 +1399,16 @@ class ClsFn(torch.autograd.Function):
         return _autograd_backward(ctx, (ctx.video, None, dlogits.contiguous(), None), 4)
 
 
-def _loss_kind(loss, pos_weight, n_classes):
-    """The checked loss kind of a supervised plan: ``"ce"`` (softmax cross-entropy, int64 labels [B]) or ``"bce"`` (binary
-    cross-entropy with logits, float32 targets [B, C]; ``pos_weight``: float32 [C] on the parameters' device, or None)."""
-    if loss not in ("ce", "bce"):
-        raise ValueError(f"loss must be 'ce' or 'bce' (got {loss!r})")
+def _loss_kind(loss, pos_weight, n_classes, label_smoothing=0.0):
+    """The checked loss kind of a supervised plan: ``"ce"`` (softmax cross-entropy, int64 labels [B]), ``"bce"`` (binary
+    cross-entropy with logits, float32 targets [B, C]; ``pos_weight``: float32 [C] on the parameters' device, or None) or
+    ``"soft_ce"`` (softmax cross-entropy against float32 distributions [B, C]; ``label_smoothing`` in [0, 1))."""
+    if loss not in ("ce", "bce", "soft_ce"):
+        raise ValueError(f"loss must be 'ce', 'bce' or 'soft_ce' (got {loss!r})")
+    if not isinstance(label_smoothing, (int, float)) or not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError(f"label_smoothing must be a number in [0, 1) (got {label_smoothing!r})")
+    if float(label_smoothing) != 0.0 and loss != "soft_ce":
+        raise ValueError("label_smoothing belongs to loss='soft_ce'")
     if pos_weight is not None:
         if loss != "bce":
             raise ValueError("pos_weight belongs to loss='bce'")
@@ -1395,22 +1418,25 @@ def _loss_kind(loss, pos_weight, n_classes):
     return loss
 
 
-def _loss_key(loss, pos_weight):
+def _loss_key(loss, pos_weight, label_smoothing=0.0):
     """What the loss kind adds to a plan's cache key: nothing for ``"ce"`` (the key of every plan compiled so far), the kind
-    and the identity of the ``pos_weight`` tensor (an external slot of the program, which keeps it alive) for ``"bce"``."""
+    and the identity of the ``pos_weight`` tensor (an external slot of the program, which keeps it alive) for ``"bce"``, the
+    kind and the smoothing (a constant of the loss record) for ``"soft_ce"``."""
+    if loss == "soft_ce":
+        return (loss, float(label_smoothing))
     return () if loss == "ce" else (loss, None if pos_weight is None else id(pos_weight))
 
 
-def cls_plan(model, video, classifier_only=False, need_grad=True, loss="ce", pos_weight=None):
+def cls_plan(model, video, classifier_only=False, need_grad=True, loss="ce", pos_weight=None, label_smoothing=0.0):
     """The cached ``ClsPlan`` of this call (same staleness rules as ``run``), or None: the caller takes the per-layer path."""
     if not eligible(model, video, need_grad=need_grad):
         return None
     trailing = (not lib.TIMING) and bool(ops.DEFER_WGRAD)
     drop = model.dropout.p if model.use_dropout else 0.0
     return _plan_for(model, ("cls", tuple(video.shape), video.device.index, trailing, bool(classifier_only), drop)
-                     + _loss_key(loss, pos_weight),
+                     + _loss_key(loss, pos_weight, label_smoothing),
                      lambda: ClsPlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD), classifier_only,
-                                     loss, pos_weight))
+                                     loss, pos_weight, label_smoothing))
 
 
 def run_cls(model, video):
@@ -1439,10 +1465,10 @@ class ProbePlan(TrainPrograms):
     ``avid_bn1d_bwd`` (no input gradient: the pooled features are constants).  No tower record: the tower is frozen.  The
     gradient buffer holds the classifiers' parameters only (``FlatParams`` over the trainable ones)."""
 
-    def __init__(self, model, vshape, device, trailing, group, loss="ce", pos_weight=None):
+    def __init__(self, model, vshape, device, trailing, group, loss="ce", pos_weight=None, label_smoothing=0.0):
         classifiers = _probe_heads(model)
-        self.loss = _loss_kind(loss, pos_weight, classifiers[0].classifier.weight.shape[0])
-        self.pos_weight = pos_weight
+        self.loss = _loss_kind(loss, pos_weight, classifiers[0].classifier.weight.shape[0], label_smoothing)
+        self.pos_weight, self.label_smoothing = pos_weight, float(label_smoothing)
         if any(p.requires_grad for p in model.feature_extractor.parameters()):
             raise Unsupported("the probe's tower is not frozen")
         b = self._open(model, device, False, trailing, group, frozen_ok=True)
@@ -1464,7 +1490,7 @@ class ProbePlan(TrainPrograms):
         self.logits = [hd["logits"] for hd in heads]
         self.n_logits = len(b.fwd)
         for i, lg in enumerate(self.logits):
-            b.loss(self.loss, lg, tap=i, pos_weight=pos_weight)
+            b.loss(self.loss, lg, tap=i, pos_weight=pos_weight, label_smoothing=label_smoothing)
         # ------------------------------------------------------------------ backward
         self._backward_begins(b)
         for i, hd in enumerate(heads):
@@ -1506,13 +1532,14 @@ class ProbeFn(torch.autograd.Function):
         return _autograd_backward(ctx, (ctx.video, None, dl, None), 2)
 
 
-def probe_plan(model, video, need_grad=True, loss="ce", pos_weight=None):
+def probe_plan(model, video, need_grad=True, loss="ce", pos_weight=None, label_smoothing=0.0):
     """The cached ``ProbePlan`` of this call (same staleness rules as ``run``), or None: the caller takes the per-layer path."""
     if not eligible(model, video, need_grad=need_grad):
         return None
     trailing = (not lib.TIMING) and bool(ops.DEFER_WGRAD)
-    return _plan_for(model, ("probe", tuple(video.shape), video.device.index, trailing) + _loss_key(loss, pos_weight),
-                     lambda: ProbePlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD), loss, pos_weight))
+    return _plan_for(model, ("probe", tuple(video.shape), video.device.index, trailing) + _loss_key(loss, pos_weight, label_smoothing),
+                     lambda: ProbePlan(model, tuple(video.shape), video.device, trailing, bool(ops.GROUP_WGRAD), loss, pos_weight,
+                                       label_smoothing))
 
 
 def run_probe(model, video):

@@ -1,5 +1,6 @@
 // Action-recognition fine-tuning head: dropout and the classifier's softmax cross-entropy / clip-averaged confidence, and its
-// multi-label sibling (binary cross-entropy with logits: the reference has no multi-label code; torch's expression is the contract).
+// multi-label sibling (binary cross-entropy with logits: the reference has no multi-label code; torch's expression is the contract),
+// and the softmax cross-entropy against a distribution (label smoothing, mixup / CutMix targets, distillation; torch's again).
 //
 // Reference ops replaced: utils/eval_utils.py:203-213 (torch.nn.Dropout inside ClassificationWrapper),
 // eval-action-recg.py:150-165 (CrossEntropyLoss, Softmax, .view(V, clips, -1).mean(1), metrics_utils.accuracy top-1 / top-5).
@@ -295,6 +296,168 @@ __global__ __launch_bounds__(64) void mlabel_final_kernel(int G, const MlPart* _
 }
 
 // ---------------------------------------------------------------------------------------------
+// Soft-target softmax cross-entropy: logits [V * clips][C] (C <= 1024) against a DISTRIBUTION per video, targets [V][C] —
+// torch's F.cross_entropy(logits, target_probs, label_smoothing = eps), mean reduction: t' = t (1 - eps) + eps / C, row loss
+// = sum_c t'[c] (lse(row) - x[c]), d/dx[c] = softmax[c] * S - t'[c] with S = sum_c t'[c] (the targets are NOT renormalised,
+// as torch does not).  mlabel_loss_kernel's shape: workgroup g takes the videos g, g + G, ... (G = min(V, ML_MAX_GRID)),
+// thread i the columns i, i + 256, ... (in registers: a row is read once); per video one workgroup reduction for S, the
+// argmax of the targets (the video's label; ties to the lower index) and the validity of the row, per clip row one for the
+// max and one for the sum of exponentials (log-softmax goes through the row max), then one for the label's rank in the
+// confidence (cls_loss_kernel's rule).  A workgroup reduction is a wave butterfly, then the waves in order: every float sum
+// has one fixed order.  The element losses are added in double per thread in the order met, the threads' sums as in
+// mlabel_loss_kernel into one MlPart (top = top-1 hits, pairs = top-5 hits), and mlabel_final_kernel adds the parts in
+// index order out of a slab of the same ring.  No floating-point atomics; the same bits on every run.
+// A video with a negative or non-finite target sets AVID_DEVERR_SOFT_TARGET and counts no hit.
+// ---------------------------------------------------------------------------------------------
+constexpr int SC_WAVES = ML_THREADS / 64;
+
+__device__ __forceinline__ float sc_block_sum(float v, float* s, int lane, int wave) {
+  v = wave_sum(v);
+  if (lane == 0) s[wave] = v;
+  __syncthreads();
+  float r = s[0];
+#pragma unroll
+  for (int w = 1; w < SC_WAVES; ++w) r += s[w];
+  return r;
+}
+
+__global__ __launch_bounds__(ML_THREADS) void soft_ce_loss_kernel(int V, int clips, int C, const float* __restrict__ logits,
+                                                                  const float* __restrict__ targets, float eps, float grad_scale,
+                                                                  float* __restrict__ conf, float* __restrict__ dlogits,
+                                                                  int* __restrict__ err, MlPart* __restrict__ part) {
+  // one slot per reduction site: a slot is written again only behind a later site's barrier, which every reader has reached
+  __shared__ float s_sum[SC_WAVES], s_tv[SC_WAVES], s_max[SC_WAVES], s_den[SC_WAVES], s_cl;
+  __shared__ int s_ti[SC_WAVES], s_above[SC_WAVES];
+  __shared__ double s_loss[SC_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float dscale = grad_scale / (float)((long long)V * clips);
+  const float keep = 1.f - eps, spread = eps / (float)C, inv_clips = 1.f / (float)clips;
+  double tloss = 0.0;
+  long long top1 = 0, top5 = 0;      // (thread 0's)
+  bool bad = false;
+  for (int v = blockIdx.x; v < V; v += gridDim.x) {
+    float tp[ML_COLS], acc[ML_COLS];
+    float ssum = 0.f, bv = -INFINITY;
+    int bi = 0x7fffffff;
+    bool vbad = false;
+#pragma unroll
+    for (int j = 0; j < ML_COLS; ++j) {
+      const int c = tid + j * ML_THREADS;
+      tp[j] = acc[j] = 0.f;
+      if (c < C) {
+        const float t = targets[(long long)v * C + c];
+        vbad = vbad || !(t >= 0.f && t < INFINITY);
+        tp[j] = fmaf(t, keep, spread);
+        ssum += tp[j];
+        if (t > bv) {                 // (ascending columns: strict > keeps the lower index)
+          bv = t;
+          bi = c;
+        }
+      }
+    }
+    const float S = sc_block_sum(ssum, s_sum, lane, wave);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      s_tv[wave] = bv;
+      s_ti[wave] = bi;
+    }
+    vbad = __syncthreads_or(vbad ? 1 : 0) != 0;
+    bv = s_tv[0];
+    bi = s_ti[0];
+#pragma unroll
+    for (int w = 1; w < SC_WAVES; ++w)
+      if (s_tv[w] > bv || (s_tv[w] == bv && s_ti[w] < bi)) {
+        bv = s_tv[w];
+        bi = s_ti[w];
+      }
+    bad = bad || vbad;
+    const int label = (vbad || bi >= C) ? -1 : bi;
+    for (int k = 0; k < clips; ++k) {
+      const long long row = (long long)v * clips + k;
+      float x[ML_COLS], m = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < ML_COLS; ++j) {
+        const int c = tid + j * ML_THREADS;
+        x[j] = c < C ? logits[row * C + c] : -INFINITY;
+        m = fmaxf(m, x[j]);
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+      if (lane == 0) s_max[wave] = m;
+      __syncthreads();
+      m = s_max[0];
+#pragma unroll
+      for (int w = 1; w < SC_WAVES; ++w) m = fmaxf(m, s_max[w]);
+      float e[ML_COLS], den = 0.f;
+#pragma unroll
+      for (int j = 0; j < ML_COLS; ++j) {
+        e[j] = tid + j * ML_THREADS < C ? expf(x[j] - m) : 0.f;
+        den += e[j];
+      }
+      den = sc_block_sum(den, s_den, lane, wave);
+      const float lse = logf(den) + m, inv_den = 1.f / den;
+#pragma unroll
+      for (int j = 0; j < ML_COLS; ++j) {
+        const int c = tid + j * ML_THREADS;
+        if (c < C) {
+          tloss += (double)(tp[j] * (lse - x[j]));
+          const float pr = e[j] * inv_den;
+          acc[j] += pr;
+          if (dlogits) dlogits[row * C + c] = (pr * S - tp[j]) * dscale;
+        }
+      }
+    }
+    // the confidence, and the label's rank in it: classes strictly above, plus equal ones at a lower index
+#pragma unroll
+    for (int j = 0; j < ML_COLS; ++j) {
+      const int c = tid + j * ML_THREADS;
+      acc[j] *= inv_clips;
+      if (c < C) {
+        if (conf) conf[(long long)v * C + c] = acc[j];
+        if (c == label) s_cl = acc[j];
+      }
+    }
+    __syncthreads();
+    const float cl = s_cl;
+    int above = 0;
+#pragma unroll
+    for (int j = 0; j < ML_COLS; ++j) {
+      const int c = tid + j * ML_THREADS;
+      if (c < C && label >= 0) above += (acc[j] > cl || (acc[j] == cl && c < label)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+    if (lane == 0) s_above[wave] = above;
+    __syncthreads();
+    if (tid == 0 && label >= 0) {
+      above = 0;
+      for (int w = 0; w < SC_WAVES; ++w) above += s_above[w];
+      top1 += above < 1 ? 1 : 0;
+      top5 += above < 5 ? 1 : 0;
+    }
+  }
+  if (bad && err && tid == 0) atomicOr(err, AVID_DEVERR_SOFT_TARGET);
+  tloss = wave_sum_d(tloss);
+  if (lane == 0) s_loss[wave] = tloss;
+  __syncthreads();
+  if (tid == 0) {
+    double l = 0.0;
+    for (int w = 0; w < SC_WAVES; ++w) l += s_loss[w];
+    part[blockIdx.x].loss = l;
+    part[blockIdx.x].top = top1;
+    part[blockIdx.x].pairs = top5;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The classifier Linear(F, C) for any C (the heads' igemm takes C in multiples of 64; 101 / 51 classes are not).
 // Forward: one wave per output (b, c), a dot product over F.  Backward: one thread per dW / db / dx element, each a sum
 // over the batch (dW, db) or over the classes (dx) in index order.  Deterministic; a few MFLOP per step.
@@ -406,19 +569,25 @@ extern "C" int avid_cls_loss(int V, int clips, int C, const float* logits, const
   return check_launch("cls_loss");
 }
 
+// The next slab of the ring of partial sums (avid_mlabel_loss and avid_soft_ce_loss draw from the one ring), or nullptr.
+static MlPart* ml_next_slab(const char* who) {
+  static std::atomic<unsigned> ring{0};
+  MlPart* slabs = nullptr;
+  hipError_t he = hipGetSymbolAddress(reinterpret_cast<void**>(&slabs), HIP_SYMBOL(g_ml_part));
+  if (he != hipSuccess) {
+    set_error("%s: %s", who, hipGetErrorString(he));
+    return nullptr;
+  }
+  return slabs + (size_t)(ring.fetch_add(1) % ML_RING) * ML_MAX_GRID;
+}
+
 extern "C" int avid_mlabel_loss(int V, int clips, int C, const float* logits, const float* targets, const float* pos_weight,
                                 float grad_scale, float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err,
                                 avid_stream_t stream) {
   AVID_REQUIRE(V > 0 && clips > 0 && C > 0 && C <= CLS_MAX_C && logits && targets && loss, AVID_E_BADARG,
                "mlabel_loss: bad arguments (V %d, clips %d, C %d: C must be in [1, %d])", V, clips, C, CLS_MAX_C);
-  static std::atomic<unsigned> ring{0};
-  MlPart* slabs = nullptr;
-  hipError_t he = hipGetSymbolAddress(reinterpret_cast<void**>(&slabs), HIP_SYMBOL(g_ml_part));
-  if (he != hipSuccess) {
-    set_error("mlabel_loss: %s", hipGetErrorString(he));
-    return AVID_E_HIP;
-  }
-  MlPart* part = slabs + (size_t)(ring.fetch_add(1) % ML_RING) * ML_MAX_GRID;
+  MlPart* part = ml_next_slab("mlabel_loss");
+  if (!part) return AVID_E_HIP;
   hipStream_t s = (hipStream_t)stream;
   const int G = V < ML_MAX_GRID ? V : ML_MAX_GRID;
   const double elems = (double)V * clips * C;
@@ -432,4 +601,28 @@ extern "C" int avid_mlabel_loss(int V, int clips, int C, const float* logits, co
   ScopedTimer t(s, "mlabel_final_kernel", 0.0, 32.0 * G);
   hipLaunchKernelGGL(mlabel_final_kernel, dim3(1), dim3(64), 0, s, G, part, elems, loss, (long long*)hits);
   return check_launch("mlabel_loss (final)");
+}
+
+extern "C" int avid_soft_ce_loss(int V, int clips, int C, const float* logits, const float* targets, float label_smoothing,
+                                 float grad_scale, float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err,
+                                 avid_stream_t stream) {
+  AVID_REQUIRE(V > 0 && clips > 0 && C > 0 && C <= CLS_MAX_C && logits && targets && loss, AVID_E_BADARG,
+               "soft_ce_loss: bad arguments (V %d, clips %d, C %d: C must be in [1, %d])", V, clips, C, CLS_MAX_C);
+  AVID_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, AVID_E_BADARG, "soft_ce_loss: label_smoothing = %g outside [0, 1)",
+               (double)label_smoothing);
+  MlPart* part = ml_next_slab("soft_ce_loss");
+  if (!part) return AVID_E_HIP;
+  hipStream_t s = (hipStream_t)stream;
+  const int G = V < ML_MAX_GRID ? V : ML_MAX_GRID;
+  const double rows = (double)V * clips, elems = rows * C;
+  {
+    ScopedTimer t(s, "soft_ce_loss_kernel", 0.0, elems * (dlogits ? 8.0 : 4.0) + 4.0 * (double)V * C * (conf ? 2.0 : 1.0));
+    hipLaunchKernelGGL(soft_ce_loss_kernel, dim3(G), dim3(ML_THREADS), 0, s, V, clips, C, logits, targets, label_smoothing,
+                       grad_scale, conf, dlogits, err, part);
+  }
+  int rc = check_launch("soft_ce_loss");
+  if (rc != AVID_OK) return rc;
+  ScopedTimer t(s, "mlabel_final_kernel", 0.0, 32.0 * G);
+  hipLaunchKernelGGL(mlabel_final_kernel, dim3(1), dim3(64), 0, s, G, part, rows, loss, (long long*)hits);
+  return check_launch("soft_ce_loss (final)");
 }

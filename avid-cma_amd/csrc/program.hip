@@ -327,6 +327,10 @@ extern "C" int avid_program_run(const avid_instr* prog, int begin, int end, void
         rc = avid_mlabel_loss(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), in.f[0], F(t[3]), F(t[4]),
                               reinterpret_cast<int64_t*>(P(t[5])), F(t[6]), reinterpret_cast<int32_t*>(P(t[7])), s);
         break;
+      case AVID_OP_SOFT_CE_LOSS:
+        rc = avid_soft_ce_loss(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), in.f[1], in.f[0], F(t[2]), F(t[3]),
+                               reinterpret_cast<int64_t*>(P(t[4])), F(t[5]), reinterpret_cast<int32_t*>(P(t[6])), s);
+        break;
       case AVID_OP_CLS_LINEAR_FWD:
         rc = avid_cls_linear_fwd(in.i[0], in.i[1], in.i[2], F(t[0]), F(t[1]), F(t[2]), F(t[3]), s);
         break;

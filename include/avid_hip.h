@@ -414,6 +414,8 @@ int avid_counter_add(uint64_t* counter, uint64_t inc, avid_stream_t stream);
 #define AVID_DEVERR_CLS_LABEL 8    /* avid_cls_loss: label outside [0, C) */
 #define AVID_DEVERR_MLABEL_TARGET 16 /* avid_mlabel_loss: target outside [0, 1] or not finite */
 #define AVID_DEVERR_RANK_SCORE 32  /* avid_rank_metrics: NaN score */
+#define AVID_DEVERR_SOFT_TARGET 64 /* avid_soft_ce_loss: target negative or not finite */
+#define AVID_DEVERR_MIX_INDEX 128  /* avid_batch_mix: perm[b] outside [0, B) */
 
 /* Action-recognition fine-tuning head (utils/eval_utils.py:193-214, eval-action-recg.py:150-165) — classify.hip.
  *
@@ -455,6 +457,48 @@ int avid_cls_loss(int V, int clips, int C, const float* logits, const int64_t* l
 int avid_mlabel_loss(int V, int clips, int C, const float* logits, const float* targets, const float* pos_weight,
                      float grad_scale, float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err,
                      avid_stream_t stream);
+/* Softmax cross-entropy against a DISTRIBUTION (version >= 168): label smoothing, mixup / CutMix targets, distillation —
+ * torch's F.cross_entropy(logits, target_probs, label_smoothing = eps) with mean reduction, of logits [V * clips][C]
+ * (1 <= C <= 1024) against targets [V][C] float32 (a video's clips share its targets), 0 <= label_smoothing < 1
+ * (AVID_E_BADARG otherwise).  The targets are NOT renormalised (torch does not): with t'[c] = t[c] (1 - eps) + eps / C and
+ * S = sum_c t'[c] (not assumed to be 1),
+ *   row loss    = sum_c t'[c] (lse(row) - x[c]), lse = log(sum_c exp(x[c] - max)) + max   (log-softmax through the row max)
+ *   loss[0]     = mean of the row losses over the V * clips rows
+ *   dlogits     = (softmax(row)[c] * S - t'[c]) * grad_scale / (V * clips)                 (nullable)
+ *   conf [V][C] = mean over each video's clips of softmax(row), as avid_cls_loss's         (nullable)
+ *   hits[2]     (nullable) = top-1 / top-5 hits by avid_cls_loss's rank rule; a video's label is the argmax of its target
+ *                row, ties in the targets and in the confidences to the lower class index
+ * A target that is negative or not finite ORs AVID_DEVERR_SOFT_TARGET into err (nullable); such a video counts no hit and
+ * its outputs are whatever the arithmetic gives.  A grid over the videos (min(V, 1024) workgroups of 256 threads, a thread
+ * holds its columns of a row in registers), every float sum of a row in one fixed order, the element losses added in double,
+ * one partial sum per workgroup, the partial sums added in index order by a second small launch (avid_mlabel_loss's, out
+ * of a slab of the same ring: 16 slabs per device drawn round-robin per call of either function).  No floating-point
+ * atomics: every output has the same bits on every run and under every avid_set_cu_budget. */
+int avid_soft_ce_loss(int V, int clips, int C, const float* logits, const float* targets, float label_smoothing,
+                      float grad_scale, float* loss, float* conf, int64_t* hits, float* dlogits, int32_t* err,
+                      avid_stream_t stream);
+/* Mixup and CutMix of a batch in one launch (version >= 168) — batchmix.hip.  x, y: [B][Cin][T][H][W] float32, channel-first
+ * as the stems read them (a spectrogram [B][1][T][F] is Cin = 1, T = 1, H = T, W = F); y must not overlap x (AVID_E_BADARG).
+ * perm [B] int64: the partner of every sample (NULL: the identity); lam [B] float32 in [0, 1] (NULL: all ones).
+ *   mode AVID_MIX_MIXUP    y[b] = lam[b] * x[b] + (1 - lam[b]) * x[perm[b]]: two products, one difference and one sum, each
+ *                          rounded on its own (never contracted into an fma) — torch's float32 expression bit for bit
+ *   mode AVID_MIX_CUTMIX   box [B][4] int32 = (h0, h1, w0, w1), half-open: y[b][.., h, w] = x[perm[b]][.., h, w] inside the
+ *                          box (all channels and frames), x[b][.., h, w] outside — an exact copy; an empty box copies x[b];
+ *                          lam enters the targets only
+ *   targets (t_out [B][n_classes] nullable: skipped)   t_out[b][c] = lam[b] * t[b][c] + (1 - lam[b]) * t[perm[b]][c] by the
+ *                          same four roundings; t is t_in [B][n_classes], or the one-hot of labels_in [B] int64 — exactly one
+ *                          of the two is non-NULL
+ * x and y may both be NULL: the targets alone (with perm and lam NULL: the one-hot rows of labels_in).
+ * A perm[b] outside [0, B) ORs AVID_DEVERR_MIX_INDEX into err (nullable); nothing out of bounds is read, that sample and its
+ * targets are copied unmixed.  A label outside [0, n_classes) ORs AVID_DEVERR_CLS_LABEL and is a zero row.
+ * Any H, W; a sample of fewer than 2^31 floats.  16-byte vectors over the aligned body of every output sample, a source that
+ * is not 16-byte aligned at the same element is read in dwords; memory-bound (mixup 12, CutMix 8 bytes per element).
+ * Every output element is computed by one thread from its own inputs: the same bits on every run. */
+#define AVID_MIX_MIXUP 0
+#define AVID_MIX_CUTMIX 1
+int avid_batch_mix(int mode, int64_t B, int64_t Cin, int64_t T, int64_t H, int64_t W, const float* x, const int64_t* perm,
+                   const float* lam, const int32_t* box, float* y, int64_t n_classes, const float* t_in,
+                   const int64_t* labels_in, float* t_out, int32_t* err, avid_stream_t stream);
 /* The classifier Linear(Fin, C) for any C (avid_conv_fwd's igemm takes Cout in multiples of 64):
  * y [B][C] = x [B][Fin] . w [C][Fin]^T + bias (bias nullable).  Backward: dw = dy^T . x, db = column sums of dy (nullable),
  * dx = dy . w (nullable).  Each output is one sum in index order: deterministic. */
@@ -903,6 +947,8 @@ enum {
   AVID_OP_MAXPOOL_FWD = 32,      /* i0..4 B T H W C; t: x y argmax: avid_maxpool_hw3s2_fwd (the stem's pool behind such a BatchNorm) */
   /* multi-label fine-tuning / probing (version >= 167) */
   AVID_OP_MLABEL_LOSS = 33,      /* i0 V, i1 clips, i2 C; f0 grad_scale; t: logits targets pos_weight loss conf hits dlogits err */
+  /* soft-target fine-tuning / probing: label smoothing, mixup / CutMix targets (version >= 168) */
+  AVID_OP_SOFT_CE_LOSS = 34,     /* i0 V, i1 clips, i2 C; f0 grad_scale, f1 label_smoothing; t: logits targets loss conf hits dlogits err */
   AVID_OP_COUNT_
 };
 
