@@ -87,6 +87,11 @@ class StepGuard(C.Structure):
                 ("skipped_total", C.c_int64), ("steps_total", C.c_int64)]
 
 
+class EmaDesc(C.Structure):
+    """Mirror of ``avid_ema_desc`` (include/avid_hip.h): the weight average an averaging optimizer launch updates."""
+    _fields_ = [("ema", C.c_void_p), ("decay", C.c_double), ("warmup", C.c_int), ("updates_dev", C.c_void_p)]
+
+
 class CritDesc(C.Structure):
     """Mirror of ``avid_crit_desc`` (include/avid_hip.h): one call of ``avid_crit_fused``."""
     _fields_ = [(n, C.c_int32) for n in ("bs", "P", "K", "Kw", "D", "mask")] + [("N", C.c_int64)] + \
@@ -265,6 +270,10 @@ SIGNATURES = {
     "avid_sgd_flat_guarded": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp, _vp]),
     "avid_counter_add_unless": (_i, [_vp, _u64, _vp, _vp]),
     "avid_guard_restore": (_i, [_i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "avid_adam_flat_ema": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp, C.POINTER(EmaDesc), _vp]),
+    "avid_sgd_flat_ema": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp, C.POINTER(EmaDesc), _vp]),
+    "avid_ema_flat": (_i, [_i64, _vp, _vp, C.c_double, _i, _vp, _vp, _vp]),
+    "avid_swap_flat": (_i, [_i64, _vp, _vp, _vp]),
     "avid_probe_spin": (_i, [_i, _vp]),
     "avid_stream_wait": (_i, [_vp, _vp]),
     "avid_clock_probe": (_i, [_i, _vp, _vp]),

@@ -1853,6 +1853,92 @@ def guard_restore(dst, idx, saved, guard):
     lib.call("avid_guard_restore", rows, D, _p(dst), _p(idx), _p(saved), _p(guard.record), _stream())
 
 
+# ---- the weight average (EMA): e = e + w * (p - e), w = (float)(1 - d) — include/avid_hip.h, "Weight averaging"
+def _flat_fp32(who, *ts):
+    """The flat buffers of one launch: device tensors, contiguous fp32, all of one size (None entries are optional ones)."""
+    ts = [t for t in ts if t is not None]
+    _need_cuda(*ts)
+    if any(t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ts[0].numel() for t in ts):
+        raise AvidHipError(f"{who}: contiguous fp32 buffers of one size")
+
+
+def _ema_args(who, ema, decay, warmup, updates_dev, guard):
+    """(avid_ema_desc, guard record or None) of an averaging launch, the refusals the host can make before it."""
+    decay = float(decay)
+    if not 0.0 <= decay < 1.0:                 # (NaN fails both comparisons)
+        raise AvidHipError(f"{who}: decay must be in [0, 1) (got {decay})")
+    if updates_dev is not None:
+        _need_cuda(updates_dev)
+        if updates_dev.dtype != torch.int64 or updates_dev.numel() != 1:
+            raise AvidHipError(f"{who}: updates_dev is one int64 on the device")
+    elif warmup:
+        raise AvidHipError(f"{who}: warm-up reads the number of updates from updates_dev")
+    if guard is not None:
+        _need_cuda(guard.record)
+    desc = lib.EmaDesc(ema.data_ptr(), decay, int(bool(warmup)), None if updates_dev is None else updates_dev.data_ptr())
+    return desc, (None if guard is None else guard.record)
+
+
+def ema_counter_add(updates_dev, guard=None):
+    """The averaging update counter goes up by one on the stream — unless ``guard`` says the step was skipped.  Once per
+    applied step, behind every launch of that step that reads it."""
+    _need_cuda(updates_dev)
+    if guard is None:
+        lib.call("avid_counter_add", _p(updates_dev), 1, _stream())
+    else:
+        lib.call("avid_counter_add_unless", _p(updates_dev), 1, _p(guard.record), _stream())
+
+
+def adam_flat_ema(p, g, m, v, ema, lr, beta1, beta2, eps, wd, step, decay, guard=None, grad_scale=1.0, step_dev=None,
+                  lr_dev=None, advance=True, warmup=False, updates_dev=None, ema_advance=True):
+    """``adam_flat`` (``guard=None``) or ``adam_flat_guarded``, and in the same launch ``ema = ema + w * (p_new - ema)``: p, m, v
+    come out with the bits of those.  ``warmup``: d = min(decay, (1 + k) / (10 + k)) with k read from ``updates_dev`` (0-d int64
+    device tensor).  ``ema_advance``: advance ``updates_dev`` behind the launch (False: another launch of the same step
+    follows and must read the same k — the caller advances it with ``ema_counter_add()``), as ``advance`` does for ``step_dev``."""
+    _flat_fp32("adam_flat_ema", p, g, m, v, ema)
+    desc, rec = _ema_args("adam_flat_ema", ema, decay, warmup, updates_dev, guard)
+    st = _stream()
+    if step_dev is not None and advance:
+        if guard is None:
+            lib.call("avid_counter_add", _p(step_dev), 1, st)
+        else:
+            lib.call("avid_counter_add_unless", _p(step_dev), 1, _p(rec), st)
+    lib.call("avid_adam_flat_ema", p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2), float(eps),
+             float(wd), int(step), _p(step_dev), _p(lr_dev), float(grad_scale), _p(rec), C.byref(desc), st)
+    if updates_dev is not None and ema_advance:
+        ema_counter_add(updates_dev, guard)
+
+
+def sgd_flat_ema(p, g, buf, ema, lr, momentum, wd, decay, guard=None, nesterov=False, grad_scale=1.0, lr_dev=None,
+                 warmup=False, updates_dev=None, ema_advance=True):
+    """``sgd_flat`` (``guard=None``) or ``sgd_flat_guarded`` with the average in the same launch (see ``adam_flat_ema``)."""
+    _flat_fp32("sgd_flat_ema", p, g, buf, ema)
+    desc, rec = _ema_args("sgd_flat_ema", ema, decay, warmup, updates_dev, guard)
+    lib.call("avid_sgd_flat_ema", p.numel(), _p(p), _p(g), _p(buf), float(lr), float(momentum), float(wd), int(bool(nesterov)),
+             _p(lr_dev), float(grad_scale), _p(rec), C.byref(desc), _stream())
+    if updates_dev is not None and ema_advance:
+        ema_counter_add(updates_dev, guard)
+
+
+def ema_flat(ema, p, decay, warmup=False, updates_dev=None, guard=None, advance=True):
+    """``ema = ema + w * (p - ema)`` in a pass of its own (``avid_ema_flat``): the BatchNorm running statistics behind the
+    optimizer, or the parameters of a caller's own optimizer.  ``guard``: a skipped step writes nothing.  ``advance``: as
+    ``adam_flat_ema``'s ``ema_advance``."""
+    _flat_fp32("ema_flat", ema, p)
+    desc, rec = _ema_args("ema_flat", ema, decay, warmup, updates_dev, guard)
+    if ema.numel():
+        lib.call("avid_ema_flat", ema.numel(), _p(ema), _p(p), desc.decay, desc.warmup, _p(updates_dev), _p(rec), _stream())
+    if updates_dev is not None and advance:
+        ema_counter_add(updates_dev, guard)
+
+
+def swap_flat(a, b):
+    """Exchange the contents of two flat fp32 buffers of one size in place, in one launch (``avid_swap_flat``); the same
+    buffer twice or overlapping buffers raise."""
+    _flat_fp32("swap_flat", a, b)
+    lib.call("avid_swap_flat", a.numel(), _p(a), _p(b), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # fine-tuning head (classify.hip): dropout, softmax cross-entropy / clip-averaged confidence
 # ------------------------------------------------------------------------------------------------

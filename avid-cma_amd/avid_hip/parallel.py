@@ -27,8 +27,10 @@ kernel needs the GPU.  BatchNorm statistics stay per-rank — the reference has 
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
+import warnings
 import weakref
 import torch
 import torch.distributed as dist
@@ -463,6 +465,16 @@ def _virtual_ranks_arg(who, virtual_ranks, broadcast_buffers="step"):
     return R
 
 
+def _ema_decay_arg(who, ema_decay):
+    """An engine's ``ema_decay`` as a float in [0, 1), None for no weight average, or the ValueError that names it."""
+    if ema_decay is None:
+        return None
+    d = float(ema_decay)
+    if not 0.0 <= d < 1.0:                             # (NaN fails both comparisons)
+        raise ValueError(f"{who}: ema_decay must be in [0, 1), or None for no weight average (got {ema_decay})")
+    return d
+
+
 def _sgd_param_group(lr, momentum, weight_decay, nesterov):
     """``param_groups[0]`` (without ``params``) as the installed torch.optim.SGD writes it for these hyper-parameters."""
     probe = torch.optim.SGD([torch.zeros(1)], lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
@@ -502,12 +514,25 @@ class AdamStep(EngineCore):
     non-finite (``ops.guard_nonfinite``: a ReLU can keep a NaN channel out of the gradient).  A skipped step leaves the parameters, the optimizer state, ``t_dev``, the BatchNorm running
     statistics, ``num_batches_tracked`` (and ``TrainStep``: both memory banks) exactly as it found them; what still advances
     is the host's ``t`` (it counts ATTEMPTED steps: ``t - int(t_dev) == int(guard.skipped_total)`` for Adam; ``state_dict``
-    saves ``t_dev``), the negative sampler's position and the dropout offset — the next step draws fresh ones."""
+    saves ``t_dev``), the negative sampler's position and the dropout offset — the next step draws fresh ones.
+
+    The weight average, off by default (``ema_decay=None``: nothing below is allocated or launched).  ``ema_decay`` in [0, 1):
+    ``ema``, laid out like ``flat.flat`` and started as its copy (timm's rule), follows the parameters by ``e = e + w * (p - e)``,
+    ``w = (float)(1 - d)``, inside the optimizer launch itself (``ops.adam_flat_ema`` / ``ops.sgd_flat_ema``, over the slice the
+    optimizer updates: a ``classifier_only`` engine averages the classifier and keeps the copy elsewhere); ``ema_warmup``:
+    ``d = min(ema_decay, (1 + k) / (10 + k))`` with ``k = ema_updates``, a 0-d device int64 that counts the applied updates;
+    ``ema_buffers``: ``ema_buffers_flat`` averages the BatchNorm running statistics the step leaves by one ``ops.ema_flat``
+    launch behind the optimizer (``num_batches_tracked`` is not averaged; with ``ema_buffers=False`` evaluation under the
+    average uses the live statistics).  One update per step — per global step with ``virtual_ranks`` — a skipped step leaves
+    ``ema``, ``ema_updates`` and the averaged statistics as it found them, a captured graph carries the update.
+    ``with ema_weights():`` makes the model the averaged one in place, ``ema_state_dict()`` returns it, ``ema_reset()``
+    restarts it from the current weights; ``state_dict()`` gains the key ``avid_ema``.  The average is per rank and fp32."""
 
     virtual_ranks = 1        # ranks whose gradients the buffer holds the SUM of, per process (the step engines' virtual_ranks=R)
 
     def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False,
-                 max_grad_norm=None, skip_nonfinite=False, **core):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_buffers=True, **core):
+        ema_decay = _ema_decay_arg(type(self).__name__, ema_decay)
         if optimizer not in ("adam", "sgd"):
             raise ValueError("optimizer must be 'adam' or 'sgd'")
         if optimizer == "sgd" and (momentum < 0 or (nesterov and momentum == 0)):
@@ -532,6 +557,17 @@ class AdamStep(EngineCore):
         dev = self.flat.flat.device if self.flat.flat.is_cuda else None
         # the learning rate lives in device memory as well: a captured graph freezes by-value arguments
         self.lr_dev = torch.full((), float(lr), dtype=torch.float32, device=dev) if dev is not None else None
+        # the weight average (``ema_decay``): laid out like the flat parameters and started as their copy, the counter of
+        # applied averaging updates a device word — a captured graph reads and advances it there
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema = self.ema_updates = self.ema_buffers_flat = None
+        self._ema_swapped = False
+        if ema_decay is not None:
+            self.ema = self.flat.flat.detach().clone()
+            self.ema_updates = torch.zeros((), dtype=torch.int64, device=self.flat.flat.device)
+            fb = self.flat_buffers.flat
+            if ema_buffers and fb is not None:
+                self.ema_buffers_flat = fb.detach().clone()
         self.m = self.v = self.t_dev = self.momentum_buffer = None
         if optimizer == "sgd":
             if self.momentum != 0:
@@ -586,12 +622,15 @@ class AdamStep(EngineCore):
         if self._guard_nbt:
             torch._foreach_sub_(self._guard_nbt, [self.guard.skipped.to(torch.int64)] * len(self._guard_nbt))
 
-    def _update(self, begin=0, end=None, advance=True):
+    def _update(self, begin=0, end=None, advance=True, last=True):
         """One optimizer launch over elements [begin, end) of the flat buffers with the engine's hyper-parameters (Adam: step
         ``self.t``; ``advance=False``: another slice of the same step, the device step counter stays.  SGD has no counter).
-        With the step guard on: the guarded kernels, which obey the record ``_guard_judge`` filled."""
+        With the step guard on: the guarded kernels, which obey the record ``_guard_judge`` filled.  With ``ema_decay``: the
+        averaging forms of the same kernels (``last=False``: another slice of the same step follows)."""
         from . import ops
         s = slice(begin, end)
+        if self.ema is not None:
+            return self._update_averaging(s, advance, last)
         if self.guard is not None:
             if self.optimizer == "sgd":
                 buf = self.momentum_buffer
@@ -611,9 +650,138 @@ class AdamStep(EngineCore):
                       self.eps, self.wd, self.t, grad_scale=1.0 / (self.buckets.world * self.virtual_ranks), step_dev=self.t_dev,
                       lr_dev=self.lr_dev, advance=advance)
 
+    def _update_averaging(self, s, advance, last):
+        """``_update`` with the weight average on: the averaging form of the engine's optimizer kernel over the same slice —
+        guarded or not — which leaves ``ema[s]`` updated from the parameters it has just written.  Behind the step's last
+        slice: one ``ops.ema_flat`` over the BatchNorm running statistics (final by now: rank 0's, after the guard's restore)
+        with the same weight and the same guard, then the counter of updates goes up by one — unless the step was skipped.
+        Every launch of a step reads the same count."""
+        from . import ops
+        self._ema_live("step")
+        fb = self.flat_buffers.flat if self.ema_buffers_flat is not None else None
+        kw = dict(guard=self.guard, grad_scale=self._grad_scale(), lr_dev=self.lr_dev, warmup=self.ema_warmup,
+                  updates_dev=self.ema_updates, ema_advance=last and fb is None)
+        if self.optimizer == "sgd":
+            buf = self.momentum_buffer
+            ops.sgd_flat_ema(self.flat.flat[s], self.flat.grad[s], None if buf is None else buf[s], self.ema[s], self.lr,
+                             self.momentum, self.wd, self.ema_decay, nesterov=self.nesterov, **kw)
+        else:
+            ops.adam_flat_ema(self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.ema[s], self.lr, self.betas[0],
+                              self.betas[1], self.eps, self.wd, self.t, self.ema_decay, step_dev=self.t_dev, advance=advance,
+                              **kw)
+        if last and fb is not None:
+            ops.ema_flat(self.ema_buffers_flat, fb, self.ema_decay, self.ema_warmup, self.ema_updates, self.guard)
+
     def optimizer_step(self):
         self.t += 1
         self._update()
+
+    # ---- the weight average (``ema_decay``)
+    def _ema_on(self, what):
+        if self.ema is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: the engine was built without ema_decay, it keeps no average")
+
+    def _ema_live(self, what):
+        """Raise inside ``ema_weights()``: the model holds the average there, a step or a checkpoint would take it for the
+        live weights."""
+        if self._ema_swapped:
+            raise RuntimeError(f"{type(self).__name__}.{what} inside `with ema_weights():` — the model holds the averaged "
+                               "weights there; leave the block first")
+
+    def ema_reset(self):
+        """The average becomes a copy of the current parameters (and running statistics) and the counter of updates zero:
+        call it after loading model weights from a checkpoint that carries no average."""
+        self._ema_on("ema_reset")
+        self._ema_live("ema_reset")
+        self.ema.copy_(self.flat.flat)
+        if self.ema_buffers_flat is not None:
+            self.ema_buffers_flat.copy_(self.flat_buffers.flat)
+        self.ema_updates.zero_()
+
+    def _ema_exchange(self):
+        """The flat parameters <-> their average (and the running statistics <-> theirs), in place: ``ops.swap_flat``.  No
+        address changes — sealed programs, cached plans and inference programs read the exchanged values — and every
+        parameter's version counter goes up, as after any in-place write."""
+        from . import ops
+        ops.swap_flat(self.flat.flat, self.ema)
+        if self.ema_buffers_flat is not None:
+            ops.swap_flat(self.flat_buffers.flat, self.ema_buffers_flat)
+        bump = getattr(torch.autograd.graph, "increment_version", None) or torch._C._increment_version
+        for p in self.flat.params:
+            bump(p)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with step.ema_weights():`` — inside the block the model IS the averaged model: ``evaluate``, ``Inference(model)``,
+        ``KNNEval(model=...)``, a per-layer forward and ``model.state_dict()`` see the average (with ``ema_buffers`` also the
+        averaged running statistics, otherwise the live ones).  Two exchange launches on entry, two on exit; on exit — also by
+        an exception — the live weights and statistics are bit for bit what they were.  ``step()`` inside the block raises."""
+        self._ema_on("ema_weights")
+        self._ema_live("ema_weights")
+        self._ema_exchange()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_exchange()
+            self._ema_swapped = False
+
+    def _ema_buffer_views(self):
+        """[(name in ``model.state_dict()``, its view of ``ema_buffers_flat``)] for every buffer the flat statistics buffer
+        holds (``num_batches_tracked`` and anything else outside it is not averaged)."""
+        fb = self.flat_buffers.flat
+        if self.ema_buffers_flat is None or fb is None:
+            return []
+        lo, size, out = fb.data_ptr(), fb.element_size(), []
+        for name, b in self.model.named_buffers():
+            off = (b.data_ptr() - lo) // size
+            if b.is_floating_point() and b.numel() and 0 <= off and off + b.numel() <= fb.numel():
+                out.append((name, self.ema_buffers_flat[off:off + b.numel()].view(b.shape)))
+        return out
+
+    def ema_state_dict(self):
+        """``model.state_dict()``'s keys and shapes with the averaged tensors where the average covers them — the trainable
+        parameters and, with ``ema_buffers``, the running statistics — and copies of the live ones elsewhere (frozen
+        parameters, ``num_batches_tracked``): loads into a fresh model with ``load_state_dict(strict=True)``."""
+        self._ema_on("ema_state_dict")
+        self._ema_live("ema_state_dict")
+        sd = type(self.model.state_dict())((k, v.detach().clone()) for k, v in self.model.state_dict().items())
+        slot = {id(p): i for i, p in enumerate(self.flat.params)}
+        for name, p in self.model.named_parameters():
+            if id(p) in slot and name in sd:
+                sd[name] = self.flat.view(self.ema, slot[id(p)]).detach().clone()
+        for name, view in self._ema_buffer_views():
+            if name in sd:
+                sd[name] = view.detach().clone()
+        return sd
+
+    def _ema_checkpoint(self):
+        """The ``avid_ema`` entry of ``state_dict()``: the average of every parameter the optimizer holds under torch's
+        parameter index (``_param_order``), the averaged statistics by name, the hyper-parameters and the count of updates."""
+        views = self._ema_buffer_views()
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "num_updates": int(self.ema_updates),
+                "params": {k: self._slice(self.ema, i).detach().clone() for k, i, _ in self._param_order()},
+                "buffers": {name: v.detach().clone() for name, v in views} if self.ema_buffers_flat is not None else None}
+
+    def _load_ema_checkpoint(self, saved):
+        if self.ema is None:
+            return                                   # (an engine without an average ignores the checkpoint's)
+        if saved is None:
+            warnings.warn(f"{type(self).__name__}.load_state_dict: the checkpoint carries no weight average (avid_ema); the "
+                          "engine keeps its current one — call ema_reset() to restart it from the loaded weights")
+            return
+        self._ema_live("load_state_dict")
+        self.ema_decay, self.ema_warmup = _ema_decay_arg(type(self).__name__, saved["decay"]), bool(saved["warmup"])
+        for k, i, _ in self._param_order():
+            self._slice(self.ema, i).copy_(saved["params"].get(k, saved["params"].get(str(k))))
+        if self.ema_buffers_flat is not None:
+            if saved.get("buffers") is None:
+                warnings.warn(f"{type(self).__name__}.load_state_dict: the checkpoint's average carries no running statistics; "
+                              "the engine keeps its current averaged statistics")
+            else:
+                for name, view in self._ema_buffer_views():
+                    view.copy_(saved["buffers"][name])
+        self.ema_updates.fill_(int(saved["num_updates"]))
 
     # ---- a virtual-rank step (``virtual_ranks`` = R > 1): the ranks of an R-rank job, shard after shard on this one GPU
     def _virtual_buffers(self):
@@ -797,7 +965,15 @@ class AdamStep(EngineCore):
 
     def state_dict(self):
         """torch.optim.Adam's (SGD's) format.  Adam's ``step`` is the device counter ``t_dev``: the steps APPLIED — with the step
-        guard on it lags the host's ``t`` (attempted steps) by ``guard.skipped_total``."""
+        guard on it lags the host's ``t`` (attempted steps) by ``guard.skipped_total``.  With ``ema_decay`` one more top-level
+        key, ``avid_ema`` (``_ema_checkpoint``); without it the dict is the optimizer's alone."""
+        sd = self._optimizer_state_dict()
+        if self.ema is not None:
+            self._ema_live("state_dict")
+            sd["avid_ema"] = self._ema_checkpoint()
+        return sd
+
+    def _optimizer_state_dict(self):
         if self.optimizer == "sgd":
             return self._sgd_state_dict()
         step = float(int(self.t_dev) if self.t_dev is not None else self.t)
@@ -814,6 +990,10 @@ class AdamStep(EngineCore):
                                   "params": list(range(nparams))}]}
 
     def load_state_dict(self, sd):
+        self._load_optimizer_state_dict(sd)
+        self._load_ema_checkpoint(sd.get("avid_ema"))
+
+    def _load_optimizer_state_dict(self, sd):
         if self.optimizer == "sgd":
             return self._load_sgd_state_dict(sd)
         g = _require_format(type(self).__name__, sd, "Adam")
@@ -834,7 +1014,7 @@ class TrainStep(AdamStep):
 
     def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 virtual_ranks=1, max_grad_norm=None, skip_nonfinite=False):
+                 virtual_ranks=1, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_buffers=True):
         """``broadcast_buffers``: see ``EngineCore``.  ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``.
         ``max_grad_norm`` / ``skip_nonfinite``: the step guard, see ``AdamStep``.  Here a skipped step also puts back the bank
         rows it updated, the optimizer gives up its overlapped early slice (it would run before the norm is known), and the
@@ -845,8 +1025,8 @@ class TrainStep(AdamStep):
         records in rank order, rank 0's running statistics.  One process only, ``broadcast_buffers="step"``, no ``capture()``."""
         R = _virtual_ranks_arg("TrainStep", virtual_ranks, broadcast_buffers)
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                         bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                         ema_buffers=ema_buffers, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.criterion = criterion
         self.graph = None
         self.virtual_ranks = R
@@ -1112,7 +1292,7 @@ class TrainStep(AdamStep):
         self.t += 1
         main, fourth = torch.cuda.current_stream(), pl.stream_objs[3]
         with torch.cuda.stream(fourth):
-            self._update(0, pl.adam_early)
+            self._update(0, pl.adam_early, last=False)
         main.wait_stream(fourth)
         self._update(pl.adam_early, advance=False)
 
@@ -1143,6 +1323,7 @@ class TrainStep(AdamStep):
                 mult.reseed(saved["seed"], saved["offset"])
 
     def step(self, video, audio, index):
+        self._ema_live("step")
         self._step_plan = None
         loss = self.forward_backward(video, audio, index)
         pl = self._step_plan
@@ -1185,6 +1366,7 @@ class TrainStep(AdamStep):
             self._sa.copy_(audio, non_blocking=True)
         if index is not None:
             self._si.copy_(index, non_blocking=True)
+        self._ema_live("replay")
         self.graph.replay()
         self._poll_errors()
         self.t += 1
@@ -1692,7 +1874,8 @@ class FinetuneStep(AdamStep):
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None, label_smoothing=0.0):
+                 max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None, label_smoothing=0.0,
+                 ema_decay=None, ema_warmup=False, ema_buffers=True):
         """``loss``: ``"ce"`` (default), ``"soft_ce"`` or ``"bce"``.  ``"soft_ce"``: softmax cross-entropy against a distribution
         (mixup / CutMix targets from ``datasets.gpu_mix.GpuBatchMix``, a teacher's probabilities) with ``label_smoothing`` in
         [0, 1): ``step(x, targets)`` takes float32 targets [B, C], ``step(x, labels)`` int64 labels [B] (made one-hot on the
@@ -1709,8 +1892,8 @@ class FinetuneStep(AdamStep):
         statistics from before shard 0's forward): see ``AdamStep``.  ``virtual_ranks``: see the class."""
         R = _virtual_ranks_arg("FinetuneStep", virtual_ranks, broadcast_buffers)
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                         bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                         ema_buffers=ema_buffers, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
         self._set_loss(loss, pos_weight, lambda: model.classifier.weight.shape[0], label_smoothing)
@@ -1758,6 +1941,7 @@ class FinetuneStep(AdamStep):
     def step(self, video, labels):
         """(loss [], hits [2] int64: top-1 / top-5 hits of the batch) as device tensors.  ``virtual_ranks`` > 1: the mean of the
         ranks' losses and the sum of their hits, over the global batch [R * b, ...]."""
+        self._ema_live("step")
         if self.virtual_ranks > 1:
             return self._virtual_step(video, labels)
         video, labels = self._labelled(video, labels)
@@ -1864,7 +2048,7 @@ class ProbeStep(AdamStep):
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
                  nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None,
-                 label_smoothing=0.0):
+                 label_smoothing=0.0, ema_decay=None, ema_warmup=False, ema_buffers=True):
         """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``.
         ``virtual_ranks``: see the class.  ``loss`` / ``pos_weight`` / ``label_smoothing``: as ``FinetuneStep``'s — ``"bce"`` ends
         every tap in ``avid_mlabel_loss`` against float32 targets [B, C], ``"soft_ce"`` in ``avid_soft_ce_loss`` against float32
@@ -1873,7 +2057,8 @@ class ProbeStep(AdamStep):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, broadcast_buffers="off")
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                         ema_buffers=ema_buffers, broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
         self._set_loss(loss, pos_weight, lambda: next(iter(model.classifiers)).classifier.weight.shape[0], label_smoothing)
         self.virtual_ranks = R
@@ -1892,6 +2077,7 @@ class ProbeStep(AdamStep):
     def step(self, video, labels):
         """(losses [n_taps], hits [n_taps, 2] int64: top-1 / top-5 hits of the batch per tap) as device tensors.
         ``virtual_ranks`` > 1: per tap the mean of the ranks' losses and the sum of their hits, over the global batch."""
+        self._ema_live("step")
         if self.virtual_ranks > 1:
             return self._virtual_step(video, labels)
         video, labels = self._labelled(video, labels)

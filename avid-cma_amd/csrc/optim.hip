@@ -369,6 +369,259 @@ __global__ __launch_bounds__(256) void guard_restore_kernel(long long rows, long
   }
 }
 
+// ---- the weight average (EMA) ----------------------------------------------------------------------------------------------
+// e = e + w * (p - e): the difference, the product and the sum each rounded to fp32 on its own (torch's unfused
+// `e + (p - e) * w`; the numpy restatement of tests/_ema_ref.py, bit for bit).
+__device__ __forceinline__ float ema_element(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float t = w * d;
+  return e + t;
+}
+
+// w = (float)(1 - d), formed once per launch in double: d is the decay, or — warm-up — min(decay, (1 + k) / (10 + k)) with k
+// the averaging updates applied so far, read from the device counter (a captured graph freezes by-value arguments).
+__device__ __forceinline__ float ema_weight(double decay, int warmup, const long long* __restrict__ updates_dev) {
+  double d = decay;
+  if (warmup) {
+    const double k = (double)*updates_dev;
+    const double r = (1.0 + k) / (10.0 + k);
+    if (r < d) d = r;
+  }
+  return (float)(1.0 - d);
+}
+
+// One element of Adam with every contraction spelled out, so that the averaging kernels below have the bits of
+// adam_flat_kernel / adam_flat_guarded_kernel whatever the compiler would choose here.  Those two were left to the compiler,
+// and their code objects are the specification: the vector loop has m = fma(b1, m, (1 - b1) * gg) and v = fma(b2, v, ((1 - b2)
+// * gg) * gg); the n % 4 tail has m = fma(1 - b1, gg, b1 * m) and v = b2 * v + ((1 - b2) * gg) * gg, unfused; both have
+// denom = fma(sqrt(v), inv_sqrt_bc2, eps) and p = fma(-step_size, m / denom, p).
+template <bool TAIL>
+__device__ __forceinline__ void adam_element(float& p, float gg, float& m, float& v, float b1, float b2, float eps,
+                                             float step_size, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  const float c1 = 1.f - b1, c2 = 1.f - b2;
+  const float s = c2 * gg;
+  const float d = s * gg;
+  if (TAIL) {
+    const float t = b1 * m;
+    m = __builtin_fmaf(c1, gg, t);
+    const float u = b2 * v;
+    v = u + d;
+  } else {
+    const float a = c1 * gg;
+    m = __builtin_fmaf(b1, m, a);
+    v = __builtin_fmaf(b2, v, d);
+  }
+  const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+  const float q = m / denom;
+  p = __builtin_fmaf(-step_size, q, p);
+}
+
+// The gradient term in front of it.  Unclipped: adam_grad_term<false>, fma(g, grad_scale, wd * p), loop and tail alike.
+// Clipped, t = (g * grad_scale) * coef: the guarded kernel's loop has fma(wd, p, t), its tail t + wd * p unfused.
+template <bool CLIP, bool TAIL>
+__device__ __forceinline__ float adam_ema_grad_term(float g, float p, float grad_scale, float wd, float coef) {
+#pragma clang fp contract(off)
+  if (!CLIP) return adam_grad_term<false>(g, p, grad_scale, wd, coef);
+  float t = g * grad_scale;
+  t = t * coef;
+  if (!TAIL) return __builtin_fmaf(wd, p, t);
+  const float u = wd * p;
+  return u + t;
+}
+
+template <bool CLIP>
+__device__ __forceinline__ void adam_ema_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, float* __restrict__ e, long long n4, long long n, float b1,
+                                              float b2, float eps, float wd, float step_size, float inv_sqrt_bc2,
+                                              float grad_scale, float coef, float w) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
+    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
+    floatx4 mv = reinterpret_cast<floatx4*>(m)[i];
+    floatx4 vv = reinterpret_cast<floatx4*>(v)[i];
+    floatx4 ev = reinterpret_cast<floatx4*>(e)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], mj = mv[j], vj = vv[j];
+      const float gg = adam_ema_grad_term<CLIP, false>(gv[j], pj, grad_scale, wd, coef);
+      adam_element<false>(pj, gg, mj, vj, b1, b2, eps, step_size, inv_sqrt_bc2);
+      pv[j] = pj;
+      mv[j] = mj;
+      vv[j] = vj;
+      ev[j] = ema_element(ev[j], pj, w);
+    }
+    reinterpret_cast<floatx4*>(p)[i] = pv;
+    reinterpret_cast<floatx4*>(m)[i] = mv;
+    reinterpret_cast<floatx4*>(v)[i] = vv;
+    reinterpret_cast<floatx4*>(e)[i] = ev;
+  }
+  // tail (n % 4) handled by block 0
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    float pi = p[i], mi = m[i], vi = v[i];
+    const float gg = adam_ema_grad_term<CLIP, true>(g[i], pi, grad_scale, wd, coef);
+    adam_element<true>(pi, gg, mi, vi, b1, b2, eps, step_size, inv_sqrt_bc2);
+    p[i] = pi;
+    m[i] = mi;
+    v[i] = vi;
+    e[i] = ema_element(e[i], pi, w);
+  }
+}
+
+// adam_flat_kernel, then e[i] from the p[i] it has just computed — one more 4-byte read and write per element instead of a
+// pass of its own that reads p again.
+__global__ __launch_bounds__(256) void adam_flat_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ e, long long n4, long long n, float b1,
+                                                            float b2, float eps, float wd, float step_size, double inv_bc1,
+                                                            float inv_sqrt_bc2, float grad_scale, float lr,
+                                                            const long long* __restrict__ step_dev,
+                                                            const float* __restrict__ lr_dev, double decay, int warmup,
+                                                            const long long* __restrict__ updates_dev) {
+  if (lr_dev) {   // as adam_flat_kernel
+    lr = *lr_dev;
+    step_size = (float)((double)lr * inv_bc1);
+  }
+  if (step_dev) {
+    const double t = (double)*step_dev;
+    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
+  }
+  const float w = ema_weight(decay, warmup, updates_dev);
+  adam_ema_span<false>(p, g, m, v, e, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, 1.f, w);
+}
+
+// adam_flat_guarded_kernel, then the same: a skipped step writes nothing, e included.
+__global__ __launch_bounds__(256) void adam_flat_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                    float* __restrict__ m, float* __restrict__ v,
+                                                                    float* __restrict__ e, long long n4, long long n,
+                                                                    float b1, float b2, float eps, float wd, float step_size,
+                                                                    double inv_bc1, float inv_sqrt_bc2, float grad_scale,
+                                                                    float lr, const long long* __restrict__ step_dev,
+                                                                    const float* __restrict__ lr_dev, double decay, int warmup,
+                                                                    const long long* __restrict__ updates_dev,
+                                                                    const avid_step_guard* __restrict__ guard) {
+  if (guard->skip) return;
+  const float coef = guard->clip_coef;
+  if (lr_dev) {
+    lr = *lr_dev;
+    step_size = (float)((double)lr * inv_bc1);
+  }
+  if (step_dev) {
+    const double t = (double)*step_dev;
+    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
+  }
+  const float w = ema_weight(decay, warmup, updates_dev);
+  if (coef == 1.f)
+    adam_ema_span<false>(p, g, m, v, e, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef, w);
+  else
+    adam_ema_span<true>(p, g, m, v, e, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef, w);
+}
+
+// sgd_flat_kernel's / sgd_flat_guarded_kernel's element (sgd_element_clipped with coef 1.0f is sgd_element: times one is
+// exact), then the average.
+__device__ __forceinline__ void sgd_ema_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                             float* __restrict__ e, long long n4, long long n, float lr, float momentum,
+                                             float wd, bool nesterov, float grad_scale, float coef, float w) {
+  const bool has_buf = buf != nullptr;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
+    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
+    floatx4 ev = reinterpret_cast<floatx4*>(e)[i];
+    floatx4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (has_buf) bv = reinterpret_cast<floatx4*>(buf)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], bj = bv[j];
+      sgd_element_clipped(pj, gv[j], bj, has_buf, lr, momentum, wd, nesterov, grad_scale, coef);
+      pv[j] = pj;
+      bv[j] = bj;
+      ev[j] = ema_element(ev[j], pj, w);
+    }
+    reinterpret_cast<floatx4*>(p)[i] = pv;
+    if (has_buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
+    reinterpret_cast<floatx4*>(e)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    float pi = p[i], bi = has_buf ? buf[i] : 0.f;
+    sgd_element_clipped(pi, g[i], bi, has_buf, lr, momentum, wd, nesterov, grad_scale, coef);
+    p[i] = pi;
+    if (has_buf) buf[i] = bi;
+    e[i] = ema_element(e[i], pi, w);
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ buf, float* __restrict__ e, long long n4,
+                                                           long long n, float lr, float momentum, float wd, int nesterov,
+                                                           float grad_scale, const float* __restrict__ lr_dev, double decay,
+                                                           int warmup, const long long* __restrict__ updates_dev) {
+  if (lr_dev) lr = *lr_dev;
+  const float w = ema_weight(decay, warmup, updates_dev);
+  sgd_ema_span(p, g, buf, e, n4, n, lr, momentum, wd, nesterov != 0, grad_scale, 1.f, w);
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                   float* __restrict__ buf, float* __restrict__ e,
+                                                                   long long n4, long long n, float lr, float momentum,
+                                                                   float wd, int nesterov, float grad_scale,
+                                                                   const float* __restrict__ lr_dev, double decay, int warmup,
+                                                                   const long long* __restrict__ updates_dev,
+                                                                   const avid_step_guard* __restrict__ guard) {
+  if (guard->skip) return;
+  const float coef = guard->clip_coef;
+  if (lr_dev) lr = *lr_dev;
+  const float w = ema_weight(decay, warmup, updates_dev);
+  sgd_ema_span(p, g, buf, e, n4, n, lr, momentum, wd, nesterov != 0, grad_scale, coef, w);
+}
+
+// The same rule in a pass of its own: e from a p that somebody else wrote (the BatchNorm running statistics; a caller's
+// own optimizer).  guard: nullable; a skip writes nothing.
+__global__ __launch_bounds__(256) void ema_flat_kernel(float* __restrict__ e, const float* __restrict__ p, long long n4,
+                                                       long long n, double decay, int warmup,
+                                                       const long long* __restrict__ updates_dev,
+                                                       const avid_step_guard* __restrict__ guard) {
+  if (guard && guard->skip) return;
+  const float w = ema_weight(decay, warmup, updates_dev);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    floatx4 ev = reinterpret_cast<floatx4*>(e)[i];
+    const floatx4 pv = reinterpret_cast<const floatx4*>(p)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = ema_element(ev[j], pv[j], w);
+    reinterpret_cast<floatx4*>(e)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    e[i] = ema_element(e[i], p[i], w);
+  }
+}
+
+// a <-> b: every element read from both buffers and written to both by one thread.  n4 vectors (0 unless both pointers are
+// 16-byte aligned), then the scalar elements: the tail, or everything.  The buffers are disjoint (the host checks).
+__global__ __launch_bounds__(256) void swap_flat_kernel(float* __restrict__ a, float* __restrict__ b, long long n4,
+                                                        long long n) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = tid; i < n4; i += stride) {
+    const floatx4 av = reinterpret_cast<floatx4*>(a)[i];
+    const floatx4 bv = reinterpret_cast<floatx4*>(b)[i];
+    reinterpret_cast<floatx4*>(a)[i] = bv;
+    reinterpret_cast<floatx4*>(b)[i] = av;
+  }
+  for (long long i = n4 * 4 + tid; i < n; i += stride) {
+    const float x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
+}
+
 }  // namespace avid
 
 using namespace avid;
@@ -527,4 +780,112 @@ extern "C" int avid_guard_restore(int64_t rows, int64_t D, float* dst, const int
   hipLaunchKernelGGL(guard_restore_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (long long)rows,
                      (long long)D, dst, (const long long*)idx, saved, guard);
   return check_launch("guard_restore");
+}
+
+// ---- the weight average (EMA)
+static int ema_desc_check(const char* who, const avid_ema_desc* ema, char* msg, size_t cap) {
+  const char* bad = nullptr;
+  if (!ema || !ema->ema) bad = "needs its average buffer";
+  else if (((uintptr_t)ema->ema & 15) != 0) bad = "the average must be 16-byte aligned";
+  else if (!(ema->decay >= 0.0 && ema->decay < 1.0)) bad = "decay must be in [0, 1)";
+  else if (ema->warmup && !ema->updates_dev) bad = "warm-up needs the device counter of updates";
+  else if (((uintptr_t)ema->updates_dev & 7) != 0) bad = "the counter of updates must be 8-byte aligned";
+  if (!bad) return 0;
+  snprintf(msg, cap, "%s: %s", who, bad);
+  return 1;
+}
+
+extern "C" int avid_adam_flat_ema(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev,
+                                  float grad_scale, const avid_step_guard* guard, const avid_ema_desc* ema,
+                                  avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g && m && v && (step >= 1 || step_dev), AVID_E_BADARG, "adam_flat_ema: bad argument");
+  if (step < 1) step = 1;
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
+               "adam_flat_ema: buffers must be 16-byte aligned");
+  AVID_REQUIRE(((uintptr_t)guard & 7) == 0, AVID_E_BADARG, "adam_flat_ema: the guard record must be 8-byte aligned");
+  char msg[128];
+  AVID_REQUIRE(!ema_desc_check("adam_flat_ema", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float step_size = (float)((double)lr / bc1);
+  const double inv_bc1 = 1.0 / bc1;
+  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  const long long n4 = n / 4;
+  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  if (guard) {
+    ScopedTimer t((hipStream_t)stream, "adam_flat_ema_guarded_kernel", 0.0, 36.0 * n);
+    hipLaunchKernelGGL(adam_flat_ema_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       ema->ema, n4, (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale,
+                       lr, (const long long*)step_dev, lr_dev, ema->decay, (int)ema->warmup,
+                       (const long long*)ema->updates_dev, guard);
+  } else {
+    ScopedTimer t((hipStream_t)stream, "adam_flat_ema_kernel", 0.0, 36.0 * n);
+    hipLaunchKernelGGL(adam_flat_ema_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema->ema, n4,
+                       (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
+                       (const long long*)step_dev, lr_dev, ema->decay, (int)ema->warmup, (const long long*)ema->updates_dev);
+  }
+  return check_launch("adam_flat_ema");
+}
+
+extern "C" int avid_sgd_flat_ema(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
+                                 int nesterov, const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                                 const avid_ema_desc* ema, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g, AVID_E_BADARG, "sgd_flat_ema: bad argument");
+  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat_ema: momentum needs its buffer");
+  if (momentum == 0.f) buf = nullptr;
+  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat_ema: nesterov needs momentum");
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
+               "sgd_flat_ema: buffers must be 16-byte aligned");
+  AVID_REQUIRE(((uintptr_t)guard & 7) == 0, AVID_E_BADARG, "sgd_flat_ema: the guard record must be 8-byte aligned");
+  char msg[128];
+  AVID_REQUIRE(!ema_desc_check("sgd_flat_ema", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  const long long n4 = n / 4;
+  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  if (guard) {
+    ScopedTimer t((hipStream_t)stream, "sgd_flat_ema_guarded_kernel", 0.0, (buf ? 28.0 : 20.0) * n);
+    hipLaunchKernelGGL(sgd_flat_ema_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema->ema,
+                       n4, (long long)n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev, ema->decay, (int)ema->warmup,
+                       (const long long*)ema->updates_dev, guard);
+  } else {
+    ScopedTimer t((hipStream_t)stream, "sgd_flat_ema_kernel", 0.0, (buf ? 28.0 : 20.0) * n);
+    hipLaunchKernelGGL(sgd_flat_ema_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema->ema, n4,
+                       (long long)n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev, ema->decay, (int)ema->warmup,
+                       (const long long*)ema->updates_dev);
+  }
+  return check_launch("sgd_flat_ema");
+}
+
+extern "C" int avid_ema_flat(int64_t n, float* e, const float* p, double decay, int warmup, const int64_t* updates_dev,
+                             const avid_step_guard* guard, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && e && p, AVID_E_BADARG, "ema_flat: bad argument");
+  AVID_REQUIRE((((uintptr_t)e | (uintptr_t)p) & 15) == 0, AVID_E_BADARG, "ema_flat: buffers must be 16-byte aligned");
+  AVID_REQUIRE(decay >= 0.0 && decay < 1.0, AVID_E_BADARG, "ema_flat: decay must be in [0, 1)");
+  AVID_REQUIRE(!warmup || updates_dev, AVID_E_BADARG, "ema_flat: warm-up needs the device counter of updates");
+  AVID_REQUIRE((((uintptr_t)updates_dev | (uintptr_t)guard) & 7) == 0, AVID_E_BADARG,
+               "ema_flat: the counter and the guard record must be 8-byte aligned");
+  const long long n4 = n / 4;
+  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
+  if (grid > 4096) grid = 4096;
+  ScopedTimer t((hipStream_t)stream, "ema_flat_kernel", 0.0, 12.0 * n);
+  hipLaunchKernelGGL(ema_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, p, n4, (long long)n, decay,
+                     warmup, (const long long*)updates_dev, guard);
+  return check_launch("ema_flat");
+}
+
+extern "C" int avid_swap_flat(int64_t n, float* a, float* b, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && a && b, AVID_E_BADARG, "swap_flat: bad argument");
+  AVID_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0, AVID_E_BADARG, "swap_flat: buffers must be 4-byte aligned");
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+  AVID_REQUIRE(a0 + bytes <= b0 || b0 + bytes <= a0, AVID_E_BADARG, "swap_flat: the two buffers overlap");
+  const bool vec = ((a0 | b0) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  const long long work = vec ? (n4 > 0 ? n4 : 1) : (long long)n;
+  long long grid = ceil_div(work, 256);
+  if (grid > 4096) grid = 4096;
+  ScopedTimer t((hipStream_t)stream, "swap_flat_kernel", 0.0, 16.0 * n);
+  hipLaunchKernelGGL(swap_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, b, n4, (long long)n);
+  return check_launch("swap_flat");
 }

@@ -790,6 +790,40 @@ int avid_counter_add_unless(uint64_t* counter, uint64_t inc, const avid_step_gua
 int avid_guard_restore(int64_t rows, int64_t D, float* dst, const int64_t* idx, const float* saved,
                        const avid_step_guard* guard, avid_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Weight averaging (EMA), fused into the optimizer launch — avid_hip/parallel.py: AdamStep(ema_decay=).
+ * The rule, per element and in fp32 with the difference, the product and the sum each rounded on its own:
+ *   e = e + w * (p_new - e)          (torch's unfused e + (p - e) * w; within one ulp of torch.lerp)
+ *   w = (float)(1.0 - d), formed once per launch in double; d = decay, or with warmup
+ *   d = min(decay, (1 + k) / (10 + k)), k = *updates_dev: the averaging updates applied before this one.
+ * The kernels read k and never write it: the caller advances the counter once per applied step, behind every
+ * launch of that step (avid_counter_add, or avid_counter_add_unless under a guard).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct avid_ema_desc {
+    float*         ema;          /* the average: n floats laid out like p, 16-byte aligned */
+    double         decay;        /* in [0, 1) */
+    int            warmup;       /* nonzero: the warm-up rule above; needs updates_dev */
+    const int64_t* updates_dev;  /* device counter k (nullable without warmup), 8-byte aligned */
+} avid_ema_desc;
+/* avid_adam_flat / avid_sgd_flat (guard == NULL) or their guarded forms (guard != NULL), then e[i] from the p[i] just
+ * computed, in the same launch: p, m, v, buf come out with the bits of those entry points.  Under guard->skip nothing is
+ * written, the average included.  n <= 0, a null or misaligned buffer, a decay outside [0, 1) or warmup without its
+ * counter is AVID_E_BADARG, before anything is launched. */
+int avid_adam_flat_ema(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev,
+                       float grad_scale, const avid_step_guard* guard, const avid_ema_desc* ema, avid_stream_t stream);
+int avid_sgd_flat_ema(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
+                      int nesterov, const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                      const avid_ema_desc* ema, avid_stream_t stream);
+/* The same rule in a pass of its own over p as somebody else left it (the BatchNorm running statistics, a caller's own
+ * optimizer).  guard: nullable; with guard->skip nothing is written.  e and p 16-byte aligned. */
+int avid_ema_flat(int64_t n, float* e, const float* p, double decay, int warmup, const int64_t* updates_dev,
+                  const avid_step_guard* guard, avid_stream_t stream);
+/* a <-> b over n floats, in place: every element is read from both buffers and written to both by one thread.  16-byte
+ * vectors where both pointers are 16-byte aligned, a scalar path otherwise (any 4-byte aligned addresses).  a == b or any
+ * overlap of the two buffers, n <= 0 or a null pointer is AVID_E_BADARG. */
+int avid_swap_flat(int64_t n, float* a, float* b, avid_stream_t stream);
+
 /* Video clip front end: frames [B][T][H][W][3] uint8 (what the decoder / augmentation hands over)
  * -> out [B][3][T][H][W] fp32 = ((u / 255) - mean[c]) / std[c], the reference's ClipToTensor + Normalize
  * (utils/videotransforms/volume_transforms.py:14-66, tensor_transforms.py:13-37; datasets/preprocessing.py:45-48)
