@@ -92,6 +92,26 @@ class EmaDesc(C.Structure):
     _fields_ = [("ema", C.c_void_p), ("decay", C.c_double), ("warmup", C.c_int), ("updates_dev", C.c_void_p)]
 
 
+class Segment(C.Structure):
+    """Mirror of ``avid_segment`` (include/avid_hip.h): one tensor of a flat buffer and the hyper-parameters it takes."""
+    _fields_ = [("offset", C.c_int64), ("numel", C.c_int64), ("lr_scale", C.c_float), ("weight_decay", C.c_float),
+                ("adapt", C.c_int32), ("first_chunk", C.c_int32)]
+
+
+class SegChunk(C.Structure):
+    """Mirror of ``avid_seg_chunk``: AVID_SEG_CHUNK floats of one segment, or what is left of it."""
+    _fields_ = [("start", C.c_int64), ("len", C.c_int32), ("seg", C.c_int32)]
+
+
+class SegmentTable(C.Structure):
+    """Mirror of ``avid_segment_table``: the host and the device copies of the segment and chunk records."""
+    _fields_ = [("S", C.c_int32), ("n_chunks", C.c_int32), ("seg_host", C.c_void_p), ("seg_dev", C.c_void_p),
+                ("chunk_host", C.c_void_p), ("chunk_dev", C.c_void_p)]
+
+
+SEG_CHUNK = 4096                 # AVID_SEG_CHUNK
+
+
 class CritDesc(C.Structure):
     """Mirror of ``avid_crit_desc`` (include/avid_hip.h): one call of ``avid_crit_fused``."""
     _fields_ = [(n, C.c_int32) for n in ("bs", "P", "K", "Kw", "D", "mask")] + [("N", C.c_int64)] + \
@@ -274,6 +294,15 @@ SIGNATURES = {
     "avid_sgd_flat_ema": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp, C.POINTER(EmaDesc), _vp]),
     "avid_ema_flat": (_i, [_i64, _vp, _vp, C.c_double, _i, _vp, _vp, _vp]),
     "avid_swap_flat": (_i, [_i64, _vp, _vp, _vp]),
+    "avid_segment_chunks": (_i, [C.c_int32, C.POINTER(Segment), C.POINTER(SegChunk), C.c_int32]),
+    "avid_segment_sumsq_workspace_bytes": (_sz, [C.POINTER(SegmentTable)]),
+    "avid_segment_sumsq": (_i, [C.POINTER(SegmentTable), _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avid_sgd_flat_table": (_i, [C.POINTER(SegmentTable), _i64, _vp, _vp, _vp, _f, _f, _i, _vp, _f, _f, _vp, _vp,
+                                 C.POINTER(EmaDesc), _vp, _sz, _vp]),
+    "avid_adam_flat_table": (_i, [C.POINTER(SegmentTable), _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp,
+                                  C.POINTER(EmaDesc), _vp]),
+    "avid_lamb_flat": (_i, [C.POINTER(SegmentTable), _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp, _vp,
+                            C.POINTER(EmaDesc), _vp, _sz, _vp]),
     "avid_probe_spin": (_i, [_i, _vp]),
     "avid_stream_wait": (_i, [_vp, _vp]),
     "avid_clock_probe": (_i, [_i, _vp, _vp]),

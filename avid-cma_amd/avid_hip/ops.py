@@ -11,6 +11,7 @@ memory as ``[Cout][kt][kh][kw][Cin]`` (torch ``channels_last_3d``); see ``make_w
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import struct
 
@@ -1937,6 +1938,189 @@ def swap_flat(a, b):
     buffer twice or overlapping buffers raise."""
     _flat_fp32("swap_flat", a, b)
     lib.call("avid_swap_flat", a.numel(), _p(a), _p(b), _stream())
+
+
+# ---- segment tables: per-tensor hyper-parameters, per-segment norms, LARS / LAMB — include/avid_hip.h, "Per-tensor ..."
+class SegmentTable:
+    """``avid_segment_table`` for the tensors of a flat fp32 buffer: where each lies and the ``lr_scale`` / ``weight_decay`` /
+    ``adapt`` it takes, the chunk list the kernels walk, both in host memory (every call validates them) and uploaded once.
+
+    ``layout``: a ``parallel.FlatParams`` (its ``offsets`` and ``params``), or a list of (offset, numel) pairs.  ``begin`` /
+    ``end``: only the tensors inside elements [begin, end) of the layout, with offsets counted from ``begin`` — the table of
+    the slice ``buf[begin:end]``.  ``lr_scale`` / ``weight_decay`` / ``adapt``: one value for all, or one per tensor of the
+    layout.  ``trust``: float32 [S] on the device, the factor LARS / LAMB last applied to each segment (ones before).
+    Refused here, before anything reaches the library: an empty table, an offset that is negative or no multiple of 4,
+    segments that are not increasing or overlap, a segment that ends behind ``numel``, values that are not finite."""
+
+    def __init__(self, layout, lr_scale=1.0, weight_decay=0.0, adapt=True, device=None, begin=0, end=None, numel=None):
+        if hasattr(layout, "offsets") and hasattr(layout, "params"):
+            pairs = [(int(o), int(p.numel())) for o, p in zip(layout.offsets, layout.params)]
+            total = int(layout.numel)
+            device = layout.flat.device if device is None else device
+        else:
+            pairs = [(int(o), int(n)) for o, n in layout]
+            total = max((o + n for o, n in pairs), default=0) if numel is None else int(numel)
+        if device is None:
+            raise AvidHipError("SegmentTable: a device is needed for the uploaded copy")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        end = total if end is None else int(end)
+        begin = int(begin)
+
+        def per_tensor(name, val, conv):
+            vals = list(val) if isinstance(val, (list, tuple)) else [val] * len(pairs)
+            if len(vals) != len(pairs):
+                raise AvidHipError(f"SegmentTable: {name} has {len(vals)} values for {len(pairs)} tensors")
+            return [conv(x) for x in vals]
+        scales, decays = per_tensor("lr_scale", lr_scale, float), per_tensor("weight_decay", weight_decay, float)
+        adapts = per_tensor("adapt", adapt, lambda x: int(bool(x)))
+        if any(o < 0 for o, _ in pairs):
+            raise AvidHipError("SegmentTable: a negative offset")
+        keep = [i for i, (o, n) in enumerate(pairs) if begin <= o and o + n <= end]
+        if any(not (o + n <= begin or end <= o) for i, (o, n) in enumerate(pairs) if i not in keep):
+            raise AvidHipError(f"SegmentTable: a tensor straddles the slice [{begin}, {end})")
+        if not keep:
+            raise AvidHipError("SegmentTable: no tensor lies in the slice")
+        self.index = keep                                    # the layout's tensor behind each segment
+        self.numel = end - begin
+        self.S = len(keep)
+        last = 0
+        for s, i in enumerate(keep):
+            o, n = pairs[i][0] - begin, pairs[i][1]
+            what = None
+            if o < 0 or o % 4:
+                what = f"offset {o} is negative or not 16-byte aligned"
+            elif o < last:
+                what = f"offset {o} lies in front of the end {last} of the segment before (not increasing, or overlapping)"
+            elif n <= 0 or o + n > self.numel:
+                what = f"[{o}, {o + n}) is empty or ends behind the buffer's {self.numel} elements"
+            elif not (math.isfinite(scales[i]) and math.isfinite(decays[i])):
+                what = f"lr_scale {scales[i]} / weight_decay {decays[i]} is not finite"
+            if what:
+                raise AvidHipError(f"SegmentTable: segment {s}: {what}")
+            last = o + n
+        self.segs = (lib.Segment * self.S)(*[lib.Segment(pairs[i][0] - begin, pairs[i][1], scales[i], decays[i], adapts[i], 0)
+                                             for i in keep])
+        count = lib.raw("avid_segment_chunks")
+        self.n_chunks = count(self.S, self.segs, None, 0)
+        lib.check(min(self.n_chunks, 0), "avid_segment_chunks")
+        self.chunks = (lib.SegChunk * self.n_chunks)()
+        lib.check(min(count(self.S, self.segs, self.chunks, self.n_chunks), 0), "avid_segment_chunks")
+        self.seg_dev, self.chunk_dev = self._upload(self.segs, device), self._upload(self.chunks, device)
+        self.trust = torch.full((self.S,), 1.0, dtype=torch.float32, device=device)
+        self.desc = lib.SegmentTable(self.S, self.n_chunks, C.addressof(self.segs), self.seg_dev.data_ptr(),
+                                     C.addressof(self.chunks), self.chunk_dev.data_ptr())
+        self.device = device
+
+    @staticmethod
+    def _upload(records, device):
+        host = torch.frombuffer(records, dtype=torch.uint8)
+        dev = torch.empty(host.numel(), dtype=torch.uint8, device=device)
+        dev.copy_(host)
+        return dev
+
+    lr_scale = property(lambda self: [s.lr_scale for s in self.segs])
+    weight_decay = property(lambda self: [s.weight_decay for s in self.segs])
+    adapt = property(lambda self: [bool(s.adapt) for s in self.segs])
+    offsets = property(lambda self: [s.offset for s in self.segs])
+    numels = property(lambda self: [s.numel for s in self.segs])
+
+    def workspace_bytes(self):
+        return int(lib.raw("avid_segment_sumsq_workspace_bytes")(C.byref(self.desc)))
+
+
+def _table_args(who, table, *ts):
+    _flat_fp32(who, *ts)
+    if not isinstance(table, SegmentTable):
+        raise AvidHipError(f"{who}: the table is an ops.SegmentTable")
+    first = next(t for t in ts if t is not None)
+    if first.numel() != table.numel or first.device != table.device:
+        raise AvidHipError(f"{who}: the table describes a buffer of {table.numel} elements on {table.device}, the buffers "
+                           f"have {first.numel()} on {first.device}")
+
+
+def _table_ema(who, ema, decay, warmup, updates_dev, guard):
+    """(pointer to an avid_ema_desc or None, guard record or None, the descriptor to keep alive)."""
+    if ema is None:
+        if guard is not None:
+            _need_cuda(guard.record)
+        return None, (None if guard is None else guard.record), None
+    desc, rec = _ema_args(who, ema, decay, warmup, updates_dev, guard)
+    return C.byref(desc), rec, desc
+
+
+def segment_sumsq(table, x, y=None, guard=None):
+    """float64 [S, 2] on the device: per segment of ``table`` the sum of squares of ``x`` and of ``y`` (zeros without ``y``),
+    accumulated in double in a fixed order (``avid_segment_sumsq``): the same bits from run to run and under every CU budget."""
+    _table_args("segment_sumsq", table, x, y)
+    sums = torch.zeros((table.S, 2), dtype=torch.float64, device=x.device)
+    ws = workspace(x.device, table.workspace_bytes())
+    lib.call("avid_segment_sumsq", C.byref(table.desc), x.numel(), _p(x), _p(y), _p(sums),
+             None if guard is None else _p(guard.record), _p(ws), ws.numel(), _stream())
+    return sums
+
+
+def sgd_flat_table(table, p, g, buf, lr, momentum, nesterov=False, grad_scale=1.0, lr_dev=None, trust_coefficient=None,
+                   guard=None, ema=None, decay=None, warmup=False, updates_dev=None, ema_advance=True):
+    """``sgd_flat`` with every segment's own learning rate (the fp32 product ``lr * lr_scale``) and weight decay
+    (``avid_sgd_flat_table``); elements outside the segments are not touched.  ``trust_coefficient`` (> 0): LARS — a norm pass
+    fills ``table.trust`` with ``q = trust_coefficient * |p| / |g~ + wd p|`` per adapted segment (1 where a norm is 0), the update
+    multiplies ``g~ + wd p`` by it in front of the momentum.  ``guard`` / ``ema`` (with ``decay``, ``warmup``, ``updates_dev``,
+    ``ema_advance`` as ``sgd_flat_ema``'s): optional, the same one kernel."""
+    _table_args("sgd_flat_table", table, p, g, buf, ema)
+    eptr, rec, keep = _table_ema("sgd_flat_table", ema, decay, warmup, updates_dev, guard)
+    trust, ws, nws, eta = None, None, 0, 0.0
+    if trust_coefficient is not None:
+        eta = float(trust_coefficient)
+        if not (eta > 0 and math.isfinite(eta)):
+            raise AvidHipError(f"sgd_flat_table: the trust coefficient must be finite and > 0 (got {trust_coefficient})")
+        trust = table.trust
+        ws = workspace(p.device, table.workspace_bytes())
+        nws = ws.numel()
+    lib.call("avid_sgd_flat_table", C.byref(table.desc), p.numel(), _p(p), _p(g), _p(buf), float(lr), float(momentum),
+             int(bool(nesterov)), _p(lr_dev), float(grad_scale), eta, _p(trust), _p(rec), eptr, _p(ws), nws, _stream())
+    if ema is not None and updates_dev is not None and ema_advance:
+        ema_counter_add(updates_dev, guard)
+
+
+def _table_step(step_dev, advance, guard, rec, st):
+    if step_dev is not None and advance:
+        if guard is None:
+            lib.call("avid_counter_add", _p(step_dev), 1, st)
+        else:
+            lib.call("avid_counter_add_unless", _p(step_dev), 1, _p(rec), st)
+
+
+def adam_flat_table(table, p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, lr_dev=None, advance=True,
+                    guard=None, ema=None, decay=None, warmup=False, updates_dev=None, ema_advance=True):
+    """``adam_flat`` with every segment's own learning rate and (L2) weight decay (``avid_adam_flat_table``); ``step_dev`` /
+    ``lr_dev`` / ``advance`` as ``adam_flat``'s, ``guard`` / ``ema`` as ``sgd_flat_table``'s."""
+    _table_args("adam_flat_table", table, p, g, m, v, ema)
+    eptr, rec, keep = _table_ema("adam_flat_table", ema, decay, warmup, updates_dev, guard)
+    st = _stream()
+    _table_step(step_dev, advance, guard, rec, st)
+    lib.call("avid_adam_flat_table", C.byref(table.desc), p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1),
+             float(beta2), float(eps), int(step), _p(step_dev), _p(lr_dev), float(grad_scale), _p(rec), eptr, st)
+    if ema is not None and updates_dev is not None and ema_advance:
+        ema_counter_add(updates_dev, guard)
+
+
+def lamb_flat(table, p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, lr_dev=None, advance=True,
+              guard=None, ema=None, decay=None, warmup=False, updates_dev=None, ema_advance=True):
+    """LAMB over the segments of ``table`` in two passes (``avid_lamb_flat``): Adam's moments of the scaled gradient (no L2
+    term), ``u = m^ / (sqrt(v^) + eps) + wd p``, ``table.trust`` = ``|p| / |u|`` per adapted segment (1 where a norm is 0),
+    ``p -= lr_s * trust * u``.  The gradient is left as it was.  Arguments as ``adam_flat_table``'s."""
+    _table_args("lamb_flat", table, p, g, m, v, ema)
+    eptr, rec, keep = _table_ema("lamb_flat", ema, decay, warmup, updates_dev, guard)
+    st = _stream()
+    _table_step(step_dev, advance, guard, rec, st)
+    ws = workspace(p.device, table.workspace_bytes())
+    lib.call("avid_lamb_flat", C.byref(table.desc), p.numel(), _p(p), _p(g), _p(m), _p(v), float(lr), float(beta1), float(beta2),
+             float(eps), int(step), _p(step_dev), _p(lr_dev), float(grad_scale), _p(table.trust), _p(rec), eptr, _p(ws),
+             ws.numel(), st)
+    if ema is not None and updates_dev is not None and ema_advance:
+        ema_counter_add(updates_dev, guard)
 
 
 # ------------------------------------------------------------------------------------------------

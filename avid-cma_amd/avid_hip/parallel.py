@@ -19,6 +19,8 @@ What the reference does with ``DistributedDataParallel`` + ``torch.optim.Adam``
                      format (the reference's CheckpointManager saves ``optimizer.state_dict()``, main-avid.py:115,127,138).
                      ``optimizer="sgd"``: the other optimizer of ``build_optimizer`` (utils/main_utils.py:242-248) instead —
                      one flat SGD launch, one momentum buffer, torch.optim.SGD's checkpoint format.
+                     ``param_rules`` (per-tensor lr scale / weight decay) and ``optimizer="lars"`` / ``"lamb"`` run the
+                     table-driven kernels over an ``ops.SegmentTable`` of the flat layout.
 * ``TrainStep``    — AdamStep for pretraining: fwd -> criterion -> bwd (+ overlapped all-reduce) -> Adam; hipGraph capture
                      (``FinetuneStep``: for action-recognition fine-tuning).
 
@@ -30,6 +32,7 @@ from __future__ import annotations
 import contextlib
 import math
 import os
+import re
 import warnings
 import weakref
 import torch
@@ -495,6 +498,53 @@ def _require_format(who, sd, want):
     return g
 
 
+_RULE_KEYS = ("lr_scale", "weight_decay", "adapt")
+
+
+def rules_no_decay_1d(model):
+    """``param_rules`` of the usual exclusion: every trainable tensor with ``ndim <= 1`` (BatchNorm weights and biases, the other
+    biases) takes ``weight_decay=0`` and ``adapt=False``.  One anchored pattern per tensor; put rules of your own in front of
+    them (the first match wins)."""
+    return [("^" + re.escape(n) + "$", {"weight_decay": 0.0, "adapt": False})
+            for n, p in model.named_parameters() if p.requires_grad and p.ndim <= 1]
+
+
+def _resolve_param_rules(who, named, rules):
+    """{name: {key: value}} of the overrides ``rules`` — (pattern, dict) pairs, the first ``re.search`` match on the name wins —
+    give the (name, parameter) pairs ``named``; the ValueError for an unknown key, a value that is not a finite number >= 0,
+    or a rule whose pattern matches no name."""
+    named = list(named)
+    rules = list(rules or [])
+    compiled = []
+    for k, rule in enumerate(rules):
+        if not (isinstance(rule, (tuple, list)) and len(rule) == 2 and isinstance(rule[1], dict)):
+            raise ValueError(f"{who}: param_rules[{k}] is not a (pattern, dict) pair")
+        pattern, values = rule
+        unknown = sorted(set(values) - set(_RULE_KEYS))
+        if unknown:
+            raise ValueError(f"{who}: param_rules[{k}] ({pattern!r}) has unknown key(s) {unknown}; the keys are {list(_RULE_KEYS)}")
+        clean = {}
+        for key, val in values.items():
+            if key == "adapt":
+                clean[key] = bool(val)
+                continue
+            val = float(val)
+            if not (math.isfinite(val) and val >= 0):
+                raise ValueError(f"{who}: param_rules[{k}] ({pattern!r}): {key} must be a finite number >= 0 (got {val})")
+            clean[key] = val
+        rx = re.compile(pattern)
+        if not any(rx.search(n) for n, _ in named):
+            raise ValueError(f"{who}: param_rules[{k}] ({pattern!r}) matches no trainable parameter")
+        compiled.append((rx, clean))
+    out = {}
+    for n, _ in named:
+        for rx, clean in compiled:
+            if rx.search(n):
+                out[n] = dict(clean)
+                break
+    return out
+
+
 class AdamStep(EngineCore):
     """The core plus Adam over the flat buffers: one fused launch per step (or per slice of the buffers), moments ``m`` / ``v``,
     the step count and learning rate in device memory as well (a captured graph reads them there).
@@ -503,6 +553,19 @@ class AdamStep(EngineCore):
     the same one launch per slice (``ops.sgd_flat``).  Its only state is ``momentum_buffer``, laid out like the flat
     parameters (None without momentum); ``m`` / ``v`` / ``t_dev`` are None — the update needs no step count, a zero buffer
     is torch's first step — and ``t`` just counts steps on the host.  ``state_dict`` is then torch.optim.SGD's.
+
+    ``optimizer="lars"`` (with ``momentum``, ``nesterov``, ``trust_coefficient``) is the SGD family with a trust factor per
+    tensor, ``q = trust_coefficient * |p| / |g~ + wd p|`` on the update in front of the momentum; ``optimizer="lamb"`` (with
+    ``betas``, ``eps``) is the Adam family with ``r = |p| / |u|`` on ``u = m^ / (sqrt(v^) + eps) + wd p``.  Both run the
+    table-driven kernels (``ops.sgd_flat_table`` / ``ops.lamb_flat``): the norms are per-tensor sums in double in a fixed order,
+    the factors stay on the device (``trust``), nothing synchronises the host.  Checkpoints are torch.optim.SGD's / Adam's.
+    ``param_rules``: (pattern, dict) pairs, the first ``re.search`` match on a parameter's ``named_parameters()`` name wins;
+    the dict may set ``lr_scale``, ``weight_decay`` and ``adapt`` (False: no trust ratio) for the tensors it matches, the
+    others keep the engine's values (``rules_no_decay_1d(model)``: the usual exclusion of BatchNorm and biases).  An unknown
+    key or a rule that matches nothing raises.  With rules ``"adam"`` / ``"sgd"`` run ``ops.adam_flat_table`` /
+    ``ops.sgd_flat_table``; without them exactly the kernels they always ran.  A table-driven step runs its optimizer in
+    one piece (as a guarded step does).  ``state_dict()`` gains the key ``avid_param_table`` (name, ``lr_scale``,
+    ``weight_decay``, ``adapt`` per tensor), which ``load_state_dict`` compares with the engine's own.
 
     The step guard, off by default (``guard`` is None and nothing below is launched).  ``max_grad_norm`` (> 0, finite):
     ``torch.nn.utils.clip_grad_norm_``'s rule on the norm of the averaged flat gradient; ``skip_nonfinite=True``: a step whose
@@ -531,12 +594,19 @@ class AdamStep(EngineCore):
     virtual_ranks = 1        # ranks whose gradients the buffer holds the SUM of, per process (the step engines' virtual_ranks=R)
 
     def __init__(self, model, lr, betas, eps, weight_decay, optimizer="adam", momentum=0.0, nesterov=False,
-                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_buffers=True, **core):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_buffers=True,
+                 param_rules=None, trust_coefficient=0.001, **core):
         ema_decay = _ema_decay_arg(type(self).__name__, ema_decay)
-        if optimizer not in ("adam", "sgd"):
-            raise ValueError("optimizer must be 'adam' or 'sgd'")
-        if optimizer == "sgd" and (momentum < 0 or (nesterov and momentum == 0)):
+        if optimizer not in ("adam", "sgd", "lars", "lamb"):
+            raise ValueError("optimizer must be 'adam', 'sgd', 'lars' or 'lamb'")
+        if optimizer in ("sgd", "lars") and (momentum < 0 or (nesterov and momentum == 0)):
             raise ValueError("SGD: momentum must be >= 0, and Nesterov momentum requires a momentum")
+        trust_coefficient = float(trust_coefficient)
+        if optimizer == "lars" and not (trust_coefficient > 0 and math.isfinite(trust_coefficient)):
+            raise ValueError(f"LARS: trust_coefficient must be a finite number > 0 (got {trust_coefficient})")
+        # resolved before anything is flattened: a bad rule leaves the model as it was
+        overrides = _resolve_param_rules(type(self).__name__, ((n, p) for n, p in model.named_parameters() if p.requires_grad),
+                                         param_rules)
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not (max_grad_norm > 0 and math.isfinite(max_grad_norm)):
@@ -551,6 +621,14 @@ class AdamStep(EngineCore):
             from . import ops
             self.guard = ops.StepGuard(self.flat.flat.device)
         self.optimizer = optimizer
+        self._sgd_family = optimizer in ("sgd", "lars")
+        self.trust_coefficient = trust_coefficient
+        # the table-driven kernels: with rules, and always under LARS / LAMB (whose trust ratios are per tensor)
+        self._table_on = param_rules is not None or optimizer in ("lars", "lamb")
+        names = {id(p): n for n, p in model.named_parameters()}
+        self._param_names = [names[id(p)] for p in self.flat.params]          # by slot of the flat layout
+        self._param_overrides = [overrides.get(n, {}) for n in self._param_names]
+        self._tables = {}
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.momentum, self.nesterov = float(momentum), bool(nesterov)
         self.t = 0
@@ -569,7 +647,7 @@ class AdamStep(EngineCore):
             if ema_buffers and fb is not None:
                 self.ema_buffers_flat = fb.detach().clone()
         self.m = self.v = self.t_dev = self.momentum_buffer = None
-        if optimizer == "sgd":
+        if self._sgd_family:
             if self.momentum != 0:
                 self.momentum_buffer = torch.zeros_like(self.flat.flat)
             return
@@ -629,6 +707,8 @@ class AdamStep(EngineCore):
         averaging forms of the same kernels (``last=False``: another slice of the same step follows)."""
         from . import ops
         s = slice(begin, end)
+        if self._table_on:
+            return self._update_table(begin, end, advance, last)
         if self.ema is not None:
             return self._update_averaging(s, advance, last)
         if self.guard is not None:
@@ -671,6 +751,85 @@ class AdamStep(EngineCore):
                               **kw)
         if last and fb is not None:
             ops.ema_flat(self.ema_buffers_flat, fb, self.ema_decay, self.ema_warmup, self.ema_updates, self.guard)
+
+    # ---- per-tensor hyper-parameters and trust ratios (``param_rules``, ``optimizer="lars"`` / ``"lamb"``)
+    def param_values(self):
+        """[(name, lr_scale, weight_decay, adapt)] by slot of the flat layout: the engine's base values (``lr_scale`` 1, its
+        ``weight_decay``, ``adapt`` True) under the overrides of the first matching rule."""
+        return [(n, float(o.get("lr_scale", 1.0)), float(o.get("weight_decay", self.wd)), bool(o.get("adapt", True)))
+                for n, o in zip(self._param_names, self._param_overrides)]
+
+    def _update_range(self):
+        """[begin, end) of the flat buffers the optimizer updates (``FinetuneStep(classifier_only=True)``: the classifier's)."""
+        return 0, self.flat.numel
+
+    def segment_table(self, begin=None, end=None):
+        """The ``ops.SegmentTable`` of elements [begin, end) of the flat buffers (default: the slice the optimizer updates),
+        built once per slice and per set of values; its ``trust`` holds the factors the last LARS / LAMB step applied."""
+        if begin is None:
+            begin, end = self._update_range()
+        end = self.flat.numel if end is None else end
+        key = (begin, end)
+        hit = self._tables.get(key)
+        if hit is None or hit[0] != self.wd:               # (a loaded checkpoint may change the base weight decay)
+            from . import ops
+            vals = self.param_values()
+            tab = ops.SegmentTable(self.flat, [v[1] for v in vals], [v[2] for v in vals], [v[3] for v in vals], begin=begin, end=end)
+            if hit is not None and hit[1].S == tab.S:
+                tab.trust.copy_(hit[1].trust)
+            hit = (self.wd, tab)
+            self._tables[key] = hit
+        return hit[1]
+
+    @property
+    def trust(self):
+        """float32 [S] on the device: the trust factor of every tensor the optimizer updates, in the flat layout's order, as the
+        last applied LARS / LAMB step left it (ones before the first; None for an engine without trust ratios)."""
+        return self.segment_table().trust if self.optimizer in ("lars", "lamb") else None
+
+    def _update_table(self, begin, end, advance, last):
+        """``_update`` through the table-driven kernels (one kernel per family: guard and average are nullable arguments)."""
+        from . import ops
+        end = self.flat.numel if end is None else end
+        s = slice(begin, end)
+        tab = self.segment_table(begin, end)
+        kw = dict(grad_scale=self._grad_scale(), lr_dev=self.lr_dev, guard=self.guard)
+        fb = None
+        if self.ema is not None:
+            self._ema_live("step")
+            fb = self.flat_buffers.flat if self.ema_buffers_flat is not None else None
+            kw.update(ema=self.ema[s], decay=self.ema_decay, warmup=self.ema_warmup, updates_dev=self.ema_updates,
+                      ema_advance=last and fb is None)
+        if self._sgd_family:
+            buf = self.momentum_buffer
+            ops.sgd_flat_table(tab, self.flat.flat[s], self.flat.grad[s], None if buf is None else buf[s], self.lr, self.momentum,
+                               self.nesterov, trust_coefficient=self.trust_coefficient if self.optimizer == "lars" else None, **kw)
+        else:
+            fn = ops.lamb_flat if self.optimizer == "lamb" else ops.adam_flat_table
+            fn(tab, self.flat.flat[s], self.flat.grad[s], self.m[s], self.v[s], self.lr, self.betas[0], self.betas[1], self.eps,
+               self.t, step_dev=self.t_dev, advance=advance, **kw)
+        if last and fb is not None:
+            ops.ema_flat(self.ema_buffers_flat, fb, self.ema_decay, self.ema_warmup, self.ema_updates, self.guard)
+
+    def _param_table_checkpoint(self):
+        vals = self.param_values()
+        return [{"name": vals[i][0], "lr_scale": vals[i][1], "weight_decay": vals[i][2], "adapt": vals[i][3]}
+                for _, i, _ in self._param_order()]
+
+    def _check_param_table(self, saved):
+        """``load_state_dict``: the checkpoint's ``avid_param_table`` against this engine's, tensor by tensor."""
+        if saved is None:
+            return
+        mine = self._param_table_checkpoint()
+        for a, b in zip(saved, mine):
+            if dict(a) != b:
+                raise ValueError(f"{type(self).__name__}.load_state_dict: the checkpoint's avid_param_table differs from this "
+                                 f"engine's at tensor {b['name']!r}: saved {dict(a)}, here {b}")
+        if len(saved) != len(mine):
+            k = min(len(saved), len(mine))
+            name = (mine[k] if len(mine) > k else saved[k])["name"]
+            raise ValueError(f"{type(self).__name__}.load_state_dict: the checkpoint's avid_param_table holds {len(saved)} "
+                             f"tensors, this engine's {len(mine)}: the first one without a partner is {name!r}")
 
     def optimizer_step(self):
         self.t += 1
@@ -968,13 +1127,15 @@ class AdamStep(EngineCore):
         guard on it lags the host's ``t`` (attempted steps) by ``guard.skipped_total``.  With ``ema_decay`` one more top-level
         key, ``avid_ema`` (``_ema_checkpoint``); without it the dict is the optimizer's alone."""
         sd = self._optimizer_state_dict()
+        if self._table_on:
+            sd["avid_param_table"] = self._param_table_checkpoint()
         if self.ema is not None:
             self._ema_live("state_dict")
             sd["avid_ema"] = self._ema_checkpoint()
         return sd
 
     def _optimizer_state_dict(self):
-        if self.optimizer == "sgd":
+        if self._sgd_family:
             return self._sgd_state_dict()
         step = float(int(self.t_dev) if self.t_dev is not None else self.t)
         state = {}
@@ -991,10 +1152,11 @@ class AdamStep(EngineCore):
 
     def load_state_dict(self, sd):
         self._load_optimizer_state_dict(sd)
+        self._check_param_table(sd.get("avid_param_table"))
         self._load_ema_checkpoint(sd.get("avid_ema"))
 
     def _load_optimizer_state_dict(self, sd):
-        if self.optimizer == "sgd":
+        if self._sgd_family:
             return self._load_sgd_state_dict(sd)
         g = _require_format(type(self).__name__, sd, "Adam")
         self.betas, self.eps, self.wd = tuple(g["betas"]), g["eps"], g["weight_decay"]
@@ -1014,7 +1176,8 @@ class TrainStep(AdamStep):
 
     def __init__(self, model, criterion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
-                 virtual_ranks=1, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_buffers=True):
+                 virtual_ranks=1, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_buffers=True,
+                 param_rules=None, trust_coefficient=0.001):
         """``broadcast_buffers``: see ``EngineCore``.  ``optimizer`` / ``momentum`` / ``nesterov``: see ``AdamStep``.
         ``max_grad_norm`` / ``skip_nonfinite``: the step guard, see ``AdamStep``.  Here a skipped step also puts back the bank
         rows it updated, the optimizer gives up its overlapped early slice (it would run before the norm is known), and the
@@ -1026,7 +1189,8 @@ class TrainStep(AdamStep):
         R = _virtual_ranks_arg("TrainStep", virtual_ranks, broadcast_buffers)
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                         ema_buffers=ema_buffers, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+                         ema_buffers=ema_buffers, param_rules=param_rules, trust_coefficient=trust_coefficient,
+                         bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.criterion = criterion
         self.graph = None
         self.virtual_ranks = R
@@ -1328,7 +1492,7 @@ class TrainStep(AdamStep):
         loss = self.forward_backward(video, audio, index)
         pl = self._step_plan
         if (pl is not None and pl.adam_early and not self.buckets.comm and not lib.TIMING and self.virtual_ranks == 1
-                and self.guard is None):
+                and self.guard is None and not self._table_on):
             self._optimizer_step_overlapped(pl)
         else:
             self.optimizer_step()
@@ -1875,7 +2039,7 @@ class FinetuneStep(AdamStep):
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, classifier_only=False,
                  bucket_bytes=16 << 20, broadcast_buffers="step", optimizer="adam", momentum=0.0, nesterov=False,
                  max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None, label_smoothing=0.0,
-                 ema_decay=None, ema_warmup=False, ema_buffers=True):
+                 ema_decay=None, ema_warmup=False, ema_buffers=True, param_rules=None, trust_coefficient=0.001):
         """``loss``: ``"ce"`` (default), ``"soft_ce"`` or ``"bce"``.  ``"soft_ce"``: softmax cross-entropy against a distribution
         (mixup / CutMix targets from ``datasets.gpu_mix.GpuBatchMix``, a teacher's probabilities) with ``label_smoothing`` in
         [0, 1): ``step(x, targets)`` takes float32 targets [B, C], ``step(x, labels)`` int64 labels [B] (made one-hot on the
@@ -1893,7 +2057,8 @@ class FinetuneStep(AdamStep):
         R = _virtual_ranks_arg("FinetuneStep", virtual_ranks, broadcast_buffers)
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                         ema_buffers=ema_buffers, bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
+                         ema_buffers=ema_buffers, param_rules=param_rules, trust_coefficient=trust_coefficient,
+                         bucket_bytes=bucket_bytes, broadcast_buffers=broadcast_buffers)
         self.classifier_only = bool(classifier_only)
         self.n_cls = self.flat.offsets[2] if len(self.flat.params) > 2 else self.flat.numel   # (reverse order: classifier bias, weight first)
         self._set_loss(loss, pos_weight, lambda: model.classifier.weight.shape[0], label_smoothing)
@@ -2003,6 +2168,9 @@ class FinetuneStep(AdamStep):
         self.rank_losses, self.rank_hits = out[:, 0], out[:, 2:6].view(torch.int64)
         return self.rank_losses.mean(), self.rank_hits.sum(0)
 
+    def _update_range(self):
+        return 0, (self.n_cls if self.classifier_only else self.flat.numel)
+
     def _param_order(self):
         order = super()._param_order()
         if self.classifier_only:           # the warm-up optimizer holds the classifier's parameters only
@@ -2048,7 +2216,8 @@ class ProbeStep(AdamStep):
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="adam", momentum=0.0,
                  nesterov=False, max_grad_norm=None, skip_nonfinite=False, virtual_ranks=1, loss="ce", pos_weight=None,
-                 label_smoothing=0.0, ema_decay=None, ema_warmup=False, ema_buffers=True):
+                 label_smoothing=0.0, ema_decay=None, ema_warmup=False, ema_buffers=True, param_rules=None,
+                 trust_coefficient=0.001):
         """``optimizer`` / ``momentum`` / ``nesterov``, ``max_grad_norm`` / ``skip_nonfinite`` (the step guard): see ``AdamStep``.
         ``virtual_ranks``: see the class.  ``loss`` / ``pos_weight`` / ``label_smoothing``: as ``FinetuneStep``'s — ``"bce"`` ends
         every tap in ``avid_mlabel_loss`` against float32 targets [B, C], ``"soft_ce"`` in ``avid_soft_ce_loss`` against float32
@@ -2058,7 +2227,8 @@ class ProbeStep(AdamStep):
             raise NotImplementedError("ProbeStep runs in a single process (the linear probe's config is not distributed)")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                         ema_buffers=ema_buffers, broadcast_buffers="off")
+                         ema_buffers=ema_buffers, param_rules=param_rules, trust_coefficient=trust_coefficient,
+                         broadcast_buffers="off")
         self.n_taps = len(model.classifiers)
         self._set_loss(loss, pos_weight, lambda: next(iter(model.classifiers)).classifier.weight.shape[0], label_smoothing)
         self.virtual_ranks = R

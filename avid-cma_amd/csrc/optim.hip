@@ -622,6 +622,480 @@ __global__ __launch_bounds__(256) void swap_flat_kernel(float* __restrict__ a, f
   }
 }
 
+// ---- segment tables: per-tensor hyper-parameters, per-segment norms, LARS / LAMB ------------------------------------------
+// A workgroup takes CHUNKS (AVID_SEG_CHUNK floats of one segment: chunk c, c + gridDim.x, ...), finds its segment in the chunk
+// record and walks the chunk's 16-byte vectors (a segment starts on a 16-byte boundary, a chunk is a multiple of it); the up to
+// three elements behind a segment's last vector are scalar accesses of threads 0..2, so that nothing outside a segment — the
+// padding between tensors — is read into a sum or written.  What an element becomes depends on its own index only.
+constexpr int SEG_THREADS = 256;
+
+struct SegArgs {
+  const avid_segment* segs;
+  const avid_seg_chunk* chunks;
+  int n_chunks;
+  float* p;            // (the plain sums: x)
+  const float* g;      // (the plain sums: y, nullable)
+  float* m;
+  float* v;
+  float* buf;
+  float* e;            // the weight average, nullable
+  float lr, momentum, b1, b2, eps, grad_scale;
+  int nesterov;
+  double bc1, inv_bc1;           // 1 - beta1^step and its reciprocal, from the host's step
+  float inv_sqrt_bc2;            // (float)(1 / sqrt(1 - beta2^step))
+  const long long* step_dev;
+  const float* lr_dev;
+  const avid_step_guard* guard;
+  const float* trust;            // per-segment factor the update applies, nullable (1.0f)
+  double decay;
+  int warmup;
+  const long long* updates_dev;
+  double* partials;              // [n_chunks][2]
+};
+
+// What a launch reads once: the skip word, the clip coefficient, the learning rate and Adam's bias corrections as
+// adam_flat_kernel forms them (step_case 0: by value, 1: lr_dev alone, 2: step_dev), the averaging weight.
+struct SegTerms {
+  float coef, lr, inv_sqrt_bc2, c1, w;
+  double bc1, inv_bc1;
+  int step_case;
+};
+
+__device__ __forceinline__ bool seg_terms(const SegArgs& a, bool adam, SegTerms& t) {
+  if (a.guard && a.guard->skip) return false;
+  t.coef = a.guard ? a.guard->clip_coef : 1.f;
+  t.lr = a.lr_dev ? *a.lr_dev : a.lr;
+  t.bc1 = a.bc1;
+  t.inv_bc1 = a.inv_bc1;
+  t.inv_sqrt_bc2 = a.inv_sqrt_bc2;
+  t.step_case = a.lr_dev ? 1 : 0;
+  if (adam && a.step_dev) {
+    const double s = (double)*a.step_dev;
+    t.bc1 = 1.0 - pow((double)a.b1, s);
+    t.inv_bc1 = 1.0 / t.bc1;
+    t.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, s)));
+    t.step_case = 2;
+  }
+  t.c1 = (float)t.inv_bc1;
+  t.w = a.e ? ema_weight(a.decay, a.warmup, a.updates_dev) : 0.f;
+  return true;
+}
+
+// The learning rate of a segment: one fp32 product (times 1.0f is exact).
+__device__ __forceinline__ float seg_lr(float lr, float lr_scale) {
+#pragma clang fp contract(off)
+  const float s = lr * lr_scale;
+  return s;
+}
+
+// adam_flat_kernel's step size for a segment's learning rate, in the case the launch is in.
+__device__ __forceinline__ float seg_adam_step_size(float lr_s, const SegTerms& t) {
+  return t.step_case == 1 ? (float)((double)lr_s * t.inv_bc1) : (float)((double)lr_s / t.bc1);
+}
+
+// Two block sums at once, guard_block_sum's order each; thread 0 stores the chunk's pair.  (Ends in a barrier: the next chunk
+// of the same workgroup writes the same LDS words.)
+__device__ __forceinline__ void seg_store_partial(double sa, double sb, double* lds, double* __restrict__ partials, int c) {
+  sa = wave_sum_d(sa);
+  sb = wave_sum_d(sb);
+  if ((threadIdx.x & 63) == 0) {
+    lds[threadIdx.x >> 6] = sa;
+    lds[4 + (threadIdx.x >> 6)] = sb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[2 * (long long)c] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+    partials[2 * (long long)c + 1] = ((lds[4] + lds[5]) + lds[6]) + lds[7];
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void seg_sumsq_kernel(SegArgs a) {
+  __shared__ double lds[8];
+  if (a.guard && a.guard->skip) return;
+  const float* __restrict__ x = a.p;
+  const float* __restrict__ y = a.g;
+  for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+    const avid_seg_chunk ck = a.chunks[c];
+    const int nv = ck.len >> 2, tail = ck.len & 3;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
+      const floatx4 xv = reinterpret_cast<const floatx4*>(x + ck.start)[i];
+      a0 += (double)xv[0] * (double)xv[0];
+      a1 += (double)xv[1] * (double)xv[1];
+      a2 += (double)xv[2] * (double)xv[2];
+      a3 += (double)xv[3] * (double)xv[3];
+      if (y) {
+        const floatx4 yv = reinterpret_cast<const floatx4*>(y + ck.start)[i];
+        b0 += (double)yv[0] * (double)yv[0];
+        b1 += (double)yv[1] * (double)yv[1];
+        b2 += (double)yv[2] * (double)yv[2];
+        b3 += (double)yv[3] * (double)yv[3];
+      }
+    }
+    if ((int)threadIdx.x < tail) {
+      const long long i = ck.start + nv * 4 + threadIdx.x;
+      a0 += (double)x[i] * (double)x[i];
+      if (y) b0 += (double)y[i] * (double)y[i];
+    }
+    seg_store_partial((a0 + a1) + (a2 + a3), (b0 + b1) + (b2 + b3), lds, a.partials, c);
+  }
+}
+
+// d of the SGD family up to the weight-decay term: what the trust factor's norm is taken of, and what the update goes on
+// from — the same operations in both places.
+__device__ __forceinline__ float sgd_table_d(float g, float p, float grad_scale, float coef, float wd) {
+#pragma clang fp contract(off)
+  float d = g * grad_scale;
+  d = d * coef;
+  if (wd != 0.f) {
+    const float t = wd * p;
+    d = d + t;
+  }
+  return d;
+}
+
+// sgd_element_clipped with the factor q on d in front of the momentum (q == 1.0f: its bits).
+__device__ __forceinline__ void sgd_table_element(float& p, float g, float& b, bool has_buf, float lr, float momentum, float wd,
+                                                  bool nesterov, float grad_scale, float coef, float q) {
+#pragma clang fp contract(off)
+  float d = sgd_table_d(g, p, grad_scale, coef, wd);
+  d = q * d;
+  if (has_buf) {
+    const float t = momentum * b;
+    b = t + d;
+    if (nesterov) {
+      const float u = momentum * b;
+      d = d + u;
+    } else {
+      d = b;
+    }
+  }
+  const float s = lr * d;
+  p = p - s;
+}
+
+// The norm pass of LARS: per chunk the sums of p^2 and of d^2.
+__global__ __launch_bounds__(SEG_THREADS) void sgd_table_norm_kernel(SegArgs a) {
+  __shared__ double lds[8];
+  SegTerms t;
+  if (!seg_terms(a, false, t)) return;
+  const float* __restrict__ p = a.p;
+  const float* __restrict__ g = a.g;
+  for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+    const avid_seg_chunk ck = a.chunks[c];
+    const float wd = a.segs[ck.seg].weight_decay;
+    const int nv = ck.len >> 2, tail = ck.len & 3;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
+      const floatx4 pv = reinterpret_cast<const floatx4*>(p + ck.start)[i];
+      const floatx4 gv = reinterpret_cast<const floatx4*>(g + ck.start)[i];
+      const float d0 = sgd_table_d(gv[0], pv[0], a.grad_scale, t.coef, wd), d1 = sgd_table_d(gv[1], pv[1], a.grad_scale, t.coef, wd);
+      const float d2 = sgd_table_d(gv[2], pv[2], a.grad_scale, t.coef, wd), d3 = sgd_table_d(gv[3], pv[3], a.grad_scale, t.coef, wd);
+      a0 += (double)pv[0] * (double)pv[0];
+      a1 += (double)pv[1] * (double)pv[1];
+      a2 += (double)pv[2] * (double)pv[2];
+      a3 += (double)pv[3] * (double)pv[3];
+      b0 += (double)d0 * (double)d0;
+      b1 += (double)d1 * (double)d1;
+      b2 += (double)d2 * (double)d2;
+      b3 += (double)d3 * (double)d3;
+    }
+    if ((int)threadIdx.x < tail) {
+      const long long i = ck.start + nv * 4 + threadIdx.x;
+      const float pi = p[i], d = sgd_table_d(g[i], pi, a.grad_scale, t.coef, wd);
+      a0 += (double)pi * (double)pi;
+      b0 += (double)d * (double)d;
+    }
+    seg_store_partial((a0 + a1) + (a2 + a3), (b0 + b1) + (b2 + b3), lds, a.partials, c);
+  }
+}
+
+// One wave per segment adds its chunks' pairs in index order; sums (nullable) takes them, trust (nullable) the factor
+// (float)(eta * (sqrt(sum a) / sqrt(sum b))) of an adapted segment whose two sums are > 0, 1.0f otherwise.
+// The adds are one dependent chain per sum — pair 0, 1, 2, ... exactly as a single thread would add them, which every lane does
+// redundantly — but the loads are not: lane l fetches pair k0 + l of a tile of 64 (the next tile while this one is added) and
+// the chain reads them lane by lane.  (One thread with one pair per round trip took 107 us over the 21.3 M parameters' 5 282
+// partials — the largest tensor alone has 576 — three times the norm pass in front of it.)
+__device__ __forceinline__ void seg_finish_tile(double a, double b, int cnt, double& sa, double& sb) {
+  if (cnt == 64) {
+#pragma unroll
+    for (int j = 0; j < 64; ++j) {
+      sa += __shfl(a, j, 64);
+      sb += __shfl(b, j, 64);
+    }
+    return;
+  }
+  for (int j = 0; j < cnt; ++j) {
+    sa += __shfl(a, j, 64);
+    sb += __shfl(b, j, 64);
+  }
+}
+
+__global__ __launch_bounds__(64) void seg_finish_kernel(const avid_segment* __restrict__ segs, int S,
+                                                        const double* __restrict__ partials, double eta,
+                                                        double* __restrict__ sums, float* __restrict__ trust,
+                                                        const avid_step_guard* __restrict__ guard) {
+  if (guard && guard->skip) return;
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (s >= S) return;
+  const avid_segment sg = segs[s];
+  const long long nck = (sg.numel + AVID_SEG_CHUNK - 1) / AVID_SEG_CHUNK;
+  const double* __restrict__ mine = partials + 2 * (long long)sg.first_chunk;
+  double sa = 0.0, sb = 0.0, a = 0.0, b = 0.0;
+  if (lane < nck) {
+    a = mine[2 * lane];
+    b = mine[2 * lane + 1];
+  }
+  for (long long k0 = 0; k0 < nck; k0 += 64) {
+    const long long next = k0 + 64 + lane;
+    double na = 0.0, nb = 0.0;
+    if (next < nck) {
+      na = mine[2 * next];
+      nb = mine[2 * next + 1];
+    }
+    const long long left = nck - k0;
+    seg_finish_tile(a, b, left < 64 ? (int)left : 64, sa, sb);
+    a = na;
+    b = nb;
+  }
+  if (lane != 0) return;
+  if (sums) {
+    sums[2 * s] = sa;
+    sums[2 * s + 1] = sb;
+  }
+  if (trust) {
+    float q = 1.f;
+    if (sg.adapt && sa > 0.0 && sb > 0.0) q = (float)(eta * (sqrt(sa) / sqrt(sb)));
+    trust[s] = q;
+  }
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void sgd_flat_table_kernel(SegArgs a) {
+  SegTerms t;
+  if (!seg_terms(a, false, t)) return;
+  float* __restrict__ p = a.p;
+  const float* __restrict__ g = a.g;
+  float* __restrict__ buf = a.buf;
+  float* __restrict__ e = a.e;
+  const bool has_buf = buf != nullptr, nesterov = a.nesterov != 0;
+  for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+    const avid_seg_chunk ck = a.chunks[c];
+    const avid_segment sg = a.segs[ck.seg];
+    const float lr = seg_lr(t.lr, sg.lr_scale), wd = sg.weight_decay, q = a.trust ? a.trust[ck.seg] : 1.f;
+    const int nv = ck.len >> 2, tail = ck.len & 3;
+    for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
+      floatx4 pv = reinterpret_cast<floatx4*>(p + ck.start)[i];
+      const floatx4 gv = reinterpret_cast<const floatx4*>(g + ck.start)[i];
+      floatx4 bv = {0.f, 0.f, 0.f, 0.f}, ev = {0.f, 0.f, 0.f, 0.f};
+      if (has_buf) bv = reinterpret_cast<floatx4*>(buf + ck.start)[i];
+      if (e) ev = reinterpret_cast<floatx4*>(e + ck.start)[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = pv[j], bj = bv[j];
+        sgd_table_element(pj, gv[j], bj, has_buf, lr, a.momentum, wd, nesterov, a.grad_scale, t.coef, q);
+        pv[j] = pj;
+        bv[j] = bj;
+        if (e) ev[j] = ema_element(ev[j], pj, t.w);
+      }
+      reinterpret_cast<floatx4*>(p + ck.start)[i] = pv;
+      if (has_buf) reinterpret_cast<floatx4*>(buf + ck.start)[i] = bv;
+      if (e) reinterpret_cast<floatx4*>(e + ck.start)[i] = ev;
+    }
+    if ((int)threadIdx.x < tail) {
+      const long long i = ck.start + nv * 4 + threadIdx.x;
+      float pi = p[i], bi = has_buf ? buf[i] : 0.f;
+      sgd_table_element(pi, g[i], bi, has_buf, lr, a.momentum, wd, nesterov, a.grad_scale, t.coef, q);
+      p[i] = pi;
+      if (has_buf) buf[i] = bi;
+      if (e) e[i] = ema_element(e[i], pi, t.w);
+    }
+  }
+}
+
+// The gradient term of the Adam family.  Unclipped: adam_flat_kernel's fma(g, grad_scale, wd * p).  Clipped: the scaled
+// gradient, then the decay term added unfused — what the unclipped form gives for a gradient scaled beforehand by a power of two.
+__device__ __forceinline__ float adam_table_grad_term(float g, float p, float grad_scale, float wd, float coef) {
+#pragma clang fp contract(off)
+  if (coef == 1.f) return adam_grad_term<false>(g, p, grad_scale, wd, coef);
+  float t = g * grad_scale;
+  t = t * coef;
+  const float u = wd * p;
+  return u + t;
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void adam_flat_table_kernel(SegArgs a) {
+  SegTerms t;
+  if (!seg_terms(a, true, t)) return;
+  float* __restrict__ p = a.p;
+  const float* __restrict__ g = a.g;
+  float* __restrict__ m = a.m;
+  float* __restrict__ v = a.v;
+  float* __restrict__ e = a.e;
+  for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+    const avid_seg_chunk ck = a.chunks[c];
+    const avid_segment sg = a.segs[ck.seg];
+    const float step_size = seg_adam_step_size(seg_lr(t.lr, sg.lr_scale), t), wd = sg.weight_decay;
+    const int nv = ck.len >> 2, tail = ck.len & 3;
+    for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
+      floatx4 pv = reinterpret_cast<floatx4*>(p + ck.start)[i];
+      const floatx4 gv = reinterpret_cast<const floatx4*>(g + ck.start)[i];
+      floatx4 mv = reinterpret_cast<floatx4*>(m + ck.start)[i];
+      floatx4 vv = reinterpret_cast<floatx4*>(v + ck.start)[i];
+      floatx4 ev = {0.f, 0.f, 0.f, 0.f};
+      if (e) ev = reinterpret_cast<floatx4*>(e + ck.start)[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = pv[j], mj = mv[j], vj = vv[j];
+        const float gg = adam_table_grad_term(gv[j], pj, a.grad_scale, wd, t.coef);
+        adam_element<false>(pj, gg, mj, vj, a.b1, a.b2, a.eps, step_size, t.inv_sqrt_bc2);
+        pv[j] = pj;
+        mv[j] = mj;
+        vv[j] = vj;
+        if (e) ev[j] = ema_element(ev[j], pj, t.w);
+      }
+      reinterpret_cast<floatx4*>(p + ck.start)[i] = pv;
+      reinterpret_cast<floatx4*>(m + ck.start)[i] = mv;
+      reinterpret_cast<floatx4*>(v + ck.start)[i] = vv;
+      if (e) reinterpret_cast<floatx4*>(e + ck.start)[i] = ev;
+    }
+    if ((int)threadIdx.x < tail) {
+      const long long i = ck.start + nv * 4 + threadIdx.x;
+      float pi = p[i], mi = m[i], vi = v[i];
+      const float gg = adam_table_grad_term(g[i], pi, a.grad_scale, wd, t.coef);
+      adam_element<false>(pi, gg, mi, vi, a.b1, a.b2, a.eps, step_size, t.inv_sqrt_bc2);
+      p[i] = pi;
+      m[i] = mi;
+      v[i] = vi;
+      if (e) e[i] = ema_element(e[i], pi, t.w);
+    }
+  }
+}
+
+// LAMB.  The moments: adam_flat_kernel's vector-loop recurrences on gg = fma(g, grad_scale, 0 * p), which is (g * grad_scale) + 0.0f.
+__device__ __forceinline__ void lamb_moments(float g, float& m, float& v, float b1, float b2, float grad_scale, float coef) {
+#pragma clang fp contract(off)
+  float gg = g * grad_scale;
+  gg = gg * coef;
+  gg = gg + 0.f;
+  const float c1 = 1.f - b1, c2 = 1.f - b2;
+  const float s = c2 * gg;
+  const float d = s * gg;
+  const float a = c1 * gg;
+  m = __builtin_fmaf(b1, m, a);
+  v = __builtin_fmaf(b2, v, d);
+}
+
+// u = (m * c1) / (sqrt(v) * c2 + eps) + wd * p: the same operations in both passes.
+__device__ __forceinline__ float lamb_u(float p, float m, float v, float c1, float c2, float eps, float wd) {
+#pragma clang fp contract(off)
+  const float mh = m * c1;
+  float den = sqrtf(v) * c2;
+  den = den + eps;
+  float u = mh / den;
+  if (wd != 0.f) {
+    const float t = wd * p;
+    u = u + t;
+  }
+  return u;
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void lamb_moments_kernel(SegArgs a) {
+  __shared__ double lds[8];
+  SegTerms t;
+  if (!seg_terms(a, true, t)) return;
+  const float* __restrict__ p = a.p;
+  const float* __restrict__ g = a.g;
+  float* __restrict__ m = a.m;
+  float* __restrict__ v = a.v;
+  for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+    const avid_seg_chunk ck = a.chunks[c];
+    const float wd = a.segs[ck.seg].weight_decay;
+    const int nv = ck.len >> 2, tail = ck.len & 3;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
+      const floatx4 pv = reinterpret_cast<const floatx4*>(p + ck.start)[i];
+      const floatx4 gv = reinterpret_cast<const floatx4*>(g + ck.start)[i];
+      floatx4 mv = reinterpret_cast<floatx4*>(m + ck.start)[i];
+      floatx4 vv = reinterpret_cast<floatx4*>(v + ck.start)[i];
+      float u[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float mj = mv[j], vj = vv[j];
+        lamb_moments(gv[j], mj, vj, a.b1, a.b2, a.grad_scale, t.coef);
+        mv[j] = mj;
+        vv[j] = vj;
+        u[j] = lamb_u(pv[j], mj, vj, t.c1, t.inv_sqrt_bc2, a.eps, wd);
+      }
+      reinterpret_cast<floatx4*>(m + ck.start)[i] = mv;
+      reinterpret_cast<floatx4*>(v + ck.start)[i] = vv;
+      a0 += (double)pv[0] * (double)pv[0];
+      a1 += (double)pv[1] * (double)pv[1];
+      a2 += (double)pv[2] * (double)pv[2];
+      a3 += (double)pv[3] * (double)pv[3];
+      b0 += (double)u[0] * (double)u[0];
+      b1 += (double)u[1] * (double)u[1];
+      b2 += (double)u[2] * (double)u[2];
+      b3 += (double)u[3] * (double)u[3];
+    }
+    if ((int)threadIdx.x < tail) {
+      const long long i = ck.start + nv * 4 + threadIdx.x;
+      const float pi = p[i];
+      float mi = m[i], vi = v[i];
+      lamb_moments(g[i], mi, vi, a.b1, a.b2, a.grad_scale, t.coef);
+      m[i] = mi;
+      v[i] = vi;
+      const float u = lamb_u(pi, mi, vi, t.c1, t.inv_sqrt_bc2, a.eps, wd);
+      a0 += (double)pi * (double)pi;
+      b0 += (double)u * (double)u;
+    }
+    seg_store_partial((a0 + a1) + (a2 + a3), (b0 + b1) + (b2 + b3), lds, a.partials, c);
+  }
+}
+
+__device__ __forceinline__ float lamb_apply(float p, float u, float step) {
+#pragma clang fp contract(off)
+  const float s = step * u;
+  return p - s;
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void lamb_update_kernel(SegArgs a) {
+  SegTerms t;
+  if (!seg_terms(a, true, t)) return;
+  float* __restrict__ p = a.p;
+  const float* __restrict__ m = a.m;
+  const float* __restrict__ v = a.v;
+  float* __restrict__ e = a.e;
+  for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+    const avid_seg_chunk ck = a.chunks[c];
+    const avid_segment sg = a.segs[ck.seg];
+    const float step = seg_lr(seg_lr(t.lr, sg.lr_scale), a.trust[ck.seg]), wd = sg.weight_decay;
+    const int nv = ck.len >> 2, tail = ck.len & 3;
+    for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
+      floatx4 pv = reinterpret_cast<floatx4*>(p + ck.start)[i];
+      const floatx4 mv = reinterpret_cast<const floatx4*>(m + ck.start)[i];
+      const floatx4 vv = reinterpret_cast<const floatx4*>(v + ck.start)[i];
+      floatx4 ev = {0.f, 0.f, 0.f, 0.f};
+      if (e) ev = reinterpret_cast<floatx4*>(e + ck.start)[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float u = lamb_u(pv[j], mv[j], vv[j], t.c1, t.inv_sqrt_bc2, a.eps, wd);
+        pv[j] = lamb_apply(pv[j], u, step);
+        if (e) ev[j] = ema_element(ev[j], pv[j], t.w);
+      }
+      reinterpret_cast<floatx4*>(p + ck.start)[i] = pv;
+      if (e) reinterpret_cast<floatx4*>(e + ck.start)[i] = ev;
+    }
+    if ((int)threadIdx.x < tail) {
+      const long long i = ck.start + nv * 4 + threadIdx.x;
+      const float u = lamb_u(p[i], m[i], v[i], t.c1, t.inv_sqrt_bc2, a.eps, wd);
+      const float pi = lamb_apply(p[i], u, step);
+      p[i] = pi;
+      if (e) e[i] = ema_element(e[i], pi, t.w);
+    }
+  }
+}
+
 }  // namespace avid
 
 using namespace avid;
@@ -888,4 +1362,272 @@ extern "C" int avid_swap_flat(int64_t n, float* a, float* b, avid_stream_t strea
   ScopedTimer t((hipStream_t)stream, "swap_flat_kernel", 0.0, 16.0 * n);
   hipLaunchKernelGGL(swap_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a, b, n4, (long long)n);
   return check_launch("swap_flat");
+}
+
+// ---- segment tables
+extern "C" int avid_segment_chunks(int32_t S, avid_segment* segs, avid_seg_chunk* chunks, int32_t cap) {
+  AVID_REQUIRE(S > 0 && segs, AVID_E_BADARG, "segment_chunks: bad argument");
+  long long c = 0;
+  for (int s = 0; s < S; ++s) {
+    AVID_REQUIRE(segs[s].numel > 0, AVID_E_BADARG, "segment_chunks: segment %d has numel %lld", s, (long long)segs[s].numel);
+    const long long nck = (segs[s].numel + AVID_SEG_CHUNK - 1) / AVID_SEG_CHUNK;
+    AVID_REQUIRE(c + nck < (1ll << 31), AVID_E_BADARG, "segment_chunks: too many chunks");
+    segs[s].first_chunk = (int32_t)c;
+    if (chunks) {
+      AVID_REQUIRE(c + nck <= cap, AVID_E_BADARG, "segment_chunks: the chunk list holds %d records, segment %d ends at %lld",
+                   cap, s, c + nck);
+      for (long long k = 0; k < nck; ++k) {
+        const long long left = segs[s].numel - k * AVID_SEG_CHUNK;
+        chunks[c + k].start = segs[s].offset + k * AVID_SEG_CHUNK;
+        chunks[c + k].len = (int32_t)(left < AVID_SEG_CHUNK ? left : AVID_SEG_CHUNK);
+        chunks[c + k].seg = s;
+      }
+    }
+    c += nck;
+  }
+  return (int)c;
+}
+
+// The host copy of a table against the n of the call: a message (and 1) for the first thing that is wrong.  total: the
+// elements the segments hold.
+static int table_check(const char* who, const avid_segment_table* t, int64_t n, long long* total, char* msg, size_t cap) {
+  *total = 0;
+  if (!t || t->S <= 0 || t->n_chunks <= 0 || !t->seg_host || !t->seg_dev || !t->chunk_host || !t->chunk_dev || n <= 0) {
+    snprintf(msg, cap, "%s: bad segment table (null pointer, S <= 0 or n <= 0)", who);
+    return 1;
+  }
+  if ((((uintptr_t)t->seg_dev | (uintptr_t)t->chunk_dev) & 7) != 0) {
+    snprintf(msg, cap, "%s: the device copies of the segment table must be 8-byte aligned", who);
+    return 1;
+  }
+  long long end = 0, c = 0;
+  for (int s = 0; s < t->S; ++s) {
+    const avid_segment& g = t->seg_host[s];
+    const char* bad = nullptr;
+    if (g.offset < 0 || (g.offset & 3) != 0) bad = "offset is negative or not 16-byte aligned";
+    else if (g.offset < end) bad = "offset lies inside or in front of the segment before (not increasing, or overlapping)";
+    else if (g.numel <= 0) bad = "numel <= 0";
+    else if (g.numel > n || g.offset > n - g.numel) bad = "offset + numel exceeds n";
+    else if (!(g.lr_scale - g.lr_scale == 0.f) || !(g.weight_decay - g.weight_decay == 0.f)) bad = "lr_scale or weight_decay is not finite";
+    else if (g.adapt != 0 && g.adapt != 1) bad = "adapt is neither 0 nor 1";
+    else if (g.first_chunk != c) bad = "first_chunk is not what avid_segment_chunks gives";
+    if (bad) {
+      snprintf(msg, cap, "%s: segment %d: %s", who, s, bad);
+      return 1;
+    }
+    const long long nck = (g.numel + AVID_SEG_CHUNK - 1) / AVID_SEG_CHUNK;
+    if (c + nck > t->n_chunks) {
+      snprintf(msg, cap, "%s: the chunk list is shorter than segment %d needs", who, s);
+      return 1;
+    }
+    for (long long k = 0; k < nck; ++k) {
+      const avid_seg_chunk& ck = t->chunk_host[c + k];
+      const long long left = g.numel - k * AVID_SEG_CHUNK;
+      if (ck.start != g.offset + k * AVID_SEG_CHUNK || ck.len != (left < AVID_SEG_CHUNK ? left : AVID_SEG_CHUNK) || ck.seg != s) {
+        snprintf(msg, cap, "%s: chunk %lld is not what avid_segment_chunks gives for segment %d", who, c + k, s);
+        return 1;
+      }
+    }
+    c += nck;
+    end = g.offset + g.numel;
+    *total += g.numel;
+  }
+  if (c != t->n_chunks) {
+    snprintf(msg, cap, "%s: the chunk list holds %d records, the segments need %lld", who, t->n_chunks, c);
+    return 1;
+  }
+  return 0;
+}
+
+static unsigned seg_grid(int n_chunks) {
+  const long long cap = 4ll * device_cus();
+  return (unsigned)(n_chunks < cap ? n_chunks : cap);
+}
+
+static SegArgs seg_args(const avid_segment_table* t) {
+  SegArgs a;
+  memset(&a, 0, sizeof a);
+  a.segs = t->seg_dev;
+  a.chunks = t->chunk_dev;
+  a.n_chunks = t->n_chunks;
+  a.grad_scale = 1.f;
+  a.bc1 = a.inv_bc1 = 1.0;
+  a.inv_sqrt_bc2 = 1.f;
+  return a;
+}
+
+static void seg_args_ema(SegArgs& a, const avid_ema_desc* ema) {
+  if (!ema) return;
+  a.e = ema->ema;
+  a.decay = ema->decay;
+  a.warmup = (int)ema->warmup;
+  a.updates_dev = (const long long*)ema->updates_dev;
+}
+
+static void seg_args_adam(SegArgs& a, float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev) {
+  if (step < 1) step = 1;
+  a.b1 = beta1;
+  a.b2 = beta2;
+  a.eps = eps;
+  a.bc1 = 1.0 - pow((double)beta1, (double)step);
+  a.inv_bc1 = 1.0 / a.bc1;
+  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  a.step_dev = (const long long*)step_dev;
+}
+
+extern "C" size_t avid_segment_sumsq_workspace_bytes(const avid_segment_table* table) {
+  return table && table->n_chunks > 0 ? (size_t)table->n_chunks * 2 * sizeof(double) : 0;
+}
+
+static int seg_finish(const char* who, const avid_segment_table* t, const double* partials, double eta, double* sums,
+                      float* trust, const avid_step_guard* guard, hipStream_t s) {
+  ScopedTimer tm(s, "seg_finish_kernel", 0.0, 16.0 * t->n_chunks);
+  hipLaunchKernelGGL(seg_finish_kernel, dim3((unsigned)t->S), dim3(64), 0, s, t->seg_dev, (int)t->S, partials, eta,
+                     sums, trust, guard);
+  return check_launch(who);
+}
+
+extern "C" int avid_segment_sumsq(const avid_segment_table* table, int64_t n, const float* x, const float* y, double* sums,
+                                  const avid_step_guard* guard, void* ws, size_t ws_bytes, avid_stream_t stream) {
+  char msg[192];
+  long long total;
+  AVID_REQUIRE(!table_check("segment_sumsq", table, n, &total, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  AVID_REQUIRE(x && sums && ws, AVID_E_BADARG, "segment_sumsq: null pointer");
+  AVID_REQUIRE(ws_bytes >= avid_segment_sumsq_workspace_bytes(table), AVID_E_BADARG, "segment_sumsq: workspace too small");
+  AVID_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0 && (((uintptr_t)sums | (uintptr_t)ws | (uintptr_t)guard) & 7) == 0,
+               AVID_E_BADARG, "segment_sumsq: x and y must be 16-byte, sums, the workspace and the guard record 8-byte aligned");
+  SegArgs a = seg_args(table);
+  a.p = const_cast<float*>(x);
+  a.g = y;
+  a.guard = guard;
+  a.partials = (double*)ws;
+  {
+    ScopedTimer t((hipStream_t)stream, "seg_sumsq_kernel", 2.0 * total, (y ? 8.0 : 4.0) * total);
+    hipLaunchKernelGGL(seg_sumsq_kernel, dim3(seg_grid(table->n_chunks)), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+  }
+  int rc = check_launch("segment_sumsq");
+  if (rc != AVID_OK) return rc;
+  return seg_finish("segment_sumsq", table, (const double*)ws, 1.0, sums, nullptr, guard, (hipStream_t)stream);
+}
+
+extern "C" int avid_sgd_flat_table(const avid_segment_table* table, int64_t n, float* p, const float* g, float* buf, float lr,
+                                   float momentum, int nesterov, const float* lr_dev, float grad_scale, float trust_coefficient,
+                                   float* trust, const avid_step_guard* guard, const avid_ema_desc* ema, void* ws,
+                                   size_t ws_bytes, avid_stream_t stream) {
+  char msg[192];
+  long long total;
+  AVID_REQUIRE(!table_check("sgd_flat_table", table, n, &total, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  AVID_REQUIRE(p && g, AVID_E_BADARG, "sgd_flat_table: null pointer");
+  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat_table: momentum needs its buffer");
+  if (momentum == 0.f) buf = nullptr;
+  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat_table: nesterov needs momentum");
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
+               "sgd_flat_table: buffers must be 16-byte aligned");
+  AVID_REQUIRE((((uintptr_t)guard | (uintptr_t)ws) & 7) == 0 && ((uintptr_t)trust & 3) == 0, AVID_E_BADARG,
+               "sgd_flat_table: the guard record and the workspace must be 8-byte, the trust array 4-byte aligned");
+  if (ema) AVID_REQUIRE(!ema_desc_check("sgd_flat_table", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  if (trust) {
+    AVID_REQUIRE(trust_coefficient > 0.f && trust_coefficient - trust_coefficient == 0.f, AVID_E_BADARG,
+                 "sgd_flat_table: the trust coefficient must be finite and > 0");
+    AVID_REQUIRE(ws && ws_bytes >= avid_segment_sumsq_workspace_bytes(table), AVID_E_BADARG,
+                 "sgd_flat_table: the trust factors need the workspace of avid_segment_sumsq_workspace_bytes");
+  }
+  SegArgs a = seg_args(table);
+  a.p = p;
+  a.g = g;
+  a.buf = buf;
+  a.lr = lr;
+  a.momentum = momentum;
+  a.nesterov = nesterov;
+  a.lr_dev = lr_dev;
+  a.grad_scale = grad_scale;
+  a.guard = guard;
+  a.trust = trust;
+  a.partials = (double*)ws;
+  seg_args_ema(a, ema);
+  const unsigned grid = seg_grid(table->n_chunks);
+  if (trust) {
+    {
+      ScopedTimer t((hipStream_t)stream, "sgd_table_norm_kernel", 4.0 * total, 8.0 * total);
+      hipLaunchKernelGGL(sgd_table_norm_kernel, dim3(grid), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+    }
+    int rc = check_launch("sgd_flat_table");
+    if (rc != AVID_OK) return rc;
+    rc = seg_finish("sgd_flat_table", table, (const double*)ws, (double)trust_coefficient, nullptr, trust, guard,
+                    (hipStream_t)stream);
+    if (rc != AVID_OK) return rc;
+  }
+  ScopedTimer t((hipStream_t)stream, "sgd_flat_table_kernel", 0.0, ((buf ? 20.0 : 12.0) + (ema ? 8.0 : 0.0)) * total);
+  hipLaunchKernelGGL(sgd_flat_table_kernel, dim3(grid), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("sgd_flat_table");
+}
+
+extern "C" int avid_adam_flat_table(const avid_segment_table* table, int64_t n, float* p, const float* g, float* m, float* v,
+                                    float lr, float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev,
+                                    const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                                    const avid_ema_desc* ema, avid_stream_t stream) {
+  char msg[192];
+  long long total;
+  AVID_REQUIRE(!table_check("adam_flat_table", table, n, &total, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  AVID_REQUIRE(p && g && m && v && (step >= 1 || step_dev), AVID_E_BADARG, "adam_flat_table: bad argument");
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
+               "adam_flat_table: buffers must be 16-byte aligned");
+  AVID_REQUIRE((((uintptr_t)guard | (uintptr_t)step_dev) & 7) == 0, AVID_E_BADARG,
+               "adam_flat_table: the guard record and the step counter must be 8-byte aligned");
+  if (ema) AVID_REQUIRE(!ema_desc_check("adam_flat_table", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  SegArgs a = seg_args(table);
+  a.p = p;
+  a.g = g;
+  a.m = m;
+  a.v = v;
+  a.lr = lr;
+  a.lr_dev = lr_dev;
+  a.grad_scale = grad_scale;
+  a.guard = guard;
+  seg_args_adam(a, beta1, beta2, eps, step, step_dev);
+  seg_args_ema(a, ema);
+  ScopedTimer t((hipStream_t)stream, "adam_flat_table_kernel", 0.0, (ema ? 36.0 : 28.0) * total);
+  hipLaunchKernelGGL(adam_flat_table_kernel, dim3(seg_grid(table->n_chunks)), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("adam_flat_table");
+}
+
+extern "C" int avid_lamb_flat(const avid_segment_table* table, int64_t n, float* p, const float* g, float* m, float* v, float lr,
+                              float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev, const float* lr_dev,
+                              float grad_scale, float* trust, const avid_step_guard* guard, const avid_ema_desc* ema, void* ws,
+                              size_t ws_bytes, avid_stream_t stream) {
+  char msg[192];
+  long long total;
+  AVID_REQUIRE(!table_check("lamb_flat", table, n, &total, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  AVID_REQUIRE(p && g && m && v && trust && ws && (step >= 1 || step_dev), AVID_E_BADARG, "lamb_flat: bad argument");
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
+               "lamb_flat: buffers must be 16-byte aligned");
+  AVID_REQUIRE((((uintptr_t)guard | (uintptr_t)step_dev | (uintptr_t)ws) & 7) == 0 && ((uintptr_t)trust & 3) == 0, AVID_E_BADARG,
+               "lamb_flat: the guard record, the step counter and the workspace must be 8-byte, the trust array 4-byte aligned");
+  AVID_REQUIRE(ws_bytes >= avid_segment_sumsq_workspace_bytes(table), AVID_E_BADARG, "lamb_flat: workspace too small");
+  if (ema) AVID_REQUIRE(!ema_desc_check("lamb_flat", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  SegArgs a = seg_args(table);
+  a.p = p;
+  a.g = g;
+  a.m = m;
+  a.v = v;
+  a.lr = lr;
+  a.lr_dev = lr_dev;
+  a.grad_scale = grad_scale;
+  a.guard = guard;
+  a.trust = trust;
+  a.partials = (double*)ws;
+  seg_args_adam(a, beta1, beta2, eps, step, step_dev);
+  seg_args_ema(a, ema);
+  const unsigned grid = seg_grid(table->n_chunks);
+  {
+    ScopedTimer t((hipStream_t)stream, "lamb_moments_kernel", 4.0 * total, 24.0 * total);
+    hipLaunchKernelGGL(lamb_moments_kernel, dim3(grid), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+  }
+  int rc = check_launch("lamb_flat");
+  if (rc != AVID_OK) return rc;
+  rc = seg_finish("lamb_flat", table, (const double*)ws, 1.0, nullptr, trust, guard, (hipStream_t)stream);
+  if (rc != AVID_OK) return rc;
+  ScopedTimer t((hipStream_t)stream, "lamb_update_kernel", 0.0, (ema ? 24.0 : 16.0) * total);
+  hipLaunchKernelGGL(lamb_update_kernel, dim3(grid), dim3(SEG_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("lamb_flat");
 }

@@ -824,6 +824,87 @@ int avid_ema_flat(int64_t n, float* e, const float* p, double decay, int warmup,
  * overlap of the two buffers, n <= 0 or a null pointer is AVID_E_BADARG. */
 int avid_swap_flat(int64_t n, float* a, float* b, avid_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-tensor hyper-parameters and trust ratios (LARS / LAMB) over the flat buffers — avid_hip/parallel.py:
+ * AdamStep(param_rules=, optimizer="lars" / "lamb").  A segment table says, for every tensor of a flat fp32 buffer,
+ * where it lies and which hyper-parameters it takes; elements outside every segment (the padding between tensors) are
+ * neither read into a norm nor written.  The kernels deal CHUNKS of AVID_SEG_CHUNK floats to workgroups, never segments:
+ * a host-built list says for every chunk which segment it belongs to, where it starts and how long it is.
+ * ---------------------------------------------------------------------------------------------- */
+#define AVID_SEG_CHUNK 4096
+typedef struct avid_segment {
+    int64_t offset;        /* first element; a multiple of 4 (16 bytes), not below the end of the segment before */
+    int64_t numel;         /* > 0; offset + numel <= n of the call */
+    float   lr_scale;      /* the segment's learning rate is the single fp32 product lr * lr_scale; finite */
+    float   weight_decay;  /* finite */
+    int32_t adapt;         /* 0 / 1: takes the trust ratio (LARS / LAMB); ignored by the plain table kernels */
+    int32_t first_chunk;   /* index of its first chunk; it owns ceil(numel / AVID_SEG_CHUNK) consecutive ones */
+} avid_segment;
+typedef struct avid_seg_chunk {
+    int64_t start;         /* first element: offset + k * AVID_SEG_CHUNK */
+    int32_t len;           /* AVID_SEG_CHUNK, or what is left of the segment */
+    int32_t seg;
+} avid_seg_chunk;
+typedef struct avid_segment_table {
+    int32_t S, n_chunks;
+    const avid_segment*   seg_host;    /* S records in host memory: validated on every call, before anything is launched */
+    const avid_segment*   seg_dev;     /* the same S records in device memory (uploaded once), 8-byte aligned */
+    const avid_seg_chunk* chunk_host;  /* n_chunks records, host and device alike */
+    const avid_seg_chunk* chunk_dev;
+} avid_segment_table;
+/* Fill first_chunk of segs[0, S) and, unless chunks is NULL, chunks[0, cap) with the list the kernels expect; returns
+ * the number of chunks, or AVID_E_BADARG (S <= 0, a null segs, a numel <= 0, cap too small).  Host only. */
+int avid_segment_chunks(int32_t S, avid_segment* segs, avid_seg_chunk* chunks, int32_t cap);
+/* Every entry point below validates the host copy of its table first and returns AVID_E_BADARG — the message names the
+ * entry point, nothing is launched — for: S <= 0 or a null pointer; an offset that is negative or no multiple of 4;
+ * segments that are not increasing or overlap; numel <= 0 or offset + numel > n; an lr_scale or weight_decay that is not
+ * finite; adapt outside {0, 1}; a chunk list other than avid_segment_chunks' for these segments.
+ *
+ * Per-segment sums of squares: sums[2 s] = sum of x^2 over segment s, sums[2 s + 1] = the same of y (0.0 with y == NULL).
+ * The rule of avid_grad_guard: every product exact in double, accumulated in double in a FIXED order — four accumulators
+ * per thread over its vectors of a chunk, (a0 + a1) + (a2 + a3), the xor butterfly over the wave, the four waves left to
+ * right: one double per chunk into ws; then a segment's chunk partials are added in index order, one chain per segment.  No atomics;
+ * the same bits whatever the grid, the CU budget or the scheduling.  ws: avid_segment_sumsq_workspace_bytes(table), 8-byte
+ * aligned (so sums).  guard (nullable): with guard->skip nothing is written to sums. */
+size_t avid_segment_sumsq_workspace_bytes(const avid_segment_table* table);
+int avid_segment_sumsq(const avid_segment_table* table, int64_t n, const float* x, const float* y, double* sums,
+                       const avid_step_guard* guard, void* ws, size_t ws_bytes, avid_stream_t stream);
+/* avid_sgd_flat with the segment's lr (lr * lr_scale, lr read from lr_dev when given) and weight_decay, and an optional
+ * trust factor (LARS as the FAIR self-supervised code bases have it).  Per element, every product and sum rounded to fp32
+ * on its own:
+ *   d = g * grad_scale;  d = d * clip_coef (1.0f without a guard);  if (wd_s != 0) d = d + wd_s * p;
+ *   d = q_s * d;  if (momentum != 0) { buf = momentum * buf + d;  d = nesterov ? d + momentum * buf : buf; }
+ *   p = p - lr_s * d;  ema as avid_sgd_flat_ema
+ * trust == NULL: q_s = 1 — with lr_scale 1 and one weight_decay the bits of avid_sgd_flat(_guarded, _ema).
+ * trust != NULL (float[S] in device memory; needs ws of avid_segment_sumsq_workspace_bytes(table)): a norm pass in front of
+ * the update — the sums of p^2 and of d^2, d as above up to the weight-decay term, by avid_segment_sumsq's rule — writes
+ *   trust[s] = q_s = (float)(trust_coefficient * (sqrt(sum p^2) / sqrt(sum d^2)))  if adapt_s and both sums > 0, else 1.0f
+ * (formed in double, rounded once), which the update then reads.  guard / ema: nullable; with guard->skip nothing is
+ * written, trust included. */
+int avid_sgd_flat_table(const avid_segment_table* table, int64_t n, float* p, const float* g, float* buf, float lr,
+                        float momentum, int nesterov, const float* lr_dev, float grad_scale, float trust_coefficient,
+                        float* trust, const avid_step_guard* guard, const avid_ema_desc* ema, void* ws, size_t ws_bytes,
+                        avid_stream_t stream);
+/* avid_adam_flat with the segment's lr and weight_decay: every element is computed as avid_adam_flat's 16-byte vector
+ * loop computes it (a flat buffer whose n is a multiple of 4 has no other elements), step size (float)(lr_s / (1 - beta1^t))
+ * formed as avid_adam_flat forms it in each of its three cases (by value, lr_dev, step_dev).  Under a guard with
+ * clip_coef != 1.0f the gradient term is ((g * grad_scale) * clip_coef) + wd_s * p, each operation rounded on its own. */
+int avid_adam_flat_table(const avid_segment_table* table, int64_t n, float* p, const float* g, float* m, float* v, float lr,
+                         float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev, const float* lr_dev,
+                         float grad_scale, const avid_step_guard* guard, const avid_ema_desc* ema, avid_stream_t stream);
+/* LAMB in two passes (g is never written).  With gt = (g * grad_scale) * clip_coef + 0.0f:
+ *   pass 1:  m, v as avid_adam_flat(weight_decay = 0) leaves them (the same bits);
+ *            u = (m * c1) / (sqrt(v) * c2 + eps) + wd_s * p, each operation rounded to fp32 on its own,
+ *            c1 = (float)(1 / (1 - beta1^t)), c2 = (float)(1 / sqrt(1 - beta2^t));  the sums of p^2 and u^2 per segment
+ *   finish:  trust[s] = r_s = (float)(sqrt(sum p^2) / sqrt(sum u^2))  if adapt_s and both sums > 0, else 1.0f
+ *   pass 2:  u again from the new m and v (the same operations: the same bits);  p = p - (lr_s * r_s) * u;  ema
+ * About 40 bytes per parameter against avid_adam_flat's 28.  trust: float[S] in device memory, required.  step / step_dev
+ * / lr_dev as avid_adam_flat's; with guard->skip nothing is written. */
+int avid_lamb_flat(const avid_segment_table* table, int64_t n, float* p, const float* g, float* m, float* v, float lr,
+                   float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev, const float* lr_dev,
+                   float grad_scale, float* trust, const avid_step_guard* guard, const avid_ema_desc* ema, void* ws,
+                   size_t ws_bytes, avid_stream_t stream);
+
 /* Video clip front end: frames [B][T][H][W][3] uint8 (what the decoder / augmentation hands over)
  * -> out [B][3][T][H][W] fp32 = ((u / 255) - mean[c]) / std[c], the reference's ClipToTensor + Normalize
  * (utils/videotransforms/volume_transforms.py:14-66, tensor_transforms.py:13-37; datasets/preprocessing.py:45-48)
