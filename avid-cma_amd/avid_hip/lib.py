@@ -271,6 +271,8 @@ SIGNATURES = {
                             _vp, _vp, _sz, _vp, _vp]),
     "avid_crit_fused_workspace_bytes": (_sz, [_i, _i, _i]),
     "avid_crit_fused": (_i, [C.POINTER(CritDesc), _vp, _sz, _vp, _vp]),
+    "avid_infonce_workspace_bytes": (_sz, [_i]),
+    "avid_infonce": (_i, [_i, _i, _i, _i, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "avid_bank_update2": (_i, [_i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp]),
     "avid_cma_negatives": (_i, [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "avid_cma_topk_workspace_bytes": (_sz, [_i64, _i, _i]),

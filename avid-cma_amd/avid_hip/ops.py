@@ -1627,6 +1627,96 @@ def xmodal_fused(v_emb, a_emb, y, idx, bank_v, bank_a, Z, inv_T, coeff, ws):
     return _XModalFused.apply(v_emb, a_emb, y, idx, bank_v, bank_a, Z, inv_T, coeff, ws)
 
 
+def _infonce_args(v_hat, a_hat, row0, b, inv_T, weights, grad_scale, ws):
+    """The checked arguments of ``infonce``: refuses before any launch."""
+    for name, t in (("v_hat", v_hat), ("a_hat", a_hat)):
+        if not isinstance(t, torch.Tensor):
+            raise AvidHipError(f"infonce: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise AvidHipError(f"infonce: {name} must be float32, got {t.dtype}")
+    if v_hat.dim() != 2 or tuple(a_hat.shape) != tuple(v_hat.shape) or a_hat.device != v_hat.device:
+        raise AvidHipError(f"infonce: v_hat {tuple(v_hat.shape)} and a_hat {tuple(a_hat.shape)} must be [G, D] on one device")
+    if not v_hat.is_cuda:
+        raise AvidHipError("infonce: v_hat and a_hat must be HIP device tensors — there is no CPU fallback")
+    G, D = v_hat.shape
+    if G < 1 or D % 32 or not 32 <= D <= 512:
+        raise AvidHipError(f"infonce: [G, D] = [{G}, {D}]: G >= 1 and D a multiple of 32 up to 512 expected")
+    row0 = int(row0)
+    b = G - row0 if b is None else int(b)
+    if row0 < 0 or b < 0 or row0 + b > G:
+        raise AvidHipError(f"infonce: local rows [{row0}, {row0} + {b}) outside the global batch of {G}")
+    inv_T, gs = float(inv_T), float(grad_scale)
+    try:
+        w_v2a, w_a2v = (float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise AvidHipError(f"infonce: weights = {weights!r}: (w_v2a, w_a2v) expected") from None
+    if not (0.0 < inv_T < float("inf")) or not all(0.0 <= w < float("inf") for w in (w_v2a, w_a2v)) or gs != gs:
+        raise AvidHipError(f"infonce: inv_T = {inv_T!r}, weights = ({w_v2a!r}, {w_a2v!r}), grad_scale = {gs!r}: "
+                           "finite, inv_T > 0 and weights >= 0 expected")
+    need = int(lib.raw("avid_infonce_workspace_bytes")(G))
+    if ws is not None and (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.device != v_hat.device
+                           or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need):
+        raise AvidHipError(f"infonce: the workspace must be a contiguous uint8 tensor of >= {need} bytes on {v_hat.device}")
+    return G, D, row0, b, inv_T, w_v2a, w_a2v, gs
+
+
+def _infonce_launch(v_hat, a_hat, G, D, row0, b, inv_T, w_v2a, w_a2v, gs, ws, want_grad):
+    dev = v_hat.device
+    v_hat, a_hat = v_hat.contiguous(), a_hat.contiguous()
+    if ws is None:
+        ws = workspace(dev, int(lib.raw("avid_infonce_workspace_bytes")(G)))
+    losses = torch.empty(3, dtype=torch.float32, device=dev)
+    hits = torch.empty(2, dtype=torch.int64, device=dev)
+    grads = torch.empty((2, b, D), dtype=torch.float32, device=dev) if want_grad else None
+    lib.call("avid_infonce", G, D, row0, b, _p(v_hat), _p(a_hat), inv_T, w_v2a, w_a2v, gs, _p(losses), _p(hits),
+             _p(grads[0]) if want_grad else None, _p(grads[1]) if want_grad else None, _p(ws), ws.numel(), _stream())
+    return losses, hits, grads
+
+
+class _InfoNCE(Function):
+    """(v_hat, a_hat) of the global batch -> the global loss: the launch forms the gradient rows of the local block with
+    the forward (``avid_infonce``), the backward scales them by the incoming scalar and places them in the [G, D] frames."""
+
+    @staticmethod
+    def forward(ctx, v_hat, a_hat, G, D, row0, b, inv_T, w_v2a, w_a2v, gs, ws):
+        losses, hits, grads = _infonce_launch(v_hat, a_hat, G, D, row0, b, inv_T, w_v2a, w_a2v, gs, ws, True)
+        ctx.save_for_backward(grads)
+        ctx.frame = (G, D, row0, b)
+        ctx.mark_non_differentiable(losses, hits, grads)
+        return losses[0], losses, hits, grads
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (grads,) = ctx.saved_tensors
+        G, D, row0, b = ctx.frame
+        if b == G:
+            d = grads * g                       # one launch for both embeddings
+        else:                                   # rows of other processes' samples: their owners hold those gradients
+            d = torch.zeros((2, G, D), dtype=torch.float32, device=grads.device)
+            torch.mul(grads, g, out=d[:, row0:row0 + b])
+        return d[0], d[1], None, None, None, None, None, None, None, None, None
+
+
+def infonce_workspace(device, G):
+    """Scratch of ``avid_infonce`` for a global batch of ``G`` (O(G) bytes, written before it is read: no zero-fill needed)."""
+    return torch.empty(int(lib.raw("avid_infonce_workspace_bytes")(int(G))), dtype=torch.uint8, device=device)
+
+
+def infonce(v_hat, a_hat, row0=0, b=None, inv_T=1.0 / 0.07, weights=(0.5, 0.5), grad_scale=1.0, ws=None):
+    """Symmetric in-batch InfoNCE of the unit-norm embeddings ``v_hat, a_hat [G, D]`` of the GLOBAL batch, of which rows
+    ``[row0, row0 + b)`` are local (``b=None``: all from ``row0``): ``avid_infonce``, no host synchronisation.  Returns device
+    tensors ``(loss [], losses [3] = (total, v2a, a2v), hits [2] int64, grads [2, b, D])``: ``loss`` is the global-batch loss
+    ``w_v2a * mean_i(lse_v[i] - S_ii) + w_a2v * mean_j(lse_a[j] - S_jj)``, ``hits`` the in-batch retrieval hits per direction
+    (lowest index among a row's maxima), ``grads`` = d(loss * grad_scale) / d(v_hat, a_hat) for the local rows — exact,
+    the key-role term included (``None`` when no gradient is required).  When an embedding requires a gradient ``loss`` is
+    a node of the autograd graph: backward scales ``grads`` by the incoming scalar (rows outside the block receive zero)."""
+    G, D, row0, b, inv_T, w_v2a, w_a2v, gs = _infonce_args(v_hat, a_hat, row0, b, inv_T, weights, grad_scale, ws)
+    if torch.is_grad_enabled() and (v_hat.requires_grad or a_hat.requires_grad):
+        return _InfoNCE.apply(v_hat, a_hat, G, D, row0, b, inv_T, w_v2a, w_a2v, gs, ws)
+    losses, hits, _ = _infonce_launch(v_hat, a_hat, G, D, row0, b, inv_T, w_v2a, w_a2v, gs, ws, False)
+    return losses[0], losses, hits, None
+
+
 class _CMAFused(Function):
     """The AVID+CMA criterion of a steady-state step (cross-modal instance + within-modal positive terms) in one kernel
     (``avid_cma_fused``): returns (total loss, losses[8], hats); as ``_XModalFused`` the gradient with respect to both raw

@@ -1187,6 +1187,10 @@ class TrainStep(AdamStep):
         per-rank negatives, the first step's Z the mean of the ranks', the gradient their mean, one bank update with all
         records in rank order, rank 0's running statistics.  One process only, ``broadcast_buffers="step"``, no ``capture()``."""
         R = _virtual_ranks_arg("TrainStep", virtual_ranks, broadcast_buffers)
+        if R > 1 and getattr(criterion, "in_batch_negatives", False):
+            raise ValueError(f"TrainStep(virtual_ranks={R}): {type(criterion).__name__} takes its negatives from the batch — the "
+                             "exact loss needs every shard's embeddings before any shard's backward, which a shard-after-shard "
+                             "step cannot give; virtual_ranks > 1 is not supported with an in-batch criterion")
         super().__init__(model, lr, betas, eps, weight_decay, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
                          max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup,
                          ema_buffers=ema_buffers, param_rules=param_rules, trust_coefficient=trust_coefficient,

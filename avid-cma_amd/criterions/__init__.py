@@ -4,3 +4,4 @@
 """
 from .avid import *  # noqa: F401,F403
 from .avid_cma import *  # noqa: F401,F403
+from .infonce import *  # noqa: F401,F403

@@ -657,6 +657,33 @@ typedef struct avid_crit_desc {
 } avid_crit_desc;
 size_t avid_crit_fused_workspace_bytes(int bs, int P, int K);
 int avid_crit_fused(const avid_crit_desc* d, void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream);
+/* In-batch cross-modal InfoNCE (the symmetric CLIP / GDT loss; version >= 171) — infonce.hip.  No memory bank: the keys
+ * are the other modality's embeddings of the GLOBAL batch.  v_hat, a_hat [G][D]: the unit-norm embeddings of the global
+ * batch (every process holds all of them); rows [row0, row0 + b) are the ones this process owns.  With
+ * S_ij = v_hat_i . a_hat_j * inv_T, lse_v[i] = logsumexp_j S_ij and lse_a[j] = logsumexp_i S_ij, all over the G keys:
+ *   loss[1]  = mean_i (lse_v[i] - S_ii)            (video -> audio)
+ *   loss[2]  = mean_j (lse_a[j] - S_jj)            (audio -> video)
+ *   loss[0]  = w_v2a loss[1] + w_a2v loss[2]       — over the global batch, the same on every process
+ *   hits[2]  (int64, nullable): rows i whose lowest-index maximum of S_i. is i; columns j likewise for S_.j
+ *   W_ij     = grad_scale (w_v2a (exp(S_ij - lse_v[i]) - delta_ij) + w_a2v (exp(S_ij - lse_a[j]) - delta_ij)) inv_T / G
+ *   dv [b][D]: d(grad_scale loss[0]) / d v_hat_i = sum_j W_ij a_hat_j, i = row0 .. row0 + b - 1
+ *   da [b][D]: d(grad_scale loss[0]) / d a_hat_j = sum_i W_ij v_hat_i, j = row0 .. row0 + b - 1
+ * — the exact gradient of the global loss for the local rows, the key-role term (a local sample as a negative of every
+ * other process's queries) included; dv and da are both NULL (loss and hits only) or both given.
+ * Products are fp32 FMAs, one accumulator per score fed in the order d = 0 .. D-1: a score has the same bits wherever its
+ * pair sits in a tile and whichever side is the query, so bit-identical key rows give bit-identical scores.  The softmax
+ * shifts by the row's true running maximum.  Every sum over keys runs in key order with tiles cut at absolute key
+ * indices, the loss is added up in double in index order; no floating-point atomics, no grid sized from the CU count:
+ * dv / da rows and the loss have the same bits on every run, under every avid_set_cu_budget and for every (row0, b).
+ * No [G][G] matrix is stored: ws holds lse_v, lse_a, the diagonal and the hit flags, avid_infonce_workspace_bytes(G) =
+ * 20 G bytes rounded up to 256, written before it is read (no zero-fill).  Three launches on `stream`, no host
+ * synchronisation (capturable).  Refused before anything is launched: G < 1, row0 < 0, b < 0, row0 + b > G, a null v_hat /
+ * a_hat / loss / ws, embeddings or gradients not 16-byte aligned, inv_T <= 0, a negative or non-finite weight, a short
+ * workspace (AVID_E_BADARG); D not a multiple of 32 in [32, 512] (AVID_E_UNSUPPORTED).  G = 1: loss 0, gradients 0. */
+size_t avid_infonce_workspace_bytes(int G);
+int avid_infonce(int G, int D, int row0, int b, const float* v_hat, const float* a_hat, float inv_T, float w_v2a, float w_a2v,
+                 float grad_scale, float* loss, int64_t* hits, float* dv, float* da, void* ws, size_t ws_bytes,
+                 avid_stream_t stream);
 /* avid_bank_update for both banks in one launch (criterions/avid.py:118-129): bank0 <- emb0 (momentum0), bank1 <- emb1; bit-identical to two avid_bank_update calls. */
 int avid_bank_update2(int B, int D, int64_t N, float* bank0, float* bank1, const int64_t* y, const float* emb0,
                       const float* emb1, float momentum0, float momentum1, int32_t* err, avid_stream_t stream);
