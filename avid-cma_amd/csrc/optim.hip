@@ -11,63 +11,60 @@
 
 namespace avid {
 
-__global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, long long n4,
-                                                        long long n, float b1, float b2, float eps, float wd,
-                                                        float step_size, double inv_bc1, float inv_sqrt_bc2,
-                                                        float grad_scale, float lr, const long long* __restrict__ step_dev,
-                                                        const float* __restrict__ lr_dev) {
-  if (lr_dev) {   // graph-replay safe learning rate (scheduler writes the device word); the host's lr is not used
-    lr = *lr_dev;
-    step_size = (float)((double)lr * inv_bc1);   // (recomputed below when step_dev is given)
-  }
-  if (step_dev) {  // graph-replay safe: bias corrections from the device-resident step counter
-    const double t = (double)*step_dev;
-    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
-  }
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
-    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
-    floatx4 mv = reinterpret_cast<floatx4*>(m)[i];
-    floatx4 vv = reinterpret_cast<floatx4*>(v)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gg = gv[j] * grad_scale + wd * pv[j];
-      mv[j] = b1 * mv[j] + (1.f - b1) * gg;
-      vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
-      const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-      pv[j] -= step_size * (mv[j] / denom);
-    }
-    reinterpret_cast<floatx4*>(p)[i] = pv;
-    reinterpret_cast<floatx4*>(m)[i] = mv;
-    reinterpret_cast<floatx4*>(v)[i] = vv;
-  }
-  // tail (n % 4) handled by block 0
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
-    const long long i = n4 * 4 + threadIdx.x;
-    const float gg = g[i] * grad_scale + wd * p[i];
-    m[i] = b1 * m[i] + (1.f - b1) * gg;
-    v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
-    p[i] -= step_size * (m[i] / (sqrtf(v[i]) * inv_sqrt_bc2 + eps));
-  }
+// ---- the flat optimizers ----------------------------------------------------------------------------------------------------
+// Eight kernels — {Adam, SGD} x {plain, under a guard record} x {alone, with the weight average} — are the instantiations of
+// adam_flat_body / sgd_flat_body<GUARD, EMA>: a kernel holds no code of a form it is not.  Every rounding is spelled out: the
+// element functions are compiled with contraction off and say __builtin_fmaf where a product and a sum round once.  Which pairs
+// Adam fuses — and that its vector loop, its n % 4 tail and its clipped forms do not fuse the same ones — is how the compiler once
+// contracted the first kernels, an accident, kept because a step has to keep its bits.  The specification is this source and
+// the recorded bits of tests/golden/optim_flat_bits.npz (tests/test_gpu_optim_bits.py), not a code object.
+
+// The weight average: e = e + w * (p - e), the difference, the product and the sum each rounded to fp32 on its own (torch's
+// unfused `e + (p - e) * w`; the numpy restatement of tests/_ema_ref.py, bit for bit).
+__device__ __forceinline__ float ema_element(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float t = w * d;
+  return e + t;
 }
 
-// torch's single-tensor SGD (dampening 0) for one element, in torch's order, every product and every sum rounded to fp32 on
-// its own: hipcc contracts a * b + c into one fused multiply-add by default, torch's kernels (and the numpy restatement the
-// tests hold this against, bit for bit) do not.  A zero-initialised buffer makes the first step torch's ``buf = clone(d)``.
-__device__ __forceinline__ float sgd_element(float& p, float g, float* buf, float lr, float momentum, float wd, bool nesterov,
-                                             float grad_scale) {
+// w = (float)(1 - d), formed once per launch in double: d is the decay, or — warm-up — min(decay, (1 + k) / (10 + k)) with k
+// the averaging updates applied so far, read from the device counter (a captured graph freezes by-value arguments).
+__device__ __forceinline__ float ema_weight(double decay, int warmup, const long long* __restrict__ updates_dev) {
+  double d = decay;
+  if (warmup) {
+    const double k = (double)*updates_dev;
+    const double r = (1.0 + k) / (10.0 + k);
+    if (r < d) d = r;
+  }
+  return (float)(1.0 - d);
+}
+
+// d of the SGD family up to the weight-decay term, (g * grad_scale) * coef + wd * p: what LARS takes the norm of, and what
+// the update goes on from — the same operations in both places.
+__device__ __forceinline__ float sgd_d(float g, float p, float grad_scale, float coef, float wd) {
 #pragma clang fp contract(off)
   float d = g * grad_scale;
+  d = d * coef;
   if (wd != 0.f) {
     const float t = wd * p;
     d = d + t;
   }
-  float b = 0.f;
-  if (buf) {
-    const float t = momentum * *buf;
+  return d;
+}
+
+// torch's single-tensor SGD (dampening 0) for one element on q * d, in torch's order, every product and every sum rounded to fp32
+// on its own: torch's kernels (and the numpy restatement the tests hold this against, bit for bit) do not fuse.  coef is the
+// guard's clip coefficient, q the trust factor of a segment: the unguarded kernels pass coef = 1.0f, the flat ones q = 1.0f, and
+// times 1.0f is exact.  A zero-initialised buffer makes the first step torch's ``buf = clone(d)``.  The momentum value travels
+// by reference, not behind a nullable pointer, so that nothing of it lives in a private segment.
+__device__ __forceinline__ void sgd_element(float& p, float g, float& b, bool has_buf, float lr, float momentum, float wd,
+                                            bool nesterov, float grad_scale, float coef, float q) {
+#pragma clang fp contract(off)
+  float d = sgd_d(g, p, grad_scale, coef, wd);
+  d = q * d;
+  if (has_buf) {
+    const float t = momentum * b;
     b = t + d;
     if (nesterov) {
       const float u = momentum * b;
@@ -78,39 +75,248 @@ __device__ __forceinline__ float sgd_element(float& p, float g, float* buf, floa
   }
   const float s = lr * d;
   p = p - s;
-  return b;
 }
 
-__global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ buf, long long n4, long long n, float lr,
-                                                       float momentum, float wd, int nesterov, float grad_scale,
-                                                       const float* __restrict__ lr_dev) {
-  if (lr_dev) lr = *lr_dev;   // graph-replay safe learning rate, as adam_flat_kernel's
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+// The gradient term gg of the Adam family (L2 weight decay folded into the gradient); t = (g * grad_scale) * coef, the two
+// products rounded one after the other:
+//   GRAD_UNCLIPPED    fma(g, grad_scale, wd * p)    every step whose clip coefficient is 1.0f (which is not applied)
+//   GRAD_CLIPPED_FMA  fma(wd, p, t)                 the flat kernels' vector loop
+//   GRAD_CLIPPED_SUM  wd * p + t, unfused           the flat kernels' n % 4 tail; adam_flat_table_kernel throughout
+enum { GRAD_UNCLIPPED, GRAD_CLIPPED_FMA, GRAD_CLIPPED_SUM };
+
+template <int FORM>
+__device__ __forceinline__ float adam_grad_term(float g, float p, float grad_scale, float wd, float coef) {
+#pragma clang fp contract(off)
+  if (FORM == GRAD_UNCLIPPED) {
+    const float u = wd * p;
+    return __builtin_fmaf(g, grad_scale, u);
+  }
+  float t = g * grad_scale;
+  t = t * coef;
+  if (FORM == GRAD_CLIPPED_FMA) return __builtin_fmaf(wd, p, t);
+  const float u = wd * p;
+  return u + t;
+}
+
+// Adam's moments.  Vector loop: m = fma(b1, m, (1 - b1) * gg), v = fma(b2, v, ((1 - b2) * gg) * gg); n % 4 tail: m = fma(1 - b1,
+// gg, b1 * m), v = b2 * v + ((1 - b2) * gg) * gg, unfused.  (The segment kernels use the vector-loop form for their tails too.)
+template <bool TAIL>
+__device__ __forceinline__ void adam_moments(float gg, float& m, float& v, float b1, float b2) {
+#pragma clang fp contract(off)
+  const float c1 = 1.f - b1, c2 = 1.f - b2;
+  const float s = c2 * gg;
+  const float d = s * gg;
+  if (TAIL) {
+    const float t = b1 * m;
+    m = __builtin_fmaf(c1, gg, t);
+    const float u = b2 * v;
+    v = u + d;
+  } else {
+    const float a = c1 * gg;
+    m = __builtin_fmaf(b1, m, a);
+    v = __builtin_fmaf(b2, v, d);
+  }
+}
+
+// One element of Adam behind its gradient term: the moments, denom = fma(sqrt(v), inv_sqrt_bc2, eps), p = fma(-step_size,
+// m / denom, p) (torch's single-tensor path: bias correction 1 in the step size, 2 in the denominator).
+template <bool TAIL>
+__device__ __forceinline__ void adam_element(float& p, float gg, float& m, float& v, float b1, float b2, float eps,
+                                             float step_size, float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
+  adam_moments<TAIL>(gg, m, v, b1, b2);
+  const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+  const float q = m / denom;
+  p = __builtin_fmaf(-step_size, q, p);
+}
+
+// Adam's bias corrections from the device-resident step counter (graph-replay safe): bc1 = 1 - beta1^t, (float)(1 / sqrt(1 - beta2^t)).
+__device__ __forceinline__ void adam_bias_dev(float b1, float b2, const long long* __restrict__ step_dev, double& bc1,
+                                              float& inv_sqrt_bc2) {
+  const double t = (double)*step_dev;
+  bc1 = 1.0 - pow((double)b1, t);
+  inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
+}
+
+// The block size of the eight kernels, a constant in the walks: read from the dispatch (blockDim.x) inside a device function
+// it costs every wave a vector load and a wait in front of its loop.
+constexpr int FLAT_THREADS = 256;
+
+// What a flat kernel takes: its optimizer's arguments, then — only in the forms that have them — the average's and the guard
+// record, so that a kernel's argument block holds nothing of a form it is not (the plain kernels' is the one they always had).
+struct AdamFlatArgs {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  long long n4, n;               // 16-byte vectors, elements
+  float b1, b2, eps, wd, step_size;   // step_size, inv_bc1, inv_sqrt_bc2: from the host's step
+  double inv_bc1;
+  float inv_sqrt_bc2, grad_scale, lr;
+  const long long* step_dev;     // nullable
+  const float* lr_dev;           // nullable: the learning rate a scheduler writes (a captured graph freezes lr)
+};
+
+struct SgdFlatArgs {
+  float* p;
+  const float* g;
+  float* buf;                    // the momentum buffer, nullptr exactly when momentum == 0 (the kernels' switch)
+  long long n4, n;
+  float lr, momentum, wd;
+  int nesterov;
+  float grad_scale;
+  const float* lr_dev;
+};
+
+struct EmaFlatArgs {
+  float* e;
+  double decay;
+  int warmup;
+  const long long* updates_dev;
+};
+
+// The step size and 1 / sqrt(bias correction 2) of a launch.  By value: the host's.  lr_dev alone: lr times the host's 1 / bc1
+// (the host's lr is not used).  step_dev: lr / bc1 with both corrections from the device counter.
+__device__ __forceinline__ void adam_step_terms(const AdamFlatArgs& a, float& step_size, float& inv_sqrt_bc2) {
+  float lr = a.lr;
+  step_size = a.step_size;
+  inv_sqrt_bc2 = a.inv_sqrt_bc2;
+  if (a.lr_dev) {
+    lr = *a.lr_dev;
+    step_size = (float)((double)lr * a.inv_bc1);
+  }
+  if (a.step_dev) {
+    double bc1;
+    adam_bias_dev(a.b1, a.b2, a.step_dev, bc1, inv_sqrt_bc2);
+    step_size = (float)((double)lr / bc1);
+  }
+}
+
+// The walk of a flat kernel: grid-stride over the 16-byte vectors, the n % 4 tail by block 0.  With the average, e[i] comes
+// from the p[i] just computed — one more 4-byte read and write per element instead of a pass of its own that reads p again.
+template <bool CLIP, bool EMA>
+__device__ __forceinline__ void adam_flat_walk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, float* __restrict__ e, const AdamFlatArgs& a, float step_size,
+                                               float inv_sqrt_bc2, float coef, float w) {
+  const long long n4 = a.n4, stride = (long long)gridDim.x * FLAT_THREADS;
+  for (long long i = (long long)blockIdx.x * FLAT_THREADS + threadIdx.x; i < n4; i += stride) {
     floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
     floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
-    floatx4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (buf) bv = reinterpret_cast<floatx4*>(buf)[i];
+    floatx4 mv = reinterpret_cast<floatx4*>(m)[i];
+    floatx4 vv = reinterpret_cast<floatx4*>(v)[i];
+    floatx4 ev = {0.f, 0.f, 0.f, 0.f};
+    if (EMA) ev = reinterpret_cast<floatx4*>(e)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], mj = mv[j], vj = vv[j];
+      const float gg = adam_grad_term<CLIP ? GRAD_CLIPPED_FMA : GRAD_UNCLIPPED>(gv[j], pj, a.grad_scale, a.wd, coef);
+      adam_element<false>(pj, gg, mj, vj, a.b1, a.b2, a.eps, step_size, inv_sqrt_bc2);
+      pv[j] = pj;
+      mv[j] = mj;
+      vv[j] = vj;
+      if (EMA) ev[j] = ema_element(ev[j], pj, w);
+    }
+    reinterpret_cast<floatx4*>(p)[i] = pv;
+    reinterpret_cast<floatx4*>(m)[i] = mv;
+    reinterpret_cast<floatx4*>(v)[i] = vv;
+    if (EMA) reinterpret_cast<floatx4*>(e)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(a.n - n4 * 4)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    float pi = p[i], mi = m[i], vi = v[i];
+    const float gg = adam_grad_term<CLIP ? GRAD_CLIPPED_SUM : GRAD_UNCLIPPED>(g[i], pi, a.grad_scale, a.wd, coef);
+    adam_element<true>(pi, gg, mi, vi, a.b1, a.b2, a.eps, step_size, inv_sqrt_bc2);
+    p[i] = pi;
+    m[i] = mi;
+    v[i] = vi;
+    if (EMA) e[i] = ema_element(e[i], pi, w);
+  }
+}
+
+// GUARD: nothing is written when guard->skip, e included; the gradient is scaled by guard->clip_coef on the way in, and a
+// coefficient of 1.0f takes the unclipped form, so that an unclipped step has the unguarded kernel's bits.
+template <bool GUARD, bool EMA>
+__device__ __forceinline__ void adam_flat_body(const AdamFlatArgs& a, const EmaFlatArgs& avg, const avid_step_guard* guard) {
+  if (GUARD && guard->skip) return;
+  const float coef = GUARD ? guard->clip_coef : 1.f;
+  float step_size, inv_sqrt_bc2;
+  adam_step_terms(a, step_size, inv_sqrt_bc2);
+  const float w = EMA ? ema_weight(avg.decay, avg.warmup, avg.updates_dev) : 0.f;
+  if (coef == 1.f)
+    adam_flat_walk<false, EMA>(a.p, a.g, a.m, a.v, avg.e, a, step_size, inv_sqrt_bc2, coef, w);
+  else
+    adam_flat_walk<true, EMA>(a.p, a.g, a.m, a.v, avg.e, a, step_size, inv_sqrt_bc2, coef, w);
+}
+
+template <bool EMA>
+__device__ __forceinline__ void sgd_flat_walk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                              float* __restrict__ e, const SgdFlatArgs& a, float lr, float coef, float w) {
+  const bool has_buf = buf != nullptr, nesterov = a.nesterov != 0;
+  const long long n4 = a.n4, stride = (long long)gridDim.x * FLAT_THREADS;
+  for (long long i = (long long)blockIdx.x * FLAT_THREADS + threadIdx.x; i < n4; i += stride) {
+    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
+    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
+    floatx4 bv = {0.f, 0.f, 0.f, 0.f}, ev = {0.f, 0.f, 0.f, 0.f};
+    if (EMA) ev = reinterpret_cast<floatx4*>(e)[i];
+    if (has_buf) bv = reinterpret_cast<floatx4*>(buf)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float pj = pv[j], bj = bv[j];
-      bj = sgd_element(pj, gv[j], buf ? &bj : nullptr, lr, momentum, wd, nesterov != 0, grad_scale);
+      sgd_element(pj, gv[j], bj, has_buf, lr, a.momentum, a.wd, nesterov, a.grad_scale, coef, 1.f);
       pv[j] = pj;
       bv[j] = bj;
+      if (EMA) ev[j] = ema_element(ev[j], pj, w);
     }
     reinterpret_cast<floatx4*>(p)[i] = pv;
-    if (buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
+    if (has_buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
+    if (EMA) reinterpret_cast<floatx4*>(e)[i] = ev;
   }
-  // tail (n % 4) handled by block 0
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
+  if (blockIdx.x == 0 && threadIdx.x < (int)(a.n - n4 * 4)) {
     const long long i = n4 * 4 + threadIdx.x;
-    float pi = p[i], bi = buf ? buf[i] : 0.f;
-    bi = sgd_element(pi, g[i], buf ? &bi : nullptr, lr, momentum, wd, nesterov != 0, grad_scale);
+    float pi = p[i], bi = has_buf ? buf[i] : 0.f;
+    sgd_element(pi, g[i], bi, has_buf, lr, a.momentum, a.wd, nesterov, a.grad_scale, coef, 1.f);
     p[i] = pi;
-    if (buf) buf[i] = bi;
+    if (has_buf) buf[i] = bi;
+    if (EMA) e[i] = ema_element(e[i], pi, w);
   }
 }
+
+template <bool GUARD, bool EMA>
+__device__ __forceinline__ void sgd_flat_body(const SgdFlatArgs& a, const EmaFlatArgs& avg, const avid_step_guard* guard) {
+  if (GUARD && guard->skip) return;
+  const float coef = GUARD ? guard->clip_coef : 1.f;
+  const float lr = a.lr_dev ? *a.lr_dev : a.lr;
+  const float w = EMA ? ema_weight(avg.decay, avg.warmup, avg.updates_dev) : 0.f;
+  sgd_flat_walk<EMA>(a.p, a.g, a.buf, avg.e, a, lr, coef, w);
+}
+
+__global__ __launch_bounds__(FLAT_THREADS) void adam_flat_kernel(AdamFlatArgs a) {
+  adam_flat_body<false, false>(a, EmaFlatArgs{}, nullptr);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void adam_flat_guarded_kernel(AdamFlatArgs a, const avid_step_guard* guard) {
+  adam_flat_body<true, false>(a, EmaFlatArgs{}, guard);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void adam_flat_ema_kernel(AdamFlatArgs a, EmaFlatArgs avg) {
+  adam_flat_body<false, true>(a, avg, nullptr);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void adam_flat_ema_guarded_kernel(AdamFlatArgs a, EmaFlatArgs avg,
+                                                                             const avid_step_guard* guard) {
+  adam_flat_body<true, true>(a, avg, guard);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void sgd_flat_kernel(SgdFlatArgs a) {
+  sgd_flat_body<false, false>(a, EmaFlatArgs{}, nullptr);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void sgd_flat_guarded_kernel(SgdFlatArgs a, const avid_step_guard* guard) {
+  sgd_flat_body<true, false>(a, EmaFlatArgs{}, guard);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void sgd_flat_ema_kernel(SgdFlatArgs a, EmaFlatArgs avg) {
+  sgd_flat_body<false, true>(a, avg, nullptr);
+}
+__global__ __launch_bounds__(FLAT_THREADS) void sgd_flat_ema_guarded_kernel(SgdFlatArgs a, EmaFlatArgs avg,
+                                                                            const avid_step_guard* guard) {
+  sgd_flat_body<true, true>(a, avg, guard);
+}
+
 
 // dst[i] = a[i] + b[i]: one fp32 rounding per element, every element written by exactly one thread from the two values at
 // its own index — the result does not depend on the launch geometry, and dst may BE a or b (no __restrict__: an element is
@@ -197,144 +403,6 @@ __global__ __launch_bounds__(GUARD_THREADS) void grad_guard_finish_kernel(const 
   guard->steps_total += 1;
 }
 
-// adam_flat_kernel under a guard record: nothing is written when guard->skip; the gradient term is (g * grad_scale) *
-// clip_coef, the two products rounded one after the other — and, with clip_coef == 1.0f, what adam_flat_kernel computes, so
-// that an unclipped step has its bits.  adam_flat_kernel's `g * grad_scale + wd * p` is compiled (vector loop and tail) as
-// fma(g, grad_scale, round(wd * p)); left to the compiler the same expression came out here as fma(wd, p, round(g *
-// grad_scale)) — both are contractions it may choose — so the form is spelled out (tests/test_gpu_guard.py holds the two
-// kernels together bit for bit).
-template <bool CLIP>
-__device__ __forceinline__ float adam_grad_term(float g, float p, float grad_scale, float wd, float coef) {
-  if (!CLIP) {
-    const float t = wd * p;
-    return __builtin_fmaf(g, grad_scale, t);
-  }
-  float t;
-  {
-#pragma clang fp contract(off)
-    t = g * grad_scale;
-    t = t * coef;
-  }
-  return t + wd * p;
-}
-
-template <bool CLIP>
-__device__ __forceinline__ void adam_guarded_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, long long n4, long long n, float b1, float b2,
-                                                  float eps, float wd, float step_size, float inv_sqrt_bc2, float grad_scale,
-                                                  float coef) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
-    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
-    floatx4 mv = reinterpret_cast<floatx4*>(m)[i];
-    floatx4 vv = reinterpret_cast<floatx4*>(v)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gg = adam_grad_term<CLIP>(gv[j], pv[j], grad_scale, wd, coef);
-      mv[j] = b1 * mv[j] + (1.f - b1) * gg;
-      vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
-      const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-      pv[j] -= step_size * (mv[j] / denom);
-    }
-    reinterpret_cast<floatx4*>(p)[i] = pv;
-    reinterpret_cast<floatx4*>(m)[i] = mv;
-    reinterpret_cast<floatx4*>(v)[i] = vv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
-    const long long i = n4 * 4 + threadIdx.x;
-    const float gg = adam_grad_term<CLIP>(g[i], p[i], grad_scale, wd, coef);
-    m[i] = b1 * m[i] + (1.f - b1) * gg;
-    v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
-    p[i] -= step_size * (m[i] / (sqrtf(v[i]) * inv_sqrt_bc2 + eps));
-  }
-}
-
-__global__ __launch_bounds__(256) void adam_flat_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                float* __restrict__ m, float* __restrict__ v, long long n4,
-                                                                long long n, float b1, float b2, float eps, float wd,
-                                                                float step_size, double inv_bc1, float inv_sqrt_bc2,
-                                                                float grad_scale, float lr,
-                                                                const long long* __restrict__ step_dev,
-                                                                const float* __restrict__ lr_dev,
-                                                                const avid_step_guard* __restrict__ guard) {
-  if (guard->skip) return;
-  const float coef = guard->clip_coef;
-  if (lr_dev) {   // as adam_flat_kernel
-    lr = *lr_dev;
-    step_size = (float)((double)lr * inv_bc1);
-  }
-  if (step_dev) {
-    const double t = (double)*step_dev;
-    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
-  }
-  if (coef == 1.f)
-    adam_guarded_span<false>(p, g, m, v, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef);
-  else
-    adam_guarded_span<true>(p, g, m, v, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef);
-}
-
-// sgd_flat_kernel under a guard record: sgd_element's arithmetic, operation for operation, on d = (g * grad_scale) * clip_coef —
-// each product rounded on its own; times 1.0f is exact, so an unclipped step has sgd_flat_kernel's bits.  (Its own copy
-// of the element: the momentum value travels by reference, so nothing of it lives in a private segment.)
-__device__ __forceinline__ void sgd_element_clipped(float& p, float g, float& b, bool has_buf, float lr, float momentum, float wd,
-                                                    bool nesterov, float grad_scale, float coef) {
-#pragma clang fp contract(off)
-  float d = g * grad_scale;
-  d = d * coef;
-  if (wd != 0.f) {
-    const float t = wd * p;
-    d = d + t;
-  }
-  if (has_buf) {
-    const float t = momentum * b;
-    b = t + d;
-    if (nesterov) {
-      const float u = momentum * b;
-      d = d + u;
-    } else {
-      d = b;
-    }
-  }
-  const float s = lr * d;
-  p = p - s;
-}
-
-__global__ __launch_bounds__(256) void sgd_flat_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ buf, long long n4, long long n, float lr,
-                                                               float momentum, float wd, int nesterov, float grad_scale,
-                                                               const float* __restrict__ lr_dev,
-                                                               const avid_step_guard* __restrict__ guard) {
-  if (guard->skip) return;
-  const float coef = guard->clip_coef;
-  if (lr_dev) lr = *lr_dev;
-  const bool has_buf = buf != nullptr;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
-    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
-    floatx4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (has_buf) bv = reinterpret_cast<floatx4*>(buf)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], bj = bv[j];
-      sgd_element_clipped(pj, gv[j], bj, has_buf, lr, momentum, wd, nesterov != 0, grad_scale, coef);
-      pv[j] = pj;
-      bv[j] = bj;
-    }
-    reinterpret_cast<floatx4*>(p)[i] = pv;
-    if (has_buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
-    const long long i = n4 * 4 + threadIdx.x;
-    float pi = p[i], bi = has_buf ? buf[i] : 0.f;
-    sgd_element_clipped(pi, g[i], bi, has_buf, lr, momentum, wd, nesterov != 0, grad_scale, coef);
-    p[i] = pi;
-    if (has_buf) buf[i] = bi;
-  }
-}
-
 // One block over a SMALL buffer (the 78 KB of BatchNorm running statistics): any element that is not finite turns the record
 // into a skip — clip_coef 1.0f, skipped_total advanced unless the gradient's verdict was a skip already.
 __global__ __launch_bounds__(256) void guard_nonfinite_kernel(const float* __restrict__ x, long long n,
@@ -370,218 +438,7 @@ __global__ __launch_bounds__(256) void guard_restore_kernel(long long rows, long
 }
 
 // ---- the weight average (EMA) ----------------------------------------------------------------------------------------------
-// e = e + w * (p - e): the difference, the product and the sum each rounded to fp32 on its own (torch's unfused
-// `e + (p - e) * w`; the numpy restatement of tests/_ema_ref.py, bit for bit).
-__device__ __forceinline__ float ema_element(float e, float p, float w) {
-#pragma clang fp contract(off)
-  const float d = p - e;
-  const float t = w * d;
-  return e + t;
-}
-
-// w = (float)(1 - d), formed once per launch in double: d is the decay, or — warm-up — min(decay, (1 + k) / (10 + k)) with k
-// the averaging updates applied so far, read from the device counter (a captured graph freezes by-value arguments).
-__device__ __forceinline__ float ema_weight(double decay, int warmup, const long long* __restrict__ updates_dev) {
-  double d = decay;
-  if (warmup) {
-    const double k = (double)*updates_dev;
-    const double r = (1.0 + k) / (10.0 + k);
-    if (r < d) d = r;
-  }
-  return (float)(1.0 - d);
-}
-
-// One element of Adam with every contraction spelled out, so that the averaging kernels below have the bits of
-// adam_flat_kernel / adam_flat_guarded_kernel whatever the compiler would choose here.  Those two were left to the compiler,
-// and their code objects are the specification: the vector loop has m = fma(b1, m, (1 - b1) * gg) and v = fma(b2, v, ((1 - b2)
-// * gg) * gg); the n % 4 tail has m = fma(1 - b1, gg, b1 * m) and v = b2 * v + ((1 - b2) * gg) * gg, unfused; both have
-// denom = fma(sqrt(v), inv_sqrt_bc2, eps) and p = fma(-step_size, m / denom, p).
-template <bool TAIL>
-__device__ __forceinline__ void adam_element(float& p, float gg, float& m, float& v, float b1, float b2, float eps,
-                                             float step_size, float inv_sqrt_bc2) {
-#pragma clang fp contract(off)
-  const float c1 = 1.f - b1, c2 = 1.f - b2;
-  const float s = c2 * gg;
-  const float d = s * gg;
-  if (TAIL) {
-    const float t = b1 * m;
-    m = __builtin_fmaf(c1, gg, t);
-    const float u = b2 * v;
-    v = u + d;
-  } else {
-    const float a = c1 * gg;
-    m = __builtin_fmaf(b1, m, a);
-    v = __builtin_fmaf(b2, v, d);
-  }
-  const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
-  const float q = m / denom;
-  p = __builtin_fmaf(-step_size, q, p);
-}
-
-// The gradient term in front of it.  Unclipped: adam_grad_term<false>, fma(g, grad_scale, wd * p), loop and tail alike.
-// Clipped, t = (g * grad_scale) * coef: the guarded kernel's loop has fma(wd, p, t), its tail t + wd * p unfused.
-template <bool CLIP, bool TAIL>
-__device__ __forceinline__ float adam_ema_grad_term(float g, float p, float grad_scale, float wd, float coef) {
-#pragma clang fp contract(off)
-  if (!CLIP) return adam_grad_term<false>(g, p, grad_scale, wd, coef);
-  float t = g * grad_scale;
-  t = t * coef;
-  if (!TAIL) return __builtin_fmaf(wd, p, t);
-  const float u = wd * p;
-  return u + t;
-}
-
-template <bool CLIP>
-__device__ __forceinline__ void adam_ema_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, float* __restrict__ e, long long n4, long long n, float b1,
-                                              float b2, float eps, float wd, float step_size, float inv_sqrt_bc2,
-                                              float grad_scale, float coef, float w) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
-    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
-    floatx4 mv = reinterpret_cast<floatx4*>(m)[i];
-    floatx4 vv = reinterpret_cast<floatx4*>(v)[i];
-    floatx4 ev = reinterpret_cast<floatx4*>(e)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], mj = mv[j], vj = vv[j];
-      const float gg = adam_ema_grad_term<CLIP, false>(gv[j], pj, grad_scale, wd, coef);
-      adam_element<false>(pj, gg, mj, vj, b1, b2, eps, step_size, inv_sqrt_bc2);
-      pv[j] = pj;
-      mv[j] = mj;
-      vv[j] = vj;
-      ev[j] = ema_element(ev[j], pj, w);
-    }
-    reinterpret_cast<floatx4*>(p)[i] = pv;
-    reinterpret_cast<floatx4*>(m)[i] = mv;
-    reinterpret_cast<floatx4*>(v)[i] = vv;
-    reinterpret_cast<floatx4*>(e)[i] = ev;
-  }
-  // tail (n % 4) handled by block 0
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
-    const long long i = n4 * 4 + threadIdx.x;
-    float pi = p[i], mi = m[i], vi = v[i];
-    const float gg = adam_ema_grad_term<CLIP, true>(g[i], pi, grad_scale, wd, coef);
-    adam_element<true>(pi, gg, mi, vi, b1, b2, eps, step_size, inv_sqrt_bc2);
-    p[i] = pi;
-    m[i] = mi;
-    v[i] = vi;
-    e[i] = ema_element(e[i], pi, w);
-  }
-}
-
-// adam_flat_kernel, then e[i] from the p[i] it has just computed — one more 4-byte read and write per element instead of a
-// pass of its own that reads p again.
-__global__ __launch_bounds__(256) void adam_flat_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                            float* __restrict__ m, float* __restrict__ v,
-                                                            float* __restrict__ e, long long n4, long long n, float b1,
-                                                            float b2, float eps, float wd, float step_size, double inv_bc1,
-                                                            float inv_sqrt_bc2, float grad_scale, float lr,
-                                                            const long long* __restrict__ step_dev,
-                                                            const float* __restrict__ lr_dev, double decay, int warmup,
-                                                            const long long* __restrict__ updates_dev) {
-  if (lr_dev) {   // as adam_flat_kernel
-    lr = *lr_dev;
-    step_size = (float)((double)lr * inv_bc1);
-  }
-  if (step_dev) {
-    const double t = (double)*step_dev;
-    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
-  }
-  const float w = ema_weight(decay, warmup, updates_dev);
-  adam_ema_span<false>(p, g, m, v, e, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, 1.f, w);
-}
-
-// adam_flat_guarded_kernel, then the same: a skipped step writes nothing, e included.
-__global__ __launch_bounds__(256) void adam_flat_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                    float* __restrict__ m, float* __restrict__ v,
-                                                                    float* __restrict__ e, long long n4, long long n,
-                                                                    float b1, float b2, float eps, float wd, float step_size,
-                                                                    double inv_bc1, float inv_sqrt_bc2, float grad_scale,
-                                                                    float lr, const long long* __restrict__ step_dev,
-                                                                    const float* __restrict__ lr_dev, double decay, int warmup,
-                                                                    const long long* __restrict__ updates_dev,
-                                                                    const avid_step_guard* __restrict__ guard) {
-  if (guard->skip) return;
-  const float coef = guard->clip_coef;
-  if (lr_dev) {
-    lr = *lr_dev;
-    step_size = (float)((double)lr * inv_bc1);
-  }
-  if (step_dev) {
-    const double t = (double)*step_dev;
-    step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, t)));
-  }
-  const float w = ema_weight(decay, warmup, updates_dev);
-  if (coef == 1.f)
-    adam_ema_span<false>(p, g, m, v, e, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef, w);
-  else
-    adam_ema_span<true>(p, g, m, v, e, n4, n, b1, b2, eps, wd, step_size, inv_sqrt_bc2, grad_scale, coef, w);
-}
-
-// sgd_flat_kernel's / sgd_flat_guarded_kernel's element (sgd_element_clipped with coef 1.0f is sgd_element: times one is
-// exact), then the average.
-__device__ __forceinline__ void sgd_ema_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                             float* __restrict__ e, long long n4, long long n, float lr, float momentum,
-                                             float wd, bool nesterov, float grad_scale, float coef, float w) {
-  const bool has_buf = buf != nullptr;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    floatx4 pv = reinterpret_cast<floatx4*>(p)[i];
-    floatx4 gv = reinterpret_cast<const floatx4*>(g)[i];
-    floatx4 ev = reinterpret_cast<floatx4*>(e)[i];
-    floatx4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (has_buf) bv = reinterpret_cast<floatx4*>(buf)[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float pj = pv[j], bj = bv[j];
-      sgd_element_clipped(pj, gv[j], bj, has_buf, lr, momentum, wd, nesterov, grad_scale, coef);
-      pv[j] = pj;
-      bv[j] = bj;
-      ev[j] = ema_element(ev[j], pj, w);
-    }
-    reinterpret_cast<floatx4*>(p)[i] = pv;
-    if (has_buf) reinterpret_cast<floatx4*>(buf)[i] = bv;
-    reinterpret_cast<floatx4*>(e)[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {
-    const long long i = n4 * 4 + threadIdx.x;
-    float pi = p[i], bi = has_buf ? buf[i] : 0.f;
-    sgd_element_clipped(pi, g[i], bi, has_buf, lr, momentum, wd, nesterov, grad_scale, coef);
-    p[i] = pi;
-    if (has_buf) buf[i] = bi;
-    e[i] = ema_element(e[i], pi, w);
-  }
-}
-
-__global__ __launch_bounds__(256) void sgd_flat_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ buf, float* __restrict__ e, long long n4,
-                                                           long long n, float lr, float momentum, float wd, int nesterov,
-                                                           float grad_scale, const float* __restrict__ lr_dev, double decay,
-                                                           int warmup, const long long* __restrict__ updates_dev) {
-  if (lr_dev) lr = *lr_dev;
-  const float w = ema_weight(decay, warmup, updates_dev);
-  sgd_ema_span(p, g, buf, e, n4, n, lr, momentum, wd, nesterov != 0, grad_scale, 1.f, w);
-}
-
-__global__ __launch_bounds__(256) void sgd_flat_ema_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                   float* __restrict__ buf, float* __restrict__ e,
-                                                                   long long n4, long long n, float lr, float momentum,
-                                                                   float wd, int nesterov, float grad_scale,
-                                                                   const float* __restrict__ lr_dev, double decay, int warmup,
-                                                                   const long long* __restrict__ updates_dev,
-                                                                   const avid_step_guard* __restrict__ guard) {
-  if (guard->skip) return;
-  const float coef = guard->clip_coef;
-  if (lr_dev) lr = *lr_dev;
-  const float w = ema_weight(decay, warmup, updates_dev);
-  sgd_ema_span(p, g, buf, e, n4, n, lr, momentum, wd, nesterov != 0, grad_scale, coef, w);
-}
-
-// The same rule in a pass of its own: e from a p that somebody else wrote (the BatchNorm running statistics; a caller's
+// ema_element in a pass of its own: e from a p that somebody else wrote (the BatchNorm running statistics; a caller's
 // own optimizer).  guard: nullable; a skip writes nothing.
 __global__ __launch_bounds__(256) void ema_flat_kernel(float* __restrict__ e, const float* __restrict__ p, long long n4,
                                                        long long n, double decay, int warmup,
@@ -654,7 +511,7 @@ struct SegArgs {
 };
 
 // What a launch reads once: the skip word, the clip coefficient, the learning rate and Adam's bias corrections as
-// adam_flat_kernel forms them (step_case 0: by value, 1: lr_dev alone, 2: step_dev), the averaging weight.
+// adam_step_terms forms them (step_case 0: by value, 1: lr_dev alone, 2: step_dev), the averaging weight.
 struct SegTerms {
   float coef, lr, inv_sqrt_bc2, c1, w;
   double bc1, inv_bc1;
@@ -670,10 +527,8 @@ __device__ __forceinline__ bool seg_terms(const SegArgs& a, bool adam, SegTerms&
   t.inv_sqrt_bc2 = a.inv_sqrt_bc2;
   t.step_case = a.lr_dev ? 1 : 0;
   if (adam && a.step_dev) {
-    const double s = (double)*a.step_dev;
-    t.bc1 = 1.0 - pow((double)a.b1, s);
+    adam_bias_dev(a.b1, a.b2, a.step_dev, t.bc1, t.inv_sqrt_bc2);
     t.inv_bc1 = 1.0 / t.bc1;
-    t.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a.b2, s)));
     t.step_case = 2;
   }
   t.c1 = (float)t.inv_bc1;
@@ -742,39 +597,6 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_sumsq_kernel(SegArgs a) {
   }
 }
 
-// d of the SGD family up to the weight-decay term: what the trust factor's norm is taken of, and what the update goes on
-// from — the same operations in both places.
-__device__ __forceinline__ float sgd_table_d(float g, float p, float grad_scale, float coef, float wd) {
-#pragma clang fp contract(off)
-  float d = g * grad_scale;
-  d = d * coef;
-  if (wd != 0.f) {
-    const float t = wd * p;
-    d = d + t;
-  }
-  return d;
-}
-
-// sgd_element_clipped with the factor q on d in front of the momentum (q == 1.0f: its bits).
-__device__ __forceinline__ void sgd_table_element(float& p, float g, float& b, bool has_buf, float lr, float momentum, float wd,
-                                                  bool nesterov, float grad_scale, float coef, float q) {
-#pragma clang fp contract(off)
-  float d = sgd_table_d(g, p, grad_scale, coef, wd);
-  d = q * d;
-  if (has_buf) {
-    const float t = momentum * b;
-    b = t + d;
-    if (nesterov) {
-      const float u = momentum * b;
-      d = d + u;
-    } else {
-      d = b;
-    }
-  }
-  const float s = lr * d;
-  p = p - s;
-}
-
 // The norm pass of LARS: per chunk the sums of p^2 and of d^2.
 __global__ __launch_bounds__(SEG_THREADS) void sgd_table_norm_kernel(SegArgs a) {
   __shared__ double lds[8];
@@ -790,8 +612,8 @@ __global__ __launch_bounds__(SEG_THREADS) void sgd_table_norm_kernel(SegArgs a) 
     for (int i = threadIdx.x; i < nv; i += SEG_THREADS) {
       const floatx4 pv = reinterpret_cast<const floatx4*>(p + ck.start)[i];
       const floatx4 gv = reinterpret_cast<const floatx4*>(g + ck.start)[i];
-      const float d0 = sgd_table_d(gv[0], pv[0], a.grad_scale, t.coef, wd), d1 = sgd_table_d(gv[1], pv[1], a.grad_scale, t.coef, wd);
-      const float d2 = sgd_table_d(gv[2], pv[2], a.grad_scale, t.coef, wd), d3 = sgd_table_d(gv[3], pv[3], a.grad_scale, t.coef, wd);
+      const float d0 = sgd_d(gv[0], pv[0], a.grad_scale, t.coef, wd), d1 = sgd_d(gv[1], pv[1], a.grad_scale, t.coef, wd);
+      const float d2 = sgd_d(gv[2], pv[2], a.grad_scale, t.coef, wd), d3 = sgd_d(gv[3], pv[3], a.grad_scale, t.coef, wd);
       a0 += (double)pv[0] * (double)pv[0];
       a1 += (double)pv[1] * (double)pv[1];
       a2 += (double)pv[2] * (double)pv[2];
@@ -803,7 +625,7 @@ __global__ __launch_bounds__(SEG_THREADS) void sgd_table_norm_kernel(SegArgs a) 
     }
     if ((int)threadIdx.x < tail) {
       const long long i = ck.start + nv * 4 + threadIdx.x;
-      const float pi = p[i], d = sgd_table_d(g[i], pi, a.grad_scale, t.coef, wd);
+      const float pi = p[i], d = sgd_d(g[i], pi, a.grad_scale, t.coef, wd);
       a0 += (double)pi * (double)pi;
       b0 += (double)d * (double)d;
     }
@@ -893,7 +715,7 @@ __global__ __launch_bounds__(SEG_THREADS) void sgd_flat_table_kernel(SegArgs a) 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = pv[j], bj = bv[j];
-        sgd_table_element(pj, gv[j], bj, has_buf, lr, a.momentum, wd, nesterov, a.grad_scale, t.coef, q);
+        sgd_element(pj, gv[j], bj, has_buf, lr, a.momentum, wd, nesterov, a.grad_scale, t.coef, q);
         pv[j] = pj;
         bv[j] = bj;
         if (e) ev[j] = ema_element(ev[j], pj, t.w);
@@ -905,23 +727,12 @@ __global__ __launch_bounds__(SEG_THREADS) void sgd_flat_table_kernel(SegArgs a) 
     if ((int)threadIdx.x < tail) {
       const long long i = ck.start + nv * 4 + threadIdx.x;
       float pi = p[i], bi = has_buf ? buf[i] : 0.f;
-      sgd_table_element(pi, g[i], bi, has_buf, lr, a.momentum, wd, nesterov, a.grad_scale, t.coef, q);
+      sgd_element(pi, g[i], bi, has_buf, lr, a.momentum, wd, nesterov, a.grad_scale, t.coef, q);
       p[i] = pi;
       if (has_buf) buf[i] = bi;
       if (e) e[i] = ema_element(e[i], pi, t.w);
     }
   }
-}
-
-// The gradient term of the Adam family.  Unclipped: adam_flat_kernel's fma(g, grad_scale, wd * p).  Clipped: the scaled
-// gradient, then the decay term added unfused — what the unclipped form gives for a gradient scaled beforehand by a power of two.
-__device__ __forceinline__ float adam_table_grad_term(float g, float p, float grad_scale, float wd, float coef) {
-#pragma clang fp contract(off)
-  if (coef == 1.f) return adam_grad_term<false>(g, p, grad_scale, wd, coef);
-  float t = g * grad_scale;
-  t = t * coef;
-  const float u = wd * p;
-  return u + t;
 }
 
 __global__ __launch_bounds__(SEG_THREADS) void adam_flat_table_kernel(SegArgs a) {
@@ -932,6 +743,7 @@ __global__ __launch_bounds__(SEG_THREADS) void adam_flat_table_kernel(SegArgs a)
   float* __restrict__ m = a.m;
   float* __restrict__ v = a.v;
   float* __restrict__ e = a.e;
+  const bool clip = t.coef != 1.f;   // (the clipped form is the unfused one here, vectors and tail; both use the vector-loop moments)
   for (int c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
     const avid_seg_chunk ck = a.chunks[c];
     const avid_segment sg = a.segs[ck.seg];
@@ -947,7 +759,8 @@ __global__ __launch_bounds__(SEG_THREADS) void adam_flat_table_kernel(SegArgs a)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = pv[j], mj = mv[j], vj = vv[j];
-        const float gg = adam_table_grad_term(gv[j], pj, a.grad_scale, wd, t.coef);
+        const float gg = clip ? adam_grad_term<GRAD_CLIPPED_SUM>(gv[j], pj, a.grad_scale, wd, t.coef)
+                              : adam_grad_term<GRAD_UNCLIPPED>(gv[j], pj, a.grad_scale, wd, t.coef);
         adam_element<false>(pj, gg, mj, vj, a.b1, a.b2, a.eps, step_size, t.inv_sqrt_bc2);
         pv[j] = pj;
         mv[j] = mj;
@@ -962,7 +775,8 @@ __global__ __launch_bounds__(SEG_THREADS) void adam_flat_table_kernel(SegArgs a)
     if ((int)threadIdx.x < tail) {
       const long long i = ck.start + nv * 4 + threadIdx.x;
       float pi = p[i], mi = m[i], vi = v[i];
-      const float gg = adam_table_grad_term(g[i], pi, a.grad_scale, wd, t.coef);
+      const float gg = clip ? adam_grad_term<GRAD_CLIPPED_SUM>(g[i], pi, a.grad_scale, wd, t.coef)
+                            : adam_grad_term<GRAD_UNCLIPPED>(g[i], pi, a.grad_scale, wd, t.coef);
       adam_element<false>(pi, gg, mi, vi, a.b1, a.b2, a.eps, step_size, t.inv_sqrt_bc2);
       p[i] = pi;
       m[i] = mi;
@@ -972,18 +786,13 @@ __global__ __launch_bounds__(SEG_THREADS) void adam_flat_table_kernel(SegArgs a)
   }
 }
 
-// LAMB.  The moments: adam_flat_kernel's vector-loop recurrences on gg = fma(g, grad_scale, 0 * p), which is (g * grad_scale) + 0.0f.
+// LAMB.  The moments: Adam's vector-loop recurrences on gg = fma(g, grad_scale, 0 * p), which is (g * grad_scale) + 0.0f.
 __device__ __forceinline__ void lamb_moments(float g, float& m, float& v, float b1, float b2, float grad_scale, float coef) {
 #pragma clang fp contract(off)
   float gg = g * grad_scale;
   gg = gg * coef;
   gg = gg + 0.f;
-  const float c1 = 1.f - b1, c2 = 1.f - b2;
-  const float s = c2 * gg;
-  const float d = s * gg;
-  const float a = c1 * gg;
-  m = __builtin_fmaf(b1, m, a);
-  v = __builtin_fmaf(b2, v, d);
+  adam_moments<false>(gg, m, v, b1, b2);
 }
 
 // u = (m * c1) / (sqrt(v) * c2 + eps) + wd * p: the same operations in both passes.
@@ -1100,43 +909,158 @@ __global__ __launch_bounds__(SEG_THREADS) void lamb_update_kernel(SegArgs a) {
 
 using namespace avid;
 
+// Blocks of 256 threads over `work` items (16-byte vectors, or scalar elements), one at least and 4096 at most: the kernels stride.
+static unsigned flat_grid(long long work) {
+  const long long grid = ceil_div(work > 0 ? work : 1, 256);
+  return (unsigned)(grid > 4096 ? 4096 : grid);
+}
+
+// Adam's bias corrections from a step given by value (the kernels form them again from step_dev, where there is one).
+struct AdamBias {
+  double bc1, inv_bc1;     // 1 - beta1^step and its reciprocal
+  float inv_sqrt_bc2;      // (float)(1 / sqrt(1 - beta2^step))
+};
+
+static AdamBias adam_bias(float beta1, float beta2, int64_t step) {
+  if (step < 1) step = 1;
+  AdamBias b;
+  b.bc1 = 1.0 - pow((double)beta1, (double)step);
+  b.inv_bc1 = 1.0 / b.bc1;
+  b.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  return b;
+}
+
+static int ema_desc_check(const char* who, const avid_ema_desc* ema, char* msg, size_t cap) {
+  const char* bad = nullptr;
+  if (!ema || !ema->ema) bad = "needs its average buffer";
+  else if (((uintptr_t)ema->ema & 15) != 0) bad = "the average must be 16-byte aligned";
+  else if (!(ema->decay >= 0.0 && ema->decay < 1.0)) bad = "decay must be in [0, 1)";
+  else if (ema->warmup && !ema->updates_dev) bad = "warm-up needs the device counter of updates";
+  else if (((uintptr_t)ema->updates_dev & 7) != 0) bad = "the counter of updates must be 8-byte aligned";
+  if (!bad) return 0;
+  snprintf(msg, cap, "%s: %s", who, bad);
+  return 1;
+}
+
+// ---- the flat optimizers
+// The three entry points of an optimizer differ in what they take besides the buffers: nothing; a guard record, required (its
+// alignment is not looked at); with `averaging`, a record that may be null and an averaging descriptor, both checked here.
+static int flat_average(const char* who, bool averaging, const avid_step_guard* guard, const avid_ema_desc* ema, EmaFlatArgs& avg) {
+  memset(&avg, 0, sizeof avg);
+  if (!averaging) return AVID_OK;
+  AVID_REQUIRE(((uintptr_t)guard & 7) == 0, AVID_E_BADARG, "%s: the guard record must be 8-byte aligned", who);
+  char msg[128];
+  AVID_REQUIRE(!ema_desc_check(who, ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
+  avg.e = ema->ema;
+  avg.decay = ema->decay;
+  avg.warmup = (int)ema->warmup;
+  avg.updates_dev = (const long long*)ema->updates_dev;
+  return AVID_OK;
+}
+
+static int adam_flat_launch(const char* who, bool guarded, bool averaging, int64_t n, float* p, const float* g, float* m, float* v,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                            const int64_t* step_dev, const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                            const avid_ema_desc* ema, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g && m && v && (guard || !guarded) && (step >= 1 || step_dev), AVID_E_BADARG, "%s: bad argument", who);
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
+               "%s: buffers must be 16-byte aligned", who);
+  EmaFlatArgs avg;
+  if (int rc = flat_average(who, averaging, guard, ema, avg)) return rc;
+  const AdamBias bias = adam_bias(beta1, beta2, step);
+  const AdamFlatArgs a = {p, g, m, v, n / 4, n, beta1, beta2, eps, weight_decay, (float)((double)lr / bias.bc1), bias.inv_bc1,
+                          bias.inv_sqrt_bc2, grad_scale, lr, (const long long*)step_dev, lr_dev};
+  const dim3 grid(flat_grid(a.n4)), block(FLAT_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  const double bytes = (averaging ? 36.0 : 28.0) * n;
+  if (averaging && guard) {
+    ScopedTimer t(s, "adam_flat_ema_guarded_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(adam_flat_ema_guarded_kernel, grid, block, 0, s, a, avg, guard);
+  } else if (averaging) {
+    ScopedTimer t(s, "adam_flat_ema_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(adam_flat_ema_kernel, grid, block, 0, s, a, avg);
+  } else if (guard) {
+    ScopedTimer t(s, "adam_flat_guarded_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(adam_flat_guarded_kernel, grid, block, 0, s, a, guard);
+  } else {
+    ScopedTimer t(s, "adam_flat_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(adam_flat_kernel, grid, block, 0, s, a);
+  }
+  return check_launch(who);
+}
+
+static int sgd_flat_launch(const char* who, bool guarded, bool averaging, int64_t n, float* p, const float* g, float* buf, float lr,
+                           float momentum, float weight_decay, int nesterov, const float* lr_dev, float grad_scale,
+                           const avid_step_guard* guard, const avid_ema_desc* ema, avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && p && g && (guard || !guarded), AVID_E_BADARG, "%s: bad argument", who);
+  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "%s: momentum needs its buffer", who);
+  if (momentum == 0.f) buf = nullptr;   // (the kernels take the buffer as the switch)
+  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "%s: nesterov needs momentum", who);
+  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG, "%s: buffers must be 16-byte aligned",
+               who);
+  EmaFlatArgs avg;
+  if (int rc = flat_average(who, averaging, guard, ema, avg)) return rc;
+  const SgdFlatArgs a = {p, g, buf, n / 4, n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev};
+  const dim3 grid(flat_grid(a.n4)), block(FLAT_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  const double bytes = ((buf ? 20.0 : 12.0) + (averaging ? 8.0 : 0.0)) * n;
+  if (averaging && guard) {
+    ScopedTimer t(s, "sgd_flat_ema_guarded_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(sgd_flat_ema_guarded_kernel, grid, block, 0, s, a, avg, guard);
+  } else if (averaging) {
+    ScopedTimer t(s, "sgd_flat_ema_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(sgd_flat_ema_kernel, grid, block, 0, s, a, avg);
+  } else if (guard) {
+    ScopedTimer t(s, "sgd_flat_guarded_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(sgd_flat_guarded_kernel, grid, block, 0, s, a, guard);
+  } else {
+    ScopedTimer t(s, "sgd_flat_kernel", 0.0, bytes);
+    hipLaunchKernelGGL(sgd_flat_kernel, grid, block, 0, s, a);
+  }
+  return check_launch(who);
+}
+
 extern "C" int avid_adam_flat(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
                               const float* lr_dev, float grad_scale, avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && p && g && m && v && (step >= 1 || step_dev), AVID_E_BADARG, "adam_flat: bad argument");
-  if (step < 1) step = 1;
-  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
-               "adam_flat: buffers must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const double inv_bc1 = 1.0 / bc1;
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
-  ScopedTimer t((hipStream_t)stream, "adam_flat_kernel", 0.0, 28.0 * n);
-  hipLaunchKernelGGL(adam_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4,
-                     (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
-                     (const long long*)step_dev, lr_dev);
-  return check_launch("adam_flat");
+  return adam_flat_launch("adam_flat", false, false, n, p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, lr_dev,
+                          grad_scale, nullptr, nullptr, stream);
+}
+
+extern "C" int avid_adam_flat_guarded(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
+                                      float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
+                                      const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                                      avid_stream_t stream) {
+  return adam_flat_launch("adam_flat_guarded", true, false, n, p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev,
+                          lr_dev, grad_scale, guard, nullptr, stream);
+}
+
+extern "C" int avid_adam_flat_ema(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev,
+                                  float grad_scale, const avid_step_guard* guard, const avid_ema_desc* ema,
+                                  avid_stream_t stream) {
+  return adam_flat_launch("adam_flat_ema", false, true, n, p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, lr_dev,
+                          grad_scale, guard, ema, stream);
 }
 
 extern "C" int avid_sgd_flat(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
                              int nesterov, const float* lr_dev, float grad_scale, avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && p && g, AVID_E_BADARG, "sgd_flat: bad argument");
-  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat: momentum needs its buffer");
-  if (momentum == 0.f) buf = nullptr;   // (the kernel takes the buffer as the switch)
-  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat: nesterov needs momentum");
-  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
-               "sgd_flat: buffers must be 16-byte aligned");
-  const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
-  ScopedTimer t((hipStream_t)stream, "sgd_flat_kernel", 0.0, (buf ? 20.0 : 12.0) * n);
-  hipLaunchKernelGGL(sgd_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, n4, (long long)n,
-                     lr, momentum, weight_decay, nesterov, grad_scale, lr_dev);
-  return check_launch("sgd_flat");
+  return sgd_flat_launch("sgd_flat", false, false, n, p, g, buf, lr, momentum, weight_decay, nesterov, lr_dev, grad_scale, nullptr,
+                         nullptr, stream);
+}
+
+extern "C" int avid_sgd_flat_guarded(int64_t n, float* p, const float* g, float* buf, float lr, float momentum,
+                                     float weight_decay, int nesterov, const float* lr_dev, float grad_scale,
+                                     const avid_step_guard* guard, avid_stream_t stream) {
+  return sgd_flat_launch("sgd_flat_guarded", true, false, n, p, g, buf, lr, momentum, weight_decay, nesterov, lr_dev, grad_scale,
+                         guard, nullptr, stream);
+}
+
+extern "C" int avid_sgd_flat_ema(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
+                                 int nesterov, const float* lr_dev, float grad_scale, const avid_step_guard* guard,
+                                 const avid_ema_desc* ema, avid_stream_t stream) {
+  return sgd_flat_launch("sgd_flat_ema", false, true, n, p, g, buf, lr, momentum, weight_decay, nesterov, lr_dev, grad_scale, guard,
+                         ema, stream);
 }
 
 extern "C" int avid_grad_accum_flat(int64_t n, float* dst, const float* a, const float* b, avid_stream_t stream) {
@@ -1197,47 +1121,6 @@ extern "C" int avid_guard_nonfinite(int64_t n, const float* x, avid_step_guard* 
   return check_launch("guard_nonfinite");
 }
 
-extern "C" int avid_adam_flat_guarded(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
-                                      float beta2, float eps, float weight_decay, int64_t step, const int64_t* step_dev,
-                                      const float* lr_dev, float grad_scale, const avid_step_guard* guard,
-                                      avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && p && g && m && v && guard && (step >= 1 || step_dev), AVID_E_BADARG, "adam_flat_guarded: bad argument");
-  if (step < 1) step = 1;
-  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
-               "adam_flat_guarded: buffers must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const double inv_bc1 = 1.0 / bc1;
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
-  ScopedTimer t((hipStream_t)stream, "adam_flat_guarded_kernel", 0.0, 28.0 * n);
-  hipLaunchKernelGGL(adam_flat_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4,
-                     (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
-                     (const long long*)step_dev, lr_dev, guard);
-  return check_launch("adam_flat_guarded");
-}
-
-extern "C" int avid_sgd_flat_guarded(int64_t n, float* p, const float* g, float* buf, float lr, float momentum,
-                                     float weight_decay, int nesterov, const float* lr_dev, float grad_scale,
-                                     const avid_step_guard* guard, avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && p && g && guard, AVID_E_BADARG, "sgd_flat_guarded: bad argument");
-  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat_guarded: momentum needs its buffer");
-  if (momentum == 0.f) buf = nullptr;
-  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat_guarded: nesterov needs momentum");
-  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
-               "sgd_flat_guarded: buffers must be 16-byte aligned");
-  const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
-  ScopedTimer t((hipStream_t)stream, "sgd_flat_guarded_kernel", 0.0, (buf ? 20.0 : 12.0) * n);
-  hipLaunchKernelGGL(sgd_flat_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, n4,
-                     (long long)n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev, guard);
-  return check_launch("sgd_flat_guarded");
-}
-
 extern "C" int avid_counter_add_unless(uint64_t* counter, uint64_t inc, const avid_step_guard* guard, avid_stream_t stream) {
   AVID_REQUIRE(counter && guard, AVID_E_BADARG, "counter_add_unless: null pointer");
   hipLaunchKernelGGL(counter_add_unless_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long*)counter,
@@ -1257,81 +1140,6 @@ extern "C" int avid_guard_restore(int64_t rows, int64_t D, float* dst, const int
 }
 
 // ---- the weight average (EMA)
-static int ema_desc_check(const char* who, const avid_ema_desc* ema, char* msg, size_t cap) {
-  const char* bad = nullptr;
-  if (!ema || !ema->ema) bad = "needs its average buffer";
-  else if (((uintptr_t)ema->ema & 15) != 0) bad = "the average must be 16-byte aligned";
-  else if (!(ema->decay >= 0.0 && ema->decay < 1.0)) bad = "decay must be in [0, 1)";
-  else if (ema->warmup && !ema->updates_dev) bad = "warm-up needs the device counter of updates";
-  else if (((uintptr_t)ema->updates_dev & 7) != 0) bad = "the counter of updates must be 8-byte aligned";
-  if (!bad) return 0;
-  snprintf(msg, cap, "%s: %s", who, bad);
-  return 1;
-}
-
-extern "C" int avid_adam_flat_ema(int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
-                                  float eps, float weight_decay, int64_t step, const int64_t* step_dev, const float* lr_dev,
-                                  float grad_scale, const avid_step_guard* guard, const avid_ema_desc* ema,
-                                  avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && p && g && m && v && (step >= 1 || step_dev), AVID_E_BADARG, "adam_flat_ema: bad argument");
-  if (step < 1) step = 1;
-  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, AVID_E_BADARG,
-               "adam_flat_ema: buffers must be 16-byte aligned");
-  AVID_REQUIRE(((uintptr_t)guard & 7) == 0, AVID_E_BADARG, "adam_flat_ema: the guard record must be 8-byte aligned");
-  char msg[128];
-  AVID_REQUIRE(!ema_desc_check("adam_flat_ema", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const double inv_bc1 = 1.0 / bc1;
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
-  if (guard) {
-    ScopedTimer t((hipStream_t)stream, "adam_flat_ema_guarded_kernel", 0.0, 36.0 * n);
-    hipLaunchKernelGGL(adam_flat_ema_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       ema->ema, n4, (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale,
-                       lr, (const long long*)step_dev, lr_dev, ema->decay, (int)ema->warmup,
-                       (const long long*)ema->updates_dev, guard);
-  } else {
-    ScopedTimer t((hipStream_t)stream, "adam_flat_ema_kernel", 0.0, 36.0 * n);
-    hipLaunchKernelGGL(adam_flat_ema_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema->ema, n4,
-                       (long long)n, beta1, beta2, eps, weight_decay, step_size, inv_bc1, inv_sqrt_bc2, grad_scale, lr,
-                       (const long long*)step_dev, lr_dev, ema->decay, (int)ema->warmup, (const long long*)ema->updates_dev);
-  }
-  return check_launch("adam_flat_ema");
-}
-
-extern "C" int avid_sgd_flat_ema(int64_t n, float* p, const float* g, float* buf, float lr, float momentum, float weight_decay,
-                                 int nesterov, const float* lr_dev, float grad_scale, const avid_step_guard* guard,
-                                 const avid_ema_desc* ema, avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && p && g, AVID_E_BADARG, "sgd_flat_ema: bad argument");
-  AVID_REQUIRE(buf || momentum == 0.f, AVID_E_BADARG, "sgd_flat_ema: momentum needs its buffer");
-  if (momentum == 0.f) buf = nullptr;
-  AVID_REQUIRE(!nesterov || momentum != 0.f, AVID_E_BADARG, "sgd_flat_ema: nesterov needs momentum");
-  AVID_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) == 0, AVID_E_BADARG,
-               "sgd_flat_ema: buffers must be 16-byte aligned");
-  AVID_REQUIRE(((uintptr_t)guard & 7) == 0, AVID_E_BADARG, "sgd_flat_ema: the guard record must be 8-byte aligned");
-  char msg[128];
-  AVID_REQUIRE(!ema_desc_check("sgd_flat_ema", ema, msg, sizeof msg), AVID_E_BADARG, "%s", msg);
-  const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
-  if (guard) {
-    ScopedTimer t((hipStream_t)stream, "sgd_flat_ema_guarded_kernel", 0.0, (buf ? 28.0 : 20.0) * n);
-    hipLaunchKernelGGL(sgd_flat_ema_guarded_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema->ema,
-                       n4, (long long)n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev, ema->decay, (int)ema->warmup,
-                       (const long long*)ema->updates_dev, guard);
-  } else {
-    ScopedTimer t((hipStream_t)stream, "sgd_flat_ema_kernel", 0.0, (buf ? 28.0 : 20.0) * n);
-    hipLaunchKernelGGL(sgd_flat_ema_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, buf, ema->ema, n4,
-                       (long long)n, lr, momentum, weight_decay, nesterov, grad_scale, lr_dev, ema->decay, (int)ema->warmup,
-                       (const long long*)ema->updates_dev);
-  }
-  return check_launch("sgd_flat_ema");
-}
-
 extern "C" int avid_ema_flat(int64_t n, float* e, const float* p, double decay, int warmup, const int64_t* updates_dev,
                              const avid_step_guard* guard, avid_stream_t stream) {
   AVID_REQUIRE(n > 0 && e && p, AVID_E_BADARG, "ema_flat: bad argument");
@@ -1341,10 +1149,8 @@ extern "C" int avid_ema_flat(int64_t n, float* e, const float* p, double decay, 
   AVID_REQUIRE((((uintptr_t)updates_dev | (uintptr_t)guard) & 7) == 0, AVID_E_BADARG,
                "ema_flat: the counter and the guard record must be 8-byte aligned");
   const long long n4 = n / 4;
-  long long grid = ceil_div(n4 > 0 ? n4 : 1, 256);
-  if (grid > 4096) grid = 4096;
   ScopedTimer t((hipStream_t)stream, "ema_flat_kernel", 0.0, 12.0 * n);
-  hipLaunchKernelGGL(ema_flat_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, e, p, n4, (long long)n, decay,
+  hipLaunchKernelGGL(ema_flat_kernel, dim3(flat_grid(n4)), dim3(256), 0, (hipStream_t)stream, e, p, n4, (long long)n, decay,
                      warmup, (const long long*)updates_dev, guard);
   return check_launch("ema_flat");
 }
@@ -1465,13 +1271,13 @@ static void seg_args_ema(SegArgs& a, const avid_ema_desc* ema) {
 }
 
 static void seg_args_adam(SegArgs& a, float beta1, float beta2, float eps, int64_t step, const int64_t* step_dev) {
-  if (step < 1) step = 1;
+  const AdamBias bias = adam_bias(beta1, beta2, step);
   a.b1 = beta1;
   a.b2 = beta2;
   a.eps = eps;
-  a.bc1 = 1.0 - pow((double)beta1, (double)step);
-  a.inv_bc1 = 1.0 / a.bc1;
-  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  a.bc1 = bias.bc1;
+  a.inv_bc1 = bias.inv_bc1;
+  a.inv_sqrt_bc2 = bias.inv_sqrt_bc2;
   a.step_dev = (const long long*)step_dev;
 }
 

@@ -571,8 +571,10 @@ def test_new_kernels_keep_everything_in_registers():
     """No spilled register and no private segment in any of the guard's kernels (read from the code objects: no GPU work)."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     from kernel_resources import kernel_table
-    names = ("grad_sumsq_kernel", "grad_guard_finish_kernel", "adam_flat_guarded_kernel", "sgd_flat_guarded_kernel",
-             "counter_add_unless_kernel", "guard_restore_kernel", "guard_nonfinite_kernel")
+    names = ("grad_sumsq_kernel", "grad_guard_finish_kernel", "counter_add_unless_kernel", "guard_restore_kernel",
+             "guard_nonfinite_kernel",
+             "adam_flat_kernel", "adam_flat_guarded_kernel", "adam_flat_ema_kernel", "adam_flat_ema_guarded_kernel",
+             "sgd_flat_kernel", "sgd_flat_guarded_kernel", "sgd_flat_ema_kernel", "sgd_flat_ema_guarded_kernel")
     rows = {r["name"]: r for r in kernel_table() if r["name"] in names}
     assert sorted(rows) == sorted(names)
     for name, r in rows.items():

@@ -31,7 +31,7 @@ ROLE = {
     "weight_transpose_batched_kernel": "once per step: every weight repacked / Winograd-transformed / pre-split for its kernels (one launch over a table)",
     "wino_weight_kernel": "forward Winograd transforms of the weights (per layer)", "wgrad_reduce_kernel": "fixed-order sum of weight-gradient slabs",
     "wgrad_group_reduce_kernel": "... of a grouped launch", "splitk_reduce_kernel": "fixed-order sum of split-K slabs", "splitk_reduce_stats_kernel": "... + BatchNorm partial sums",
-    "splitk_reduce_bnb_kernel": "... + BatchNorm-backward sums", "adam_flat_kernel": "Adam over the flat parameter / gradient / moment buffers, one launch",
+    "splitk_reduce_bnb_kernel": "... + BatchNorm-backward sums", "adam_flat_kernel": "Adam over the flat parameter / gradient / moment buffers, one launch (adam_flat_body<GUARD, EMA>: the family of eight flat Adam / SGD kernels, optim.hip)",
     "xmodal_fused_kernel": "criterion: draw, bank gather, scores, NCE forward + backward + bank update staging in one kernel",
 }
 def main():
