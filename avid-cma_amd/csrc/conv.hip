@@ -4056,6 +4056,12 @@ static size_t dgrad_compact_bytes(const avid_conv_desc* d) {
   return (sizeof(float) * (size_t)d->B * d->To * d->Ho * d->Wo * d->Cin + 255) / 256 * 256;
 }
 
+// A strided input gradient that dispatch_igemm<1> does not run on the persistent kernel: dx of 2^31 bytes or more
+// (the same test on the same quantities as its first branch; stride > 2 is refused before it)
+static bool strided_dgrad_leaves_pk(const avid_conv_desc* d) {
+  return (d->st > 1 || d->sh > 1 || d->sw > 1) && (long long)d->B * d->Ti * d->Hi * d->Wi * d->Cin * 4 >= (1ll << 31);
+}
+
 extern "C" size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d) {
   if (!d || validate(d)) return 0;
   if (d->x_channel_first) return 0;            // the stems (stem_dgrad_kernel) need none; no other channel-first layer has a dgrad
@@ -4064,6 +4070,9 @@ extern "C" size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d) {
     return dgrad_compact_bytes(d) + avid_conv_dgrad_workspace_bytes(&c);
   }
   const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
+  // strided with dx >= 2^31 bytes: dispatch_igemm<1> leaves the persistent kernel for igemm_kernel<..,true>, which splits
+  // nothing (a.part = nullptr) — the transposed weights are all it reads from the workspace
+  if (strided_dgrad_leaves_pk(d)) return dgrad_wt_bytes(d);
   const int nk = trim_taps(d).d.kt * d->kh * d->kw * (d->Cout / BK);
   size_t fl = igemm_ws_floats(M, d->Cin, nk, 1);
   if (d->st > 1 || d->sh > 1 || d->sw > 1) {   // strided: destination-shaped slabs of the K-split classes (<= 8 pieces)
@@ -4682,6 +4691,13 @@ extern "C" int avid_conv_kernel_name(const avid_conv_desc* d, int which, char* b
       snprintf(buf, len, "wino_kernel<1> grid=%d", wino_grid(d, 1));
     } else if (strided && dgrad_compactable(d)) {
       snprintf(buf, len, "igemm_pk_kernel over the sub-sampled grid + dx_scatter_strided_kernel");
+    } else if (strided && strided_dgrad_leaves_pk(d)) {   // dispatch_igemm<1>'s second branch: the same class table, the same rule
+      ConvArgs a{};
+      fill_common(a, &tr.d);
+      a.Td = d->Ti; a.Hd = d->Hi; a.Wd = d->Wi; a.Cd = d->Cin;
+      build_classes(a, 128);
+      const bool wide = a.Cd % 128 == 0 && (long long)a.cls_ptiles_total * (a.Cd / 128) >= 2 * 256;
+      snprintf(buf, len, "igemm_kernel<%s,1>s2 (stride-parity classes, dx >= 2 GiB)", wide ? "2,2,2,2" : "4,1,1,2");
     } else if (strided) {
       snprintf(buf, len, "igemm_pk_kernel<%s,1>s2 (stride-parity classes)", d->Cin % 128 == 0 && s2_wide() ? "2,2,2,2" : "4,1,1,2");
     } else {

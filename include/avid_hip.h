@@ -147,7 +147,11 @@ long long avid_debug_out_affine_launches(void);
  * (stem_dgrad_kernel: plain fp32 multiply-adds in one fixed order per element — the same bits on every run and under
  * every CU budget).  wt, u, addend, addend_stride and bn must be NULL (AVID_E_BADARG otherwise); no workspace
  * (avid_conv_dgrad_workspace_bytes == 0, ws may be NULL) and avid_conv_dgrad_bn_rows == 0.  Any other channel-first
- * geometry: AVID_E_UNSUPPORTED before anything is launched. */
+ * geometry: AVID_E_UNSUPPORTED before anything is launched.
+ * What avid_conv_dgrad_workspace_bytes contains: the transposed weights (Cout * taps * Cin floats, rounded up to 256 bytes)
+ * + the K-split slabs of the kernel the layer runs on — for a strided layer on the persistent kernel up to 8 dx-shaped slabs
+ * of its K-split parity classes.  A strided layer whose dx has 2^31 bytes or more does not run on the persistent kernel
+ * (igemm_kernel<..,1>s2 splits nothing): since version 172 the answer for it is the transposed weights alone. */
 size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d);
 /* bn (or NULL): dx is the COMPLETE gradient of the output of a training-mode BatchNorm(+ReLU) whose input was
  * bn->x (shape of dx) — the usual conv <- ReLU <- BN chain of models/network_blocks.py:30-60.  The dgrad epilogue
@@ -200,7 +204,10 @@ int avid_weight_transpose_batched(int n, const avid_wt_desc* descs_dev, int64_t 
 int avid_weight_transform(const avid_wt_desc* desc, avid_stream_t stream);
 
 /* Which kernel instantiation a descriptor dispatches to (which: 0 fwd, 1 dgrad, 2 wgrad), e.g.
- * "igemm_kernel<4,1,1,2,1>" — lets bench.py attribute HIP-event timings to rocprofv3 kernel names. */
+ * "igemm_kernel<4,1,1,2,1>" — lets bench.py attribute HIP-event timings to rocprofv3 kernel names.  The answer follows the
+ * launch at every size: a strided input gradient is "igemm_pk_kernel<..,1>s2 (stride-parity classes)" while dx is below
+ * 2^31 bytes and "igemm_kernel<4,1,1,2,1>s2 ..." / "igemm_kernel<2,2,2,2,1>s2 ..." from there on (version >= 172; earlier
+ * versions named the persistent kernel whatever the size). */
 int avid_conv_kernel_name(const avid_conv_desc* d, int which, char* buf, int len);
 /* Nonzero if this layer's forward (which 0) / input gradient (1) / weight gradient (2) runs on the Winograd kernels;
  * for which 0 / 1: 1 = wino_kernel, 2 = wino2_kernel (layers with >= 1.5 rounds of 64-tile units for the CUs). */
