@@ -3025,16 +3025,20 @@ struct PkPlan {
   long long tail_row0;   // rows [tail_row0, M) are produced by splitk_reduce_kernel from f slabs
   size_t ws_floats;
 };
+// the value of an integer switch of the environment (e: getenv's answer, read once by the caller's static): unset or outside
+// [lo, hi] = dflt; of an on / off switch: any non-zero integer = on
+static int env_switch(const char* e, int dflt, int lo, int hi) {
+  const int v = e ? atoi(e) : dflt;
+  return v < lo || v > hi ? dflt : v;
+}
+static bool env_flag(const char* e, bool dflt) { return e ? atoi(e) != 0 : dflt; }
 // AVID_PK_OVERLAP (development): the cost of two co-resident tail units relative to running them one after the other
 static double pk_overlap() {
-  static std::atomic<int> v{-1};
-  int m = v.load(std::memory_order_relaxed);
-  if (m < 0) {
+  static const int m = [] {
     const char* e = getenv("AVID_PK_OVERLAP");
-    m = e ? (int)(atof(e) * 1000.0) : 1000;
-    if (m < 500 || m > 1000) m = 1000;
-    v.store(m, std::memory_order_relaxed);
-  }
+    const int v = e ? (int)(atof(e) * 1000.0) : 1000;
+    return v < 500 || v > 1000 ? 1000 : v;
+  }();
   return m / 1000.0;
 }
 static PkPlan plan_pk_tile(long long M, int Cd, int nk, int tile, double* cost_out, int mode) {
@@ -3117,17 +3121,7 @@ static PkPlan plan_pk(long long M, int Cd, int nk, int mode) {
 // row of a workgroup covers ONE column block: igemm_pk_kernel's write_stats).  Outputs do not depend on the order: a unit
 // computes the same (tile, K range) and the slabs are summed in piece order.  AVID_PK_WS: 0 never, 1 (default) by the model,
 // 2 whenever the tail has no full tiles.
-static int pk_ws_mode() {
-  static std::atomic<int> v{-1};
-  int m = v.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("AVID_PK_WS");
-    m = e ? atoi(e) : 1;
-    if (m < 0 || m > 2) m = 1;
-    v.store(m, std::memory_order_relaxed);
-  }
-  return m;
-}
+static int pk_ws_mode() { static const int v = env_switch(getenv("AVID_PK_WS"), 1, 0, 2); return v; }
 static int pk_slot_xcd(int slot, int G, bool paired) {      // mirrors igemm_pk_kernel's slot numbering (pk_paired / xcd_remap)
   if (paired) return (slot % (G >> 1)) / (G >> 4);
   if (G < 8) return slot;
@@ -3244,39 +3238,15 @@ constexpr bool pk_takes_split() {
 //  0.454 -> 0.42 ms, the step 9.638 / 9.729 -> 9.548 / 9.589 ms; the wide form with the BatchNorm-backward + addend epilogue was
 //  also the last kernel of the step with spilled registers: 44)
 constexpr int S2_WIDE_DEFAULT = 0;
-static int bs_wide_mode() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVID_BS_WIDE");
-    v = e ? atoi(e) : 2;
-    if (v < 0 || v > 2) v = 2;
-  }
-  return v;
-}
+static int bs_wide_mode() { static const int v = env_switch(getenv("AVID_BS_WIDE"), 2, 0, 2); return v; }
 // The 128 x 128 tile with pre-split weights as FOUR waves of 32 rows x 128 columns (igemm_pk_kernel<4,1,1,4,*>) instead of 2 x 2
 // waves of 64 x 64: no input fragment is shared by two waves any more, so each is split once (one split per 24 matrix
 // instructions instead of two); every wave reads all four column blocks' weight fragments from LDS (12 instead of 6 reads per
 // k-step).  AVID_BS_ROWS = 1 / 0.  Same products in the same order per output element: the outputs are bit-identical.
-static bool bs_rows() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVID_BS_ROWS");
-    v = e ? (atoi(e) != 0 ? 1 : 0) : 1;
-  }
-  return v != 0;
-}
+static bool bs_rows() { static const bool v = env_flag(getenv("AVID_BS_ROWS"), true); return v; }
 // Strided input gradients (stride-parity classes) of layers whose Cin is a multiple of 128: AVID_S2_WIDE = 1 the 128 x 128 tile
 // (2 x 2 waves, both operands split in registers), 0 the 128 x 64 tile with pre-split weights (four waves of 32 x 64).
-static bool s2_wide() {
-  static std::atomic<int> v{-1};
-  int m = v.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("AVID_S2_WIDE");
-    m = e ? (atoi(e) != 0 ? 1 : 0) : S2_WIDE_DEFAULT;
-    v.store(m, std::memory_order_relaxed);
-  }
-  return m != 0;
-}
+static bool s2_wide() { static const bool v = env_flag(getenv("AVID_S2_WIDE"), S2_WIDE_DEFAULT != 0); return v; }
 static bool bs_wide(const PkPlan& pk) { return pk.tile == 0 && (bs_wide_mode() == 2 || (bs_wide_mode() == 1 && pk.full == 0)); }
 
 // avid_debug_presplit_launches (tests: which instruction sequence a layer ran); incremented from the forward thread and from
@@ -3355,13 +3325,8 @@ static int tconv_mode() {
 // forward + weight gradient 9.99 / 2.21, all three 10.10 / 2.17.  Every other matrix kernel of the step runs 3-7 % slower when
 // these kernels are in it — the clock the chip holds over the step falls with these kernels in it (they run at the lowest
 // in-kernel clock of the step, 1.75 GHz) although the package power falls too (tools/power_ab.py).
-static int tconv_mode();
 static int tconv_parts() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVID_TCONV_PARTS");
-    v = e ? atoi(e) & 7 : TCONV_PARTS_DEFAULT;
-  }
+  static const int v = getenv("AVID_TCONV_PARTS") ? atoi(getenv("AVID_TCONV_PARTS")) & 7 : TCONV_PARTS_DEFAULT;
   return tconv_mode() == 2 ? 7 : v;
 }
 // Grid of the persistent tile walkers: the fewest workgroups that need no more rounds than all CUs would (1568 tiles on 256
@@ -3375,19 +3340,6 @@ static int balanced_grid(long long ntiles) {
   if (ntiles <= cus) return (int)ntiles;
   const long long rounds = (ntiles + cus - 1) / cus;
   return (int)((ntiles + rounds - 1) / rounds);
-}
-static int tconv_grid(const ConvArgs& a) {
-  return balanced_grid(((long long)a.B * a.Hs * a.Ws + TC_P - 1) / TC_P);
-}
-static bool tconv_takes(const ConvArgs& a, int mode) {
-  if (!PK_SPLIT || !tconv_mode() || !a.wsp || !(tconv_parts() & (1 << mode))) return false;
-  if (a.kt != 3 || a.kh != 1 || a.kw != 1 || a.st != 1 || a.sh != 1 || a.sw != 1 || a.pt != 1 || a.ph != 0 || a.pw != 0) return false;
-  if (a.Cs != 64 || a.Cd != 64 || a.Ts != TC_T || a.Td != TC_T || a.Hs != a.Hd || a.Ws != a.Wd) return false;
-  if (a.bias || a.relu || a.epi_op || a.add_s[0] * a.add_s[1] * a.add_s[2] != 1) return false;
-  if (mode == 0 && a.bnb_x) return false;
-  if ((long long)a.M * 256 >= (1ll << 31) || a.wsp_nrec < TC_B_BYTES) return false;
-  const long long ntiles = ((long long)a.B * a.Hs * a.Ws + TC_P - 1) / TC_P;
-  return tconv_mode() == 2 || ntiles >= 3ll * device_cus();
 }
 
 template <int MODE, int EPI, bool AFF>
@@ -3421,9 +3373,8 @@ static std::atomic<long long> g_tconv_launches[2];
 // ... and of tconv64_kernel's forward applying an eval-mode BatchNorm to its OUTPUT (avid_debug_out_affine_launches)
 static std::atomic<long long> g_tconv_out_launches{0};
 template <int MODE>
-static int launch_tconv(ConvArgs& a, hipStream_t s) {
+static int launch_tconv(ConvArgs& a, int grid, hipStream_t s) {
   magic_for(a.Hs * a.Ws, a.mgW, a.shW);       // position -> clip
-  int grid = tconv_grid(a);
   {   // experiment: cap the input gradient's grid (AVID_TCONV_GRID1)
     static int cap = -1;
     if (cap < 0) { const char* e = getenv("AVID_TCONV_GRID1"); cap = e ? atoi(e) : 0; }
@@ -3444,54 +3395,39 @@ static int launch_tconv(ConvArgs& a, hipStream_t s) {
   return check_launch("tconv64");
 }
 
-// Parity-class table of a strided dgrad (strides are 1 or 2 per axis).
-static void build_classes(ConvArgs& a, int BM) {
-  const int S[3] = {a.st, a.sh, a.sw}, P[3] = {a.pt, a.ph, a.pw}, Kd[3] = {a.kt, a.kh, a.kw}, D[3] = {a.Td, a.Hd, a.Wd};
-  int np[3];
-  for (int x = 0; x < 3; ++x) np[x] = S[x];   // number of parities along axis x
-  a.ncls = 0;
-  int begin = 0;
-  for (int ct = 0; ct < np[0]; ++ct)
-    for (int ch = 0; ch < np[1]; ++ch)
-      for (int cw = 0; cw < np[2]; ++cw) {
-        const int c[3] = {ct, ch, cw};
-        const int k = a.ncls;
-        long long pixels = a.B;
-        for (int x = 0; x < 3; ++x) {
-          if (S[x] == 1) {
-            a.cls_p0[k][x] = 0; a.cls_n[k][x] = D[x]; a.cls_d0[k][x] = 0; a.cls_nd[k][x] = Kd[x];
-          } else {   // positions p with (p + pad) % 2 == c ; taps d with d % 2 == c
-            const int p0 = (c[x] + P[x]) & 1;
-            a.cls_p0[k][x] = p0;
-            a.cls_n[k][x] = p0 < D[x] ? (D[x] - p0 + 1) / 2 : 0;
-            a.cls_d0[k][x] = c[x];
-            a.cls_nd[k][x] = c[x] < Kd[x] ? (Kd[x] - c[x] + 1) / 2 : 0;
-          }
-          pixels *= a.cls_n[k][x];
-        }
-        if (pixels == 0) continue;
-        a.cls_begin[k] = begin;
-        begin += (int)((((pixels + BM - 1) / BM) + 1) / 2);
-        a.ncls++;
-      }
-  a.cls_begin[a.ncls] = begin;
-  a.cls_ptiles_total = begin;
+// Parity-class table of a strided dgrad (strides are 1 or 2 per axis): the route builds it from the descriptor, the launch
+// copies it into the kernel's arguments (ConvArgs::cls_*, field for field).
+struct ClassTable {
+  int ncls, ptiles_total;
+  int begin[9], p0[8][3], n[8][3], d0[8][3], nd[8][3];
+  unsigned mg[8][3];
+  int shf[8][3], f[8], ubegin[9];
+};
+static void put_classes(ConvArgs& a, const ClassTable& t) {
+  a.ncls = t.ncls;
+  a.cls_ptiles_total = t.ptiles_total;
+  memcpy(a.cls_begin, t.begin, sizeof(t.begin));
+  memcpy(a.cls_p0, t.p0, sizeof(t.p0));
+  memcpy(a.cls_n, t.n, sizeof(t.n));
+  memcpy(a.cls_d0, t.d0, sizeof(t.d0));
+  memcpy(a.cls_nd, t.nd, sizeof(t.nd));
+  memcpy(a.cls_mg, t.mg, sizeof(t.mg));
+  memcpy(a.cls_shf, t.shf, sizeof(t.shf));
+  memcpy(a.cls_f, t.f, sizeof(t.f));
+  memcpy(a.cls_ubegin, t.ubegin, sizeof(t.ubegin));
 }
 
-// Parity classes of a strided dgrad for the persistent kernel: tile-unit prefix sums, classes ordered by
-// decreasing tap count (the round-robin deal then gives every workgroup a similar mix), class extents'
-// division magics.  Classes without taps are kept: their pixels still have to be written (zeros / addend).
-static int build_classes_pk(ConvArgs& a, int BM, int ntn) {
-  const int S[3] = {a.st, a.sh, a.sw}, P[3] = {a.pt, a.ph, a.pw}, Kd[3] = {a.kt, a.kh, a.kw}, D[3] = {a.Td, a.Hd, a.Wd};
-  struct Cls { int p0[3], n[3], d0[3], nd[3]; long long pixels; int taps; };
-  Cls cl[8];
+// The non-empty classes of a layer's input gradient in parity order.  d: the layer (dead temporal taps trimmed); dx has its input's extents.
+struct Cls { int p0[3], n[3], d0[3], nd[3]; long long pixels; int taps; };
+static int parity_classes(const avid_conv_desc& d, Cls cl[8]) {
+  const int S[3] = {d.st, d.sh, d.sw}, P[3] = {d.pt, d.ph, d.pw}, Kd[3] = {d.kt, d.kh, d.kw}, D[3] = {d.Ti, d.Hi, d.Wi};
   int nc = 0;
   for (int ct = 0; ct < S[0]; ++ct)
     for (int ch = 0; ch < S[1]; ++ch)
       for (int cw = 0; cw < S[2]; ++cw) {
         const int c[3] = {ct, ch, cw};
         Cls k;
-        k.pixels = a.B;
+        k.pixels = d.B;
         k.taps = 1;
         for (int x = 0; x < 3; ++x) {
           if (S[x] == 1) {
@@ -3506,24 +3442,45 @@ static int build_classes_pk(ConvArgs& a, int BM, int ntn) {
           k.pixels *= k.n[x];
           k.taps *= k.nd[x];
         }
-        if (k.pixels == 0) continue;
-        if (k.taps == 0) k.nd[0] = k.nd[1] = k.nd[2] = 0;
-        cl[nc++] = k;
+        if (k.pixels != 0) cl[nc++] = k;
       }
+  return nc;
+}
+static void set_class(ClassTable& a, int k, const Cls& c, int begin) {
+  for (int x = 0; x < 3; ++x) { a.p0[k][x] = c.p0[x]; a.n[k][x] = c.n[x]; a.d0[k][x] = c.d0[x]; a.nd[k][x] = c.nd[x]; }
+  a.begin[k] = begin;
+}
+
+// ... for igemm_kernel<.., STRIDED>: pair-tile prefix sums
+static void build_classes(ClassTable& a, const avid_conv_desc& d, int BM) {
+  Cls cl[8];
+  a.ncls = parity_classes(d, cl);
+  int begin = 0;
+  for (int k = 0; k < a.ncls; ++k) {
+    set_class(a, k, cl[k], begin);
+    begin += (int)((((cl[k].pixels + BM - 1) / BM) + 1) / 2);
+  }
+  a.begin[a.ncls] = a.ptiles_total = begin;
+}
+
+// ... for the persistent kernel: tile-unit prefix sums, classes ordered by decreasing tap count (the round-robin deal then
+// gives every workgroup a similar mix), class extents' division magics.  Classes without taps are kept: their pixels still
+// have to be written (zeros / addend).
+static void build_classes_pk(ClassTable& a, const avid_conv_desc& d, int BM, int ntn) {
+  Cls cl[8];
+  const int nc = parity_classes(d, cl);
+  for (int k = 0; k < nc; ++k)
+    if (cl[k].taps == 0) cl[k].nd[0] = cl[k].nd[1] = cl[k].nd[2] = 0;
   for (int i = 1; i < nc; ++i)   // insertion sort, taps descending (stable)
     for (int j = i; j > 0 && cl[j].taps > cl[j - 1].taps; --j) { Cls t = cl[j]; cl[j] = cl[j - 1]; cl[j - 1] = t; }
   int begin = 0;
   for (int k = 0; k < nc; ++k) {
-    for (int x = 0; x < 3; ++x) {
-      a.cls_p0[k][x] = cl[k].p0[x]; a.cls_n[k][x] = cl[k].n[x]; a.cls_d0[k][x] = cl[k].d0[x]; a.cls_nd[k][x] = cl[k].nd[x];
-      magic_for(cl[k].n[x], a.cls_mg[k][x], a.cls_shf[k][x]);
-    }
-    a.cls_begin[k] = begin;
+    set_class(a, k, cl[k], begin);
+    for (int x = 0; x < 3; ++x) magic_for(cl[k].n[x], a.mg[k][x], a.shf[k][x]);
     begin += (int)((cl[k].pixels + BM - 1) / BM) * ntn;
   }
   a.ncls = nc;
-  a.cls_begin[nc] = begin;
-  return begin;
+  a.begin[nc] = begin;
 }
 
 // K pieces per class of a strided dgrad.  The classes differ in K (a (1,3,3) / (1,2,2) layer has classes of 4, 2, 2
@@ -3539,16 +3496,18 @@ struct StridedPlan {
   bool any_split, any_direct;
   int fmax;
 };
-static StridedPlan plan_strided(ConvArgs& k, int BM, int BN, size_t ws_floats) {
-  const int ntn = k.Cd / BN, cus = device_cus(), cpt = k.Cs / BK;
-  build_classes_pk(k, BM, ntn);
+// d: the layer (dead temporal taps trimmed); k: its class table, built here (ClassTable::f / ubegin: the plan's pieces)
+static StridedPlan plan_strided(ClassTable& k, const avid_conv_desc& d, int BM, int BN, size_t ws_floats) {
+  const int Cd = d.Cin, ntn = Cd / BN, cus = device_cus(), cpt = d.Cout / BK;
+  const long long M = (long long)d.B * d.Ti * d.Hi * d.Wi;
+  build_classes_pk(k, d, BM, ntn);
   StridedPlan pl{};
   int nk[8], tiles[8], nkmax = 0;
   long long rows[8];
   for (int c = 0; c < k.ncls; ++c) {
-    nk[c] = k.cls_nd[c][0] * k.cls_nd[c][1] * k.cls_nd[c][2] * cpt;
-    tiles[c] = k.cls_begin[c + 1] - k.cls_begin[c];
-    rows[c] = (long long)k.B * k.cls_n[c][0] * k.cls_n[c][1] * k.cls_n[c][2];
+    nk[c] = k.nd[c][0] * k.nd[c][1] * k.nd[c][2] * cpt;
+    tiles[c] = k.begin[c + 1] - k.begin[c];
+    rows[c] = (long long)d.B * k.n[c][0] * k.n[c][1] * k.n[c][2];
     nkmax = nk[c] > nkmax ? nk[c] : nkmax;
   }
   const double ovh = 2.0;                                   // k-tiles of prologue / epilogue per unit
@@ -3567,9 +3526,9 @@ static StridedPlan plan_strided(ConvArgs& k, int BM, int BN, size_t ws_floats) {
       units += (long long)tiles[c] * f[c];
       const double pc = nk[c] > 0 ? (double)((nk[c] + f[c] - 1) / f[c]) : 0.0;
       piece = pc > piece ? pc : piece;
-      if (f[c] > 1) slab_bytes += 4.0 * rows[c] * k.Cd * (2.0 * f[c] + 2.0);
+      if (f[c] > 1) slab_bytes += 4.0 * rows[c] * Cd * (2.0 * f[c] + 2.0);
     }
-    if (fmax > 1 && (size_t)fmax * (size_t)k.M * k.Cd > ws_floats) continue;   // no room for the slabs
+    if (fmax > 1 && (size_t)fmax * (size_t)M * Cd > ws_floats) continue;   // no room for the slabs
     // a CU's load: its share of all the k-tiles (+ the per-unit overhead) + one piece of imbalance
     double work = 0;
     for (int c = 0; c < k.ncls; ++c) work += (double)tiles[c] * (nk[c] + f[c] * ovh);
@@ -3586,184 +3545,35 @@ static StridedPlan plan_strided(ConvArgs& k, int BM, int BN, size_t ws_floats) {
   pl.any_direct = false;
   int ub = 0;
   for (int c = 0; c < k.ncls; ++c) {
-    k.cls_f[c] = pl.f[c];
-    k.cls_ubegin[c] = ub;
+    k.f[c] = pl.f[c];
+    k.ubegin[c] = ub;
     ub += tiles[c] * pl.f[c];
     if (pl.f[c] == 1) pl.any_direct = true;
   }
-  k.cls_ubegin[k.ncls] = ub;
+  k.ubegin[k.ncls] = ub;
   pl.grid = pl.units < 2 * cus ? pl.units : 2 * cus;
   return pl;
 }
 
-template <int MODE>
-static int dispatch_igemm(ConvArgs& a, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (MODE == 1 && (a.st > 1 || a.sh > 1 || a.sw > 1) && (long long)a.M * a.Cd * 4 < (1ll << 31) &&
-      a.st <= 2 && a.sh <= 2 && a.sw <= 2) {
-    // strided dgrad on the persistent kernel: (class tile, K piece) units dealt round-robin, heavy classes first
-    ConvArgs k = a;
-    const bool wide = a.Cd % 128 == 0 && s2_wide();
-    const int BN = wide ? 128 : 64;
-    const StridedPlan pl = plan_strided(k, 128, BN, ws ? ws_bytes / sizeof(float) : 0);
-    k.nsplit = 1;
-    k.part = static_cast<float*>(ws);
-    k.part_row_begin = 0;
-    k.pk_full = pl.units;
-    k.pk_tail_units = 0;
-    k.pk_f = 1;
-    k.pk_kps = 0;
-    k.pk_rot = 0;
-    k.pk_ws = 0;
-    const int cus = device_cus();
-    const int grid = pl.grid;
-    k.pk_paired = (grid == 2 * cus && grid % 16 == 0) ? 1 : 0;
-    // BatchNorm-backward partials: directly written tiles leave theirs in the workgroup rows [0, grid), the rows
-    // of K-split classes get theirs from the reduce (rows [grid, grid + reduce blocks))
-    if (!a.bnb_x) k.stats = nullptr;
-    int rc = wide ? launch_pk<2, 2, 2, 2, 1, true>(k, grid, s) : launch_pk<4, 1, 1, 2, 1, true>(k, grid, s);
-    if (rc || !pl.any_split) return rc;
-    ClsReduce cr{};
-    cr.Td = a.Td; cr.Hd = a.Hd; cr.Wd = a.Wd;
-    magic_for(a.Wd, cr.mgW, cr.shW);
-    magic_for(a.Hd, cr.mgH, cr.shH);
-    magic_for(a.Td, cr.mgT, cr.shT);
-    cr.pt = a.pt; cr.ph = a.ph; cr.pw = a.pw;
-    cr.s2t = a.st == 2; cr.s2h = a.sh == 2; cr.s2w = a.sw == 2;
-    for (int x = 0; x < 3; ++x) { cr.add_s[x] = a.add_s[x]; cr.add_n[x] = a.add_n[x]; }
-    for (int c = 0; c < k.ncls; ++c) {   // class -> its parity bits: positions p with (p + pad) & 1 == (cls_p0 + pad) & 1
-      const int par = (cr.s2t ? ((k.cls_p0[c][0] + a.pt) & 1) << 2 : 0) | (cr.s2h ? ((k.cls_p0[c][1] + a.ph) & 1) << 1 : 0) |
-                      (cr.s2w ? ((k.cls_p0[c][2] + a.pw) & 1) : 0);
-      cr.f_by_par[par] = k.cls_f[c];
-    }
-    double split_rows = 0;
-    for (int c = 0; c < k.ncls; ++c)
-      if (k.cls_f[c] > 1) split_rows += (double)a.B * k.cls_n[c][0] * k.cls_n[c][1] * k.cls_n[c][2];
-    const int rpb = stats_rpb(a.M, a.Cd);
-    const unsigned rgrid = (unsigned)ceil_div((long long)a.M, rpb);
-    if (a.bnb_x && a.stats) {
-      ScopedTimer t(s, "splitk_reduce_bnb_kernel", 0.0, 4.0 * split_rows * a.Cd * (pl.fmax + 2 + (a.addend ? 1 : 0)));
-      hipLaunchKernelGGL(splitk_reduce_cls_kernel<true>, dim3(rgrid), dim3(256), 0, s, k.part, a.dst, a.addend,
-                         (long long)a.M, a.Cd, rpb, cr, a.bnb_x, a.bnb_scale, a.bnb_shift, a.bnb_mean, a.bnb_invstd,
-                         a.bnb_relu, a.stats + (long long)grid * 2 * a.Cd);
-      return check_launch("splitk_reduce_cls");
-    }
-    ScopedTimer t(s, "splitk_reduce_kernel", 0.0, 4.0 * split_rows * a.Cd * (pl.fmax + 1 + (a.addend ? 1 : 0)));
-    hipLaunchKernelGGL(splitk_reduce_cls_kernel<false>, dim3(rgrid), dim3(256), 0, s, k.part, a.dst, a.addend,
-                       (long long)a.M, a.Cd, rpb, cr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
-    return check_launch("splitk_reduce_cls");
-  }
-  if (MODE == 1 && (a.st > 1 || a.sh > 1 || a.sw > 1)) {   // strided dgrad: per-parity-class dense sub-problems
-    a.nsplit = 1;
-    a.ksteps_per_split = 1 << 30;
-    a.part = nullptr;
-    build_classes(a, 128);
-    if (a.Cd % 128 == 0 && (long long)a.cls_ptiles_total * (a.Cd / 128) >= 2 * 256)
-      return launch_igemm<2, 2, 2, 2, 1, true>(a, s);
-    return launch_igemm<4, 1, 1, 2, 1, true>(a, s);
-  }
-  const int nk_total = a.kt * a.kh * a.kw * (a.Cs / BK);
-  // Everything dense goes to the persistent kernel (whole rounds + K-split tail in one launch).
-  {
-    PkPlan pk = plan_pk(a.M, a.Cd, nk_total, MODE);
-    if (tconv_takes(a, MODE)) {   // conv2x's temporal layers: taps staged once, weights resident in LDS
-      const int rows = pk.grid + (pk.f > 1 ? (int)ceil_div(a.M - pk.tail_row0, stats_rpb(a.M - pk.tail_row0, a.Cd)) : 0);
-      AVID_REQUIRE(!(MODE == 0 && has_out_affine(a) && a.stats), AVID_E_UNSUPPORTED,
-                   "conv_fwd_out: BatchNorm partial sums of a tensor that is not written");
-      if (!(a.stats && (MODE == 0 || a.bnb_x)) || rows >= tconv_grid(a)) {
-        ConvArgs k = a;
-        k.stats = (MODE == 0 || a.bnb_x) ? a.stats : nullptr;
-        k.stats_rows = rows;       // (the rows avid_conv_fwd_stats_rows / avid_conv_dgrad_bn_rows promised: the kernel zero-fills beyond its own)
-        return launch_tconv<MODE>(k, s);
-      }
-    }
-    AVID_REQUIRE(!a.in_scale, AVID_E_UNSUPPORTED,
-                 "conv_fwd_in: this layer does not run on a kernel that applies the input's BatchNorm (avid_conv_takes_in_affine)");
-    AVID_REQUIRE(!(MODE == 0 && has_out_affine(a)), AVID_E_UNSUPPORTED,
-                 "conv_fwd_out: this layer does not run on a kernel that applies the output's BatchNorm (avid_conv_takes_out_affine)");
-    if (pk.f > 1 && (ws == nullptr || ws_bytes < sizeof(float) * pk.ws_floats)) {   // no scratch: unsplit
-      AVID_REQUIRE(!a.stats, AVID_E_BADARG, "conv: BatchNorm partials need the planned workspace");
-      pk.tail_units /= pk.f;
-      pk.f = 1;
-      pk.kps = nk_total;
-      pk.tail_row0 = a.M;
-    }
-    ConvArgs k = a;
-    k.mt2_begin = 0;
-    k.mt2_count = 0;
-    k.nsplit = 1;
-    k.pk_full = pk.full;
-    k.pk_tail_units = pk.tail_units;
-    k.pk_f = pk.f;
-    k.pk_kps = pk.kps;
-    k.pk_rot = pk.rot;
-    k.pk_paired = pk.paired ? 1 : 0;
-    k.pk_ws = plan_pk_order(pk, a.M, a.Cd, nk_total, a.Cs / BK, a.wsp != nullptr);
-    k.stats = (MODE == 0 || a.bnb_x) ? a.stats : nullptr;
-    k.part = static_cast<float*>(ws);
-    k.part_row_begin = (int)pk.tail_row0;
-    magic_for(k.Wd, k.mgW, k.shW);
-    magic_for(k.Hd, k.mgH, k.shH);
-    magic_for(k.Td, k.mgT, k.shT);
-    int rc;
-    switch (pk.tile) {
-      case 0: {
-        const int e = epi_code<MODE>(k);      // (the epilogues the pre-split form is instantiated for: pk_takes_split)
-        const bool rows = k.wsp && bs_rows() && (e == 0 || e == 1 || e == 8 || e == 9);
-        rc = rows ? launch_pk<4, 1, 1, 4, MODE>(k, pk.grid, s) : launch_pk<2, 2, 2, 2, MODE>(k, pk.grid, s);
-        break;
-      }
-      default: rc = launch_pk<4, 1, 1, 2, MODE>(k, pk.grid, s); break;
-    }
-    if (rc || pk.f == 1) return rc;
-    const long long rows = a.M - pk.tail_row0, n4 = rows * a.Cd / 4, off = pk.tail_row0 * a.Cd;
-    if (MODE == 1 && a.bnb_x && a.stats) {   // the tail rows' BatchNorm-backward partials come out of the reduce
-      ScopedTimer t(s, "splitk_reduce_bnb_kernel", 0.0, 4.0 * rows * a.Cd * (pk.f + 2 + (a.addend ? 1 : 0)));
-      const int rpb = stats_rpb(rows, a.Cd);
-      hipLaunchKernelGGL(splitk_reduce_bnb_kernel, dim3((unsigned)ceil_div(rows, rpb)), dim3(256), 0, s, k.part,
-                         a.dst + off, a.addend ? a.addend + off : nullptr, rows, a.Cd, pk.f, rpb, a.bnb_x + off,
-                         a.bnb_scale, a.bnb_shift, a.bnb_mean, a.bnb_invstd, a.bnb_relu,
-                         a.stats + (long long)pk.grid * 2 * a.Cd);
-      return check_launch("splitk_reduce_bnb");
-    }
-    if (MODE == 0 && a.stats) {   // the tail rows' BatchNorm partials come out of the reduce
-      ScopedTimer t(s, "splitk_reduce_stats_kernel", 0.0, 4.0 * rows * a.Cd * (pk.f + 1 + (a.addend ? 1 : 0)));
-      const int rpb = stats_rpb(rows, a.Cd);
-      hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((unsigned)ceil_div(rows, rpb)), dim3(256), 0, s, k.part,
-                         a.dst + off, a.addend ? a.addend + off : nullptr, rows, a.Cd, pk.f, rpb,
-                         a.stats + (long long)pk.grid * 2 * a.Cd);
-      return check_launch("splitk_reduce_stats");
-    }
-    long long grid = ceil_div(n4, 256);
-    if (grid > 2048) grid = 2048;
-    ScopedTimer t(s, "splitk_reduce_kernel", 0.0, 4.0 * rows * a.Cd * (pk.f + 1 + (a.addend ? 1 : 0)));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, s, k.part, a.dst + off,
-                       a.addend ? a.addend + off : nullptr, a.bias, n4, a.Cd / 4, pk.f, a.relu);
-    return check_launch("splitk_reduce");
-  }
-}
+enum Tile { T2222, T4112, T4114, T2211 };   // <WM,WN,TM,TN> of the implicit-GEMM kernels
+static const char* const kTileName[] = {"2,2,2,2", "4,1,1,2", "4,1,1,4", "2,2,1,1"};
 
-// scratch floats the non-strided igemm dispatch wants for an M x Cd problem (mirrors dispatch_igemm)
-static size_t igemm_ws_floats(long long M, int Cd, int nk, int mode) { return plan_pk(M, Cd, nk, mode).ws_floats; }
-
-static int launch_gather(const ConvArgs& a, hipStream_t s) {
-  const long long M = a.M;
-  const bool big = ((M + 127) / 128) * (a.Cd / 64) >= 256;
+template <int WM, int WN, int TM, int TN>
+static int launch_gather_tile(const ConvArgs& a, const char* name, hipStream_t s) {
+  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const double K = (double)a.kt * a.kh * a.kw * a.Cs;
   const double srcpix = (double)a.B * a.Ts * a.Hs * a.Ws;
-  if (big) {
-    const size_t lds = sizeof(float) * 2 * (128 + 64) * LDK + sizeof(int2) * KTAB_MAX;
-    ScopedTimer t(s, "igemm_gather_kernel<4,1,1,2>", 2.0 * a.M * a.Cd * K,
-                  4.0 * (srcpix * a.Cs + (double)a.Cd * K + (double)a.M * a.Cd));
-    hipLaunchKernelGGL((igemm_gather_kernel<4, 1, 1, 2>), dim3((unsigned)(((M + 127) / 128) * (a.Cd / 64))), dim3(256),
-                       lds, s, a);
-  } else {
-    const size_t lds = sizeof(float) * 2 * (64 + 64) * LDK + sizeof(int2) * KTAB_MAX;
-    ScopedTimer t(s, "igemm_gather_kernel<2,2,1,1>", 2.0 * a.M * a.Cd * K,
-                  4.0 * (srcpix * a.Cs + (double)a.Cd * K + (double)a.M * a.Cd));
-    hipLaunchKernelGGL((igemm_gather_kernel<2, 2, 1, 1>), dim3((unsigned)(((M + 63) / 64) * (a.Cd / 64))), dim3(256),
-                       lds, s, a);
+  const size_t lds = sizeof(float) * 2 * (BM + BN) * LDK + sizeof(int2) * KTAB_MAX;
+  {
+    ScopedTimer t(s, name, 2.0 * a.M * a.Cd * K, 4.0 * (srcpix * a.Cs + (double)a.Cd * K + (double)a.M * a.Cd));
+    hipLaunchKernelGGL((igemm_gather_kernel<WM, WN, TM, TN>), dim3((unsigned)((((long long)a.M + BM - 1) / BM) * (a.Cd / BN))),
+                       dim3(256), lds, s, a);
   }
   return check_launch("igemm_gather");
+}
+static int launch_gather(const ConvArgs& a, Tile tile, hipStream_t s) {
+  return tile == T4112 ? launch_gather_tile<4, 1, 1, 2>(a, "igemm_gather_kernel<4,1,1,2>", s)
+                       : launch_gather_tile<2, 2, 1, 1>(a, "igemm_gather_kernel<2,2,1,1>", s);
 }
 
 // Dead temporal taps.  conv5x of R(2+1)D-18 sees T = 1: of its (3,1,1) kernels' three taps two only ever meet the
@@ -3779,11 +3589,7 @@ struct Trim {
 };
 static Trim trim_taps(const avid_conv_desc* d) {
   Trim t{*d, 0, d->kt, false};
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("AVID_TRIM_TAPS");
-    on = e ? atoi(e) != 0 : 1;
-  }
+  static const bool on = env_flag(getenv("AVID_TRIM_TAPS"), true);
   if (!on || d->x_channel_first || d->kt <= 1 || d->Cin % 64 || d->Cout % 64) return t;
   int lo = d->kt, hi = -1;
   for (int dt = 0; dt < d->kt; ++dt)
@@ -3799,6 +3605,7 @@ static Trim trim_taps(const avid_conv_desc* d) {
   return t;
 }
 
+// the layer's geometry in a zero-initialised ConvArgs (`ConvArgs a{}`: no partials, no addend stride, no pre-split operand)
 static void fill_common(ConvArgs& a, const avid_conv_desc* d) {
   a.kt = d->kt; a.kh = d->kh; a.kw = d->kw;
   a.st = d->st; a.sh = d->sh; a.sw = d->sw;
@@ -3806,234 +3613,8 @@ static void fill_common(ConvArgs& a, const avid_conv_desc* d) {
   a.B = d->B;
   a.nsplit = 1;
   a.ksteps_per_split = 1 << 30;
-  a.part = nullptr;
-  a.epi_op = 0;
   a.ncls = 1;
-  a.mgW = a.mgH = a.mgT = 0; a.shW = a.shH = a.shT = 0;
-  a.stats = nullptr;
-  a.bnb_x = a.bnb_scale = a.bnb_shift = a.bnb_mean = a.bnb_invstd = nullptr;
-  a.bnb_relu = 0;
-  a.cls_ptiles_total = 0;
-  a.mt2_begin = 0;
-  a.mt2_count = 0;
-  a.part_row_begin = 0;
   a.add_s[0] = a.add_s[1] = a.add_s[2] = 1;
-  a.add_n[0] = a.add_n[1] = a.add_n[2] = 0;
-  a.wsp = nullptr;
-  a.wsp_nrec = a.wsp_kstep = 0;
-  a.stats_rows = 0;
-}
-
-// C[M][N] = A[M][K] . Bq[N][K]^T, optionally combined with Cin by min / max — the similarity GEMMs of
-// the CMA search run on the same MFMA kernel as a 1x1x1 convolution over M "pixels".
-int sim_gemm_nt(const float* A, const float* Bq, float* Cout_, const float* Cin, int op, long long M, int N, int K,
-                hipStream_t s) {
-  AVID_REQUIRE(N % 64 == 0 && K % 32 == 0 && M > 0 && M < (1ll << 31), AVID_E_UNSUPPORTED,
-               "sim_gemm: need N %% 64 == 0, K %% 32 == 0 (N=%d K=%d)", N, K);
-  ConvArgs a{};
-  a.kt = a.kh = a.kw = 1; a.st = a.sh = a.sw = 1; a.pt = a.ph = a.pw = 0;
-  a.B = 1; a.Ts = 1; a.Hs = 1; a.Ws = (int)M; a.Cs = K;
-  a.Td = 1; a.Hd = 1; a.Wd = (int)M; a.Cd = N;
-  a.M = (int)M;
-  a.src = A; a.wk = Bq; a.addend = Cin; a.bias = nullptr; a.dst = Cout_;
-  a.w_row = K; a.w_nrec = (int)((long long)N * K * 4);
-  a.mode = 0; a.relu = 0; a.epi_op = op;
-  a.nsplit = 1; a.ksteps_per_split = 1 << 30; a.part = nullptr; a.ncls = 1; a.cls_ptiles_total = 0;
-  a.mt2_begin = 0; a.mt2_count = (int)((((long long)M + 127) / 128 + 1) / 2); a.part_row_begin = 0;
-  a.ssB = a.ssT = a.ssH = a.ssW = a.ssC = 0;
-  a.stats = nullptr;
-  a.bnb_x = a.bnb_scale = a.bnb_shift = a.bnb_mean = a.bnb_invstd = nullptr;
-  a.bnb_relu = 0;
-  a.mgW = a.mgH = a.mgT = 0; a.shW = a.shH = a.shT = 0;
-  a.add_s[0] = a.add_s[1] = a.add_s[2] = 1;
-  a.add_n[0] = a.add_n[1] = a.add_n[2] = 0;
-  a.wsp = nullptr;
-  a.wsp_nrec = a.wsp_kstep = 0;
-  a.stats_rows = 0;
-  // persistent kernel, no K-split (K = 128: 4 k-tiles per tile, thousands of tiles): 54 -> ~90 TFLOP/s
-  return dispatch_igemm<0>(a, nullptr, 0, s);
-}
-
-}  // namespace avid
-
-using namespace avid;
-
-// Does this layer's forward (which 0) / input gradient (1) run on the 128 x 64 tile of igemm_pk_kernel, which takes its
-// weights pre-split (avid_wt_desc mode 5 / 6) as `u`?  Mirrors avid_conv_fwd / avid_conv_dgrad / dispatch_igemm.
-static bool conv_takes_split(const avid_conv_desc* d, int which) {
-#ifdef AVID_NO_PRESPLIT   // (tools/build_variant.sh: A/B against the fp32 instruction on one box)
-  return false;
-#endif
-  if (!PK_SPLIT || d->x_channel_first) return false;
-  if (which == 0) {
-    if (d->Cin % 32 || d->Cout % 64 || wino_supported(d, 0)) return false;
-    const long long M = (long long)d->B * d->To * d->Ho * d->Wo;
-    const PkPlan pk = plan_pk(M, d->Cout, trim_taps(d).d.kt * d->kh * d->kw * (d->Cin / BK), 0);
-    return pk.tile == 1 || bs_wide(pk);
-  }
-  if (d->Cin % 64 || d->Cout % 32 || d->st > 2 || d->sh > 2 || d->sw > 2 || wino_supported(d, 1)) return false;
-  const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
-  if (d->st > 1 || d->sh > 1 || d->sw > 1) return M * d->Cin * 4 < (1ll << 31) && (d->Cin % 128 != 0 || !s2_wide());
-  const PkPlan pk = plan_pk(M, d->Cin, trim_taps(d).d.kt * d->kh * d->kw * (d->Cout / BK), 1);
-  return pk.tile == 1 || bs_wide(pk);
-}
-
-extern "C" long long avid_debug_presplit_launches(void) { return g_presplit_launches.load(std::memory_order_relaxed); }
-
-extern "C" int avid_tconv_configure(int mode) {
-  g_tconv_mode.store((mode >= 0 && mode <= 2) ? mode : -1, std::memory_order_relaxed);
-  return tconv_mode();
-}
-
-extern "C" int avid_conv_uses_split(const avid_conv_desc* d, int which) {
-  if (!d || validate(d) || which < 0 || which > 1) return 0;
-  return conv_takes_split(d, which) ? 1 : 0;
-}
-
-extern "C" size_t avid_conv_split_bytes(const avid_conv_desc* d) {
-  if (!d || validate(d)) return 0;
-  return (size_t)6 * d->Cout * d->kt * d->kh * d->kw * d->Cin;
-}
-
-// ConvArgs::wsp for an operand of N rows x (taps x C) pre-split into chunks, the first dt0 temporal taps skipped
-static void set_split_operand(ConvArgs& a, const void* planes, int N, int C, int ntaps_full, int khw, int dt0) {
-  const int kstep = (N / 64) * PK_BCH;
-  const long long off = (long long)dt0 * khw * (C / BK) * kstep, total = (long long)ntaps_full * (C / BK) * kstep;
-  a.wsp = static_cast<const char*>(planes) + off;
-  a.wsp_nrec = (int)(total - off);
-  a.wsp_kstep = kstep;
-}
-
-extern "C" size_t avid_conv_fwd_workspace_bytes(const avid_conv_desc* d) {
-  if (!d || validate(d)) return 0;
-  const bool vec = (d->Cin % 32 == 0) && !d->x_channel_first;
-  if (!vec) return stem_fwd_supported(d) ? stem_fwd_ws_bytes(d) : 0;
-  const long long M = (long long)d->B * d->To * d->Ho * d->Wo;
-  const Trim tr = trim_taps(d);
-  const int nk = tr.d.kt * d->kh * d->kw * (d->Cin / BK);
-  size_t need = sizeof(float) * igemm_ws_floats(M, d->Cout, nk, 0);
-  if (wino_supported(d, 0) && wino_ws_bytes(d, 0) > need) need = wino_ws_bytes(d, 0);
-  return need;
-}
-
-extern "C" int avid_conv_fwd_stats_rows(const avid_conv_desc* d) {
-  if (!d || validate(d)) return 0;
-  const bool vec = (d->Cin % 32 == 0) && !d->x_channel_first;
-  if (!vec) return stem_fwd_supported(d) ? stem_fwd_grid(d) : 0;     // LDS-patch stems: one row per workgroup
-  if (wino_supported(d, 0)) return wino_grid(d, 0);
-  if (d->Cout > 1024 || (256 % (d->Cout / 4)) != 0) return 0;
-  const long long M = (long long)d->B * d->To * d->Ho * d->Wo;
-  const PkPlan pk = plan_pk(M, d->Cout, trim_taps(d).d.kt * d->kh * d->kw * (d->Cin / BK), 0);
-  return pk.grid + (pk.f > 1 ? (int)ceil_div(M - pk.tail_row0, stats_rpb(M - pk.tail_row0, d->Cout)) : 0);
-}
-
-// conv2x's temporal layers at the descriptor level (the twin of tconv_takes, which sees the call's arguments): forward (which 0)
-// / input gradient (1) on tconv64_kernel — given the layer's pre-split weights
-static bool tconv_layer(const avid_conv_desc* d, int which) {
-  const bool vec = (d->Cin % 32 == 0) && !d->x_channel_first;
-  const long long tc_tiles = ((long long)d->B * d->Hi * d->Wi + TC_P - 1) / TC_P;
-  return PK_SPLIT && tconv_mode() && vec && which >= 0 && which < 2 && (tconv_parts() & (1 << which)) && d->kt == 3 && d->kh == 1 && d->kw == 1 &&
-         d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 1 && d->ph == 0 && d->pw == 0 && d->Cin == 64 && d->Cout == 64 && d->Ti == TC_T &&
-         d->To == TC_T && (long long)d->B * d->Ti * d->Hi * d->Wi * 256 < (1ll << 31) &&
-         (tconv_mode() == 2 || tc_tiles >= 3ll * device_cus());
-}
-static bool twgrad_takes(const avid_conv_desc* d);
-
-// AVID_IN_AFFINE (default 1): 0 = no layer offers to apply its input's BatchNorm (every BatchNorm writes its output)
-static bool in_affine_on() {
-  static std::atomic<int> v{-1};
-  int m = v.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("AVID_IN_AFFINE");
-    m = e ? (atoi(e) != 0 ? 1 : 0) : 1;
-    v.store(m, std::memory_order_relaxed);
-  }
-  return m != 0;
-}
-
-extern "C" int avid_conv_takes_in_affine(const avid_conv_desc* d) {
-  if (!d || validate(d) || !in_affine_on()) return 0;
-  // both readers of the layer's input have to apply the map: the forward (tconv64_kernel) and the weight gradient (twgrad64_kernel)
-  return tconv_layer(d, 0) && twgrad_takes(d) && conv_takes_split(d, 0) ? 1 : 0;
-}
-
-extern "C" long long avid_debug_in_affine_launches(int fused) { return g_tconv_launches[fused ? 1 : 0].load(std::memory_order_relaxed); }
-
-// the layers whose forward can apply the eval-mode BatchNorm (+ReLU) of their OUTPUT in the epilogue: exactly those whose
-// forward tconv_takes() sends to tconv64_kernel, given their pre-split weights (inference has no weight gradient to agree with)
-extern "C" int avid_conv_takes_out_affine(const avid_conv_desc* d) {
-  if (!d || validate(d)) return 0;
-  return tconv_layer(d, 0) && conv_takes_split(d, 0) ? 1 : 0;
-}
-
-extern "C" long long avid_debug_out_affine_launches(void) { return g_tconv_out_launches.load(std::memory_order_relaxed); }
-
-extern "C" int avid_conv_fwd(const avid_conv_desc* d, const float* x, const float* w, const float* u, const float* addend,
-                             const float* bias, int relu, float* y, float* bn_partials, void* ws, size_t ws_bytes,
-                             avid_stream_t stream) {
-  return avid_conv_fwd_in(d, x, nullptr, w, u, addend, bias, relu, y, bn_partials, ws, ws_bytes, stream);
-}
-
-extern "C" int avid_conv_fwd_in(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
-                                const float* addend, const float* bias, int relu, float* y, float* bn_partials, void* ws,
-                                size_t ws_bytes, avid_stream_t stream) {
-  return avid_conv_fwd_out(d, x, in, w, u, addend, bias, relu, nullptr, y, bn_partials, ws, ws_bytes, stream);
-}
-
-extern "C" int avid_conv_fwd_out(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
-                                 const float* addend, const float* bias, int relu, const avid_out_affine* out, float* y,
-                                 float* bn_partials, void* ws, size_t ws_bytes, avid_stream_t stream) {
-  int rc = validate(d);
-  if (rc) return rc;
-  AVID_REQUIRE(x && w && y, AVID_E_BADARG, "conv_fwd: null pointer");
-  if (out) {
-    AVID_REQUIRE(out->scale && out->shift, AVID_E_BADARG, "conv_fwd_out: null scale / shift");
-    AVID_REQUIRE(avid_conv_takes_out_affine(d) && u, AVID_E_UNSUPPORTED,
-                 "conv_fwd_out: this layer does not apply its output's BatchNorm (avid_conv_takes_out_affine; needs its pre-split weights)");
-    AVID_REQUIRE(!bias && !relu && !bn_partials, AVID_E_UNSUPPORTED,
-                 "conv_fwd_out: no bias, no ReLU in front of the BatchNorm and no BatchNorm partial sums (the un-normalised tensor is not written)");
-  }
-  if (in) {
-    AVID_REQUIRE(in->scale && in->shift, AVID_E_BADARG, "conv_fwd_in: null scale / shift");
-    AVID_REQUIRE(avid_conv_takes_in_affine(d) && u, AVID_E_UNSUPPORTED,
-                 "conv_fwd_in: this layer does not apply its input's BatchNorm (avid_conv_takes_in_affine; needs its pre-split weights)");
-  }
-  if (!out && stem_fwd_supported(d) && !addend && !bias && !relu && ws && ws_bytes >= stem_fwd_ws_bytes(d))
-    return stem_fwd(d, x, w, y, bn_partials, ws, (hipStream_t)stream);
-  if (!out && wino_supported(d, 0) && !bias && !relu) {
-    // (avid_conv_fwd_stats_rows promised this kernel's rows: without its workspace the partials would not match)
-    AVID_REQUIRE(!bn_partials || u || (ws && ws_bytes >= wino_ws_bytes(d, 0)), AVID_E_BADARG,
-                 "conv_fwd: BatchNorm partials of this layer need the planned workspace (avid_conv_fwd_workspace_bytes)");
-    if (u || (ws && ws_bytes >= wino_ws_bytes(d, 0)))
-      return wino_conv(d, 0, x, w, u, y, addend, bn_partials, nullptr, ws, (hipStream_t)stream);
-  }
-  const Trim tr = trim_taps(d);
-  ConvArgs a{};
-  fill_common(a, &tr.d);
-  a.src = x; a.addend = addend; a.bias = bias; a.dst = y;
-  {   // weights: the live temporal taps of every [kt][kh][kw][Cin] row
-    const long long tapsz = (long long)d->kh * d->kw * d->Cin, off = tr.dt0 * tapsz;
-    a.wk = w + off;
-    a.w_row = (int)(tr.kt_full * tapsz);
-    a.w_nrec = (int)(((long long)d->Cout * a.w_row - off) * 4);
-  }
-  if (u && conv_takes_split(d, 0)) set_split_operand(a, u, d->Cout, d->Cin, d->kt * d->kh * d->kw, d->kh * d->kw, tr.dt0);
-  a.Ts = d->Ti; a.Hs = d->Hi; a.Ws = d->Wi; a.Cs = d->Cin;
-  a.Td = d->To; a.Hd = d->Ho; a.Wd = d->Wo; a.Cd = d->Cout;
-  a.M = d->B * d->To * d->Ho * d->Wo;
-  a.mode = 0;
-  a.relu = relu;
-  if (in) { a.in_scale = in->scale; a.in_shift = in->shift; a.in_relu = in->relu; }
-  if (out) { a.bnb_scale = out->scale; a.bnb_shift = out->shift; a.bnb_relu = out->relu; }   // (has_out_affine)
-  fill_src_strides(d, a.ssB, a.ssT, a.ssH, a.ssW, a.ssC);
-  const bool vec = (d->Cin % 32 == 0) && !d->x_channel_first;
-  if (bn_partials) {
-    AVID_REQUIRE(vec, AVID_E_BADARG, "conv_fwd: BatchNorm partials of a stem need its workspace (and no addend / bias / ReLU)");
-    AVID_REQUIRE(!bias && !relu && avid_conv_fwd_stats_rows(d) > 0, AVID_E_UNSUPPORTED,
-                 "conv_fwd: BatchNorm partials need the persistent kernel, no bias and no ReLU");
-    a.stats = bn_partials;
-  }
-  return vec ? dispatch_igemm<0>(a, ws, ws_bytes, (hipStream_t)stream) : launch_gather(a, (hipStream_t)stream);
 }
 
 static size_t dgrad_wt_bytes(const avid_conv_desc* d) {
@@ -4056,193 +3637,8 @@ static size_t dgrad_compact_bytes(const avid_conv_desc* d) {
   return (sizeof(float) * (size_t)d->B * d->To * d->Ho * d->Wo * d->Cin + 255) / 256 * 256;
 }
 
-// A strided input gradient that dispatch_igemm<1> does not run on the persistent kernel: dx of 2^31 bytes or more
-// (the same test on the same quantities as its first branch; stride > 2 is refused before it)
-static bool strided_dgrad_leaves_pk(const avid_conv_desc* d) {
-  return (d->st > 1 || d->sh > 1 || d->sw > 1) && (long long)d->B * d->Ti * d->Hi * d->Wi * d->Cin * 4 >= (1ll << 31);
-}
-
-extern "C" size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d) {
-  if (!d || validate(d)) return 0;
-  if (d->x_channel_first) return 0;            // the stems (stem_dgrad_kernel) need none; no other channel-first layer has a dgrad
-  if (dgrad_compactable(d)) {
-    const avid_conv_desc c = dgrad_compact_desc(d);
-    return dgrad_compact_bytes(d) + avid_conv_dgrad_workspace_bytes(&c);
-  }
-  const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
-  // strided with dx >= 2^31 bytes: dispatch_igemm<1> leaves the persistent kernel for igemm_kernel<..,true>, which splits
-  // nothing (a.part = nullptr) — the transposed weights are all it reads from the workspace
-  if (strided_dgrad_leaves_pk(d)) return dgrad_wt_bytes(d);
-  const int nk = trim_taps(d).d.kt * d->kh * d->kw * (d->Cout / BK);
-  size_t fl = igemm_ws_floats(M, d->Cin, nk, 1);
-  if (d->st > 1 || d->sh > 1 || d->sw > 1) {   // strided: destination-shaped slabs of the K-split classes (<= 8 pieces)
-    const size_t want = (size_t)8 * (size_t)M * d->Cin;
-    if (want > fl) fl = want;
-  }
-  size_t need = dgrad_wt_bytes(d) + sizeof(float) * fl;
-  if (wino_supported(d, 1) && wino_ws_bytes(d, 1) > need) need = wino_ws_bytes(d, 1);
-  return need;
-}
-
-extern "C" int avid_weight_transpose_batched(int n, const avid_wt_desc* descs_dev, int64_t max_elems,
-                                             avid_stream_t stream) {
-  AVID_REQUIRE(n > 0 && descs_dev && max_elems > 0, AVID_E_BADARG, "weight_transpose_batched: bad argument");
-  hipStream_t s = (hipStream_t)stream;
-  ScopedTimer t(s, "weight_transpose_batched_kernel", 0.0, 0.0);
-  long long gx = ceil_div(max_elems, 1024);   // 32 x 32 tiles of the largest tensor, capped: blocks stride over tiles
-  if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(weight_transpose_batched_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, descs_dev);
-  return check_launch("weight_transpose_batched");
-}
-
-extern "C" int avid_weight_transform(const avid_wt_desc* desc, avid_stream_t stream) {
-  AVID_REQUIRE(desc && desc->w && desc->wt && desc->Cout > 0 && desc->Cin > 0 && desc->ntaps > 0 && desc->mode >= 0 && desc->mode <= 6,
-               AVID_E_BADARG, "weight_transform: bad descriptor");
-  AVID_REQUIRE(desc->mode < 5 || (desc->mode == 5 ? desc->Cout % 64 == 0 && desc->Cin % 32 == 0 : desc->Cin % 64 == 0 && desc->Cout % 32 == 0),
-               AVID_E_UNSUPPORTED, "weight_transform: mode %d needs 64 | rows and 32 | channels", desc->mode);
-  hipStream_t s = (hipStream_t)stream;
-  ScopedTimer t(s, "weight_transform_kernel", 0.0, 0.0);
-  long long gx = ceil_div((long long)desc->Cout * desc->ntaps * desc->Cin, 1024);
-  if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(weight_transform_kernel, dim3((unsigned)gx), dim3(256), 0, s, *desc);
-  return check_launch("weight_transform");
-}
-
-// rows of BatchNorm-backward partial sums a dgrad of this layer writes (0: this layer cannot — strided, or not on
-// the persistent kernel); dense layers: one row per workgroup + the K-split tail's reduce blocks
-extern "C" int avid_conv_dgrad_bn_rows(const avid_conv_desc* d) {
-  if (!d || validate(d)) return 0;
-  if (d->x_channel_first || d->Cin % 64 || d->Cout % 32 || d->st > 2 || d->sh > 2 || d->sw > 2) return 0;
-  if (wino_supported(d, 1)) return wino_grid(d, 1);
-  if (d->Cin > 1024 || (256 % (d->Cin / 4)) != 0) return 0;
-  const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
-  if (d->st > 1 || d->sh > 1 || d->sw > 1) {   // strided: the plan of dispatch_igemm<1>'s parity-class branch
-    if (M * d->Cin * 4 >= (1ll << 31)) return 0;
-    const Trim tr = trim_taps(d);
-    ConvArgs a{};
-    fill_common(a, &tr.d);
-    a.Td = d->Ti; a.Hd = d->Hi; a.Wd = d->Wi; a.Cd = d->Cin;
-    const int BN = d->Cin % 128 == 0 && s2_wide() ? 128 : 64;
-    a.Cs = d->Cout;
-    a.M = (int)M;
-    const StridedPlan pl = plan_strided(a, 128, BN, (size_t)8 * (size_t)M * d->Cin);
-    return pl.grid + (pl.any_split ? (int)ceil_div(M, stats_rpb(M, d->Cin)) : 0);
-  }
-  const PkPlan pk = plan_pk(M, d->Cin, trim_taps(d).d.kt * d->kh * d->kw * (d->Cout / BK), 1);
-  return pk.grid + (pk.f > 1 ? (int)ceil_div(M - pk.tail_row0, stats_rpb(M - pk.tail_row0, d->Cin)) : 0);
-}
-
-extern "C" int avid_conv_dgrad(const avid_conv_desc* d, const float* dy, const float* w, const float* wt_in,
-                               const float* u, const float* addend, const int32_t* addend_stride, float* dx, const avid_bn_bwd_fuse* bn,
-                               void* ws, size_t ws_bytes, avid_stream_t stream) {
-  int rc = validate(d);
-  if (rc) return rc;
-  if (d->x_channel_first) {                    // the stems: dx channel-first like x, straight from w, no workspace
-    AVID_REQUIRE(stem_dgrad_supported(d), AVID_E_UNSUPPORTED,
-                 "conv_dgrad: the only channel-first layers with an input gradient are the (3,7,7) / (1,7,7) stride-(1,2,2) stems");
-    AVID_REQUIRE(dy && w && dx, AVID_E_BADARG, "conv_dgrad: null pointer");
-    AVID_REQUIRE(!wt_in && !u && !addend && !addend_stride && !bn, AVID_E_BADARG,
-                 "conv_dgrad: a channel-first stem takes no wt / u / addend / addend_stride / bn");
-    return stem_dgrad(d, dy, w, dx, (hipStream_t)stream);
-  }
-  AVID_REQUIRE(dy && w && dx && ws, AVID_E_BADARG, "conv_dgrad: null pointer");
-  bool sparse_add = false;
-  if (addend && addend_stride) {
-    for (int x = 0; x < 3; ++x) {
-      AVID_REQUIRE(addend_stride[x] == 1 || addend_stride[x] == 2, AVID_E_UNSUPPORTED, "conv_dgrad: addend strides must be 1 or 2");
-      sparse_add |= addend_stride[x] == 2;
-    }
-    AVID_REQUIRE(!sparse_add || ((d->st > 1 || d->sh > 1 || d->sw > 1) &&
-                                 (long long)d->B * d->Ti * d->Hi * d->Wi * d->Cin * 4 < (1ll << 31)),
-                 AVID_E_UNSUPPORTED, "conv_dgrad: a compact addend needs a strided layer on the persistent kernel");
-  }
-  if (bn) {
-    AVID_REQUIRE(bn->x && bn->scale && bn->shift && bn->mean && bn->invstd && bn->partials, AVID_E_BADARG,
-                 "conv_dgrad: incomplete BatchNorm descriptor");
-    AVID_REQUIRE(avid_conv_dgrad_bn_rows(d) > 0, AVID_E_UNSUPPORTED,
-                 "conv_dgrad: this layer cannot produce BatchNorm-backward partial sums (avid_conv_dgrad_bn_rows == 0)");
-    AVID_REQUIRE(ws_bytes >= avid_conv_dgrad_workspace_bytes(d), AVID_E_BADARG,
-                 "conv_dgrad: BatchNorm partials need the planned workspace");
-  }
-  AVID_REQUIRE(!d->x_channel_first && d->Cin % 64 == 0 && d->Cout % 32 == 0, AVID_E_UNSUPPORTED,
-               "conv_dgrad: needs channels-last x, Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%d Cout=%d)", d->Cin,
-               d->Cout);
-  AVID_REQUIRE(d->st <= 2 && d->sh <= 2 && d->sw <= 2, AVID_E_UNSUPPORTED, "conv_dgrad: stride > 2");
-  AVID_REQUIRE(ws_bytes >= dgrad_wt_bytes(d), AVID_E_BADARG, "conv_dgrad: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  if (dgrad_compactable(d) && !bn && !sparse_add && ws_bytes >= avid_conv_dgrad_workspace_bytes(d)) {
-    const avid_conv_desc c = dgrad_compact_desc(d);
-    float* compact = static_cast<float*>(ws);
-    const size_t cb = dgrad_compact_bytes(d);
-    rc = avid_conv_dgrad(&c, dy, w, wt_in, u, nullptr, nullptr, compact, nullptr, static_cast<char*>(ws) + cb, ws_bytes - cb, stream);
-    if (rc) return rc;
-    const long long n4 = (long long)d->B * d->Ti * d->Hi * d->Wi * (d->Cin / 4);
-    long long grid = ceil_div(n4, 256 * 4);
-    if (grid > 4096) grid = 4096;
-    ScopedTimer t(s, "dx_scatter_strided_kernel", 0.0, 16.0 * n4 * (1 + (addend ? 1 : 0)) + 16.0 * n4 / (d->st * d->sh * d->sw));
-    hipLaunchKernelGGL(dx_scatter_strided_kernel, dim3((unsigned)grid), dim3(256), 0, s, compact, addend, dx, n4, d->Cin / 4, d->Ti,
-                       d->Hi, d->Wi, d->To, d->Ho, d->Wo, d->st, d->sh, d->sw);
-    return check_launch("dx_scatter_strided");
-  }
-  if (wino_supported(d, 1) && !sparse_add && (u || ws_bytes >= wino_ws_bytes(d, 1)))
-    return wino_conv(d, 1, dy, w, u, dx, addend, nullptr, bn, ws, s);   // (u: this layer's pre-transformed weights)
-  const int ntaps = d->kt * d->kh * d->kw;
-  const float* wt = wt_in;
-  const bool split = u && conv_takes_split(d, 1);      // (u: this layer's pre-split transposed weights; wt is not read)
-  if (split) wt = w;
-  if (!wt) {
-    float* wt_ws = static_cast<float*>(ws);
-    const long long nw = (long long)d->Cout * ntaps * d->Cin;
-    {
-      ScopedTimer t(s, "weight_transpose_kernel", 0.0, 8.0 * nw);
-      hipLaunchKernelGGL(weight_transpose_kernel, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, s, w, wt_ws, d->Cout,
-                         ntaps, d->Cin);
-    }
-    rc = check_launch("weight_transpose");
-    if (rc) return rc;
-    wt = wt_ws;
-  }
-  const Trim tr = trim_taps(d);
-  ConvArgs a{};
-  fill_common(a, &tr.d);
-  a.src = dy; a.addend = addend; a.bias = nullptr; a.dst = dx;
-  {   // transposed weights [Cin][kt][kh][kw][Cout]: the live temporal taps of every row
-    const long long tapsz = (long long)d->kh * d->kw * d->Cout, off = tr.dt0 * tapsz;
-    a.wk = wt + off;
-    a.w_row = (int)(tr.kt_full * tapsz);
-    a.w_nrec = (int)(((long long)d->Cin * a.w_row - off) * 4);
-  }
-  if (split) set_split_operand(a, u, d->Cin, d->Cout, ntaps, d->kh * d->kw, tr.dt0);
-  a.Ts = d->To; a.Hs = d->Ho; a.Ws = d->Wo; a.Cs = d->Cout;
-  a.Td = d->Ti; a.Hd = d->Hi; a.Wd = d->Wi; a.Cd = d->Cin;
-  a.M = d->B * d->Ti * d->Hi * d->Wi;
-  a.mode = 1;
-  a.relu = 0;
-  a.ssB = a.ssT = a.ssH = a.ssW = a.ssC = 0;
-  if (sparse_add) {
-    const int D[3] = {d->Ti, d->Hi, d->Wi};
-    for (int x = 0; x < 3; ++x) {
-      a.add_s[x] = addend_stride[x];
-      a.add_n[x] = (D[x] + addend_stride[x] - 1) / addend_stride[x];
-    }
-  }
-  if (bn) {
-    a.bnb_x = bn->x; a.bnb_scale = bn->scale; a.bnb_shift = bn->shift; a.bnb_mean = bn->mean;
-    a.bnb_invstd = bn->invstd; a.bnb_relu = bn->relu;
-    a.stats = bn->partials;
-  }
-  return dispatch_igemm<1>(a, static_cast<char*>(ws) + dgrad_wt_bytes(d), ws_bytes - dgrad_wt_bytes(d), s);
-}
-
 // weight gradients of the vector-path layers as split-bf16 products (wgrad_tab_body<.., SPLIT>); AVID_WGRAD_BF16X3=0: fp32 MFMA
-static bool wgrad_split() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("AVID_WGRAD_BF16X3");
-    on = e ? atoi(e) != 0 : 1;
-  }
-  return on != 0;
-}
+static bool wgrad_split() { static const bool on = env_flag(getenv("AVID_WGRAD_BF16X3"), true); return on; }
 
 // grouped weight gradients with the fragments split once at the LDS write (wgrad_pre_body); AVID_WGRAD_PRE=0: split per use
 static int g_wgrad_pre = -1;
@@ -4299,6 +3695,677 @@ static WgradPlan wgrad_plan(const avid_conv_desc* d) {
   return pl;
 }
 
+static int twgrad_grid(const avid_conv_desc* d) {
+  return balanced_grid(((long long)d->B * d->Hi * d->Wi + TWG_P - 1) / TWG_P);
+}
+static size_t twgrad_ws_bytes(const avid_conv_desc* d) { return sizeof(float) * (size_t)twgrad_grid(d) * 64 * 3 * 64; }
+
+// ------------------------------------------------------------------------------------------------
+// The route of a convolution: which kernel runs it, with which plan, workspace and partial rows.  conv_route() is the ONE
+// place that decides; the exported queries read a field of the route of the call the Python layer will make
+// (ConvCall::planned), the launch entries build the ConvCall of the call they got and execute its route.
+// ------------------------------------------------------------------------------------------------
+enum class Fam {
+  Refused,          // no kernel takes this layer in this direction
+  StemFwd,          // LDS-patch stem (stem.hip)
+  Gather,           // igemm_gather_kernel: Cin % 32 != 0 or channel-first x
+  Wino,             // wino.hip, forward / input gradient
+  Tconv,            // tconv64_kernel
+  PkDense,          // igemm_pk_kernel (+ a splitk_reduce*_kernel when pk.f > 1)
+  PkStrided,        // igemm_pk_kernel<.., STRIDED> over stride-parity classes (+ splitk_reduce_cls_kernel when sp.any_split)
+  IgemmStrided,     // igemm_kernel<.., STRIDED>: dx of 2 GiB or more
+  CompactScatter,   // the route of the compact (stride-1) descriptor + dx_scatter_strided_kernel
+  StemDgrad, StemWgrad, WinoWgrad,
+  Twgrad,           // twgrad64_kernel + wgrad_reduce_kernel
+  TabWgrad,         // wgrad_tab_kernel<wp.NB, wp.KC> (+ a reduce when trimmed or wp.nsplit > 1)
+  GatherWgrad,
+};
+
+// The facts of a call a route may depend on — nothing else of the arguments is looked at
+struct ConvCall {
+  bool u = false;                // the pre-split (or, Winograd: pre-transformed) weights are given
+  size_t ws_bytes = 0;           // workspace offered (0: none)
+  bool epilogue = false;         // bias, ReLU or an epilogue op
+  bool addend = false;
+  bool compact_addend = false;   // input gradient: the addend is the gradient of a sub-sampled view (addend_stride)
+  bool stats = false;            // BatchNorm partials (forward) / a BatchNorm-backward descriptor (input gradient) asked for
+  bool in_affine = false, out_affine = false;
+  // the call the Python layer makes after asking the queries: the layer's u whenever a kernel that takes one is offered (a route
+  // that reads none ignores it), the planned workspace, no bias and no ReLU
+  static ConvCall planned() {
+    ConvCall c;
+    c.u = true;
+    c.ws_bytes = ~(size_t)0;
+    return c;
+  }
+};
+
+struct ConvRoute {
+  Fam fam = Fam::Refused;
+  Tile tile = T4112;
+  Trim tr{};                 // the layer the vector-path kernels run: dead temporal taps trimmed (wgrad without scratch: not)
+  PkPlan pk{};               // PkDense; Tconv: the plan whose partial rows the caller was promised
+  int pk_ws = 0;             // ConvArgs::pk_ws (plan_pk_order)
+  ClassTable cls{};          // PkStrided / IgemmStrided
+  StridedPlan sp{};          // PkStrided
+  WgradPlan wp{};            // weight gradients
+  bool presplit = false;     // the kernel reads the pre-split weights `u`
+  bool wino_starved = false; // Winograd is this call's kernel but got neither u nor its workspace: another family runs
+  bool pk_starved = false;   // the K-split tail got no workspace: the plan was unsplit
+  int grid = 0;
+  int stats_rows = 0;        // rows of BatchNorm (forward) / BatchNorm-backward (input gradient) partials; 0: cannot
+  size_t ws_bytes = 0;       // the workspace to plan for the layer: serves every route a call of this direction can take
+};
+
+static bool presplit_on() {
+#ifdef AVID_NO_PRESPLIT   // (tools/build_variant.sh: A/B against the fp32 instruction on one box)
+  return false;
+#else
+  return PK_SPLIT;
+#endif
+}
+
+// conv2x's temporal layers: (3,1,1), 64 -> 64 channels, 8 frames — the shape tconv64_kernel and twgrad64_kernel are built for
+// (un-trimmed by construction: with 8 frames every tap is live, so the pre-split weights hold all TC_B_BYTES)
+static bool tconv_shape(const avid_conv_desc* d) {
+  return !d->x_channel_first && d->kt == 3 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 1 &&
+         d->ph == 0 && d->pw == 0 && d->Cin == 64 && d->Cout == 64 && d->Ti == TC_T && d->To == TC_T &&
+         (long long)d->B * d->Ti * d->Hi * d->Wi * 256 < (1ll << 31);
+}
+static int tconv_grid(const avid_conv_desc* d) { return balanced_grid(((long long)d->B * d->Hi * d->Wi + TC_P - 1) / TC_P); }
+// forward (which 0) / input gradient (1) on tconv64_kernel — for a call that reads the layer's pre-split weights
+static bool tconv_takes(const avid_conv_desc* d, int which, const ConvCall& c) {
+  if (!PK_SPLIT || !tconv_mode() || !(tconv_parts() & (1 << which)) || !tconv_shape(d)) return false;
+  if (c.epilogue || c.compact_addend) return false;
+  const long long ntiles = ((long long)d->B * d->Hi * d->Wi + TC_P - 1) / TC_P;
+  return tconv_mode() == 2 || ntiles >= 3ll * device_cus();
+}
+// the weight gradient on twgrad64_kernel (same switch: avid_tconv_configure)
+static bool twgrad_shape(const avid_conv_desc* d) { return PK_SPLIT && wgrad_split() && tconv_shape(d); }
+static bool twgrad_takes(const avid_conv_desc* d) {
+  if (!tconv_mode() || !(tconv_parts() & 4) || !twgrad_shape(d)) return false;
+  const long long ntiles = ((long long)d->B * d->Hi * d->Wi + TWG_P - 1) / TWG_P;
+  return tconv_mode() == 2 || ntiles >= 6ll * device_cus();
+}
+
+// rows of partial sums a persistent launch writes: one per workgroup + the K-split tail's reduce blocks (0: Cd has no reduce form)
+static int pk_rows(const PkPlan& pk, long long M, int Cd) {
+  if (Cd > 1024 || (256 % (Cd / 4)) != 0) return 0;
+  return pk.grid + (pk.f > 1 ? (int)ceil_div(M - pk.tail_row0, stats_rpb(M - pk.tail_row0, Cd)) : 0);
+}
+
+// The dense M x Cd problem of nk k-tiles (cpt per tap) behind r.pk: tconv64_kernel where it takes the call, else the persistent
+// kernel.  split_ok: the layer may read pre-split weights; ws_bytes: what the call offers for the K-split slabs.
+static void route_dense(ConvRoute& r, const avid_conv_desc* d, int which, const ConvCall& c, long long M, int Cd, int nk, int cpt,
+                        bool split_ok, size_t ws_bytes) {
+  r.presplit = c.u && split_ok && presplit_on() && (r.pk.tile == 1 || bs_wide(r.pk));
+  if (d && r.presplit && tconv_takes(d, which, c) && (!c.stats || r.stats_rows >= tconv_grid(d))) {
+    r.fam = Fam::Tconv;          // (partials: only where the promised rows cover the kernel's own, which zero-fills the rest)
+    r.grid = tconv_grid(d);
+    return;
+  }
+  r.fam = Fam::PkDense;
+  if (r.pk.f > 1 && ws_bytes < sizeof(float) * r.pk.ws_floats) {   // no scratch: unsplit
+    r.pk_starved = true;
+    r.pk.tail_units /= r.pk.f;
+    r.pk.f = 1;
+    r.pk.kps = nk;
+    r.pk.tail_row0 = M;
+  }
+  r.pk_ws = plan_pk_order(r.pk, M, Cd, nk, cpt, r.presplit);
+  // (the 128 x 128 tile with pre-split weights runs as four waves of 32 x 128 with the epilogues convolution layers use)
+  r.tile = r.pk.tile == 1 ? T4112 : (r.presplit && bs_rows() && !c.epilogue ? T4114 : T2222);
+  r.grid = r.pk.grid;
+}
+
+// A layer wino.hip supports (forward / input gradient): its workspace is planned whatever the call; the kernel runs where the
+// call's epilogue allows it and it gets its operand (the pre-transformed weights, or the workspace to transform them into)
+static bool route_wino(ConvRoute& r, const avid_conv_desc* d, int which, const ConvCall& c, bool allowed) {
+  const size_t wws = wino_ws_bytes(d, which);
+  if (wws > r.ws_bytes) r.ws_bytes = wws;
+  if (!allowed) return false;
+  r.wino_starved = !(c.u || c.ws_bytes >= wws);
+  if (r.wino_starved) return false;
+  r.fam = Fam::Wino;
+  r.grid = r.stats_rows = wino_grid(d, which);
+  return true;
+}
+
+static void route_fwd(ConvRoute& r, const avid_conv_desc* d, const ConvCall& c) {
+  const long long M = (long long)d->B * d->To * d->Ho * d->Wo;
+  if (d->Cin % 32 != 0 || d->x_channel_first) {
+    if (stem_fwd_supported(d)) {                // LDS-patch stems: one partial row per workgroup
+      r.ws_bytes = stem_fwd_ws_bytes(d);
+      if (!c.out_affine && !c.addend && !c.epilogue && c.ws_bytes >= r.ws_bytes) {
+        r.fam = Fam::StemFwd;
+        r.grid = r.stats_rows = stem_fwd_grid(d);
+        return;
+      }
+    }
+    r.fam = Fam::Gather;
+    r.tile = ((M + 127) / 128) * (d->Cout / 64) >= 256 ? T4112 : T2211;
+    return;
+  }
+  const int nk = r.tr.d.kt * d->kh * d->kw * (d->Cin / BK);
+  r.pk = plan_pk(M, d->Cout, nk, 0);
+  r.ws_bytes = sizeof(float) * r.pk.ws_floats;
+  const bool wino = wino_supported(d, 0);
+  if (wino && route_wino(r, d, 0, c, !c.out_affine && !c.epilogue)) return;
+  r.stats_rows = pk_rows(r.pk, M, d->Cout);
+  route_dense(r, d, 0, c, M, d->Cout, nk, d->Cin / BK, !wino, c.ws_bytes);
+}
+
+static ConvRoute conv_route(const avid_conv_desc* d, int which, const ConvCall& c);
+
+static void route_dgrad(ConvRoute& r, const avid_conv_desc* d, const ConvCall& c) {
+  if (d->x_channel_first) {                     // the stems: no workspace, no partials
+    if (stem_dgrad_supported(d)) r.fam = Fam::StemDgrad;
+    return;
+  }
+  if (d->Cin % 64 || d->Cout % 32) return;
+  const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
+  const int nk = r.tr.d.kt * d->kh * d->kw * (d->Cout / BK);
+  const size_t wt = dgrad_wt_bytes(d), offered = c.ws_bytes > wt ? c.ws_bytes - wt : 0;   // the transposed weights come first
+  r.pk = plan_pk(M, d->Cin, nk, 1);
+  if (d->st > 1 || d->sh > 1 || d->sw > 1) {
+    const bool over2 = d->st > 2 || d->sh > 2 || d->sw > 2, wide = d->Cin % 128 == 0 && s2_wide();
+    if (M * d->Cin * 4 >= (1ll << 31)) {        // igemm_kernel splits nothing: the transposed weights are all it reads from the workspace
+      r.fam = Fam::IgemmStrided;
+      if (!over2) build_classes(r.cls, r.tr.d, 128);
+      r.tile = d->Cin % 128 == 0 && (long long)r.cls.ptiles_total * (d->Cin / 128) >= 2 * 256 ? T2222 : T4112;
+      r.grid = r.cls.ptiles_total * (d->Cin / (r.tile == T2222 ? 128 : 64));
+      r.ws_bytes = wt;
+    } else {                                    // (class tile, K piece) units; destination-shaped slabs of the K-split classes (<= 8 pieces)
+      r.fam = Fam::PkStrided;
+      r.tile = wide ? T2222 : T4112;
+      r.presplit = c.u && presplit_on() && !over2 && !wide;
+      // (sized as before this function existed: the dense plan's slabs where they are the larger — more than plan_strided reads)
+      const size_t slabs = (size_t)8 * (size_t)M * d->Cin;
+      r.ws_bytes = wt + sizeof(float) * (r.pk.ws_floats > slabs ? r.pk.ws_floats : slabs);
+      if (!over2) {                             // (a stride above 2 is named like its neighbours but never planned: avid_conv_dgrad refuses it)
+        r.sp = plan_strided(r.cls, r.tr.d, 128, wide ? 128 : 64, offered / sizeof(float));
+        r.grid = r.sp.grid;
+        if (d->Cin <= 1024 && 256 % (d->Cin / 4) == 0)
+          r.stats_rows = r.sp.grid + (r.sp.any_split ? (int)ceil_div(M, stats_rpb(M, d->Cin)) : 0);
+      }
+    }
+    if (dgrad_compactable(d)) {                 // planned for whenever the call allows it
+      const avid_conv_desc cd = dgrad_compact_desc(d);
+      r.ws_bytes = dgrad_compact_bytes(d) + conv_route(&cd, 1, ConvCall::planned()).ws_bytes;
+      if (!c.stats && !c.compact_addend && c.ws_bytes >= r.ws_bytes) r.fam = Fam::CompactScatter;
+    }
+    return;
+  }
+  r.ws_bytes = wt + sizeof(float) * r.pk.ws_floats;
+  const bool wino = wino_supported(d, 1);
+  if (wino && route_wino(r, d, 1, c, !c.compact_addend)) return;
+  r.stats_rows = pk_rows(r.pk, M, d->Cin);
+  route_dense(r, d, 1, c, M, d->Cin, nk, d->Cout / BK, !wino, offered);
+}
+
+static void route_wgrad(ConvRoute& r, const avid_conv_desc* d, const ConvCall& c) {
+  r.wp = wgrad_plan(&r.tr.d);      // (a trimmed layer always goes through slabs: the reduce scatters them into dw)
+  r.ws_bytes = sizeof(float) * (size_t)r.wp.nsplit * d->Cout * r.tr.d.kt * d->kh * d->kw * d->Cin;
+  const bool stem = stem_wgrad_supported(d), wino = wino_wgrad_supported(d);
+  if (stem && stem_wgrad_ws_bytes(d) > r.ws_bytes) r.ws_bytes = stem_wgrad_ws_bytes(d);
+  if (wino && wino_wgrad_ws_bytes(d) > r.ws_bytes) r.ws_bytes = wino_wgrad_ws_bytes(d);
+  if (twgrad_shape(d) && twgrad_ws_bytes(d) > r.ws_bytes) r.ws_bytes = twgrad_ws_bytes(d);
+  if (stem && c.ws_bytes >= stem_wgrad_ws_bytes(d)) { r.fam = Fam::StemWgrad; return; }
+  if (wino && c.ws_bytes >= wino_wgrad_ws_bytes(d)) { r.fam = Fam::WinoWgrad; return; }
+  if (twgrad_takes(d) && c.ws_bytes >= twgrad_ws_bytes(d)) {   // conv2x's temporal layers: the taps share their split fragments
+    r.fam = Fam::Twgrad;
+    r.grid = twgrad_grid(d);
+    return;
+  }
+  if (r.tr.on && c.ws_bytes < r.ws_bytes) {     // a trimmed layer without scratch runs untrimmed
+    r.tr = Trim{*d, 0, d->kt, false};
+    r.wp = wgrad_plan(d);
+  }
+  r.fam = r.wp.vec ? Fam::TabWgrad : Fam::GatherWgrad;
+  r.grid = r.wp.kt_tiles * r.wp.n_tiles * r.wp.nsplit;
+}
+
+// d: validated.  which: 0 forward, 1 input gradient, 2 weight gradient.
+static ConvRoute conv_route(const avid_conv_desc* d, int which, const ConvCall& c) {
+  ConvRoute r;
+  r.tr = trim_taps(d);
+  if (which == 0) route_fwd(r, d, c);
+  else if (which == 1) route_dgrad(r, d, c);
+  else route_wgrad(r, d, c);
+  return r;
+}
+
+// ---- the implicit-GEMM routes' launches: argument filling, the kernel, its reduce
+template <int MODE>
+static int dispatch_igemm(ConvArgs& a, const ConvRoute& r, void* ws, hipStream_t s) {
+  if (r.fam == Fam::PkStrided) {
+    // strided dgrad on the persistent kernel: (class tile, K piece) units dealt round-robin, heavy classes first
+    ConvArgs k = a;
+    const StridedPlan& pl = r.sp;
+    put_classes(k, r.cls);
+    k.nsplit = 1;
+    k.part = static_cast<float*>(ws);
+    k.part_row_begin = 0;
+    k.pk_full = pl.units;
+    k.pk_tail_units = 0;
+    k.pk_f = 1;
+    k.pk_kps = 0;
+    k.pk_rot = 0;
+    k.pk_ws = 0;
+    const int cus = device_cus();
+    const int grid = pl.grid;
+    k.pk_paired = (grid == 2 * cus && grid % 16 == 0) ? 1 : 0;
+    // BatchNorm-backward partials: directly written tiles leave theirs in the workgroup rows [0, grid), the rows
+    // of K-split classes get theirs from the reduce (rows [grid, grid + reduce blocks))
+    if (!a.bnb_x) k.stats = nullptr;
+    int rc = r.tile == T2222 ? launch_pk<2, 2, 2, 2, 1, true>(k, grid, s) : launch_pk<4, 1, 1, 2, 1, true>(k, grid, s);
+    if (rc || !pl.any_split) return rc;
+    ClsReduce cr{};
+    cr.Td = a.Td; cr.Hd = a.Hd; cr.Wd = a.Wd;
+    magic_for(a.Wd, cr.mgW, cr.shW);
+    magic_for(a.Hd, cr.mgH, cr.shH);
+    magic_for(a.Td, cr.mgT, cr.shT);
+    cr.pt = a.pt; cr.ph = a.ph; cr.pw = a.pw;
+    cr.s2t = a.st == 2; cr.s2h = a.sh == 2; cr.s2w = a.sw == 2;
+    for (int x = 0; x < 3; ++x) { cr.add_s[x] = a.add_s[x]; cr.add_n[x] = a.add_n[x]; }
+    for (int c = 0; c < k.ncls; ++c) {   // class -> its parity bits: positions p with (p + pad) & 1 == (cls_p0 + pad) & 1
+      const int par = (cr.s2t ? ((k.cls_p0[c][0] + a.pt) & 1) << 2 : 0) | (cr.s2h ? ((k.cls_p0[c][1] + a.ph) & 1) << 1 : 0) |
+                      (cr.s2w ? ((k.cls_p0[c][2] + a.pw) & 1) : 0);
+      cr.f_by_par[par] = k.cls_f[c];
+    }
+    double split_rows = 0;
+    for (int c = 0; c < k.ncls; ++c)
+      if (k.cls_f[c] > 1) split_rows += (double)a.B * k.cls_n[c][0] * k.cls_n[c][1] * k.cls_n[c][2];
+    const int rpb = stats_rpb(a.M, a.Cd);
+    const unsigned rgrid = (unsigned)ceil_div((long long)a.M, rpb);
+    if (a.bnb_x && a.stats) {
+      ScopedTimer t(s, "splitk_reduce_bnb_kernel", 0.0, 4.0 * split_rows * a.Cd * (pl.fmax + 2 + (a.addend ? 1 : 0)));
+      hipLaunchKernelGGL(splitk_reduce_cls_kernel<true>, dim3(rgrid), dim3(256), 0, s, k.part, a.dst, a.addend,
+                         (long long)a.M, a.Cd, rpb, cr, a.bnb_x, a.bnb_scale, a.bnb_shift, a.bnb_mean, a.bnb_invstd,
+                         a.bnb_relu, a.stats + (long long)grid * 2 * a.Cd);
+      return check_launch("splitk_reduce_cls");
+    }
+    ScopedTimer t(s, "splitk_reduce_kernel", 0.0, 4.0 * split_rows * a.Cd * (pl.fmax + 1 + (a.addend ? 1 : 0)));
+    hipLaunchKernelGGL(splitk_reduce_cls_kernel<false>, dim3(rgrid), dim3(256), 0, s, k.part, a.dst, a.addend,
+                       (long long)a.M, a.Cd, rpb, cr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+    return check_launch("splitk_reduce_cls");
+  }
+  if (r.fam == Fam::IgemmStrided) {   // strided dgrad: per-parity-class dense sub-problems
+    a.nsplit = 1;
+    a.ksteps_per_split = 1 << 30;
+    a.part = nullptr;
+    put_classes(a, r.cls);
+    return r.tile == T2222 ? launch_igemm<2, 2, 2, 2, 1, true>(a, s) : launch_igemm<4, 1, 1, 2, 1, true>(a, s);
+  }
+  if (r.fam == Fam::Tconv) {   // conv2x's temporal layers: taps staged once, weights resident in LDS
+    AVID_REQUIRE(!(MODE == 0 && has_out_affine(a) && a.stats), AVID_E_UNSUPPORTED,
+                 "conv_fwd_out: BatchNorm partial sums of a tensor that is not written");
+    ConvArgs k = a;
+    k.stats = (MODE == 0 || a.bnb_x) ? a.stats : nullptr;
+    k.stats_rows = r.stats_rows;       // (the rows avid_conv_fwd_stats_rows / avid_conv_dgrad_bn_rows promised: the kernel zero-fills beyond its own)
+    return launch_tconv<MODE>(k, r.grid, s);
+  }
+  // Everything else dense goes to the persistent kernel (whole rounds + K-split tail in one launch).
+  AVID_REQUIRE(r.fam == Fam::PkDense, AVID_E_UNSUPPORTED, "conv: no implicit-GEMM kernel takes this route");
+  AVID_REQUIRE(!a.in_scale, AVID_E_UNSUPPORTED,
+               "conv_fwd_in: this layer does not run on a kernel that applies the input's BatchNorm (avid_conv_takes_in_affine)");
+  AVID_REQUIRE(!(MODE == 0 && has_out_affine(a)), AVID_E_UNSUPPORTED,
+               "conv_fwd_out: this layer does not run on a kernel that applies the output's BatchNorm (avid_conv_takes_out_affine)");
+  AVID_REQUIRE(!(r.pk_starved && a.stats), AVID_E_BADARG, "conv: BatchNorm partials need the planned workspace");
+  const PkPlan& pk = r.pk;
+  ConvArgs k = a;
+  k.mt2_begin = 0;
+  k.mt2_count = 0;
+  k.nsplit = 1;
+  k.pk_full = pk.full;
+  k.pk_tail_units = pk.tail_units;
+  k.pk_f = pk.f;
+  k.pk_kps = pk.kps;
+  k.pk_rot = pk.rot;
+  k.pk_paired = pk.paired ? 1 : 0;
+  k.pk_ws = r.pk_ws;
+  k.stats = (MODE == 0 || a.bnb_x) ? a.stats : nullptr;
+  k.part = static_cast<float*>(ws);
+  k.part_row_begin = (int)pk.tail_row0;
+  magic_for(k.Wd, k.mgW, k.shW);
+  magic_for(k.Hd, k.mgH, k.shH);
+  magic_for(k.Td, k.mgT, k.shT);
+  int rc;
+  switch (r.tile) {
+    case T4114: rc = launch_pk<4, 1, 1, 4, MODE>(k, pk.grid, s); break;
+    case T2222: rc = launch_pk<2, 2, 2, 2, MODE>(k, pk.grid, s); break;
+    default: rc = launch_pk<4, 1, 1, 2, MODE>(k, pk.grid, s); break;
+  }
+  if (rc || pk.f == 1) return rc;
+  const long long rows = a.M - pk.tail_row0, n4 = rows * a.Cd / 4, off = pk.tail_row0 * a.Cd;
+  if (MODE == 1 && a.bnb_x && a.stats) {   // the tail rows' BatchNorm-backward partials come out of the reduce
+    ScopedTimer t(s, "splitk_reduce_bnb_kernel", 0.0, 4.0 * rows * a.Cd * (pk.f + 2 + (a.addend ? 1 : 0)));
+    const int rpb = stats_rpb(rows, a.Cd);
+    hipLaunchKernelGGL(splitk_reduce_bnb_kernel, dim3((unsigned)ceil_div(rows, rpb)), dim3(256), 0, s, k.part,
+                       a.dst + off, a.addend ? a.addend + off : nullptr, rows, a.Cd, pk.f, rpb, a.bnb_x + off,
+                       a.bnb_scale, a.bnb_shift, a.bnb_mean, a.bnb_invstd, a.bnb_relu,
+                       a.stats + (long long)pk.grid * 2 * a.Cd);
+    return check_launch("splitk_reduce_bnb");
+  }
+  if (MODE == 0 && a.stats) {   // the tail rows' BatchNorm partials come out of the reduce
+    ScopedTimer t(s, "splitk_reduce_stats_kernel", 0.0, 4.0 * rows * a.Cd * (pk.f + 1 + (a.addend ? 1 : 0)));
+    const int rpb = stats_rpb(rows, a.Cd);
+    hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3((unsigned)ceil_div(rows, rpb)), dim3(256), 0, s, k.part,
+                       a.dst + off, a.addend ? a.addend + off : nullptr, rows, a.Cd, pk.f, rpb,
+                       a.stats + (long long)pk.grid * 2 * a.Cd);
+    return check_launch("splitk_reduce_stats");
+  }
+  long long grid = ceil_div(n4, 256);
+  if (grid > 2048) grid = 2048;
+  ScopedTimer t(s, "splitk_reduce_kernel", 0.0, 4.0 * rows * a.Cd * (pk.f + 1 + (a.addend ? 1 : 0)));
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, s, k.part, a.dst + off,
+                     a.addend ? a.addend + off : nullptr, a.bias, n4, a.Cd / 4, pk.f, a.relu);
+  return check_launch("splitk_reduce");
+}
+
+// C[M][N] = A[M][K] . Bq[N][K]^T, optionally combined with Cin by min / max — the similarity GEMMs of
+// the CMA search run on the same MFMA kernel as a 1x1x1 convolution over M "pixels".
+int sim_gemm_nt(const float* A, const float* Bq, float* Cout_, const float* Cin, int op, long long M, int N, int K,
+                hipStream_t s) {
+  AVID_REQUIRE(N % 64 == 0 && K % 32 == 0 && M > 0 && M < (1ll << 31), AVID_E_UNSUPPORTED,
+               "sim_gemm: need N %% 64 == 0, K %% 32 == 0 (N=%d K=%d)", N, K);
+  ConvArgs a{};
+  a.kt = a.kh = a.kw = 1; a.st = a.sh = a.sw = 1;
+  a.B = 1; a.Ts = 1; a.Hs = 1; a.Ws = (int)M; a.Cs = K;
+  a.Td = 1; a.Hd = 1; a.Wd = (int)M; a.Cd = N;
+  a.M = (int)M;
+  a.src = A; a.wk = Bq; a.addend = Cin; a.dst = Cout_;
+  a.w_row = K; a.w_nrec = (int)((long long)N * K * 4);
+  a.epi_op = op;
+  a.nsplit = 1; a.ksteps_per_split = 1 << 30; a.ncls = 1;
+  a.mt2_count = (int)((((long long)M + 127) / 128 + 1) / 2);
+  a.add_s[0] = a.add_s[1] = a.add_s[2] = 1;
+  // persistent kernel, no K-split (K = 128: 4 k-tiles per tile, thousands of tiles): 54 -> ~90 TFLOP/s
+  ConvCall c;
+  c.epilogue = op != 0;
+  c.addend = Cin != nullptr;
+  ConvRoute r;
+  r.pk = plan_pk(M, N, K / BK, 0);
+  route_dense(r, nullptr, 0, c, M, N, K / BK, K / BK, false, 0);
+  return dispatch_igemm<0>(a, r, nullptr, s);
+}
+
+}  // namespace avid
+
+using namespace avid;
+
+// ---- the queries: a field of the route of the call the Python layer will make
+static ConvRoute planned_route(const avid_conv_desc* d, int which) { return conv_route(d, which, ConvCall::planned()); }
+
+extern "C" long long avid_debug_presplit_launches(void) { return g_presplit_launches.load(std::memory_order_relaxed); }
+
+extern "C" int avid_tconv_configure(int mode) {
+  g_tconv_mode.store((mode >= 0 && mode <= 2) ? mode : -1, std::memory_order_relaxed);
+  return tconv_mode();
+}
+
+// Does this layer's forward (which 0) / input gradient (1) take its weights pre-split (avid_wt_desc mode 5 / 6) as `u`?
+extern "C" int avid_conv_uses_split(const avid_conv_desc* d, int which) {
+  if (!d || validate(d) || which < 0 || which > 1) return 0;
+  return planned_route(d, which).presplit ? 1 : 0;
+}
+
+extern "C" size_t avid_conv_split_bytes(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return (size_t)6 * d->Cout * d->kt * d->kh * d->kw * d->Cin;
+}
+
+// ConvArgs::wsp for an operand of N rows x (taps x C) pre-split into chunks, the first dt0 temporal taps skipped
+static void set_split_operand(ConvArgs& a, const void* planes, int N, int C, int ntaps_full, int khw, int dt0) {
+  const int kstep = (N / 64) * PK_BCH;
+  const long long off = (long long)dt0 * khw * (C / BK) * kstep, total = (long long)ntaps_full * (C / BK) * kstep;
+  a.wsp = static_cast<const char*>(planes) + off;
+  a.wsp_nrec = (int)(total - off);
+  a.wsp_kstep = kstep;
+}
+
+extern "C" size_t avid_conv_fwd_workspace_bytes(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return planned_route(d, 0).ws_bytes;
+}
+
+extern "C" int avid_conv_fwd_stats_rows(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return planned_route(d, 0).stats_rows;
+}
+
+// AVID_IN_AFFINE (default 1): 0 = no layer offers to apply its input's BatchNorm (every BatchNorm writes its output)
+static bool in_affine_on() { static const bool v = env_flag(getenv("AVID_IN_AFFINE"), true); return v; }
+
+// both readers of the layer's input have to apply the map: the forward (tconv64_kernel) and the weight gradient (twgrad64_kernel:
+// never a layer of a grouped weight gradient, avid_conv_wgrad_groupable, whose kernel reads x as it is)
+extern "C" int avid_conv_takes_in_affine(const avid_conv_desc* d) {
+  if (!d || validate(d) || !in_affine_on()) return 0;
+  return planned_route(d, 0).fam == Fam::Tconv && planned_route(d, 2).fam == Fam::Twgrad && !avid_conv_wgrad_groupable(d) ? 1 : 0;
+}
+
+extern "C" long long avid_debug_in_affine_launches(int fused) { return g_tconv_launches[fused ? 1 : 0].load(std::memory_order_relaxed); }
+
+// the layers whose forward can apply the eval-mode BatchNorm (+ReLU) of their OUTPUT in the epilogue: exactly those whose
+// forward runs on tconv64_kernel, given their pre-split weights (inference has no weight gradient to agree with)
+extern "C" int avid_conv_takes_out_affine(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return planned_route(d, 0).fam == Fam::Tconv ? 1 : 0;
+}
+
+extern "C" long long avid_debug_out_affine_launches(void) { return g_tconv_out_launches.load(std::memory_order_relaxed); }
+
+extern "C" int avid_conv_fwd(const avid_conv_desc* d, const float* x, const float* w, const float* u, const float* addend,
+                             const float* bias, int relu, float* y, float* bn_partials, void* ws, size_t ws_bytes,
+                             avid_stream_t stream) {
+  return avid_conv_fwd_in(d, x, nullptr, w, u, addend, bias, relu, y, bn_partials, ws, ws_bytes, stream);
+}
+
+extern "C" int avid_conv_fwd_in(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
+                                const float* addend, const float* bias, int relu, float* y, float* bn_partials, void* ws,
+                                size_t ws_bytes, avid_stream_t stream) {
+  return avid_conv_fwd_out(d, x, in, w, u, addend, bias, relu, nullptr, y, bn_partials, ws, ws_bytes, stream);
+}
+
+extern "C" int avid_conv_fwd_out(const avid_conv_desc* d, const float* x, const avid_in_affine* in, const float* w, const float* u,
+                                 const float* addend, const float* bias, int relu, const avid_out_affine* out, float* y,
+                                 float* bn_partials, void* ws, size_t ws_bytes, avid_stream_t stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  AVID_REQUIRE(x && w && y, AVID_E_BADARG, "conv_fwd: null pointer");
+  if (out) {
+    AVID_REQUIRE(out->scale && out->shift, AVID_E_BADARG, "conv_fwd_out: null scale / shift");
+    AVID_REQUIRE(avid_conv_takes_out_affine(d) && u, AVID_E_UNSUPPORTED,
+                 "conv_fwd_out: this layer does not apply its output's BatchNorm (avid_conv_takes_out_affine; needs its pre-split weights)");
+    AVID_REQUIRE(!bias && !relu && !bn_partials, AVID_E_UNSUPPORTED,
+                 "conv_fwd_out: no bias, no ReLU in front of the BatchNorm and no BatchNorm partial sums (the un-normalised tensor is not written)");
+  }
+  if (in) {
+    AVID_REQUIRE(in->scale && in->shift, AVID_E_BADARG, "conv_fwd_in: null scale / shift");
+    AVID_REQUIRE(avid_conv_takes_in_affine(d) && u, AVID_E_UNSUPPORTED,
+                 "conv_fwd_in: this layer does not apply its input's BatchNorm (avid_conv_takes_in_affine; needs its pre-split weights)");
+  }
+  ConvCall c;
+  c.u = u != nullptr;
+  c.ws_bytes = ws ? ws_bytes : 0;
+  c.epilogue = bias || relu;
+  c.addend = addend != nullptr;
+  c.stats = bn_partials != nullptr;
+  c.in_affine = in != nullptr;
+  c.out_affine = out != nullptr;
+  const ConvRoute r = conv_route(d, 0, c);
+  if (r.fam == Fam::StemFwd) return stem_fwd(d, x, w, y, bn_partials, ws, (hipStream_t)stream);
+  // (avid_conv_fwd_stats_rows promised the Winograd kernel's rows: without its workspace the partials would not match)
+  AVID_REQUIRE(!bn_partials || !r.wino_starved, AVID_E_BADARG,
+               "conv_fwd: BatchNorm partials of this layer need the planned workspace (avid_conv_fwd_workspace_bytes)");
+  if (r.fam == Fam::Wino) return wino_conv(d, 0, x, w, u, y, addend, bn_partials, nullptr, ws, (hipStream_t)stream);
+  const Trim& tr = r.tr;
+  ConvArgs a{};
+  fill_common(a, &tr.d);
+  a.src = x; a.addend = addend; a.bias = bias; a.dst = y;
+  {   // weights: the live temporal taps of every [kt][kh][kw][Cin] row
+    const long long tapsz = (long long)d->kh * d->kw * d->Cin, off = tr.dt0 * tapsz;
+    a.wk = w + off;
+    a.w_row = (int)(tr.kt_full * tapsz);
+    a.w_nrec = (int)(((long long)d->Cout * a.w_row - off) * 4);
+  }
+  if (r.presplit) set_split_operand(a, u, d->Cout, d->Cin, d->kt * d->kh * d->kw, d->kh * d->kw, tr.dt0);
+  a.Ts = d->Ti; a.Hs = d->Hi; a.Ws = d->Wi; a.Cs = d->Cin;
+  a.Td = d->To; a.Hd = d->Ho; a.Wd = d->Wo; a.Cd = d->Cout;
+  a.M = d->B * d->To * d->Ho * d->Wo;
+  a.mode = 0;
+  a.relu = relu;
+  if (in) { a.in_scale = in->scale; a.in_shift = in->shift; a.in_relu = in->relu; }
+  if (out) { a.bnb_scale = out->scale; a.bnb_shift = out->shift; a.bnb_relu = out->relu; }   // (has_out_affine)
+  fill_src_strides(d, a.ssB, a.ssT, a.ssH, a.ssW, a.ssC);
+  if (bn_partials) {
+    AVID_REQUIRE(r.fam != Fam::Gather, AVID_E_BADARG, "conv_fwd: BatchNorm partials of a stem need its workspace (and no addend / bias / ReLU)");
+    AVID_REQUIRE(!bias && !relu && r.stats_rows > 0, AVID_E_UNSUPPORTED,
+                 "conv_fwd: BatchNorm partials need the persistent kernel, no bias and no ReLU");
+    a.stats = bn_partials;
+  }
+  return r.fam == Fam::Gather ? launch_gather(a, r.tile, (hipStream_t)stream) : dispatch_igemm<0>(a, r, ws, (hipStream_t)stream);
+}
+
+extern "C" size_t avid_conv_dgrad_workspace_bytes(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return planned_route(d, 1).ws_bytes;
+}
+
+extern "C" int avid_weight_transpose_batched(int n, const avid_wt_desc* descs_dev, int64_t max_elems,
+                                             avid_stream_t stream) {
+  AVID_REQUIRE(n > 0 && descs_dev && max_elems > 0, AVID_E_BADARG, "weight_transpose_batched: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(s, "weight_transpose_batched_kernel", 0.0, 0.0);
+  long long gx = ceil_div(max_elems, 1024);   // 32 x 32 tiles of the largest tensor, capped: blocks stride over tiles
+  if (gx > 256) gx = 256;
+  hipLaunchKernelGGL(weight_transpose_batched_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, descs_dev);
+  return check_launch("weight_transpose_batched");
+}
+
+extern "C" int avid_weight_transform(const avid_wt_desc* desc, avid_stream_t stream) {
+  AVID_REQUIRE(desc && desc->w && desc->wt && desc->Cout > 0 && desc->Cin > 0 && desc->ntaps > 0 && desc->mode >= 0 && desc->mode <= 6,
+               AVID_E_BADARG, "weight_transform: bad descriptor");
+  AVID_REQUIRE(desc->mode < 5 || (desc->mode == 5 ? desc->Cout % 64 == 0 && desc->Cin % 32 == 0 : desc->Cin % 64 == 0 && desc->Cout % 32 == 0),
+               AVID_E_UNSUPPORTED, "weight_transform: mode %d needs 64 | rows and 32 | channels", desc->mode);
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(s, "weight_transform_kernel", 0.0, 0.0);
+  long long gx = ceil_div((long long)desc->Cout * desc->ntaps * desc->Cin, 1024);
+  if (gx > 256) gx = 256;
+  hipLaunchKernelGGL(weight_transform_kernel, dim3((unsigned)gx), dim3(256), 0, s, *desc);
+  return check_launch("weight_transform");
+}
+
+// rows of BatchNorm-backward partial sums a dgrad of this layer writes (0: this layer cannot)
+extern "C" int avid_conv_dgrad_bn_rows(const avid_conv_desc* d) {
+  if (!d || validate(d)) return 0;
+  return planned_route(d, 1).stats_rows;
+}
+
+extern "C" int avid_conv_dgrad(const avid_conv_desc* d, const float* dy, const float* w, const float* wt_in,
+                               const float* u, const float* addend, const int32_t* addend_stride, float* dx, const avid_bn_bwd_fuse* bn,
+                               void* ws, size_t ws_bytes, avid_stream_t stream) {
+  int rc = validate(d);
+  if (rc) return rc;
+  ConvCall c;
+  c.u = u != nullptr;
+  c.ws_bytes = ws ? ws_bytes : 0;
+  c.addend = addend != nullptr;
+  c.stats = bn != nullptr;
+  if (addend && addend_stride)
+    for (int x = 0; x < 3; ++x) c.compact_addend |= addend_stride[x] == 2;
+  const ConvRoute r = conv_route(d, 1, c);
+  if (d->x_channel_first) {                    // the stems: dx channel-first like x, straight from w, no workspace
+    AVID_REQUIRE(r.fam == Fam::StemDgrad, AVID_E_UNSUPPORTED,
+                 "conv_dgrad: the only channel-first layers with an input gradient are the (3,7,7) / (1,7,7) stride-(1,2,2) stems");
+    AVID_REQUIRE(dy && w && dx, AVID_E_BADARG, "conv_dgrad: null pointer");
+    AVID_REQUIRE(!wt_in && !u && !addend && !addend_stride && !bn, AVID_E_BADARG,
+                 "conv_dgrad: a channel-first stem takes no wt / u / addend / addend_stride / bn");
+    return stem_dgrad(d, dy, w, dx, (hipStream_t)stream);
+  }
+  AVID_REQUIRE(dy && w && dx && ws, AVID_E_BADARG, "conv_dgrad: null pointer");
+  if (addend && addend_stride) {
+    for (int x = 0; x < 3; ++x)
+      AVID_REQUIRE(addend_stride[x] == 1 || addend_stride[x] == 2, AVID_E_UNSUPPORTED, "conv_dgrad: addend strides must be 1 or 2");
+    AVID_REQUIRE(!c.compact_addend || r.fam == Fam::PkStrided, AVID_E_UNSUPPORTED,
+                 "conv_dgrad: a compact addend needs a strided layer on the persistent kernel");
+  }
+  if (bn) {
+    AVID_REQUIRE(bn->x && bn->scale && bn->shift && bn->mean && bn->invstd && bn->partials, AVID_E_BADARG,
+                 "conv_dgrad: incomplete BatchNorm descriptor");
+    AVID_REQUIRE(r.stats_rows > 0, AVID_E_UNSUPPORTED,
+                 "conv_dgrad: this layer cannot produce BatchNorm-backward partial sums (avid_conv_dgrad_bn_rows == 0)");
+    AVID_REQUIRE(ws_bytes >= r.ws_bytes, AVID_E_BADARG, "conv_dgrad: BatchNorm partials need the planned workspace");
+  }
+  AVID_REQUIRE(!d->x_channel_first && d->Cin % 64 == 0 && d->Cout % 32 == 0, AVID_E_UNSUPPORTED,
+               "conv_dgrad: needs channels-last x, Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%d Cout=%d)", d->Cin,
+               d->Cout);
+  AVID_REQUIRE(d->st <= 2 && d->sh <= 2 && d->sw <= 2, AVID_E_UNSUPPORTED, "conv_dgrad: stride > 2");
+  AVID_REQUIRE(ws_bytes >= dgrad_wt_bytes(d), AVID_E_BADARG, "conv_dgrad: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  if (r.fam == Fam::CompactScatter) {          // the compact descriptor takes a route of its own
+    const avid_conv_desc cd = dgrad_compact_desc(d);
+    float* compact = static_cast<float*>(ws);
+    const size_t cb = dgrad_compact_bytes(d);
+    rc = avid_conv_dgrad(&cd, dy, w, wt_in, u, nullptr, nullptr, compact, nullptr, static_cast<char*>(ws) + cb, ws_bytes - cb, stream);
+    if (rc) return rc;
+    const long long n4 = (long long)d->B * d->Ti * d->Hi * d->Wi * (d->Cin / 4);
+    long long grid = ceil_div(n4, 256 * 4);
+    if (grid > 4096) grid = 4096;
+    ScopedTimer t(s, "dx_scatter_strided_kernel", 0.0, 16.0 * n4 * (1 + (addend ? 1 : 0)) + 16.0 * n4 / (d->st * d->sh * d->sw));
+    hipLaunchKernelGGL(dx_scatter_strided_kernel, dim3((unsigned)grid), dim3(256), 0, s, compact, addend, dx, n4, d->Cin / 4, d->Ti,
+                       d->Hi, d->Wi, d->To, d->Ho, d->Wo, d->st, d->sh, d->sw);
+    return check_launch("dx_scatter_strided");
+  }
+  if (r.fam == Fam::Wino) return wino_conv(d, 1, dy, w, u, dx, addend, nullptr, bn, ws, s);   // (u: this layer's pre-transformed weights)
+  const int ntaps = d->kt * d->kh * d->kw;
+  const float* wt = wt_in;
+  const bool split = r.presplit;                       // (u: this layer's pre-split transposed weights; wt is not read)
+  if (split) wt = w;
+  if (!wt) {
+    float* wt_ws = static_cast<float*>(ws);
+    const long long nw = (long long)d->Cout * ntaps * d->Cin;
+    {
+      ScopedTimer t(s, "weight_transpose_kernel", 0.0, 8.0 * nw);
+      hipLaunchKernelGGL(weight_transpose_kernel, dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, s, w, wt_ws, d->Cout,
+                         ntaps, d->Cin);
+    }
+    rc = check_launch("weight_transpose");
+    if (rc) return rc;
+    wt = wt_ws;
+  }
+  const Trim& tr = r.tr;
+  ConvArgs a{};
+  fill_common(a, &tr.d);
+  a.src = dy; a.addend = addend; a.bias = nullptr; a.dst = dx;
+  {   // transposed weights [Cin][kt][kh][kw][Cout]: the live temporal taps of every row
+    const long long tapsz = (long long)d->kh * d->kw * d->Cout, off = tr.dt0 * tapsz;
+    a.wk = wt + off;
+    a.w_row = (int)(tr.kt_full * tapsz);
+    a.w_nrec = (int)(((long long)d->Cin * a.w_row - off) * 4);
+  }
+  if (split) set_split_operand(a, u, d->Cin, d->Cout, ntaps, d->kh * d->kw, tr.dt0);
+  a.Ts = d->To; a.Hs = d->Ho; a.Ws = d->Wo; a.Cs = d->Cout;
+  a.Td = d->Ti; a.Hd = d->Hi; a.Wd = d->Wi; a.Cd = d->Cin;
+  a.M = d->B * d->Ti * d->Hi * d->Wi;
+  a.mode = 1;
+  a.relu = 0;
+  a.ssB = a.ssT = a.ssH = a.ssW = a.ssC = 0;
+  if (c.compact_addend) {
+    const int D[3] = {d->Ti, d->Hi, d->Wi};
+    for (int x = 0; x < 3; ++x) {
+      a.add_s[x] = addend_stride[x];
+      a.add_n[x] = (D[x] + addend_stride[x] - 1) / addend_stride[x];
+    }
+  }
+  if (bn) {
+    a.bnb_x = bn->x; a.bnb_scale = bn->scale; a.bnb_shift = bn->shift; a.bnb_mean = bn->mean;
+    a.bnb_invstd = bn->invstd; a.bnb_relu = bn->relu;
+    a.stats = bn->partials;
+  }
+  return dispatch_igemm<1>(a, r, static_cast<char*>(ws) + dgrad_wt_bytes(d), s);
+}
+
 // kernel arguments of one layer (d: the layer with its dead temporal taps already trimmed)
 static void fill_wgrad_args(WgradArgs& a, const avid_conv_desc* d, const float* x, const float* dy, float* out,
                             const WgradPlan& pl) {
@@ -4318,31 +4385,22 @@ static void fill_wgrad_args(WgradArgs& a, const avid_conv_desc* d, const float* 
   fill_src_strides(d, a.ssB, a.ssT, a.ssH, a.ssW, a.ssC);
 }
 
-// ---- twgrad64_kernel: the layers it takes (the descriptor-level twin of tconv_takes; same switch: avid_tconv_configure)
-static bool twgrad_layer(const avid_conv_desc* d) {
-  return PK_SPLIT && wgrad_split() && !d->x_channel_first && d->kt == 3 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 &&
-         d->sw == 1 && d->pt == 1 && d->ph == 0 && d->pw == 0 && d->Cin == 64 && d->Cout == 64 && d->Ti == TC_T && d->To == TC_T &&
-         (long long)d->B * d->Ti * d->Hi * d->Wi * 256 < (1ll << 31);
-}
-static int twgrad_grid(const avid_conv_desc* d) {
-  return balanced_grid(((long long)d->B * d->Hi * d->Wi + TWG_P - 1) / TWG_P);
-}
-static size_t twgrad_ws_bytes(const avid_conv_desc* d) { return sizeof(float) * (size_t)twgrad_grid(d) * 64 * 3 * 64; }
-static bool twgrad_takes(const avid_conv_desc* d) {
-  if (!tconv_mode() || !(tconv_parts() & 4) || !twgrad_layer(d)) return false;
-  const long long ntiles = ((long long)d->B * d->Hi * d->Wi + TWG_P - 1) / TWG_P;
-  return tconv_mode() == 2 || ntiles >= 6ll * device_cus();
+template <int NB, int KC>
+static void launch_wgrad_tab(const WgradArgs& a, unsigned nwg, hipStream_t s) {
+  const size_t lds = sizeof(float) * 2 * 32 * (64 * NB + 4 + KC * WG_LD) + sizeof(uint2) * WG_TABC * 32;
+  static bool set = false;
+  if (!set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tab_kernel<NB, KC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tab_kernel<NB, KC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set = true;
+  }
+  if (wgrad_split()) hipLaunchKernelGGL((wgrad_tab_kernel<NB, KC, true>), dim3(nwg), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL((wgrad_tab_kernel<NB, KC>), dim3(nwg), dim3(256), lds, s, a);
 }
 
 extern "C" size_t avid_conv_wgrad_workspace_bytes(const avid_conv_desc* d) {
   if (!d || validate(d)) return 0;
-  const Trim tr = trim_taps(d);      // (a trimmed layer always goes through slabs: the reduce scatters them into dw)
-  WgradPlan pl = wgrad_plan(&tr.d);
-  size_t nb = sizeof(float) * (size_t)pl.nsplit * d->Cout * tr.d.kt * d->kh * d->kw * d->Cin;
-  if (stem_wgrad_supported(d) && stem_wgrad_ws_bytes(d) > nb) nb = stem_wgrad_ws_bytes(d);
-  if (wino_wgrad_supported(d) && wino_wgrad_ws_bytes(d) > nb) nb = wino_wgrad_ws_bytes(d);
-  if (twgrad_layer(d) && twgrad_ws_bytes(d) > nb) nb = twgrad_ws_bytes(d);
-  return nb;
+  return planned_route(d, 2).ws_bytes;
 }
 
 extern "C" int avid_conv_wgrad(const avid_conv_desc* d, const float* x, const float* dy, float* dw, void* ws,
@@ -4360,10 +4418,13 @@ extern "C" int avid_conv_wgrad_in(const avid_conv_desc* d, const float* x, const
     AVID_REQUIRE(avid_conv_takes_in_affine(d) && ws && ws_bytes >= twgrad_ws_bytes(d), AVID_E_UNSUPPORTED,
                  "conv_wgrad_in: this layer does not apply its input's BatchNorm (avid_conv_takes_in_affine; needs its workspace)");
   }
-  if (stem_wgrad_supported(d) && ws && ws_bytes >= stem_wgrad_ws_bytes(d))
-    return stem_wgrad(d, x, dy, dw, ws, (hipStream_t)stream);
-  if (wino_wgrad_supported(d) && ws && ws_bytes >= wino_wgrad_ws_bytes(d)) {
-    hipStream_t s = (hipStream_t)stream;
+  ConvCall c;
+  c.ws_bytes = ws ? ws_bytes : 0;
+  c.in_affine = in != nullptr;
+  const ConvRoute r = conv_route(d, 2, c);
+  hipStream_t s = (hipStream_t)stream;
+  if (r.fam == Fam::StemWgrad) return stem_wgrad(d, x, dy, dw, ws, s);
+  if (r.fam == Fam::WinoWgrad) {
     int nsplit = 1;
     rc = wino_wgrad(d, x, dy, dw, ws, &nsplit, s);
     if (rc || nsplit == 1) return rc;
@@ -4373,14 +4434,13 @@ extern "C" int avid_conv_wgrad_in(const avid_conv_desc* d, const float* x, const
                        static_cast<const float*>(ws), dw, n, nsplit);
     return check_launch("wgrad_reduce");
   }
-  if (twgrad_takes(d) && ws && ws_bytes >= twgrad_ws_bytes(d)) {   // conv2x's temporal layers: the taps share their split fragments
-    hipStream_t s = (hipStream_t)stream;
+  if (r.fam == Fam::Twgrad) {
     TwgradArgs a{};
     a.x = x; a.dy = dy; a.part = static_cast<float*>(ws);
     a.B = d->B; a.HW = d->Hi * d->Wi;
     if (in) { a.in_scale = in->scale; a.in_shift = in->shift; a.in_relu = in->relu; }
     magic_for(a.HW, a.mg, a.sh);
-    const int grid = twgrad_grid(d);
+    const int grid = r.grid;
     static bool set = false;
     if (!set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(twgrad64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TWG_LDS);
@@ -4401,18 +4461,13 @@ extern "C" int avid_conv_wgrad_in(const avid_conv_desc* d, const float* x, const
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(n, 128)), dim3(256), 0, s, static_cast<const float*>(ws), dw, n, grid);
     return check_launch("wgrad_reduce");
   }
-  Trim tr = trim_taps(d);
-  if (tr.on && !(ws && ws_bytes >= avid_conv_wgrad_workspace_bytes(d))) tr = Trim{*d, 0, d->kt, false};   // no scratch
-  const avid_conv_desc* dfull = d;
+  const Trim& tr = r.tr;
+  const WgradPlan& pl = r.wp;
   d = &tr.d;                         // from here on: the (possibly trimmed) layer
-  WgradPlan pl = wgrad_plan(d);
-  AVID_REQUIRE(pl.nsplit == 1 || (ws && ws_bytes >= avid_conv_wgrad_workspace_bytes(dfull)), AVID_E_BADARG,
-               "conv_wgrad: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
+  AVID_REQUIRE(pl.nsplit == 1 || (ws && ws_bytes >= r.ws_bytes), AVID_E_BADARG, "conv_wgrad: workspace too small");
   WgradArgs a;
   fill_wgrad_args(a, d, x, dy, (pl.nsplit == 1 && !tr.on) ? dw : static_cast<float*>(ws), pl);
   dim3 grid((unsigned)(pl.kt_tiles * pl.n_tiles), (unsigned)pl.nsplit);
-  dim3 grid_pp((unsigned)(pl.kt_tiles * pl.n_tiles), (unsigned)((pl.nsplit + 1) / 2));   // two splits per workgroup
   {
     const double K = (double)a.kt * a.kh * a.kw * a.Cs;
     const double srcpix = (double)a.B * a.Ts * a.Hs * a.Ws;
@@ -4422,29 +4477,9 @@ extern "C" int avid_conv_wgrad_in(const avid_conv_desc* d, const float* x, const
       const size_t lds = sizeof(float) * 4 * 32 * WG_LD + sizeof(int2) * 64;
       hipLaunchKernelGGL(wgrad_gather_kernel, grid, dim3(256), lds, s, a);
     } else if (pl.NB == 1) {
-      const size_t lds = sizeof(float) * 2 * 32 * (64 * 1 + 4 + 3 * WG_LD) + sizeof(uint2) * WG_TABC * 32;
-      static bool set = false;
-      if (!set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tab_kernel<1, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tab_kernel<1, 3, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        set = true;
-      }
-      if (wgrad_split()) hipLaunchKernelGGL((wgrad_tab_kernel<1, 3, true>), dim3(grid.x * grid.y), dim3(256), lds, s, a);
-      else hipLaunchKernelGGL((wgrad_tab_kernel<1, 3>), dim3(grid.x * grid.y), dim3(256), lds, s, a);
+      launch_wgrad_tab<1, 3>(a, grid.x * grid.y, s);
     } else {
-      const size_t lds = sizeof(float) * 2 * 32 * (64 * 2 + 4 + 2 * WG_LD) + sizeof(uint2) * WG_TABC * 32;
-      static bool set = false;
-      if (!set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tab_kernel<2, 2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tab_kernel<2, 2, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        set = true;
-      }
-      if (wgrad_split()) hipLaunchKernelGGL((wgrad_tab_kernel<2, 2, true>), dim3(grid.x * grid.y), dim3(256), lds, s, a);
-      else hipLaunchKernelGGL((wgrad_tab_kernel<2, 2>), dim3(grid.x * grid.y), dim3(256), lds, s, a);
+      launch_wgrad_tab<2, 2>(a, grid.x * grid.y, s);
     }
   }
   rc = check_launch("wgrad");
@@ -4470,10 +4505,8 @@ extern "C" int avid_conv_wgrad_in(const avid_conv_desc* d, const float* x, const
 // ---- grouped weight gradients (wgrad_group_kernel)
 extern "C" int avid_conv_wgrad_groupable(const avid_conv_desc* d) {
   if (!d || validate(d)) return 0;
-  if (stem_wgrad_supported(d) || wino_wgrad_supported(d)) return 0;
-  const Trim tr = trim_taps(d);
-  const WgradPlan pl = wgrad_plan(&tr.d);
-  return pl.vec && pl.NB == 2 && pl.KC == 2;
+  const ConvRoute r = planned_route(d, 2);
+  return r.fam == Fam::TabWgrad && r.wp.NB == 2 && r.wp.KC == 2;
 }
 
 struct GroupLayer {
@@ -4638,83 +4671,43 @@ extern "C" int avid_conv_wgrad_group(int n, const avid_wgrad_item* items, void* 
 }
 
 extern "C" int avid_conv_uses_wino(const avid_conv_desc* d, int which) {
-  if (!d || validate(d)) return 0;
-  if (which == 2) return wino_wgrad_supported(d) ? 1 : 0;
-  return (which == 0 || which == 1) && wino_supported(d, which) ? wino_variant(d, which) : 0;
+  if (!d || validate(d) || which < 0 || which > 2) return 0;
+  const Fam fam = planned_route(d, which).fam;
+  if (which == 2) return fam == Fam::WinoWgrad ? 1 : 0;
+  return fam == Fam::Wino ? wino_variant(d, which) : 0;
 }
 
+// the planned route in words: the kernel's name with the template arguments a profile shows, and the plan
 extern "C" int avid_conv_kernel_name(const avid_conv_desc* d, int which, char* buf, int len) {
   int rc = validate(d);
   if (rc) return rc;
   AVID_REQUIRE(buf && len > 0 && which >= 0 && which <= 2, AVID_E_BADARG, "conv_kernel_name: bad argument");
-  const bool vec = (d->Cin % 32 == 0) && !d->x_channel_first;
-  const Trim tr = trim_taps(d);
-  const int ktl = tr.d.kt;           // live temporal taps
-  auto pk_name = [&](long long M, int Cd, int nk, int mode) {
-    const PkPlan pk = plan_pk(M, Cd, nk, mode);
-    static const char* kPk[] = {"2,2,2,2", "4,1,1,2", "4,2,2,2", "4,2,2,1", "2,1,2,2"};
-    // (the 128 x 128 tile of a layer that is handed its pre-split weights runs as four waves of 32 x 128 with the epilogues
-    //  convolution layers use — dispatch_igemm's `rows`; a caller that passes no table or a bias / ReLU epilogue gets <2,2,2,2>)
-    const char* tile = pk.tile == 0 && bs_rows() && conv_takes_split(d, mode) ? "4,1,1,4" : kPk[pk.tile];
-    const int cs = mode == 0 ? d->Cin : d->Cout;
-    const int ws = plan_pk_order(pk, M, Cd, nk, cs / BK, conv_takes_split(d, mode));
-    snprintf(buf, len, "igemm_pk_kernel<%s,%d> full=%d tail_units=%d f=%d%s", tile, mode, pk.full, pk.tail_units, pk.f,
-             ws ? " weight-stationary" : "");
-  };
-  // conv2x's temporal layers (given their pre-split weights): tconv64_kernel — the descriptor-level form of tconv_takes
-  const long long tc_tiles = ((long long)d->B * d->Hi * d->Wi + TC_P - 1) / TC_P;
-  const bool tc = tconv_layer(d, which);
-  if (tc) {
-    snprintf(buf, len, "tconv64_kernel<%d> grid=%d", which, balanced_grid(tc_tiles));
-    return AVID_OK;
-  }
-  if (which == 0) {
-    const long long M = (long long)d->B * d->To * d->Ho * d->Wo;
-    if (!vec) {
-      if (stem_fwd_supported(d))
-        snprintf(buf, len, stem_fwd_is_split(d) ? (stem_fwd_is_presplit(d) ? "stem_fwd3p_kernel<%d,%d>" : "stem_fwd3_kernel<%d,%d>")
-                                                : "stem_fwd_kernel<%d,%d>", d->Cin, d->kt);
-      else
-        snprintf(buf, len, "igemm_gather_kernel<%s>", ((M + 127) / 128) * (d->Cout / 64) >= 256 ? "4,1,1,2" : "2,2,1,1");
-    } else if (wino_supported(d, 0)) {
-      snprintf(buf, len, "wino_kernel<0> grid=%d", wino_grid(d, 0));
-    } else {
-      pk_name(M, d->Cout, ktl * d->kh * d->kw * (d->Cin / BK), 0);
-    }
-  } else if (which == 1) {
-    const long long M = (long long)d->B * d->Ti * d->Hi * d->Wi;
-    const bool strided = d->st > 1 || d->sh > 1 || d->sw > 1;
-    if (d->x_channel_first) {
-      AVID_REQUIRE(stem_dgrad_supported(d), AVID_E_UNSUPPORTED, "conv_kernel_name: this channel-first layer has no input gradient");
-      snprintf(buf, len, "stem_dgrad_kernel<%d,%d>", d->Cin, d->kt);
-    } else if (wino_supported(d, 1)) {
-      snprintf(buf, len, "wino_kernel<1> grid=%d", wino_grid(d, 1));
-    } else if (strided && dgrad_compactable(d)) {
-      snprintf(buf, len, "igemm_pk_kernel over the sub-sampled grid + dx_scatter_strided_kernel");
-    } else if (strided && strided_dgrad_leaves_pk(d)) {   // dispatch_igemm<1>'s second branch: the same class table, the same rule
-      ConvArgs a{};
-      fill_common(a, &tr.d);
-      a.Td = d->Ti; a.Hd = d->Hi; a.Wd = d->Wi; a.Cd = d->Cin;
-      build_classes(a, 128);
-      const bool wide = a.Cd % 128 == 0 && (long long)a.cls_ptiles_total * (a.Cd / 128) >= 2 * 256;
-      snprintf(buf, len, "igemm_kernel<%s,1>s2 (stride-parity classes, dx >= 2 GiB)", wide ? "2,2,2,2" : "4,1,1,2");
-    } else if (strided) {
-      snprintf(buf, len, "igemm_pk_kernel<%s,1>s2 (stride-parity classes)", d->Cin % 128 == 0 && s2_wide() ? "2,2,2,2" : "4,1,1,2");
-    } else {
-      pk_name(M, d->Cin, ktl * d->kh * d->kw * (d->Cout / BK), 1);
-    }
-  } else {
-    WgradPlan pl = wgrad_plan(&tr.d);
-    if (twgrad_takes(d)) {
-      snprintf(buf, len, "twgrad64_kernel grid=%d", twgrad_grid(d));
-      return AVID_OK;
-    }
-    if (wino_wgrad_supported(d))
-      snprintf(buf, len, "wino_wgrad_kernel");
-    else if (!pl.vec)
-      snprintf(buf, len, stem_wgrad_supported(d) ? "stem_wgrad_kernel splits=%d" : "wgrad_gather_kernel splits=%d", pl.nsplit);
-    else
-      snprintf(buf, len, "wgrad_tab_kernel<%d,%d> splits=%d", pl.NB, pl.KC, pl.nsplit);
+  const ConvRoute r = planned_route(d, which);
+  const char* tile = kTileName[r.tile];
+  switch (r.fam) {
+    case Fam::Refused:
+      AVID_REQUIRE(!d->x_channel_first, AVID_E_UNSUPPORTED, "conv_kernel_name: this channel-first layer has no input gradient");
+      AVID_REQUIRE(false, AVID_E_UNSUPPORTED, "conv_kernel_name: this layer has no input gradient (Cin %% 64, Cout %% 32)");
+    case Fam::StemFwd:
+      snprintf(buf, len, stem_fwd_is_split(d) ? (stem_fwd_is_presplit(d) ? "stem_fwd3p_kernel<%d,%d>" : "stem_fwd3_kernel<%d,%d>")
+                                              : "stem_fwd_kernel<%d,%d>", d->Cin, d->kt);
+      break;
+    case Fam::Gather: snprintf(buf, len, "igemm_gather_kernel<%s>", tile); break;
+    case Fam::Wino: snprintf(buf, len, "wino_kernel<%d> grid=%d", which, r.grid); break;
+    case Fam::Tconv: snprintf(buf, len, "tconv64_kernel<%d> grid=%d", which, r.grid); break;
+    case Fam::PkDense:
+      snprintf(buf, len, "igemm_pk_kernel<%s,%d> full=%d tail_units=%d f=%d%s", tile, which, r.pk.full, r.pk.tail_units, r.pk.f,
+               r.pk_ws ? " weight-stationary" : "");
+      break;
+    case Fam::PkStrided: snprintf(buf, len, "igemm_pk_kernel<%s,1>s2 (stride-parity classes)", tile); break;
+    case Fam::IgemmStrided: snprintf(buf, len, "igemm_kernel<%s,1>s2 (stride-parity classes, dx >= 2 GiB)", tile); break;
+    case Fam::CompactScatter: snprintf(buf, len, "igemm_pk_kernel over the sub-sampled grid + dx_scatter_strided_kernel"); break;
+    case Fam::StemDgrad: snprintf(buf, len, "stem_dgrad_kernel<%d,%d>", d->Cin, d->kt); break;
+    case Fam::StemWgrad: snprintf(buf, len, "stem_wgrad_kernel splits=%d", r.wp.nsplit); break;
+    case Fam::WinoWgrad: snprintf(buf, len, "wino_wgrad_kernel"); break;
+    case Fam::Twgrad: snprintf(buf, len, "twgrad64_kernel grid=%d", r.grid); break;
+    case Fam::TabWgrad: snprintf(buf, len, "wgrad_tab_kernel<%d,%d> splits=%d", r.wp.NB, r.wp.KC, r.wp.nsplit); break;
+    case Fam::GatherWgrad: snprintf(buf, len, "wgrad_gather_kernel splits=%d", r.wp.nsplit); break;
   }
   return AVID_OK;
 }
