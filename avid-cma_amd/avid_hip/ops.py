@@ -1586,28 +1586,23 @@ def bank_update_pair(bank0, bank1, y, emb0, emb1, momentum0, momentum1):
 FUSED_CRITERION = os.environ.get("AVID_FUSED_CRITERION", "1") == "1"
 
 
-class _XModalFused(Function):
-    """The whole cross-modal criterion of a steady-state step in one kernel (``avid_xmodal_fused``): returns
-    (total loss, losses[4], v_hat, a_hat); the gradient of the total loss with respect to both raw embeddings is formed
-    in the forward pass (Z is a constant) and only scaled by the upstream gradient in backward."""
+class _FusedCriterion(Function):
+    """The criterion of a steady-state step in one kernel (``avid_xmodal_fused``, ``avid_cma_fused``, ``avid_crit_fused``: the
+    checked ``launch(v_emb, a_emb, hats, grads, losses)`` of the entry point): returns (total loss = losses[total_at],
+    losses[n_losses], hats = the normalised embeddings).  The gradient of the total loss with respect to both raw embeddings is
+    formed in the forward pass (Z is a constant) and only scaled by the upstream gradient in backward."""
 
     @staticmethod
-    def forward(ctx, v_emb, a_emb, y, idx, bank_v, bank_a, Z, inv_T, coeff, ws):
-        _need_cuda(v_emb, a_emb, y, idx, bank_v, bank_a, Z, ws)
-        v_emb, a_emb, y, idx = v_emb.contiguous(), a_emb.contiguous(), y.contiguous(), idx.contiguous()
+    def forward(ctx, v_emb, a_emb, n_losses, total_at, launch):
+        v_emb, a_emb = v_emb.contiguous(), a_emb.contiguous()
         bs, D = v_emb.shape
-        K = idx.shape[1]
-        if y.dtype != torch.int64 or idx.dtype != torch.int64 or not bank_v.is_contiguous() or not bank_a.is_contiguous():
-            raise AvidHipError("xmodal_fused: y / idx must be int64 and the banks contiguous")
         dev = v_emb.device
         hats = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
         grads = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
-        losses = torch.empty(4, dtype=torch.float32, device=dev)
-        lib.call("avid_xmodal_fused", bs, K, D, bank_v.shape[0], _p(v_emb), _p(a_emb), _p(y), _p(idx), _p(bank_v),
-                 _p(bank_a), float(inv_T), _p(Z), float(coeff), _p(hats[0]), _p(hats[1]), _p(losses), _p(grads[0]),
-                 _p(grads[1]), _p(ws), ws.numel(), DeviceErrors.get(dev).ptr(), _stream())
+        losses = torch.empty(n_losses, dtype=torch.float32, device=dev)
+        launch(v_emb, a_emb, hats, grads, losses)
         ctx.save_for_backward(grads)
-        total = losses[3]
+        total = losses[total_at]
         ctx.mark_non_differentiable(losses, hats)
         return total, losses, hats
 
@@ -1615,7 +1610,7 @@ class _XModalFused(Function):
     def backward(ctx, dtotal, _dl, _dh):
         (grads,) = ctx.saved_tensors
         g = grads * dtotal                      # one launch for both embeddings
-        return g[0], g[1], None, None, None, None, None, None, None, None
+        return g[0], g[1], None, None, None
 
 
 def xmodal_fused_workspace(device, bs, K):
@@ -1624,7 +1619,19 @@ def xmodal_fused_workspace(device, bs, K):
 
 
 def xmodal_fused(v_emb, a_emb, y, idx, bank_v, bank_a, Z, inv_T, coeff, ws):
-    return _XModalFused.apply(v_emb, a_emb, y, idx, bank_v, bank_a, Z, inv_T, coeff, ws)
+    """The whole cross-modal criterion: (total, losses[4] = (L_v2a, L_a2v, their mean, coeff * that), hats)."""
+    _need_cuda(v_emb, a_emb, y, idx, bank_v, bank_a, Z, ws)
+    y, idx = y.contiguous(), idx.contiguous()
+    bs, D = v_emb.shape
+    K = idx.shape[1]
+    if y.dtype != torch.int64 or idx.dtype != torch.int64 or not bank_v.is_contiguous() or not bank_a.is_contiguous():
+        raise AvidHipError("xmodal_fused: y / idx must be int64 and the banks contiguous")
+
+    def launch(v, a, hats, grads, losses):
+        lib.call("avid_xmodal_fused", bs, K, D, bank_v.shape[0], _p(v), _p(a), _p(y), _p(idx), _p(bank_v), _p(bank_a),
+                 float(inv_T), _p(Z), float(coeff), _p(hats[0]), _p(hats[1]), _p(losses), _p(grads[0]), _p(grads[1]), _p(ws),
+                 ws.numel(), DeviceErrors.get(v.device).ptr(), _stream())
+    return _FusedCriterion.apply(v_emb, a_emb, 4, 3, launch)
 
 
 def _infonce_args(v_hat, a_hat, row0, b, inv_T, weights, grad_scale, ws):
@@ -1717,44 +1724,25 @@ def infonce(v_hat, a_hat, row0=0, b=None, inv_T=1.0 / 0.07, weights=(0.5, 0.5), 
     return losses[0], losses, hits, None
 
 
-class _CMAFused(Function):
-    """The AVID+CMA criterion of a steady-state step (cross-modal instance + within-modal positive terms) in one kernel
-    (``avid_cma_fused``): returns (total loss, losses[8], hats); as ``_XModalFused`` the gradient with respect to both raw
-    embeddings is formed in the forward pass and only scaled in backward."""
-
-    @staticmethod
-    def forward(ctx, v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, coeff_inst, coeff_pos, ws):
-        _need_cuda(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, ws)
-        v_emb, a_emb, y, pos, idx = v_emb.contiguous(), a_emb.contiguous(), y.contiguous(), pos.contiguous(), idx.contiguous()
-        bs, D = v_emb.shape
-        P, K = pos.shape[1], idx.shape[1]
-        if any(t.dtype != torch.int64 for t in (y, pos, idx)) or not bank_v.is_contiguous() or not bank_a.is_contiguous():
-            raise AvidHipError("cma_fused: y / pos / idx must be int64 and the banks contiguous")
-        dev = v_emb.device
-        hats = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
-        grads = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
-        losses = torch.empty(8, dtype=torch.float32, device=dev)
-        lib.call("avid_cma_fused", bs, P, K, int(Kw), D, bank_v.shape[0], _p(v_emb), _p(a_emb), _p(y), _p(pos), _p(idx),
-                 _p(bank_v), _p(bank_a), float(inv_T), _p(Z), float(coeff_inst), float(coeff_pos), _p(hats[0]), _p(hats[1]),
-                 _p(losses), _p(grads[0]), _p(grads[1]), _p(ws), ws.numel(), DeviceErrors.get(dev).ptr(), _stream())
-        ctx.save_for_backward(grads)
-        total = losses[6]
-        ctx.mark_non_differentiable(losses, hats)
-        return total, losses, hats
-
-    @staticmethod
-    def backward(ctx, dtotal, _dl, _dh):
-        (grads,) = ctx.saved_tensors
-        g = grads * dtotal
-        return (g[0], g[1]) + (None,) * 11
-
-
 def cma_fused_workspace(device, bs, P, K):
     return torch.zeros(int(lib.raw("avid_cma_fused_workspace_bytes")(int(bs), int(P), int(K))), dtype=torch.uint8, device=device)
 
 
 def cma_fused(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, coeff_inst, coeff_pos, ws):
-    return _CMAFused.apply(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, coeff_inst, coeff_pos, ws)
+    """The AVID+CMA criterion with its stock term set (cross-modal instance + within-modal positive terms): (total, losses[8] =
+    (the four terms, the two group means, the total, unused), hats)."""
+    _need_cuda(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, ws)
+    y, pos, idx = y.contiguous(), pos.contiguous(), idx.contiguous()
+    bs, D = v_emb.shape
+    P, K = pos.shape[1], idx.shape[1]
+    if any(t.dtype != torch.int64 for t in (y, pos, idx)) or not bank_v.is_contiguous() or not bank_a.is_contiguous():
+        raise AvidHipError("cma_fused: y / pos / idx must be int64 and the banks contiguous")
+
+    def launch(v, a, hats, grads, losses):
+        lib.call("avid_cma_fused", bs, P, K, int(Kw), D, bank_v.shape[0], _p(v), _p(a), _p(y), _p(pos), _p(idx), _p(bank_v),
+                 _p(bank_a), float(inv_T), _p(Z), float(coeff_inst), float(coeff_pos), _p(hats[0]), _p(hats[1]), _p(losses),
+                 _p(grads[0]), _p(grads[1]), _p(ws), ws.numel(), DeviceErrors.get(v.device).ptr(), _stream())
+    return _FusedCriterion.apply(v_emb, a_emb, 8, 6, launch)
 
 
 CRIT_X_INST, CRIT_W_INST, CRIT_X_POS, CRIT_W_POS = lib.CRIT_X_INST, lib.CRIT_W_INST, lib.CRIT_X_POS, lib.CRIT_W_POS
@@ -1763,69 +1751,49 @@ CRIT_TERMS = ("inst-v2a", "inst-a2v", "inst-v2v", "inst-a2a", "pos-v2a", "pos-a2
 CRIT_GROUP_MEAN, CRIT_TOTAL = 8, 12
 
 
-class _CritFused(Function):
-    """Any term set of the AVID / AVID+CMA criterion of a steady-state step in one kernel (``avid_crit_fused``): returns
-    (total loss, losses[16], hats); as ``_CMAFused`` the gradient with respect to both raw embeddings is formed in the
-    forward pass and only scaled in backward.  ``pos`` is None (or [bs][0]) for a term set without positives."""
-
-    @staticmethod
-    def forward(ctx, v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, mask, coeffs, ws):
-        if pos is not None and pos.shape[1] == 0:
-            pos = None
-        _need_cuda(*[t for t in (v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, ws) if t is not None])
-        v_emb, a_emb, y, idx = v_emb.contiguous(), a_emb.contiguous(), y.contiguous(), idx.contiguous()
-        pos = None if pos is None else pos.contiguous()
-        mask, Kw, coeffs = int(mask), int(Kw), [float(c) for c in coeffs]
-        if v_emb.dim() != 2 or a_emb.shape != v_emb.shape or idx.dim() != 2 or y.shape[0] != v_emb.shape[0] \
-                or idx.shape[0] != v_emb.shape[0] or (pos is not None and (pos.dim() != 2 or pos.shape[0] != v_emb.shape[0])):
-            raise AvidHipError("crit_fused: v_emb / a_emb [bs][D], y [bs], pos [bs][P], idx [bs][K] disagree in shape")
-        bs, D = v_emb.shape
-        P, K = (0 if pos is None else pos.shape[1]), idx.shape[1]
-        if any(t.dtype != torch.int64 for t in (y, idx) + (() if pos is None else (pos,))) or not bank_v.is_contiguous() \
-                or not bank_a.is_contiguous():
-            raise AvidHipError("crit_fused: y / pos / idx must be int64 and the banks contiguous")
-        if any(t.dtype != torch.float32 for t in (v_emb, a_emb, bank_v, bank_a, Z)):
-            raise AvidHipError("crit_fused: embeddings, banks and Z must be float32")
-        if tuple(bank_v.shape) != tuple(bank_a.shape) or bank_v.dim() != 2 or bank_v.shape[1] != D:
-            raise AvidHipError(f"crit_fused: banks {tuple(bank_v.shape)} / {tuple(bank_a.shape)} do not fit embeddings of width {D}")
-        if not 1 <= mask <= 15:
-            raise AvidHipError(f"crit_fused: mask {mask} names no term")
-        if len(coeffs) != 4:
-            raise AvidHipError("crit_fused: four coefficients (X_INST, W_INST, X_POS, W_POS)")
-        if mask & (CRIT_X_POS | CRIT_W_POS) and P < 1:
-            raise AvidHipError("crit_fused: a positive-set term needs pos [bs][P >= 1]")
-        if not 1 <= Kw <= K:
-            raise AvidHipError(f"crit_fused: Kw={Kw} outside 1..K={K}")
-        dev = v_emb.device
-        hats = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
-        grads = torch.empty((2, bs, D), dtype=torch.float32, device=dev)
-        losses = torch.empty(16, dtype=torch.float32, device=dev)
-        a = lambda t: None if t is None else t.data_ptr()       # noqa: E731  (structure fields take the address itself)
-        d = lib.CritDesc(bs=bs, P=P, K=K, Kw=Kw, D=D, mask=mask, N=bank_v.shape[0], v_emb=a(v_emb), a_emb=a(a_emb), y=a(y),
-                         pos=a(pos), idx=a(idx), bank_v=a(bank_v), bank_a=a(bank_a), Z=a(Z), inv_T=float(inv_T),
-                         coeff=(C.c_float * 4)(*coeffs), v_hat=a(hats[0]), a_hat=a(hats[1]), losses=a(losses),
-                         dv=a(grads[0]), da=a(grads[1]))
-        lib.call("avid_crit_fused", C.byref(d), _p(ws), ws.numel(), DeviceErrors.get(dev).ptr(), _stream())
-        ctx.save_for_backward(grads)
-        total = losses[CRIT_TOTAL]
-        ctx.mark_non_differentiable(losses, hats)
-        return total, losses, hats
-
-    @staticmethod
-    def backward(ctx, dtotal, _dl, _dh):
-        (grads,) = ctx.saved_tensors
-        g = grads * dtotal
-        return (g[0], g[1]) + (None,) * 11
-
-
 def crit_fused_workspace(device, bs, P, K):
     """Zero-filled scratch of ``avid_crit_fused`` (its device ticket re-arms itself): one per criterion object."""
     return torch.zeros(int(lib.raw("avid_crit_fused_workspace_bytes")(int(bs), int(P), int(K))), dtype=torch.uint8, device=device)
 
 
 def crit_fused(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, mask, coeffs, ws):
-    """``mask``: CRIT_X_INST | CRIT_W_INST | CRIT_X_POS | CRIT_W_POS; ``coeffs``: the four groups' coefficients in that order."""
-    return _CritFused.apply(v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, inv_T, Kw, mask, tuple(coeffs), ws)
+    """Any term set of the AVID / AVID+CMA criterion: (total, losses[16], hats).  ``mask``: CRIT_X_INST | CRIT_W_INST | CRIT_X_POS |
+    CRIT_W_POS; ``coeffs``: the four groups' coefficients in that order; ``pos`` is None (or [bs][0]) for a term set without positives."""
+    if pos is not None and pos.shape[1] == 0:
+        pos = None
+    _need_cuda(*[t for t in (v_emb, a_emb, y, pos, idx, bank_v, bank_a, Z, ws) if t is not None])
+    y, idx = y.contiguous(), idx.contiguous()
+    pos = None if pos is None else pos.contiguous()
+    mask, Kw, coeffs = int(mask), int(Kw), [float(c) for c in coeffs]
+    if v_emb.dim() != 2 or a_emb.shape != v_emb.shape or idx.dim() != 2 or y.shape[0] != v_emb.shape[0] \
+            or idx.shape[0] != v_emb.shape[0] or (pos is not None and (pos.dim() != 2 or pos.shape[0] != v_emb.shape[0])):
+        raise AvidHipError("crit_fused: v_emb / a_emb [bs][D], y [bs], pos [bs][P], idx [bs][K] disagree in shape")
+    bs, D = v_emb.shape
+    P, K = (0 if pos is None else pos.shape[1]), idx.shape[1]
+    if any(t.dtype != torch.int64 for t in (y, idx) + (() if pos is None else (pos,))) or not bank_v.is_contiguous() \
+            or not bank_a.is_contiguous():
+        raise AvidHipError("crit_fused: y / pos / idx must be int64 and the banks contiguous")
+    if any(t.dtype != torch.float32 for t in (v_emb, a_emb, bank_v, bank_a, Z)):
+        raise AvidHipError("crit_fused: embeddings, banks and Z must be float32")
+    if tuple(bank_v.shape) != tuple(bank_a.shape) or bank_v.dim() != 2 or bank_v.shape[1] != D:
+        raise AvidHipError(f"crit_fused: banks {tuple(bank_v.shape)} / {tuple(bank_a.shape)} do not fit embeddings of width {D}")
+    if not 1 <= mask <= 15:
+        raise AvidHipError(f"crit_fused: mask {mask} names no term")
+    if len(coeffs) != 4:
+        raise AvidHipError("crit_fused: four coefficients (X_INST, W_INST, X_POS, W_POS)")
+    if mask & (CRIT_X_POS | CRIT_W_POS) and P < 1:
+        raise AvidHipError("crit_fused: a positive-set term needs pos [bs][P >= 1]")
+    if not 1 <= Kw <= K:
+        raise AvidHipError(f"crit_fused: Kw={Kw} outside 1..K={K}")
+
+    def launch(v, a, hats, grads, losses):
+        ad = lambda t: None if t is None else t.data_ptr()      # noqa: E731  (structure fields take the address itself)
+        d = lib.CritDesc(bs=bs, P=P, K=K, Kw=Kw, D=D, mask=mask, N=bank_v.shape[0], v_emb=ad(v), a_emb=ad(a), y=ad(y),
+                         pos=ad(pos), idx=ad(idx), bank_v=ad(bank_v), bank_a=ad(bank_a), Z=ad(Z), inv_T=float(inv_T),
+                         coeff=(C.c_float * 4)(*coeffs), v_hat=ad(hats[0]), a_hat=ad(hats[1]), losses=ad(losses),
+                         dv=ad(grads[0]), da=ad(grads[1]))
+        lib.call("avid_crit_fused", C.byref(d), _p(ws), ws.numel(), DeviceErrors.get(v.device).ptr(), _stream())
+    return _FusedCriterion.apply(v_emb, a_emb, 16, CRIT_TOTAL, launch)
 
 
 def cma_negatives(positive_set, y, rand_idx):

@@ -69,8 +69,6 @@ __global__ void alias_draw_kernel(long long n, long long K, const float* __restr
 // wave keeps its 16 independent 512-B row reads in flight.
 // ---------------------------------------------------------------------------------------------
 constexpr int SC_ROWS_PER_BLOCK = 64;
-constexpr int XM_ROWS_DEFAULT = 64;      // xmodal_fused_kernel / cma_fused_kernel: rows per block, non-temporal row loads
-constexpr int XM_NT_DEFAULT = 0;
 
 template <int DPL>  // floats per lane: D = 64 * DPL
 __global__ __launch_bounds__(256) void bank_scores_fwd_kernel(const long long* __restrict__ idx,
@@ -324,299 +322,353 @@ __global__ __launch_bounds__(256) void bank_update_kernel(float* __restrict__ ba
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused cross-modal criterion (criterions/avid.py:52-71 + criterions/nce.py:38-58 with the partition constant already
-// frozen, nce.py:22-24): normalise both embeddings, gather the SAME rows of both banks, scores / T, the NCE terms —
-// and, because Z is a constant after the first batch, the gradient with respect to the embeddings in the same pass,
-// while a gathered row is still in registers:  d emb_hat = sum_j (dL / ds_j) row_j / T,  then the backward of
-// F.normalize.  No score tensors, no snapshot of the gathered rows (the unfused path keeps one because the banks are
-// updated before backward runs, criterions/avid.py:78), no second gather.
-//   grid (splits of the K + 1 rows, sample); block = 4 waves x 16 rows (x 2 banks) in flight, as bank_scores_fwd_kernel.
-//   Every block leaves its partial gradients / loss terms in ws; xmodal_finish_kernel (second launch, one block per
-//   sample) folds them in split order and applies the normalisation's backward; the last of its blocks folds the
-//   per-sample losses in sample order: fixed summation order, one re-armed ticket (the scratch is zeroed once by the
-//   caller).  (A first version folded inside the first kernel behind two device-scope fences per block and per-sample
-//   tickets: 129 us for the 1088 blocks of a step instead of ~25.)
+// Fused criterion of a steady-state step (criterions/avid.py:52-71, criterions/avid_cma.py:150-194, 338-358 over
+// criterions/nce.py:38-58 with the partition constant already frozen, nce.py:22-24): normalise both embeddings, gather the
+// SAME rows of both banks, scores / T, the NCE terms — and, because Z is a constant after the first batch, the gradient with
+// respect to the embeddings in the same pass, while a gathered row is still in registers:
+// d emb_hat = sum_j (dL / ds_j) row_j / T,  then the backward of F.normalize.  No score tensors, no snapshot of the gathered
+// rows (the unfused path keeps one because the banks are updated before backward runs, criterions/avid.py:78), no second gather.
+//   Rows of a sample = self (y) | P positives (pos, P may be 0) | K negatives (idx).  grid (blocks of 64 rows, sample); block =
+//   4 waves x 16 rows (x 2 banks) in flight, as bank_scores_fwd_kernel.  Every block leaves its partial gradients / loss terms
+//   in ws; the finish (second launch, one block per sample) folds them in split order and applies the normalisation's
+//   backward; the last of its blocks folds the per-sample losses in sample order: fixed summation order, one re-armed ticket
+//   (the scratch is zeroed once by the caller).  (A first version folded inside the first kernel behind two device-scope
+//   fences per block and per-sample tickets: 129 us for the 1088 blocks of a step instead of ~25.)
+// One body (crit_fused_body) and one finish (crit_finish_body) serve the three entry points.  What differs between the forms
+// is the term evaluation between the gather and the fold, the number of loss terms and the final losses layout:
+//   FORM_XMODAL   avid_xmodal_fused: X_INST alone, eval_xmodal, 2 terms, losses[4], coefficient c[0] applied by the finish
+//   FORM_CMA      avid_cma_fused: X_INST | W_POS, eval_cma, 4 terms, losses[8], coefficients c[0] / c[3] folded into the weights
+//   FORM_GENERAL  avid_crit_fused: any term set MASK, eval_general<MASK>, 8 terms, losses[16], coefficients c[0..3] likewise
+// The evaluators stay three because their arithmetic differs in bits that tests and golden steps see (where the chain runs,
+// fp64 or fp32 loss sums): tests/test_gpu_crit_bits.py replays all three against recorded bits.
 // ---------------------------------------------------------------------------------------------
-struct XModalArgs {
+constexpr int CRIT_X_INST = 1, CRIT_W_INST = 2, CRIT_X_POS = 4, CRIT_W_POS = 8;
+enum { FORM_XMODAL, FORM_CMA, FORM_GENERAL };
+constexpr int crit_terms(int form) { return form == FORM_XMODAL ? 2 : (form == FORM_CMA ? 4 : 8); }   // loss terms per block / sample
+
+struct CritArgs {
   const float* v_emb; const float* a_emb;          // raw embeddings [bs][128]
-  const long long* y; const long long* idx;        // [bs], [bs][K]
+  const long long* y; const long long* pos; const long long* idx;   // [bs], [bs][P], [bs][K]
   const float* bank_v; const float* bank_a;        // view1_mem (video), view2_mem (audio)
   const float* Z;
   float* v_hat; float* a_hat;                      // normalised embeddings [bs][128]
-  float* losses;                                   // [4]: L_v2a, L_a2v, (L_v2a + L_a2v) / 2, coeff * that
+  float* losses;                                   // [4] / [8] / [16] by form (include/avid_hip.h)
   float* dv; float* da;                            // d(total) / d(raw embedding) [bs][128]
   float* part_g;                                   // [bs][S][2][128]
-  double* part_l;                                  // [bs][S][2]
-  double* samp_l;                                  // [bs][2]
+  double* part_l;                                  // [bs][S][terms]
+  double* samp_l;                                  // [bs][terms]
   unsigned* tickets;                               // [bs + 1]
   float* norms;                                    // [2][bs]: |v_emb|, |a_emb| (clamped as F.normalize does)
   int* err;
   long long N;
-  int bs, K, S;
-  float inv_T, coeff;
-  // CMA form (criterions/avid_cma.py:150-194 with cross-modal instance + within-modal positive terms): rows = self | P
-  // positives (pos[b][.]) | K negatives; the first Kw negatives also serve the within-modal terms; cI / cP: the two
-  // groups' normalised coefficients (folded into the gradients as they are accumulated: coeff = 1 then)
-  const long long* pos;
-  int P, Kw;
-  float cI, cP;
+  int bs, P, K, Kw, S;                             // Kw: the first Kw negatives also serve the W_POS terms
+  float inv_T;
+  float c[4];                                      // group coefficients: X_INST, W_INST, X_POS, W_POS
 };
 
 // Lane layout (round 4): SIXTEEN lanes per bank row (8 consecutive floats each: two 16-byte loads per row and bank), four
 // rows per wave at a time — a row's dot product is a 4-step reduction inside its lane group instead of a 6-step one over
 // the wave, the exp / log / divide chain of four rows runs in parallel lanes, and a wave issues 64 16-byte loads instead of
-// 64 4-byte ones for the same 16 rows (29.3 -> see DESIGN 3.6).
-// CMA: four score sets per gathered row pair instead of two — inst-v2a / inst-a2v (self row positive, the K negatives) and
-// pos-v2v / pos-a2a (the P positives, each 1 / P of the positive term; the first Kw negatives): the same rows of both
-// banks, two more dot products per row, and both embeddings receive gradient from both banks.
-// RB rows (of both banks) per block: 64 = 16 per wave in flight (round 4), 128 = 32 per wave — the gather is a chain of two
-// dependent memory round trips (indices, rows) per block whatever its size, and what bounds it on the 2 M-row banks is how
-// many row requests the memory system holds at once (round 5).  NT: the rows with non-temporal loads (read
-// once per step; at 2 M rows nothing of them survives in L2 / MALL until the next step anyway).
-template <bool CMA, int RB, bool NT>
-__global__ __launch_bounds__(256) void xmodal_fused_kernel(const XModalArgs p) {
-  constexpr int D = 128, RPW = RB / 4, NU = RPW / 4, NL = CMA ? 4 : 2;
-  constexpr int SC_ROWS_PER_BLOCK = RB;
+// 64 4-byte ones for the same 16 rows (29.3 -> see DESIGN 3.6).  64 rows (of both banks) per block = 16 per wave in flight,
+// plain loads: 128 rows per block and non-temporal loads were measured and gained nothing.
+constexpr int CRIT_RB = 64, CRIT_RPW = CRIT_RB / 4, CRIT_NU = CRIT_RPW / 4;
+
+struct CritTile {                        // what the shared front of crit_fused_body hands a term evaluator
+  float ev[8], ea[8];                    // this lane's 8 components of the normalised embeddings
+  floatx4 ra[CRIT_NU][2], rv[CRIT_NU][2];   // audio-bank rows (scored against the video embedding) and video-bank rows: unit u of
+                                         // this lane group is row jw + 4 u + grp (rows past j1 re-read row 0: to be discarded)
+  float gv[8], ga[8];                    // d total / d v_hat, d total / d a_hat (x T, unscaled): this group's rows
+  int lane, sub, grp, jw, j1, PP;
+};
+
+__device__ __forceinline__ float group_sum(float v) {       // over the 16 lanes of a row group
+  v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
+  return v;
+}
+__device__ __forceinline__ float dot8(const floatx4 (&r)[2], const float (&e)[8]) {
+  float d = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { d = fmaf(r[0][k], e[k], d); d = fmaf(r[1][k], e[4 + k], d); }
+  return d;
+}
+__device__ __forceinline__ void axpy8(float g, const floatx4 (&r)[2], float (&acc)[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { acc[k] = fmaf(g, r[0][k], acc[k]); acc[4 + k] = fmaf(g, r[1][k], acc[4 + k]); }
+}
+
+// normalised embeddings: this lane's 8 components (every lane group computes the norms; one group of the sample stores)
+__device__ __forceinline__ void crit_normalise(const CritArgs& p, int b, int sub, bool store, float (&ev)[8], float (&ea)[8]) {
+  constexpr int D = 128;
+  const floatx4 v0 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8);
+  const floatx4 v1 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8 + 4);
+  const floatx4 a0 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8);
+  const floatx4 a1 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8 + 4);
+  float sv = 0.f, sa = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    ev[k] = v0[k]; ev[4 + k] = v1[k]; ea[k] = a0[k]; ea[4 + k] = a1[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { sv = fmaf(ev[k], ev[k], sv); sa = fmaf(ea[k], ea[k], sa); }
+  const float nv = fmaxf(sqrtf(group_sum(sv)), 1e-12f);
+  const float na = fmaxf(sqrtf(group_sum(sa)), 1e-12f);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { ev[k] /= nv; ea[k] /= na; }
+  if (store) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      p.v_hat[(long long)b * D + sub * 8 + k] = ev[k];
+      p.a_hat[(long long)b * D + sub * 8 + k] = ea[k];
+    }
+    if (sub == 0) { p.norms[b] = nv; p.norms[p.bs + b] = na; }
+  }
+}
+
+// the bank row of row jj of sample b: 0 the sample's own row y, 1..PP the positives pos[b][jj - 1], then the negatives.  The
+// reference raises on an id outside the bank (avid.py:57-62): flag it (raised by the host at its next poll), never read outside
+__device__ __forceinline__ long long crit_row_id(const CritArgs& p, int b, int jj, int PP) {
+  long long id = jj == 0 ? p.y[b] : (jj <= PP ? p.pos[(long long)b * PP + jj - 1] : p.idx[(long long)b * p.K + jj - 1 - PP]);
+  if (id < 0 || id >= p.N) {
+    if (p.err) atomicOr(p.err, AVID_DEVERR_BANK_INDEX);
+    id = id < 0 ? 0 : p.N - 1;
+  }
+  return id;
+}
+
+__device__ __forceinline__ void crit_gather(const CritArgs& p, long long row, int sub, floatx4 (&a)[2], floatx4 (&v)[2]) {
+  const float* pa = p.bank_a + row * 128 + sub * 8;
+  const float* pv = p.bank_v + row * 128 + sub * 8;
+  a[0] = *reinterpret_cast<const floatx4*>(pa); a[1] = *reinterpret_cast<const floatx4*>(pa + 4);
+  v[0] = *reinterpret_cast<const floatx4*>(pv); v[1] = *reinterpret_cast<const floatx4*>(pv + 4);
+}
+
+// Stock cross-modal evaluator.  The exp / log / divide chain of a row runs ONCE — lane `sub` = u of a row group takes unit u's two
+// scores, so the NU units' chains run side by side in NU lanes of every group instead of one after the other in all 16 (round 5:
+// the chain was 3/4 of the kernel's instructions; the kernel is bound by them, not by the gather — consecutive rows instead of
+// random ones take the same time, tools/xmodal_bench.py XB_SEQ=1).  `extra`: this wave also carries the sample's own row (xa / xv).
+__device__ __forceinline__ void eval_xmodal(const CritArgs& p, CritTile& t, bool extra, const floatx4 (&xa)[2],
+                                            const floatx4 (&xv)[2], double (&L)[2]) {
+  constexpr int NU = CRIT_NU;
+  const float KZ = (float)p.K * p.Z[0];
+  double lv = 0, la = 0;
+  float ms1 = 0.f, ms2 = 0.f;
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const float s1 = group_sum(dot8(t.ra[u], t.ev)) * p.inv_T, s2 = group_sum(dot8(t.rv[u], t.ea)) * p.inv_T;
+    if (t.sub == u) { ms1 = s1; ms2 = s2; }
+  }
+  bool xlane = false;                          // this lane carries the extra unit (row 0): lane sub = NU of group 0
+  if (extra) {
+    const float s1 = group_sum(dot8(xa, t.ev)) * p.inv_T, s2 = group_sum(dot8(xv, t.ea)) * p.inv_T;
+    xlane = t.sub == NU && t.grp == 0;
+    if (xlane) { ms1 = s1; ms2 = s2; }
+  }
+  float g1m = 0.f, g2m = 0.f;
+  {
+    const int j = xlane ? 0 : t.jw + t.sub * 4 + t.grp;          // the row of unit `sub` of this group
+    if (xlane || (t.sub < NU && j < t.j1)) {
+      const float e1 = expf(ms1), e2 = expf(ms2);
+      if (j == 0) {            // -log(e / (e + KZ));  d / ds = -KZ / (e + KZ)
+        lv += (double)(-logf(e1 / (e1 + KZ))); la += (double)(-logf(e2 / (e2 + KZ)));
+        g1m = -(KZ / (e1 + KZ)); g2m = -(KZ / (e2 + KZ));
+      } else {                 // -log(KZ / (e + KZ));  d / ds = e / (e + KZ)
+        lv += (double)(-logf(KZ / (e1 + KZ))); la += (double)(-logf(KZ / (e2 + KZ)));
+        g1m = e1 / (e1 + KZ); g2m = e2 / (e2 + KZ);
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const float g1 = __shfl(g1m, (t.lane & 48) | u, 64), g2 = __shfl(g2m, (t.lane & 48) | u, 64);   // 0 for rows past the end
+    axpy8(g1, t.ra[u], t.gv);
+    axpy8(g2, t.rv[u], t.ga);
+  }
+  if (extra) {
+    const float gx1 = __shfl(g1m, NU, 64), gx2 = __shfl(g2m, NU, 64);
+    axpy8(t.grp == 0 ? gx1 : 0.f, xa, t.gv);       // (every group loaded the row: count it once)
+    axpy8(t.grp == 0 ? gx2 : 0.f, xv, t.ga);
+  }
+  // the units' loss terms sit in lanes sub = 0 .. NU of a group: into lane sub = 0
+#pragma unroll
+  for (int o = 1; o < 2 * NU; o <<= 1) { lv += __shfl_xor(lv, o, 64); la += __shfl_xor(la, o, 64); }
+  L[0] = lv; L[1] = la;
+}
+
+// Stock CMA evaluator (X_INST | W_POS): four score sets per gathered row pair — inst-v2a / inst-a2v (self row positive, the K
+// negatives) and pos-v2v / pos-a2a (the P positives, each 1 / P of the positive term; the first Kw negatives): both embeddings
+// receive gradient from both banks.  Loss terms accumulate in fp64 (lane sub = 0 of a group holds them).
+__device__ __forceinline__ void eval_cma(const CritArgs& p, CritTile& t, double (&L)[4]) {
+  const float KZ = (float)p.K * p.Z[0], KZw = (float)p.Kw * p.Z[0];
+  const float invP = 1.f / (float)p.P;
+  double lv = 0, la = 0, lw = 0, lx = 0;
+#pragma unroll
+  for (int u = 0; u < CRIT_NU; ++u) {
+    const int j = t.jw + u * 4 + t.grp;
+    const float s1 = group_sum(dot8(t.ra[u], t.ev)) * p.inv_T;     // v2a: video embedding . audio bank
+    const float s2 = group_sum(dot8(t.rv[u], t.ea)) * p.inv_T;     // a2v
+    const float s3 = group_sum(dot8(t.rv[u], t.ev)) * p.inv_T;     // v2v: video embedding . video bank
+    const float s4 = group_sum(dot8(t.ra[u], t.ea)) * p.inv_T;     // a2a
+    if (j < t.j1) {
+      const int n = j - 1 - t.PP;                 // index among the negatives (< 0: self / positive)
+      float g1 = 0.f, g2 = 0.f, g3 = 0.f, g4 = 0.f;
+      if (j == 0 || n >= 0) {                   // instance terms: self positive, every negative
+        const float e1 = expf(s1), e2 = expf(s2);
+        if (j == 0) {
+          if (t.sub == 0) { lv += (double)(-logf(e1 / (e1 + KZ))); la += (double)(-logf(e2 / (e2 + KZ))); }
+          g1 = -(KZ / (e1 + KZ)); g2 = -(KZ / (e2 + KZ));
+        } else {
+          if (t.sub == 0) { lv += (double)(-logf(KZ / (e1 + KZ))); la += (double)(-logf(KZ / (e2 + KZ))); }
+          g1 = e1 / (e1 + KZ); g2 = e2 / (e2 + KZ);
+        }
+      }
+      if (j != 0 && n < p.Kw) {                 // within-modal terms: the positives (mean over P), the first Kw negatives
+        const float e3 = expf(s3), e4 = expf(s4);
+        if (n < 0) {
+          if (t.sub == 0) { lw += (double)(-logf(e3 / (e3 + KZw)) * invP); lx += (double)(-logf(e4 / (e4 + KZw)) * invP); }
+          g3 = -(KZw / (e3 + KZw)) * invP; g4 = -(KZw / (e4 + KZw)) * invP;
+        } else {
+          if (t.sub == 0) { lw += (double)(-logf(KZw / (e3 + KZw))); lx += (double)(-logf(KZw / (e4 + KZw))); }
+          g3 = e3 / (e3 + KZw); g4 = e4 / (e4 + KZw);
+        }
+      }
+      g1 *= p.c[0]; g2 *= p.c[0]; g3 *= p.c[3]; g4 *= p.c[3];
+      axpy8(g1, t.ra[u], t.gv); axpy8(g3, t.rv[u], t.gv);
+      axpy8(g2, t.rv[u], t.ga); axpy8(g4, t.ra[u], t.ga);
+    }
+  }
+  L[0] = lv; L[1] = la; L[2] = lw; L[3] = lx;
+}
+
+// General evaluator: a row pair's four dot products are formed only if a term of MASK reads them, and every term adds its
+// dL/ds (times its group's coefficient) to the weight of the row it was scored against — a negative's v2a score under
+// X_INST | X_POS carries both.
+//   terms (part_l / losses order): 0 inst-v2a  1 inst-a2v | 2 inst-v2v  3 inst-a2a | 4 pos-v2a  5 pos-a2v | 6 pos-v2v  7 pos-a2a
+// A lane's loss terms: at most NU = 4 per term, summed in fp32 here (each is an fp32 logf) and in fp64 from the fold on — eight
+// fp64 accumulators live across the row loop cost the fourth wave per SIMD.
+template <int MASK>
+__device__ __forceinline__ void eval_general(const CritArgs& p, CritTile& t, double (&L)[8]) {
+  constexpr bool XI = (MASK & CRIT_X_INST) != 0, WI = (MASK & CRIT_W_INST) != 0;
+  constexpr bool XP = (MASK & CRIT_X_POS) != 0, WP = (MASK & CRIT_W_POS) != 0;
+  constexpr bool XS = XI || XP, WS = WI || WP;      // cross-modal / within-modal dot products needed
+  const float KZ = (float)p.K * p.Z[0];
+  const float KZw = (float)p.Kw * p.Z[0];
+  const float invP = (XP || WP) ? 1.f / (float)t.PP : 0.f;
+  float Lf[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) Lf[q] = 0.f;
+#pragma unroll
+  for (int u = 0; u < CRIT_NU; ++u) {
+    const int j = t.jw + u * 4 + t.grp;
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    if (XS) { s1 = group_sum(dot8(t.ra[u], t.ev)) * p.inv_T; s2 = group_sum(dot8(t.rv[u], t.ea)) * p.inv_T; }    // v2a, a2v
+    if (WS) { s3 = group_sum(dot8(t.rv[u], t.ev)) * p.inv_T; s4 = group_sum(dot8(t.ra[u], t.ea)) * p.inv_T; }    // v2v, a2a
+    if (j < t.j1) {
+      const int n = j - 1 - t.PP;             // index among the negatives (< 0: self / positive)
+      const bool self = j == 0, neg = n >= 0;
+      float g1 = 0.f, g2 = 0.f, g3 = 0.f, g4 = 0.f;
+      if (XS && (neg || (self ? XI : XP))) {
+        const float e1 = expf(s1), e2 = expf(s2);
+        if (neg) {                          // -log(KZ / (e + KZ));  d / ds = e / (e + KZ)
+          const float q1 = e1 / (e1 + KZ), q2 = e2 / (e2 + KZ);
+          if (t.sub == 0) {
+            const float t1 = -logf(KZ / (e1 + KZ)), t2 = -logf(KZ / (e2 + KZ));
+            if (XI) { Lf[0] += t1; Lf[1] += t2; }
+            if (XP) { Lf[4] += t1; Lf[5] += t2; }
+          }
+          if (XI) { g1 = q1 * p.c[0]; g2 = q2 * p.c[0]; }
+          if (XP) { g1 = fmaf(q1, p.c[2], g1); g2 = fmaf(q2, p.c[2], g2); }
+        } else if (self) {                  // -log(e / (e + KZ));  d / ds = -KZ / (e + KZ)
+          if (t.sub == 0) { Lf[0] += -logf(e1 / (e1 + KZ)); Lf[1] += -logf(e2 / (e2 + KZ)); }
+          g1 = -(KZ / (e1 + KZ)) * p.c[0]; g2 = -(KZ / (e2 + KZ)) * p.c[0];
+        } else {                            // one of the P positives: 1 / P of the positive term
+          if (t.sub == 0) { Lf[4] += -logf(e1 / (e1 + KZ)) * invP; Lf[5] += -logf(e2 / (e2 + KZ)) * invP; }
+          g1 = -(KZ / (e1 + KZ)) * invP * p.c[2]; g2 = -(KZ / (e2 + KZ)) * invP * p.c[2];
+        }
+      }
+      if (WS && (neg ? (WI || n < p.Kw) : (self ? WI : WP))) {
+        const float e3 = expf(s3), e4 = expf(s4);
+        if (neg) {
+          if (WI) {                         // every negative, K Z
+            if (t.sub == 0) { Lf[2] += -logf(KZ / (e3 + KZ)); Lf[3] += -logf(KZ / (e4 + KZ)); }
+            g3 = e3 / (e3 + KZ) * p.c[1]; g4 = e4 / (e4 + KZ) * p.c[1];
+          }
+          if (WP && n < p.Kw) {             // the first Kw negatives, Kw Z
+            if (t.sub == 0) { Lf[6] += -logf(KZw / (e3 + KZw)); Lf[7] += -logf(KZw / (e4 + KZw)); }
+            g3 = fmaf(e3 / (e3 + KZw), p.c[3], g3); g4 = fmaf(e4 / (e4 + KZw), p.c[3], g4);
+          }
+        } else if (self) {
+          if (t.sub == 0) { Lf[2] += -logf(e3 / (e3 + KZ)); Lf[3] += -logf(e4 / (e4 + KZ)); }
+          g3 = -(KZ / (e3 + KZ)) * p.c[1]; g4 = -(KZ / (e4 + KZ)) * p.c[1];
+        } else {
+          if (t.sub == 0) { Lf[6] += -logf(e3 / (e3 + KZw)) * invP; Lf[7] += -logf(e4 / (e4 + KZw)) * invP; }
+          g3 = -(KZw / (e3 + KZw)) * invP * p.c[3]; g4 = -(KZw / (e4 + KZw)) * invP * p.c[3];
+        }
+      }
+      if (XS) { axpy8(g1, t.ra[u], t.gv); axpy8(g2, t.rv[u], t.ga); }
+      if (WS) { axpy8(g3, t.rv[u], t.gv); axpy8(g4, t.ra[u], t.ga); }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) L[q] = (double)Lf[q];          // (a term that is off: 0)
+}
+
+// First launch.  MASK: the term set (FORM_GENERAL evaluates exactly it; the stock forms pass theirs).
+//   Cross-modal form: the blocks split the K NEGATIVES (rows 1 .. K) and the sample's own row 0 rides as an extra unit in wave 0
+//   of split 0 — K + 1 = 1025 rows cut into blocks of 64 were 17 blocks per sample, the 17th with one row: 1088 blocks for the
+//   1024 that are resident at once (four waves per SIMD), i.e. a second round for 64 one-row blocks behind the first one's
+//   whole latency chain (round 5).  The other forms cut all 1 + P + K rows into blocks.
+template <int FORM, int MASK>
+__device__ __forceinline__ void crit_fused_body(const CritArgs& p) {
+  constexpr int D = 128, RB = CRIT_RB, RPW = CRIT_RPW, NU = CRIT_NU, NL = crit_terms(FORM);
   __shared__ float sh_g[4][2][D];
   __shared__ double sh_l[4][NL];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane & 15, grp = lane >> 4;
-  const int b = blockIdx.y, split = blockIdx.x, R = (CMA ? p.P : 0) + p.K + 1;
-  auto group_sum = [](float v) {                       // over the 16 lanes of a row group
-    v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
-    return v;
-  };
-  // normalised embeddings: this lane's 8 components (every lane group computes the norms)
-  float ev[8], ea[8], nv, na;
-  {
-    const floatx4 v0 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8);
-    const floatx4 v1 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8 + 4);
-    const floatx4 a0 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8);
-    const floatx4 a1 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8 + 4);
-    float sv = 0.f, sa = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ev[k] = v0[k]; ev[4 + k] = v1[k]; ea[k] = a0[k]; ea[4 + k] = a1[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sv = fmaf(ev[k], ev[k], sv); sa = fmaf(ea[k], ea[k], sa); }
-    nv = fmaxf(sqrtf(group_sum(sv)), 1e-12f);
-    na = fmaxf(sqrtf(group_sum(sa)), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { ev[k] /= nv; ea[k] /= na; }
-    if (split == 0 && wave == 0 && grp == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        p.v_hat[(long long)b * D + sub * 8 + k] = ev[k];
-        p.a_hat[(long long)b * D + sub * 8 + k] = ea[k];
-      }
-      if (sub == 0) { p.norms[b] = nv; p.norms[p.bs + b] = na; }
-    }
-  }
-  const float KZ = (float)p.K * p.Z[0];
-  const float KZw = CMA ? (float)p.Kw * p.Z[0] : 0.f;
-  const int PP = CMA ? p.P : 0;
-  // Cross-modal form: the blocks split the K NEGATIVES (rows 1 .. K) and the sample's own row 0 rides as an extra unit in
-  // wave 0 of split 0 — K + 1 = 1025 rows cut into blocks of 64 were 17 blocks per sample, the 17th with one row: 1088 blocks
-  // for the 1024 that are resident at once (108 registers: four waves per SIMD), i.e. a second round for 64 one-row blocks
-  // behind the first one's whole latency chain (round 5).
-  const int j0 = (CMA ? 0 : 1) + split * SC_ROWS_PER_BLOCK, j1 = min(j0 + SC_ROWS_PER_BLOCK, R);
-  const int jw = j0 + wave * RPW;
-  const bool extra = !CMA && split == 0 && wave == 0;      // (wave-uniform)
-  // row j = 0 is the positive (the sample's own row y), [CMA: rows 1..P the positives pos[b][j - 1],] then the negatives
+  const int b = blockIdx.y, split = blockIdx.x;
+  CritTile t;
+  t.lane = lane; t.sub = lane & 15; t.grp = lane >> 4;
+  t.PP = FORM == FORM_XMODAL ? 0 : p.P;
+  crit_normalise(p, b, t.sub, split == 0 && wave == 0 && t.grp == 0, t.ev, t.ea);
+  const int j0 = (FORM == FORM_XMODAL ? 1 : 0) + split * RB;
+  t.j1 = min(j0 + RB, t.PP + p.K + 1);
+  t.jw = j0 + wave * RPW;
+  const bool extra = FORM == FORM_XMODAL && split == 0 && wave == 0;      // (wave-uniform)
+  // a wave owns 16 consecutive rows: lanes 0..15 fetch their ids (lane 16 the extra unit's), then every row load is issued
+  // before the first use
+  const bool xid = extra && lane == RPW;
   long long mine = 0;
-  if ((lane < RPW && jw + lane < j1) || (extra && lane == RPW)) {
-    const int jj = lane == RPW ? 0 : jw + lane;
-    mine = jj == 0 ? p.y[b] : (jj <= PP ? p.pos[(long long)b * PP + jj - 1] : p.idx[(long long)b * p.K + jj - 1 - PP]);
-    if (mine < 0 || mine >= p.N) {
-      if (p.err) atomicOr(p.err, AVID_DEVERR_BANK_INDEX);
-      mine = mine < 0 ? 0 : p.N - 1;
-    }
-  }
+  if ((lane < RPW && t.jw + lane < t.j1) || xid) mine = crit_row_id(p, b, xid ? 0 : t.jw + lane, t.PP);
   floatx4 xa[2] = {}, xv[2] = {};        // the extra unit's rows (row 0 of the sample)
-  if (extra) {
-    const long long row = __shfl(mine, RPW, 64);
-    const float* pa = p.bank_a + row * D + sub * 8;
-    const float* pv = p.bank_v + row * D + sub * 8;
-    xa[0] = *reinterpret_cast<const floatx4*>(pa); xa[1] = *reinterpret_cast<const floatx4*>(pa + 4);
-    xv[0] = *reinterpret_cast<const floatx4*>(pv); xv[1] = *reinterpret_cast<const floatx4*>(pv + 4);
-  }
-  floatx4 ra[NU][2], rv[NU][2];          // audio-bank rows (scored against the video embedding) and video-bank rows
+  if (extra) crit_gather(p, __shfl(mine, RPW, 64), t.sub, xa, xv);
 #pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const long long row = __shfl(mine, u * 4 + grp, 64);
-    const float* pa = p.bank_a + row * D + sub * 8;
-    const float* pv = p.bank_v + row * D + sub * 8;
-    if (NT) {
-      ra[u][0] = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(pa)); ra[u][1] = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(pa + 4));
-      rv[u][0] = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(pv)); rv[u][1] = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(pv + 4));
-    } else {
-      ra[u][0] = *reinterpret_cast<const floatx4*>(pa); ra[u][1] = *reinterpret_cast<const floatx4*>(pa + 4);
-      rv[u][0] = *reinterpret_cast<const floatx4*>(pv); rv[u][1] = *reinterpret_cast<const floatx4*>(pv + 4);
-    }
-  }
-  float gv[8], ga[8];                    // d L_v2a / d v_hat, d L_a2v / d a_hat (x T, unscaled): this group's rows
+  for (int u = 0; u < NU; ++u) crit_gather(p, __shfl(mine, u * 4 + t.grp, 64), t.sub, t.ra[u], t.rv[u]);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) gv[k] = ga[k] = 0.f;
-  double lv = 0, la = 0, lw = 0, lx = 0;
-  const float invP = CMA ? 1.f / (float)p.P : 0.f;
-  if (!CMA) {
-    // Cross-modal form: the exp / log / divide chain of a row runs ONCE — lane `sub` = u of a row group takes unit u's two
-    // scores, so the NU units' chains run side by side in NU lanes of every group instead of one after the other in all 16
-    // (round 5: the chain was 3/4 of the kernel's instructions; the kernel is bound by them, not by the gather — consecutive
-    // rows instead of random ones take the same time, tools/xmodal_bench.py XB_SEQ=1).
-    float ms1 = 0.f, ms2 = 0.f;
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      float d1 = 0.f, d2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        d1 = fmaf(ra[u][0][k], ev[k], d1); d1 = fmaf(ra[u][1][k], ev[4 + k], d1);
-        d2 = fmaf(rv[u][0][k], ea[k], d2); d2 = fmaf(rv[u][1][k], ea[4 + k], d2);
-      }
-      const float s1 = group_sum(d1) * p.inv_T, s2 = group_sum(d2) * p.inv_T;
-      if (sub == u) { ms1 = s1; ms2 = s2; }
-    }
-    bool xlane = false;                          // this lane carries the extra unit (row 0): lane sub = NU of group 0
-    if (extra) {
-      float d1 = 0.f, d2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        d1 = fmaf(xa[0][k], ev[k], d1); d1 = fmaf(xa[1][k], ev[4 + k], d1);
-        d2 = fmaf(xv[0][k], ea[k], d2); d2 = fmaf(xv[1][k], ea[4 + k], d2);
-      }
-      const float s1 = group_sum(d1) * p.inv_T, s2 = group_sum(d2) * p.inv_T;
-      xlane = sub == NU && grp == 0;
-      if (xlane) { ms1 = s1; ms2 = s2; }
-    }
-    float g1m = 0.f, g2m = 0.f;
-    {
-      const int j = xlane ? 0 : jw + sub * 4 + grp;          // the row of unit `sub` of this group
-      if (xlane || (sub < NU && j < j1)) {
-        const float e1 = expf(ms1), e2 = expf(ms2);
-        if (j == 0) {            // -log(e / (e + KZ));  d / ds = -KZ / (e + KZ)
-          lv += (double)(-logf(e1 / (e1 + KZ))); la += (double)(-logf(e2 / (e2 + KZ)));
-          g1m = -(KZ / (e1 + KZ)); g2m = -(KZ / (e2 + KZ));
-        } else {                 // -log(KZ / (e + KZ));  d / ds = e / (e + KZ)
-          lv += (double)(-logf(KZ / (e1 + KZ))); la += (double)(-logf(KZ / (e2 + KZ)));
-          g1m = e1 / (e1 + KZ); g2m = e2 / (e2 + KZ);
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const float g1 = __shfl(g1m, (lane & 48) | u, 64), g2 = __shfl(g2m, (lane & 48) | u, 64);   // 0 for rows past the end
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        gv[k] = fmaf(g1, ra[u][0][k], gv[k]); gv[4 + k] = fmaf(g1, ra[u][1][k], gv[4 + k]);
-        ga[k] = fmaf(g2, rv[u][0][k], ga[k]); ga[4 + k] = fmaf(g2, rv[u][1][k], ga[4 + k]);
-      }
-    }
-    if (extra) {
-      const float gx1 = __shfl(g1m, NU, 64), gx2 = __shfl(g2m, NU, 64);
-      const float g1 = grp == 0 ? gx1 : 0.f, g2 = grp == 0 ? gx2 : 0.f;      // (every group loaded the row: count it once)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        gv[k] = fmaf(g1, xa[0][k], gv[k]); gv[4 + k] = fmaf(g1, xa[1][k], gv[4 + k]);
-        ga[k] = fmaf(g2, xv[0][k], ga[k]); ga[4 + k] = fmaf(g2, xv[1][k], ga[4 + k]);
-      }
-    }
-    // the units' loss terms sit in lanes sub = 0 .. NU of a group: into lane sub = 0
-#pragma unroll
-    for (int o = 1; o < 2 * NU; o <<= 1) { lv += __shfl_xor(lv, o, 64); la += __shfl_xor(la, o, 64); }
-  }
-#pragma unroll
-  for (int u = 0; CMA && u < NU; ++u) {
-    const int j = jw + u * 4 + grp;
-    float d1 = 0.f, d2 = 0.f, d3 = 0.f, d4 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      d1 = fmaf(ra[u][0][k], ev[k], d1); d1 = fmaf(ra[u][1][k], ev[4 + k], d1);
-      d2 = fmaf(rv[u][0][k], ea[k], d2); d2 = fmaf(rv[u][1][k], ea[4 + k], d2);
-      if (CMA) {
-        d3 = fmaf(rv[u][0][k], ev[k], d3); d3 = fmaf(rv[u][1][k], ev[4 + k], d3);
-        d4 = fmaf(ra[u][0][k], ea[k], d4); d4 = fmaf(ra[u][1][k], ea[4 + k], d4);
-      }
-    }
-    const float s1 = group_sum(d1) * p.inv_T;     // v2a: video embedding . audio bank
-    const float s2 = group_sum(d2) * p.inv_T;     // a2v
-    if (CMA) {
-      const float s3 = group_sum(d3) * p.inv_T;   // v2v: video embedding . video bank
-      const float s4 = group_sum(d4) * p.inv_T;   // a2a
-      if (j < j1) {
-        const int n = j - 1 - PP;                 // index among the negatives (< 0: self / positive)
-        float g1 = 0.f, g2 = 0.f, g3 = 0.f, g4 = 0.f;
-        if (j == 0 || n >= 0) {                   // instance terms: self positive, every negative
-          const float e1 = expf(s1), e2 = expf(s2);
-          if (j == 0) {
-            if (sub == 0) { lv += (double)(-logf(e1 / (e1 + KZ))); la += (double)(-logf(e2 / (e2 + KZ))); }
-            g1 = -(KZ / (e1 + KZ)); g2 = -(KZ / (e2 + KZ));
-          } else {
-            if (sub == 0) { lv += (double)(-logf(KZ / (e1 + KZ))); la += (double)(-logf(KZ / (e2 + KZ))); }
-            g1 = e1 / (e1 + KZ); g2 = e2 / (e2 + KZ);
-          }
-        }
-        if (j != 0 && n < p.Kw) {                 // within-modal terms: the positives (mean over P), the first Kw negatives
-          const float e3 = expf(s3), e4 = expf(s4);
-          if (n < 0) {
-            if (sub == 0) { lw += (double)(-logf(e3 / (e3 + KZw)) * invP); lx += (double)(-logf(e4 / (e4 + KZw)) * invP); }
-            g3 = -(KZw / (e3 + KZw)) * invP; g4 = -(KZw / (e4 + KZw)) * invP;
-          } else {
-            if (sub == 0) { lw += (double)(-logf(KZw / (e3 + KZw))); lx += (double)(-logf(KZw / (e4 + KZw))); }
-            g3 = e3 / (e3 + KZw); g4 = e4 / (e4 + KZw);
-          }
-        }
-        g1 *= p.cI; g2 *= p.cI; g3 *= p.cP; g4 *= p.cP;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          gv[k] = fmaf(g1, ra[u][0][k], gv[k]); gv[4 + k] = fmaf(g1, ra[u][1][k], gv[4 + k]);
-          gv[k] = fmaf(g3, rv[u][0][k], gv[k]); gv[4 + k] = fmaf(g3, rv[u][1][k], gv[4 + k]);
-          ga[k] = fmaf(g2, rv[u][0][k], ga[k]); ga[4 + k] = fmaf(g2, rv[u][1][k], ga[4 + k]);
-          ga[k] = fmaf(g4, ra[u][0][k], ga[k]); ga[4 + k] = fmaf(g4, ra[u][1][k], ga[4 + k]);
-        }
-      }
-    } else if (j < j1) {
-      const float e1 = expf(s1), e2 = expf(s2);
-      float g1, g2;
-      if (j == 0) {            // -log(e / (e + KZ));  d / ds = -KZ / (e + KZ)
-        if (sub == 0) { lv += (double)(-logf(e1 / (e1 + KZ))); la += (double)(-logf(e2 / (e2 + KZ))); }
-        g1 = -(KZ / (e1 + KZ)); g2 = -(KZ / (e2 + KZ));
-      } else {                 // -log(KZ / (e + KZ));  d / ds = e / (e + KZ)
-        if (sub == 0) { lv += (double)(-logf(KZ / (e1 + KZ))); la += (double)(-logf(KZ / (e2 + KZ))); }
-        g1 = e1 / (e1 + KZ); g2 = e2 / (e2 + KZ);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        gv[k] = fmaf(g1, ra[u][0][k], gv[k]); gv[4 + k] = fmaf(g1, ra[u][1][k], gv[4 + k]);
-        ga[k] = fmaf(g2, rv[u][0][k], ga[k]); ga[4 + k] = fmaf(g2, rv[u][1][k], ga[4 + k]);
-      }
-    }
-  }
+  for (int k = 0; k < 8; ++k) t.gv[k] = t.ga[k] = 0.f;
+  double L[NL];
+  if constexpr (FORM == FORM_XMODAL) eval_xmodal(p, t, extra, xa, xv, L);
+  else if constexpr (FORM == FORM_CMA) eval_cma(p, t, L);
+  else eval_general<MASK>(p, t, L);
   // fold the four row groups of the wave (fixed order: (g0 + g1) + (g2 + g3)), then the four waves through LDS
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    gv[k] += __shfl_xor(gv[k], 16, 64); gv[k] += __shfl_xor(gv[k], 32, 64);
-    ga[k] += __shfl_xor(ga[k], 16, 64); ga[k] += __shfl_xor(ga[k], 32, 64);
+    t.gv[k] += __shfl_xor(t.gv[k], 16, 64); t.gv[k] += __shfl_xor(t.gv[k], 32, 64);
+    t.ga[k] += __shfl_xor(t.ga[k], 16, 64); t.ga[k] += __shfl_xor(t.ga[k], 32, 64);
   }
-  lv += __shfl_xor(lv, 16, 64); lv += __shfl_xor(lv, 32, 64);
-  la += __shfl_xor(la, 16, 64); la += __shfl_xor(la, 32, 64);
-  if (CMA) {
-    lw += __shfl_xor(lw, 16, 64); lw += __shfl_xor(lw, 32, 64);
-    lx += __shfl_xor(lx, 16, 64); lx += __shfl_xor(lx, 32, 64);
-  }
-  if (grp == 0) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { sh_g[wave][0][sub * 8 + k] = gv[k]; sh_g[wave][1][sub * 8 + k] = ga[k]; }
+  for (int q = 0; q < NL; ++q)
+    if (FORM != FORM_GENERAL || ((MASK >> (q >> 1)) & 1)) { L[q] += __shfl_xor(L[q], 16, 64); L[q] += __shfl_xor(L[q], 32, 64); }
+  if (t.grp == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sh_g[wave][0][t.sub * 8 + k] = t.gv[k]; sh_g[wave][1][t.sub * 8 + k] = t.ga[k]; }
   }
   if (lane == 0) {
-    sh_l[wave][0] = lv; sh_l[wave][1] = la;
-    if (CMA) { sh_l[wave][2] = lw; sh_l[wave][3] = lx; }
+#pragma unroll
+    for (int q = 0; q < NL; ++q) sh_l[wave][q] = L[q];
   }
   __syncthreads();
   float* pg = p.part_g + ((long long)b * p.S + split) * 2 * D;
   {
-    const int t = threadIdx.x;                       // 256 threads = 2 x 128 gradient components
-    pg[t] = ((&sh_g[0][0][0])[t] + (&sh_g[1][0][0])[t]) + ((&sh_g[2][0][0])[t] + (&sh_g[3][0][0])[t]);   // [which][d] contiguous
+    const int i = threadIdx.x;                       // 256 threads = 2 x 128 gradient components
+    pg[i] = ((&sh_g[0][0][0])[i] + (&sh_g[1][0][0])[i]) + ((&sh_g[2][0][0])[i] + (&sh_g[3][0][0])[i]);   // [which][d] contiguous
   }
   if (threadIdx.x < NL) {
     double* pl = p.part_l + ((long long)b * p.S + split) * NL;
@@ -625,12 +677,12 @@ __global__ __launch_bounds__(256) void xmodal_fused_kernel(const XModalArgs p) {
   }
 }
 
-// second launch of the fused criterion: one block per sample folds the S partial gradients in split order (the kernel
-// boundary makes them visible: no fences around the 1088 producer blocks), applies the backward of F.normalize and
-// leaves the sample's two loss terms; the last of the bs blocks (device ticket, re-armed) folds those in sample order.
-template <bool CMA>
-__global__ __launch_bounds__(256) void xmodal_finish_kernel(const XModalArgs p) {
-  constexpr int D = 128, NL = CMA ? 4 : 2;
+// Second launch: one block per sample folds the S partial gradients in split order (the kernel boundary makes them visible:
+// no fences around the producer blocks), applies the backward of F.normalize and leaves the sample's loss terms; the last of
+// the bs blocks (device ticket, re-armed) folds those in sample order and writes the form's losses.
+template <int FORM>
+__device__ __forceinline__ void crit_finish_body(const CritArgs& p) {
+  constexpr int D = 128, NL = crit_terms(FORM);
   __shared__ float sh_dot[4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, which = t >> 7, d = t & 127;
   const int b = blockIdx.x;
@@ -645,8 +697,10 @@ __global__ __launch_bounds__(256) void xmodal_finish_kernel(const XModalArgs p) 
     g += g0; g += g1; g += g2; g += g3;
   }
   for (; sidx < p.S; ++sidx) g += pg[(long long)sidx * 2 * D];
-  // d total / d score = coeff * 1/2 * 1/bs * dL/ds;  d emb_hat = that * row / T
-  g *= p.coeff * 0.5f / (float)p.bs * p.inv_T;
+  // d total / d score = coeff_g * 1/2 * 1/bs * dL/ds;  d emb_hat = that * row / T.  The cross-modal form's one coefficient is
+  // applied here, the other forms' are already in the weights
+  if (FORM == FORM_XMODAL) g *= p.c[0] * 0.5f / (float)p.bs * p.inv_T;
+  else g *= 0.5f / (float)p.bs * p.inv_T;
   // dx = (dy - y <y, dy>) / norm
   const float dot = wave_sum(g * eh);
   if (lane == 0) sh_dot[wave] = dot;
@@ -695,318 +749,55 @@ __global__ __launch_bounds__(256) void xmodal_finish_kernel(const XModalArgs p) 
     }
   }
   if (lane == 0) {
-    float L[NL];
+    // criterions/avid.py:216-232, criterions/avid_cma.py:338-358: every group the mean of its two directions, the total their
+    // weighted sum in group order
+    if constexpr (FORM == FORM_GENERAL) {            // losses[16]: eight terms, four group means (a group that is off: 0), total
+      float total = 0.f;
 #pragma unroll
-    for (int q = 0; q < NL; ++q) { L[q] = (float)(tot[q] / (double)p.bs); p.losses[q] = L[q]; }
-    if (CMA) {     // criterions/avid_cma.py:338-358: every group the mean of its two directions, the total their weighted sum
-      const float gi = L[0] / 2.f + L[1] / 2.f, gp = L[2] / 2.f + L[3] / 2.f;
-      p.losses[4] = gi;
-      p.losses[5] = gp;
-      p.losses[6] = gi * p.cI + gp * p.cP;
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const float la = (float)(tot[2 * g4] / (double)p.bs), lb = (float)(tot[2 * g4 + 1] / (double)p.bs);
+        const float gm = la / 2.f + lb / 2.f;
+        p.losses[2 * g4] = la;
+        p.losses[2 * g4 + 1] = lb;
+        p.losses[8 + g4] = gm;
+        total = g4 == 0 ? gm * p.c[0] : total + gm * p.c[g4];
+      }
+      p.losses[12] = total;
+      p.losses[13] = p.losses[14] = p.losses[15] = 0.f;
     } else {
-      const float xl = L[0] / 2.f + L[1] / 2.f;      // criterions/avid.py:221-222
-      p.losses[2] = xl;
-      p.losses[3] = xl * p.coeff;
+      float Lq[NL];
+#pragma unroll
+      for (int q = 0; q < NL; ++q) { Lq[q] = (float)(tot[q] / (double)p.bs); p.losses[q] = Lq[q]; }
+      if constexpr (FORM == FORM_CMA) {              // losses[8]: four terms, two group means, total, (unused)
+        const float gi = Lq[0] / 2.f + Lq[1] / 2.f, gp = Lq[2] / 2.f + Lq[3] / 2.f;
+        p.losses[4] = gi;
+        p.losses[5] = gp;
+        p.losses[6] = gi * p.c[0] + gp * p.c[3];
+      } else {                                       // losses[4]: L_v2a, L_a2v, their mean, coeff * that
+        const float xl = Lq[0] / 2.f + Lq[1] / 2.f;
+        p.losses[2] = xl;
+        p.losses[3] = xl * p.c[0];
+      }
     }
     __hip_atomic_store(&p.tickets[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // re-arm
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// The general fused criterion (avid_crit_fused): the CMA form of xmodal_fused_kernel with the term set as a template
-// parameter.  Rows = self | P positives (P may be 0) | K negatives, cut into blocks of 64 as there; a row pair's four dot
-// products are formed only if a term of MASK reads them, and every term adds its dL/ds (times its group's coefficient) to
-// the weight of the row it was scored against — a negative's v2a score under X_INST | X_POS carries both.
-//   terms (part_l / losses order): 0 inst-v2a  1 inst-a2v | 2 inst-v2v  3 inst-a2a | 4 pos-v2a  5 pos-a2v | 6 pos-v2v  7 pos-a2a
-// Same lane layout, same fold, same two launches (crit_finish_kernel = xmodal_finish_kernel with eight terms).
-// ---------------------------------------------------------------------------------------------
-constexpr int CRIT_X_INST = 1, CRIT_W_INST = 2, CRIT_X_POS = 4, CRIT_W_POS = 8, CRIT_NL = 8;
-
-struct CritArgs {
-  const float* v_emb; const float* a_emb;          // raw embeddings [bs][128]
-  const long long* y; const long long* pos; const long long* idx;   // [bs], [bs][P], [bs][K]
-  const float* bank_v; const float* bank_a;
-  const float* Z;
-  float* v_hat; float* a_hat;
-  float* losses;                                   // [16]
-  float* dv; float* da;
-  float* part_g;                                   // [bs][S][2][128]
-  double* part_l;                                  // [bs][S][8]
-  double* samp_l;                                  // [bs][8]
-  unsigned* tickets;                               // [bs + 1]
-  float* norms;                                    // [2][bs]
-  int* err;
-  long long N;
-  int bs, P, K, Kw, S;
-  float inv_T;
-  float c[4];                                      // group coefficients: X_INST, W_INST, X_POS, W_POS
-};
-
-// Four waves per SIMD (<= 128 registers), as the stock forms run: every term set the criterions can ask for fits without a
-// spill; W_INST together with W_POS (both within-modal chains on one score pair: reachable through the C-ABI only) does not,
-// and runs at three.
+// The entry points' kernels.  The general form is pinned at four waves per SIMD (<= 128 registers), as the stock forms run: every
+// term set the criterions can ask for fits without a spill; W_INST together with W_POS (both within-modal chains on one score
+// pair: reachable through the C-ABI only) does not, and runs at three.
+template <bool CMA>
+__global__ __launch_bounds__(256) void xmodal_fused_kernel(const CritArgs p) {
+  crit_fused_body<CMA ? FORM_CMA : FORM_XMODAL, CMA ? (CRIT_X_INST | CRIT_W_POS) : CRIT_X_INST>(p);
+}
 template <int MASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MASK & 10) == 10 ? 3 : 4, 4)))
 void crit_fused_kernel(const CritArgs p) {
-  constexpr int D = 128, RB = 64, RPW = RB / 4, NU = RPW / 4;
-  constexpr bool XI = (MASK & CRIT_X_INST) != 0, WI = (MASK & CRIT_W_INST) != 0;
-  constexpr bool XP = (MASK & CRIT_X_POS) != 0, WP = (MASK & CRIT_W_POS) != 0;
-  constexpr bool XS = XI || XP, WS = WI || WP;      // cross-modal / within-modal dot products needed
-  __shared__ float sh_g[4][2][D];
-  __shared__ double sh_l[4][CRIT_NL];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane & 15, grp = lane >> 4;
-  const int b = blockIdx.y, split = blockIdx.x, PP = p.P, R = PP + p.K + 1;
-  auto group_sum = [](float v) {
-    v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
-    return v;
-  };
-  float ev[8], ea[8], nv, na;
-  {
-    const floatx4 v0 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8);
-    const floatx4 v1 = *reinterpret_cast<const floatx4*>(p.v_emb + (long long)b * D + sub * 8 + 4);
-    const floatx4 a0 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8);
-    const floatx4 a1 = *reinterpret_cast<const floatx4*>(p.a_emb + (long long)b * D + sub * 8 + 4);
-    float sv = 0.f, sa = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ev[k] = v0[k]; ev[4 + k] = v1[k]; ea[k] = a0[k]; ea[4 + k] = a1[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sv = fmaf(ev[k], ev[k], sv); sa = fmaf(ea[k], ea[k], sa); }
-    nv = fmaxf(sqrtf(group_sum(sv)), 1e-12f);
-    na = fmaxf(sqrtf(group_sum(sa)), 1e-12f);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { ev[k] /= nv; ea[k] /= na; }
-    if (split == 0 && wave == 0 && grp == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        p.v_hat[(long long)b * D + sub * 8 + k] = ev[k];
-        p.a_hat[(long long)b * D + sub * 8 + k] = ea[k];
-      }
-      if (sub == 0) { p.norms[b] = nv; p.norms[p.bs + b] = na; }
-    }
-  }
-  const float KZ = (float)p.K * p.Z[0];
-  const float KZw = (float)p.Kw * p.Z[0];
-  const float invP = (XP || WP) ? 1.f / (float)PP : 0.f;
-  const int j0 = split * RB, j1 = min(j0 + RB, R);
-  const int jw = j0 + wave * RPW;
-  // row j = 0: the sample's own row y; rows 1..P: the positives pos[b][j - 1]; then the negatives
-  long long mine = 0;
-  if (lane < RPW && jw + lane < j1) {
-    const int jj = jw + lane;
-    mine = jj == 0 ? p.y[b] : (jj <= PP ? p.pos[(long long)b * PP + jj - 1] : p.idx[(long long)b * p.K + jj - 1 - PP]);
-    if (mine < 0 || mine >= p.N) {
-      if (p.err) atomicOr(p.err, AVID_DEVERR_BANK_INDEX);
-      mine = mine < 0 ? 0 : p.N - 1;
-    }
-  }
-  floatx4 ra[NU][2], rv[NU][2];          // audio-bank rows and video-bank rows (rows past j1 re-read row 0: discarded below)
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const long long row = __shfl(mine, u * 4 + grp, 64);
-    const float* pa = p.bank_a + row * D + sub * 8;
-    const float* pv = p.bank_v + row * D + sub * 8;
-    ra[u][0] = *reinterpret_cast<const floatx4*>(pa); ra[u][1] = *reinterpret_cast<const floatx4*>(pa + 4);
-    rv[u][0] = *reinterpret_cast<const floatx4*>(pv); rv[u][1] = *reinterpret_cast<const floatx4*>(pv + 4);
-  }
-  float gv[8], ga[8];                    // d total / d v_hat, d total / d a_hat (x T, x 2 bs): this group's rows
-#pragma unroll
-  for (int k = 0; k < 8; ++k) gv[k] = ga[k] = 0.f;
-  // a lane's loss terms: at most NU = 4 per term, summed in fp32 here (each is an fp32 logf) and in fp64 from the fold on —
-  // eight fp64 accumulators live across the row loop cost the fourth wave per SIMD
-  float Lf[CRIT_NL];
-#pragma unroll
-  for (int q = 0; q < CRIT_NL; ++q) Lf[q] = 0.f;
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const int j = jw + u * 4 + grp;
-    float d1 = 0.f, d2 = 0.f, d3 = 0.f, d4 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (XS) {
-        d1 = fmaf(ra[u][0][k], ev[k], d1); d1 = fmaf(ra[u][1][k], ev[4 + k], d1);
-        d2 = fmaf(rv[u][0][k], ea[k], d2); d2 = fmaf(rv[u][1][k], ea[4 + k], d2);
-      }
-      if (WS) {
-        d3 = fmaf(rv[u][0][k], ev[k], d3); d3 = fmaf(rv[u][1][k], ev[4 + k], d3);
-        d4 = fmaf(ra[u][0][k], ea[k], d4); d4 = fmaf(ra[u][1][k], ea[4 + k], d4);
-      }
-    }
-    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
-    if (XS) { s1 = group_sum(d1) * p.inv_T; s2 = group_sum(d2) * p.inv_T; }    // v2a, a2v
-    if (WS) { s3 = group_sum(d3) * p.inv_T; s4 = group_sum(d4) * p.inv_T; }    // v2v, a2a
-    if (j < j1) {
-      const int n = j - 1 - PP;             // index among the negatives (< 0: self / positive)
-      const bool self = j == 0, neg = n >= 0;
-      float g1 = 0.f, g2 = 0.f, g3 = 0.f, g4 = 0.f;
-      if (XS && (neg || (self ? XI : XP))) {
-        const float e1 = expf(s1), e2 = expf(s2);
-        if (neg) {                          // -log(KZ / (e + KZ));  d / ds = e / (e + KZ)
-          const float q1 = e1 / (e1 + KZ), q2 = e2 / (e2 + KZ);
-          if (sub == 0) {
-            const float t1 = -logf(KZ / (e1 + KZ)), t2 = -logf(KZ / (e2 + KZ));
-            if (XI) { Lf[0] += t1; Lf[1] += t2; }
-            if (XP) { Lf[4] += t1; Lf[5] += t2; }
-          }
-          if (XI) { g1 = q1 * p.c[0]; g2 = q2 * p.c[0]; }
-          if (XP) { g1 = fmaf(q1, p.c[2], g1); g2 = fmaf(q2, p.c[2], g2); }
-        } else if (self) {                  // -log(e / (e + KZ));  d / ds = -KZ / (e + KZ)
-          if (sub == 0) { Lf[0] += -logf(e1 / (e1 + KZ)); Lf[1] += -logf(e2 / (e2 + KZ)); }
-          g1 = -(KZ / (e1 + KZ)) * p.c[0]; g2 = -(KZ / (e2 + KZ)) * p.c[0];
-        } else {                            // one of the P positives: 1 / P of the positive term
-          if (sub == 0) { Lf[4] += -logf(e1 / (e1 + KZ)) * invP; Lf[5] += -logf(e2 / (e2 + KZ)) * invP; }
-          g1 = -(KZ / (e1 + KZ)) * invP * p.c[2]; g2 = -(KZ / (e2 + KZ)) * invP * p.c[2];
-        }
-      }
-      if (WS && (neg ? (WI || n < p.Kw) : (self ? WI : WP))) {
-        const float e3 = expf(s3), e4 = expf(s4);
-        if (neg) {
-          if (WI) {                         // every negative, K Z
-            if (sub == 0) { Lf[2] += -logf(KZ / (e3 + KZ)); Lf[3] += -logf(KZ / (e4 + KZ)); }
-            g3 = e3 / (e3 + KZ) * p.c[1]; g4 = e4 / (e4 + KZ) * p.c[1];
-          }
-          if (WP && n < p.Kw) {             // the first Kw negatives, Kw Z
-            if (sub == 0) { Lf[6] += -logf(KZw / (e3 + KZw)); Lf[7] += -logf(KZw / (e4 + KZw)); }
-            g3 = fmaf(e3 / (e3 + KZw), p.c[3], g3); g4 = fmaf(e4 / (e4 + KZw), p.c[3], g4);
-          }
-        } else if (self) {
-          if (sub == 0) { Lf[2] += -logf(e3 / (e3 + KZ)); Lf[3] += -logf(e4 / (e4 + KZ)); }
-          g3 = -(KZ / (e3 + KZ)) * p.c[1]; g4 = -(KZ / (e4 + KZ)) * p.c[1];
-        } else {
-          if (sub == 0) { Lf[6] += -logf(e3 / (e3 + KZw)) * invP; Lf[7] += -logf(e4 / (e4 + KZw)) * invP; }
-          g3 = -(KZw / (e3 + KZw)) * invP * p.c[3]; g4 = -(KZw / (e4 + KZw)) * invP * p.c[3];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (XS) {
-          gv[k] = fmaf(g1, ra[u][0][k], gv[k]); gv[4 + k] = fmaf(g1, ra[u][1][k], gv[4 + k]);
-          ga[k] = fmaf(g2, rv[u][0][k], ga[k]); ga[4 + k] = fmaf(g2, rv[u][1][k], ga[4 + k]);
-        }
-        if (WS) {
-          gv[k] = fmaf(g3, rv[u][0][k], gv[k]); gv[4 + k] = fmaf(g3, rv[u][1][k], gv[4 + k]);
-          ga[k] = fmaf(g4, ra[u][0][k], ga[k]); ga[4 + k] = fmaf(g4, ra[u][1][k], ga[4 + k]);
-        }
-      }
-    }
-  }
-  // fold the four row groups of the wave (fixed order: (g0 + g1) + (g2 + g3)), then the four waves through LDS
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    gv[k] += __shfl_xor(gv[k], 16, 64); gv[k] += __shfl_xor(gv[k], 32, 64);
-    ga[k] += __shfl_xor(ga[k], 16, 64); ga[k] += __shfl_xor(ga[k], 32, 64);
-  }
-  double L[CRIT_NL];
-#pragma unroll
-  for (int q = 0; q < CRIT_NL; ++q) {
-    L[q] = (double)Lf[q];
-    if ((MASK >> (q >> 1)) & 1) { L[q] += __shfl_xor(L[q], 16, 64); L[q] += __shfl_xor(L[q], 32, 64); }
-  }
-  if (grp == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sh_g[wave][0][sub * 8 + k] = gv[k]; sh_g[wave][1][sub * 8 + k] = ga[k]; }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < CRIT_NL; ++q) sh_l[wave][q] = L[q];          // (a term that is off: 0)
-  }
-  __syncthreads();
-  float* pg = p.part_g + ((long long)b * p.S + split) * 2 * D;
-  {
-    const int t = threadIdx.x;                       // 256 threads = 2 x 128 gradient components
-    pg[t] = ((&sh_g[0][0][0])[t] + (&sh_g[1][0][0])[t]) + ((&sh_g[2][0][0])[t] + (&sh_g[3][0][0])[t]);
-  }
-  if (threadIdx.x < CRIT_NL) {
-    double* pl = p.part_l + ((long long)b * p.S + split) * CRIT_NL;
-    const int q = threadIdx.x;
-    pl[q] = (sh_l[0][q] + sh_l[1][q]) + (sh_l[2][q] + sh_l[3][q]);
-  }
+  crit_fused_body<FORM_GENERAL, MASK>(p);
 }
-
-// second launch: xmodal_finish_kernel for eight terms and four groups
-__global__ __launch_bounds__(256) void crit_finish_kernel(const CritArgs p) {
-  constexpr int D = 128, NL = CRIT_NL;
-  __shared__ float sh_dot[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, which = t >> 7, d = t & 127;
-  const int b = blockIdx.x;
-  const float eh = (which == 0 ? p.v_hat : p.a_hat)[(long long)b * D + d];
-  const float nrm = p.norms[which * p.bs + b];
-  const float* pg = p.part_g + (long long)b * p.S * 2 * D + t;
-  float g = 0.f;
-  int sidx = 0;
-  for (; sidx + 4 <= p.S; sidx += 4) {               // four independent loads per trip, summed in split order
-    const float g0 = pg[(long long)sidx * 2 * D], g1 = pg[(long long)(sidx + 1) * 2 * D];
-    const float g2 = pg[(long long)(sidx + 2) * 2 * D], g3 = pg[(long long)(sidx + 3) * 2 * D];
-    g += g0; g += g1; g += g2; g += g3;
-  }
-  for (; sidx < p.S; ++sidx) g += pg[(long long)sidx * 2 * D];
-  // d total / d score = coeff_g * 1/2 * 1/bs * dL/ds (the coefficient is already in);  d emb_hat = that * row / T
-  g *= 0.5f / (float)p.bs * p.inv_T;
-  const float dot = wave_sum(g * eh);
-  if (lane == 0) sh_dot[wave] = dot;
-  __syncthreads();
-  const float full = sh_dot[which * 2] + sh_dot[which * 2 + 1];
-  (which == 0 ? p.dv : p.da)[(long long)b * D + d] = (g - eh * full) / nrm;
-  if (wave != 0) return;
-  double l[NL];
-  {
-    const double* pl = p.part_l + (long long)b * p.S * NL;
-#pragma unroll
-    for (int q = 0; q < NL; ++q) l[q] = 0;
-    for (int base = 0; base < p.S; base += 64) {
-      const int i = base + lane;
-      double v[NL];
-#pragma unroll
-      for (int q = 0; q < NL; ++q) v[q] = i < p.S ? pl[NL * i + q] : 0.0;
-      for (int k = 0; k < 64 && base + k < p.S; ++k) {
-#pragma unroll
-        for (int q = 0; q < NL; ++q) l[q] += __shfl(v[q], k, 64);
-      }
-    }
-  }
-  unsigned last = 0;
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < NL; ++q) __hip_atomic_store(p.samp_l + NL * b + q, l[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    last = atomicAdd(&p.tickets[0], 1u) == (unsigned)p.bs - 1 ? 1u : 0u;
-  }
-  last = __shfl(last, 0, 64);
-  if (!last) return;
-  __threadfence();
-  double tot[NL];
-#pragma unroll
-  for (int q = 0; q < NL; ++q) tot[q] = 0;
-  for (int base = 0; base < p.bs; base += 64) {      // 64 samples per trip in flight, summed in sample order
-    const int i = base + lane;
-    double v[NL];
-#pragma unroll
-    for (int q = 0; q < NL; ++q) v[q] = i < p.bs ? __hip_atomic_load(p.samp_l + NL * i + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-    for (int k = 0; k < 64 && base + k < p.bs; ++k) {
-#pragma unroll
-      for (int q = 0; q < NL; ++q) tot[q] += __shfl(v[q], k, 64);
-    }
-  }
-  if (lane == 0) {
-    // criterions/avid.py:216-232, criterions/avid_cma.py:338-358: every group the mean of its two directions, the total
-    // their weighted sum in group order (a group that is off: 0)
-    float total = 0.f;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const float la = (float)(tot[2 * g4] / (double)p.bs), lb = (float)(tot[2 * g4 + 1] / (double)p.bs);
-      const float gm = la / 2.f + lb / 2.f;
-      p.losses[2 * g4] = la;
-      p.losses[2 * g4 + 1] = lb;
-      p.losses[8 + g4] = gm;
-      total = g4 == 0 ? gm * p.c[0] : total + gm * p.c[g4];
-    }
-    p.losses[12] = total;
-    p.losses[13] = p.losses[14] = p.losses[15] = 0.f;
-    __hip_atomic_store(&p.tickets[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // re-arm
-  }
-}
+template <bool CMA>
+__global__ __launch_bounds__(256) void xmodal_finish_kernel(const CritArgs p) { crit_finish_body<CMA ? FORM_CMA : FORM_XMODAL>(p); }
+__global__ __launch_bounds__(256) void crit_finish_kernel(const CritArgs p) { crit_finish_body<FORM_GENERAL>(p); }
 
 // both banks in one launch (criterions/avid.py:118-129): blockIdx.y picks the bank
 __global__ __launch_bounds__(256) void bank_update2_kernel(float* __restrict__ bank0, float* __restrict__ bank1,
@@ -1184,57 +975,53 @@ extern "C" int avid_cma_negatives(int bs, int K, int P, int64_t N, const int32_t
   return check_launch("cma_negatives");
 }
 
-// rows per block / non-temporal row loads of the fused criterion kernels: AVID_XM_ROWS (64 | 128), AVID_XM_NT (0 | 1)
-static int xm_rows() {
-  static int v = 0;
-  if (!v) {
-    const char* e = getenv("AVID_XM_ROWS");
-    v = e && atoi(e) == 64 ? 64 : (e && atoi(e) == 128 ? 128 : XM_ROWS_DEFAULT);
-  }
-  return v;
-}
-static bool xm_nt() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVID_XM_NT");
-    v = e ? (atoi(e) != 0) : XM_NT_DEFAULT;
-  }
-  return v != 0;
-}
 static size_t fused_ws_bytes(int bs, int rows, int nl) {
-  const size_t S = (size_t)ceil_div(rows, 64);      // (sized for the smaller block: either setting fits)
+  const size_t S = (size_t)ceil_div(rows, 64);
   return (size_t)bs * S * 2 * 128 * 4 + (size_t)bs * S * nl * 8 + (size_t)bs * nl * 8 + ((size_t)bs + 1) * 4 + (size_t)bs * 2 * 4 + 64;
 }
-extern "C" size_t avid_xmodal_fused_workspace_bytes(int bs, int K) { return fused_ws_bytes(bs, K + 1, 2); }
-extern "C" size_t avid_cma_fused_workspace_bytes(int bs, int P, int K) { return fused_ws_bytes(bs, 1 + P + K, 4); }
+extern "C" size_t avid_xmodal_fused_workspace_bytes(int bs, int K) { return fused_ws_bytes(bs, K + 1, crit_terms(FORM_XMODAL)); }
+extern "C" size_t avid_cma_fused_workspace_bytes(int bs, int P, int K) { return fused_ws_bytes(bs, 1 + P + K, crit_terms(FORM_CMA)); }
+extern "C" size_t avid_crit_fused_workspace_bytes(int bs, int P, int K) {
+  if (bs <= 0 || P < 0 || K <= 0) return 0;
+  return fused_ws_bytes(bs, 1 + P + K, crit_terms(FORM_GENERAL));
+}
 
-// scratch layout + the two launches shared by avid_xmodal_fused / avid_cma_fused
-template <bool CMA>
-static int fused_launch(XModalArgs& a, int rows, void* ws, hipStream_t s) {
-  constexpr int NL = CMA ? 4 : 2;
-  const int rb = xm_rows();
-  a.S = (int)ceil_div(CMA ? rows : rows - 1, rb);       // cross-modal: the negatives in blocks, row 0 rides in the first
-  char* w = static_cast<char*>(ws);                 // (zero-filled once by the caller: the tickets re-arm themselves)
-  a.part_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * a.S * NL * 8;
-  a.samp_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * NL * 8;
+// what the entry points' timers report: two dot products and two weighted sums per score pair the term set reads; bytes: the
+// gathered rows of both banks, read once (rows = 1 + P + K)
+static double crit_flops(int mask, int bs, int rows) {
+  const int pairs = ((mask & (CRIT_X_INST | CRIT_X_POS)) ? 1 : 0) + ((mask & (CRIT_W_INST | CRIT_W_POS)) ? 1 : 0);
+  return pairs * 2.0 * 2.0 * 2.0 * bs * rows * 128;
+}
+static double crit_bytes(int bs, int rows) { return 2.0 * 4.0 * bs * rows * 128.0; }
+
+// scratch layout + the two launches of the three fused entry points (`a` validated and filled by them, the timer theirs)
+static int crit_launch(CritArgs& a, int form, int mask, int rows, void* ws, hipStream_t s) {
+  static const char* const main_op[] = {"xmodal_fused", "cma_fused", "crit_fused"};
+  static const char* const finish_op[] = {"xmodal_finish", "cma_finish", "crit_finish"};
+  const size_t nl = (size_t)crit_terms(form);
+  a.S = (int)ceil_div(form == FORM_XMODAL ? rows - 1 : rows, CRIT_RB);   // cross-modal: the negatives in blocks, row 0 rides in the first
+  char* w = static_cast<char*>(ws);                 // (zero-filled once by the caller: the ticket re-arms itself)
+  a.part_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * a.S * nl * 8;
+  a.samp_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * nl * 8;
   a.part_g = reinterpret_cast<float*>(w); w += (size_t)a.bs * a.S * 2 * 128 * 4;
   a.tickets = reinterpret_cast<unsigned*>(w); w += ((size_t)a.bs + 1) * 4;
   a.norms = reinterpret_cast<float*>(w);
-  // bytes: the gathered rows of both banks, read once
-  ScopedTimer t(s, CMA ? "cma_fused_kernel" : "xmodal_fused_kernel", (CMA ? 2.0 : 1.0) * 2.0 * 2.0 * 2.0 * a.bs * rows * 128,
-                2.0 * 4.0 * a.bs * rows * 128.0);
-  const dim3 grid((unsigned)a.S, (unsigned)a.bs);
-  if (rb == 128) {
-    if (xm_nt()) hipLaunchKernelGGL((xmodal_fused_kernel<CMA, 128, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((xmodal_fused_kernel<CMA, 128, false>), grid, dim3(256), 0, s, a);
-  } else {
-    if (xm_nt()) hipLaunchKernelGGL((xmodal_fused_kernel<CMA, 64, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((xmodal_fused_kernel<CMA, 64, false>), grid, dim3(256), 0, s, a);
+  const dim3 grid((unsigned)a.S, (unsigned)a.bs), fgrid((unsigned)a.bs);
+  if (form == FORM_XMODAL) hipLaunchKernelGGL(xmodal_fused_kernel<false>, grid, dim3(256), 0, s, a);
+  else if (form == FORM_CMA) hipLaunchKernelGGL(xmodal_fused_kernel<true>, grid, dim3(256), 0, s, a);
+  else switch (mask) {
+#define AVID_CRIT_CASE(M) case M: hipLaunchKernelGGL(crit_fused_kernel<M>, grid, dim3(256), 0, s, a); break;
+    AVID_CRIT_CASE(1) AVID_CRIT_CASE(2) AVID_CRIT_CASE(3) AVID_CRIT_CASE(4) AVID_CRIT_CASE(5)
+    AVID_CRIT_CASE(6) AVID_CRIT_CASE(7) AVID_CRIT_CASE(8) AVID_CRIT_CASE(9) AVID_CRIT_CASE(10)
+    AVID_CRIT_CASE(11) AVID_CRIT_CASE(12) AVID_CRIT_CASE(13) AVID_CRIT_CASE(14) default: AVID_CRIT_CASE(15)
+#undef AVID_CRIT_CASE
   }
-  int rc = check_launch(CMA ? "cma_fused" : "xmodal_fused");
+  int rc = check_launch(main_op[form]);
   if (rc) return rc;
-  hipLaunchKernelGGL(xmodal_finish_kernel<CMA>, dim3((unsigned)a.bs), dim3(256), 0, s, a);
-  return check_launch(CMA ? "cma_finish" : "xmodal_finish");
+  if (form == FORM_XMODAL) hipLaunchKernelGGL(xmodal_finish_kernel<false>, fgrid, dim3(256), 0, s, a);
+  else if (form == FORM_CMA) hipLaunchKernelGGL(xmodal_finish_kernel<true>, fgrid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(crit_finish_kernel, fgrid, dim3(256), 0, s, a);
+  return check_launch(finish_op[form]);
 }
 
 extern "C" int avid_xmodal_fused(int bs, int K, int D, int64_t N, const float* v_emb, const float* a_emb, const int64_t* y,
@@ -1245,12 +1032,13 @@ extern "C" int avid_xmodal_fused(int bs, int K, int D, int64_t N, const float* v
                    dv && da && ws, AVID_E_BADARG, "xmodal_fused: bad argument");
   AVID_REQUIRE(D == 128, AVID_E_UNSUPPORTED, "xmodal_fused: D=%d unsupported (128 only; use the unfused ops)", D);
   AVID_REQUIRE(ws_bytes >= avid_xmodal_fused_workspace_bytes(bs, K), AVID_E_BADARG, "xmodal_fused: workspace too small");
-  XModalArgs a;
+  CritArgs a = {};
   a.v_emb = v_emb; a.a_emb = a_emb; a.y = (const long long*)y; a.idx = (const long long*)idx;
   a.bank_v = bank_v; a.bank_a = bank_a; a.Z = Z; a.v_hat = v_hat; a.a_hat = a_hat; a.losses = losses; a.dv = dv; a.da = da;
-  a.err = err; a.N = N; a.bs = bs; a.K = K; a.inv_T = inv_T; a.coeff = coeff;
-  a.pos = nullptr; a.P = 0; a.Kw = 0; a.cI = a.cP = 0.f;
-  return fused_launch<false>(a, K + 1, ws, (hipStream_t)stream);
+  a.err = err; a.N = N; a.bs = bs; a.K = K; a.inv_T = inv_T; a.c[0] = coeff;
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(s, "xmodal_fused_kernel", crit_flops(CRIT_X_INST, bs, K + 1), crit_bytes(bs, K + 1));
+  return crit_launch(a, FORM_XMODAL, CRIT_X_INST, K + 1, ws, s);
 }
 
 extern "C" int avid_cma_fused(int bs, int P, int K, int Kw, int D, int64_t N, const float* v_emb, const float* a_emb,
@@ -1261,17 +1049,13 @@ extern "C" int avid_cma_fused(int bs, int P, int K, int Kw, int D, int64_t N, co
                    v_hat && a_hat && losses && dv && da && ws, AVID_E_BADARG, "cma_fused: bad argument");
   AVID_REQUIRE(D == 128, AVID_E_UNSUPPORTED, "cma_fused: D=%d unsupported (128 only; use the unfused ops)", D);
   AVID_REQUIRE(ws_bytes >= avid_cma_fused_workspace_bytes(bs, P, K), AVID_E_BADARG, "cma_fused: workspace too small");
-  XModalArgs a;
-  a.v_emb = v_emb; a.a_emb = a_emb; a.y = (const long long*)y; a.idx = (const long long*)idx;
+  CritArgs a = {};
+  a.v_emb = v_emb; a.a_emb = a_emb; a.y = (const long long*)y; a.pos = (const long long*)pos; a.idx = (const long long*)idx;
   a.bank_v = bank_v; a.bank_a = bank_a; a.Z = Z; a.v_hat = v_hat; a.a_hat = a_hat; a.losses = losses; a.dv = dv; a.da = da;
-  a.err = err; a.N = N; a.bs = bs; a.K = K; a.inv_T = inv_T; a.coeff = 1.f;
-  a.pos = (const long long*)pos; a.P = P; a.Kw = Kw; a.cI = coeff_inst; a.cP = coeff_pos;
-  return fused_launch<true>(a, 1 + P + K, ws, (hipStream_t)stream);
-}
-
-extern "C" size_t avid_crit_fused_workspace_bytes(int bs, int P, int K) {
-  if (bs <= 0 || P < 0 || K <= 0) return 0;
-  return fused_ws_bytes(bs, 1 + P + K, CRIT_NL);
+  a.err = err; a.N = N; a.bs = bs; a.P = P; a.K = K; a.Kw = Kw; a.inv_T = inv_T; a.c[0] = coeff_inst; a.c[3] = coeff_pos;
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(s, "cma_fused_kernel", crit_flops(CRIT_X_INST | CRIT_W_POS, bs, 1 + P + K), crit_bytes(bs, 1 + P + K));
+  return crit_launch(a, FORM_CMA, CRIT_X_INST | CRIT_W_POS, 1 + P + K, ws, s);
 }
 
 extern "C" int avid_crit_fused(const avid_crit_desc* d, void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream) {
@@ -1285,35 +1069,15 @@ extern "C" int avid_crit_fused(const avid_crit_desc* d, void* ws, size_t ws_byte
   AVID_REQUIRE(d->v_emb && d->a_emb && d->y && d->idx && (d->pos || d->P == 0) && d->bank_v && d->bank_a && d->Z && d->v_hat &&
                    d->a_hat && d->losses && d->dv && d->da && ws, AVID_E_BADARG, "crit_fused: null pointer");
   AVID_REQUIRE(ws_bytes >= avid_crit_fused_workspace_bytes(d->bs, d->P, d->K), AVID_E_BADARG, "crit_fused: workspace too small");
-  CritArgs a;
+  CritArgs a = {};
   a.v_emb = d->v_emb; a.a_emb = d->a_emb; a.y = (const long long*)d->y; a.pos = (const long long*)d->pos;
   a.idx = (const long long*)d->idx; a.bank_v = d->bank_v; a.bank_a = d->bank_a; a.Z = d->Z; a.v_hat = d->v_hat; a.a_hat = d->a_hat;
   a.losses = d->losses; a.dv = d->dv; a.da = d->da; a.err = err; a.N = d->N; a.bs = d->bs; a.P = d->P; a.K = d->K; a.Kw = d->Kw;
   a.inv_T = d->inv_T;
   for (int g = 0; g < 4; ++g) a.c[g] = d->coeff[g];
-  const int rows = 1 + d->P + d->K;
-  a.S = (int)ceil_div(rows, 64);
-  char* w = static_cast<char*>(ws);                 // (zero-filled once by the caller: the ticket re-arms itself)
-  a.part_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * a.S * CRIT_NL * 8;
-  a.samp_l = reinterpret_cast<double*>(w); w += (size_t)a.bs * CRIT_NL * 8;
-  a.part_g = reinterpret_cast<float*>(w); w += (size_t)a.bs * a.S * 2 * 128 * 4;
-  a.tickets = reinterpret_cast<unsigned*>(w); w += ((size_t)a.bs + 1) * 4;
-  a.norms = reinterpret_cast<float*>(w);
   hipStream_t s = (hipStream_t)stream;
-  const int pairs = ((d->mask & (CRIT_X_INST | CRIT_X_POS)) ? 1 : 0) + ((d->mask & (CRIT_W_INST | CRIT_W_POS)) ? 1 : 0);
-  ScopedTimer t(s, "crit_fused_kernel", pairs * 2.0 * 2.0 * 2.0 * a.bs * rows * 128, 2.0 * 4.0 * a.bs * rows * 128.0);
-  const dim3 grid((unsigned)a.S, (unsigned)a.bs);
-  switch (d->mask) {
-#define AVID_CRIT_CASE(M) case M: hipLaunchKernelGGL(crit_fused_kernel<M>, grid, dim3(256), 0, s, a); break;
-    AVID_CRIT_CASE(1) AVID_CRIT_CASE(2) AVID_CRIT_CASE(3) AVID_CRIT_CASE(4) AVID_CRIT_CASE(5)
-    AVID_CRIT_CASE(6) AVID_CRIT_CASE(7) AVID_CRIT_CASE(8) AVID_CRIT_CASE(9) AVID_CRIT_CASE(10)
-    AVID_CRIT_CASE(11) AVID_CRIT_CASE(12) AVID_CRIT_CASE(13) AVID_CRIT_CASE(14) default: AVID_CRIT_CASE(15)
-#undef AVID_CRIT_CASE
-  }
-  int rc = check_launch("crit_fused");
-  if (rc) return rc;
-  hipLaunchKernelGGL(crit_finish_kernel, dim3((unsigned)a.bs), dim3(256), 0, s, a);
-  return check_launch("crit_finish");
+  ScopedTimer t(s, "crit_fused_kernel", crit_flops(d->mask, d->bs, 1 + d->P + d->K), crit_bytes(d->bs, 1 + d->P + d->K));
+  return crit_launch(a, FORM_GENERAL, d->mask, 1 + d->P + d->K, ws, s);
 }
 
 extern "C" int avid_bank_update2(int B, int D, int64_t N, float* bank0, float* bank1, const int64_t* y, const float* emb0,

@@ -318,3 +318,13 @@ def test_timer_name_is_the_name_the_profiler_shows():
     assert timer_name("avid::crit_finish_kernel(avid::CritArgs)") == "crit_finish_kernel"
     src = open(os.path.join(REPO, "avid-cma_amd", "csrc", "criterion.hip")).read()
     assert 'ScopedTimer t(s, "crit_fused_kernel"' in src
+
+
+def test_workspace_queries_answer_what_they_answered_when_the_bits_were_recorded(golden):
+    """tests/golden/crit_fused_bits.npz (tools/record_crit_bits.py) holds the three workspace-size queries' answers for every
+    (bs, P, K) of its cases, from the library the bits were recorded with: the queries answer the same today."""
+    import tools_path  # noqa: F401
+    import record_crit_bits as B
+    want = golden("crit_fused_bits")["ws_queries"]
+    assert want.dtype == np.int64 and want.shape == (len({B.bs_p_k(c) for c in B.cases()}), 6) and (want[:, 3:] > 0).all()
+    assert np.array_equal(B.ws_queries(), want)

@@ -1,5 +1,5 @@
 """Dev tool: the criterion alone — forward + backward + bank update — for the term sets that take the general fused kernel
-(ops.crit_fused), against the unfused chain of the same criterion object (ops.FUSED_CRITERION off), at bs 64, K 1024, 240 k-row
+(ops.crit_fused) and the stock AVID+CMA set (ops.cma_fused), against the unfused chain of the same criterion object (ops.FUSED_CRITERION off), at bs 64, K 1024, 240 k-row
 banks.  Times are the library's HIP-event timers summed over every library launch of a step (torch's own glue kernels of the
 unfused chain — cat, slice copies, the gradient adds — are NOT in them: the unfused figure is a lower bound), plus the step's
 wall time between two stream events.  The two paths alternate round by round in one process; per path the median over the
@@ -45,7 +45,8 @@ def cma(coeffs):
     return crit
 
 
-SETS = {"self-avid": lambda: avid(0., 1.), "joint-avid": lambda: avid(1., 1.), "cma-three-groups": lambda: cma((1., 0., 1., 1.))}
+SETS = {"self-avid": lambda: avid(0., 1.), "joint-avid": lambda: avid(1., 1.), "cma-three-groups": lambda: cma((1., 0., 1., 1.)),
+        "cma-stock": lambda: cma((1., 0., 0., 1.))}
 result = {}
 for name, make in SETS.items():
     crit = make()

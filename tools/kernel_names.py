@@ -21,7 +21,7 @@ KEEP = {
     "wgrad_group_kernel": 0,       # <SPLIT,PRE>
     "wgrad_tab_kernel": 2,         # <NB,KC | SPLIT>
     "wgrad_kernel": 2,
-    "xmodal_fused_kernel": 0,      # <CMA,ROWS,NT>: CMA = true is timed as cma_fused_kernel
+    "xmodal_fused_kernel": 0,      # <CMA> (<CMA,ROWS,NT> in profiles of older builds): CMA = true is timed as cma_fused_kernel
     "xmodal_finish_kernel": 0,
     "crit_fused_kernel": 0,        # <MASK>: the term set of avid_crit_fused
     "bank_scores_fwd_kernel": 0,   # <rows per wave>

@@ -1,6 +1,6 @@
 """Dev tool: the fused cross-modal criterion kernel alone (criterions/avid.py:52-71 + nce.py:38-58) on banks of 240k and
-2M rows — time per launch (library HIP events) and the gathered rows' read bandwidth.  AVID_XM_ROWS / AVID_XM_NT select
-the variant (csrc/criterion.hip).  usage: python tools/xmodal_bench.py [reps=20]"""
+2M rows — time per launch (library HIP events) and the gathered rows' read bandwidth.  AVID_HIP_LIB selects another build of
+the library for an A/B (fresh processes, alternating).  usage: python tools/xmodal_bench.py [reps=20]"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "avid-cma_amd"))
