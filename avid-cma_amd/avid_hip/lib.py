@@ -282,6 +282,11 @@ SIGNATURES = {
     "avid_knn_vote": (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "avid_rank_metrics_workspace_bytes": (_sz, [_i64, _i]),
     "avid_rank_metrics": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "avid_svm_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "avid_svm_scores": (_i, [_i64, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "avid_svm_xt": (_i, [_i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "avid_svm_hinge": (_i, [_i64, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "avid_svm_loss": (_i, [_i64, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp, _vp]),
     "avid_adam_flat": (_i, [_i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _vp, _vp, _f, _vp]),
     "avid_sgd_flat": (_i, [_i64, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _f, _vp]),
     "avid_grad_accum_flat": (_i, [_i64, _vp, _vp, _vp, _vp]),

@@ -237,7 +237,8 @@ class DeviceErrors:
             16: "mlabel_loss: target outside [0, 1] or not finite",
             32: "rank_metrics: NaN score",
             64: "soft_ce_loss: target negative or not finite",
-            128: "batch_mix: partner index outside [0, batch)"}
+            128: "batch_mix: partner index outside [0, batch)",
+            256: "svm: label outside [0, n_classes)"}
     _inst = {}
 
     def __init__(self, device):
@@ -260,9 +261,9 @@ class DeviceErrors:
         self.host.zero_()
         self.event = None
         what = "; ".join(m for b, m in self._MSG.items() if code & b) or f"code {code}"
-        cls = (LabelError if code & 8 else IndexError if code & 7 else TargetError if code & 16 else ScoreError if code & 32
-               else TargetError if code & 64 else IndexError)
-        kind = "index out of range" if code & (15 | 128) else "value out of range"
+        cls = (LabelError if code & (8 | 256) else IndexError if code & 7 else TargetError if code & 16 else ScoreError
+               if code & 32 else TargetError if code & 64 else IndexError)
+        kind = "index out of range" if code & (15 | 128 | 256) else "value out of range"
         raise cls(f"avid_hip: {kind} in a device kernel — {what}")
 
     def poll(self):
@@ -2734,3 +2735,203 @@ def knn_vote(idx, sim, gallery_labels, n_classes, T=0.07, query_labels=None):
     lib.call("avid_knn_vote", Q, k, _p(idx), _p(sim), _p(gallery_labels), gallery_labels.numel(), int(n_classes), 1.0 / float(T),
              _p(query_labels), _p(scores), _p(pred5), _p(first), _stream())
     return scores, pred5, first
+
+
+# ------------------------------------------------------------------------------------------------
+# Linear one-vs-all SVM on frozen features (csrc/svm.hip): the two products, and the full-batch solver built on them
+# ------------------------------------------------------------------------------------------------
+SVM_SLICE_ROWS = 512       # rows of X per slice of avid_svm_xt (csrc/svm.hip: SVM_SLICE)
+SVM_LADDER = 16            # step sizes 2^0 .. 2^-15 of the line search (csrc/svm.hip: SVM_LADDER)
+SVM_ARMIJO = 1e-2          # sufficient-decrease constant (liblinear's eta)
+SVM_CG_TOL = 0.1           # the inner conjugate gradient stops at |residual| <= 0.1 |gradient| (liblinear's eps_cg)
+
+
+def _svm_ws(dev, N, F, C):
+    need = int(lib.raw("avid_svm_workspace_bytes")(N, F, C))
+    if need == 0:
+        raise AvidHipError(f"svm: N = {N}, F = {F}, C = {C} outside 1 <= N < 2^31, F >= 1, C >= 1")
+    return workspace(dev, need)
+
+
+def _svm_x(who, x):
+    _knn_arg(f"{who}: x", x, torch.float32)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise AvidHipError(f"{who}: x must be [N, F] with N >= 1 and F >= 1, got {tuple(x.shape)}")
+    return x.shape
+
+
+def svm_scores(x, w, bias=None):
+    """``z [N, C] = x . w^T + bias`` — ``avid_svm_scores``: ``x [N, F]``, ``w [C, F]``, ``bias [C]`` or None; fp32, contiguous,
+    on one device.  Exact fp32 products, one summation order per element whatever the row block it is passed in."""
+    N, F = _svm_x("svm_scores", x)
+    _knn_arg("svm_scores: w", w, torch.float32)
+    if w.dim() != 2 or w.shape[1] != F or w.shape[0] < 1 or w.device != x.device:
+        raise AvidHipError(f"svm_scores: w must be [C, {F}] on {x.device}, got {tuple(w.shape)} on {w.device}")
+    C_ = w.shape[0]
+    if bias is not None:
+        _knn_arg("svm_scores: bias", bias, torch.float32, (C_,))
+    z = torch.empty((N, C_), dtype=torch.float32, device=x.device)
+    lib.call("avid_svm_scores", N, F, C_, _p(x), _p(w), _p(bias), _p(z), _stream())
+    return z
+
+
+def svm_xt(x, d, colsum=True):
+    """``(g [C, F], gb [C]) = (d^T . x, column sums of d)`` — ``avid_svm_xt``: ``x [N, F]``, ``d [N, C]``; fp32, contiguous, on one
+    device.  The rows are reduced in slices of ``SVM_SLICE_ROWS`` added in order: no atomics, the same bits on every run and
+    under every CU budget.  ``colsum=False`` returns ``gb = None``."""
+    N, F = _svm_x("svm_xt", x)
+    _knn_arg("svm_xt: d", d, torch.float32)
+    if d.dim() != 2 or d.shape[0] != N or d.shape[1] < 1 or d.device != x.device:
+        raise AvidHipError(f"svm_xt: d must be [{N}, C] on {x.device}, got {tuple(d.shape)} on {d.device}")
+    C_ = d.shape[1]
+    ws = _svm_ws(x.device, N, F, C_)
+    g = torch.empty((C_, F), dtype=torch.float32, device=x.device)
+    gb = torch.empty(C_, dtype=torch.float32, device=x.device) if colsum else None
+    lib.call("avid_svm_xt", N, F, C_, _p(x), _p(d), _p(g), _p(gb), _p(ws), ws.numel(), _stream())
+    return g, gb
+
+
+def _svm_dot(a, b):
+    """Per-class inner product of two (coef [C, F], beta [C]) pairs, in double."""
+    return (a[0].double() * b[0].double()).sum(1) + a[1].double() * b[1].double()
+
+
+def svm_fit(X, labels, n_classes, cost=1.0, pos_weight=None, intercept_scaling=1.0, tol=1e-4, max_iter=100, init=None,
+            cg_max=50):
+    """One-vs-all linear SVM, liblinear's L2-regularised L2-loss primal (scikit-learn's ``LinearSVC`` default): per class c,
+    with y = +1 where ``labels == c`` else -1, minimise over (w, beta)
+
+        0.5 |w|^2 + 0.5 beta^2 + sum_i cost_ic max(0, 1 - y_i (w . x_i + s beta))^2,
+
+    ``cost_ic = cost * pos_weight[c]`` on the positive rows, ``cost`` elsewhere, ``s = intercept_scaling`` (the intercept is
+    a regularised constant feature).  ``X [N, F]`` fp32 contiguous on the device, ``labels`` integer ``[N]`` in
+    ``[0, n_classes)`` (a class without a positive row is legal), ``pos_weight`` None or ``[n_classes]``.
+
+    Method: truncated Newton, all classes in lock-step, so that every pass over ``X`` (``avid_svm_scores`` / ``avid_svm_xt``)
+    serves every class: an inner conjugate gradient on ``H v = v + 2 X~^T (A * cost * X~ v)`` (A: the rows with
+    ``1 - y z > 0``) down to ``SVM_CG_TOL`` of the gradient norm or ``cg_max`` steps, then a backtracking Armijo search over
+    the steps ``2^0 .. 2^-15`` that needs ``z`` and ``X~ d`` only (``avid_svm_loss``).  Per-class scalars stay in device
+    tensors; a converged class is frozen by a mask; the host reads one flag per (inner or outer) iteration.
+    Stopping rule, per class: ``|grad f_c| <= tol |grad f_c(0)|``.  Hitting ``max_iter`` (or a line search that finds no
+    step) flags the class and does not raise.  ``init = (coef, intercept)`` warm-starts the solve (a sweep over ``cost``).
+
+    Returns ``(coef [C, F], intercept [C] = s beta, info)``; ``info``: device tensors per class — ``objective`` and
+    ``grad_norm`` / ``grad_norm0`` (float64), ``iterations`` (int64, the Newton steps taken), ``converged`` (bool)."""
+    N, F = _svm_x("svm_fit", X)
+    dev = X.device
+    C_ = int(n_classes)
+    s = float(intercept_scaling)
+    if C_ < 1:
+        raise AvidHipError("svm_fit: n_classes must be >= 1")
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.device == dev) or labels.is_floating_point() \
+            or labels.dtype == torch.bool or tuple(labels.shape) != (N,):
+        raise AvidHipError(f"svm_fit: labels must be an integer tensor [{N}] on {dev}")
+    if not (float(cost) > 0.0 and math.isfinite(float(cost)) and s > 0.0 and math.isfinite(s) and float(tol) > 0.0):
+        raise AvidHipError("svm_fit: cost, intercept_scaling and tol must be positive and finite")
+    if int(max_iter) < 0 or int(cg_max) < 1:
+        raise AvidHipError("svm_fit: max_iter must be >= 0 and cg_max >= 1")
+    if pos_weight is not None:
+        _knn_arg("svm_fit: pos_weight", pos_weight, torch.float32, (C_,))
+    if init is not None:
+        _knn_arg("svm_fit: init coef", init[0], torch.float32, (C_, F))
+        _knn_arg("svm_fit: init intercept", init[1], torch.float32, (C_,))
+    cost = float(cost)
+    lab = labels.to(torch.int32).contiguous()
+    ws = _svm_ws(dev, N, F, C_)
+    errs = DeviceErrors.get(dev)
+    st = _stream()
+
+    def scores(v):
+        z = torch.empty((N, C_), dtype=torch.float32, device=dev)
+        bias = v[1] * s                  # (held until the call has been issued)
+        lib.call("avid_svm_scores", N, F, C_, _p(X), _p(v[0]), _p(bias), _p(z), st)
+        return z
+
+    def hinge(z, xv=None):
+        out = torch.empty((N, C_), dtype=torch.float32, device=dev)
+        lib.call("avid_svm_hinge", N, C_, _p(z), _p(lab), cost, _p(pos_weight), _p(xv), _p(out), errs.ptr(), st)
+        return out
+
+    def xt(d):
+        g = torch.empty((C_, F), dtype=torch.float32, device=dev)
+        gb = torch.empty(C_, dtype=torch.float32, device=dev)
+        lib.call("avid_svm_xt", N, F, C_, _p(X), _p(d), _p(g), _p(gb), _p(ws), ws.numel(), st)
+        return g, gb * s
+
+    def loss(z, zd, K):
+        out = torch.empty((K, C_), dtype=torch.float64, device=dev)
+        lib.call("avid_svm_loss", N, C_, K, _p(z), _p(zd), _p(lab), cost, _p(pos_weight), _p(out), _p(ws), ws.numel(),
+                 errs.ptr(), st)
+        return out
+
+    def grad(v, z):
+        G, gb = xt(hinge(z))
+        return torch.sub(v[0], G, alpha=2.0), torch.sub(v[1], gb, alpha=2.0)
+
+    def hess(p, z):
+        G, gb = xt(hinge(z, scores(p)))
+        return torch.add(p[0], G, alpha=2.0), torch.add(p[1], gb, alpha=2.0)
+
+    with torch.no_grad():
+        zero = (torch.zeros((C_, F), dtype=torch.float32, device=dev), torch.zeros(C_, dtype=torch.float32, device=dev))
+        z0 = torch.zeros((N, C_), dtype=torch.float32, device=dev)
+        g0 = grad(zero, z0)
+        gn0 = _svm_dot(g0, g0).sqrt()
+        if init is None:
+            w, z, g = zero, z0, g0
+        else:
+            w = (init[0].clone(), init[1] / s)
+            z = scores(w)
+            g = grad(w, z)
+        iterations = torch.zeros(C_, dtype=torch.int64, device=dev)
+        stalled = torch.zeros(C_, dtype=torch.bool, device=dev)
+        alphas = torch.tensor([2.0 ** -k for k in range(SVM_LADDER)], dtype=torch.float64, device=dev)[:, None]
+        it = 0
+        while True:
+            gn = _svm_dot(g, g).sqrt()
+            conv = gn <= float(tol) * gn0
+            active = ~conv & ~stalled
+            more = it < int(max_iter) and bool(active.any())          # the one flag the host reads per Newton step
+            if it == 0:
+                errs.check()
+            if not more:
+                break
+            it += 1
+            # ---- inner conjugate gradient: H d = -g on the active classes
+            on = active.to(torch.float32)
+            r = (-g[0] * on[:, None], -g[1] * on)
+            d = (torch.zeros_like(r[0]), torch.zeros_like(r[1]))
+            p = (r[0].clone(), r[1].clone())
+            rs = _svm_dot(r, r)
+            stop2 = (SVM_CG_TOL * gn) ** 2
+            cg_on = active & (rs > stop2)
+            for _ in range(int(cg_max)):
+                Hp = hess(p, z)
+                pHp = _svm_dot(p, Hp)
+                a = torch.where(cg_on & (pHp > 0), rs / pHp, torch.zeros_like(rs)).to(torch.float32)
+                d = (d[0] + a[:, None] * p[0], d[1] + a * p[1])
+                r = (r[0] - a[:, None] * Hp[0], r[1] - a * Hp[1])
+                rs_new = _svm_dot(r, r)
+                cg_on = cg_on & (rs_new > stop2) & (pHp > 0)
+                b = torch.where(cg_on, rs_new / rs, torch.zeros_like(rs)).to(torch.float32)
+                p = (r[0] + b[:, None] * p[0], r[1] + b * p[1])
+                rs = rs_new
+                if not bool(cg_on.any()):
+                    break
+            # ---- backtracking Armijo search over the ladder of steps, from z and X~ d alone
+            zd = scores(d)
+            ww, wd, dd, gd = _svm_dot(w, w), _svm_dot(w, d), _svm_dot(d, d), _svm_dot(g, d)
+            f_at = 0.5 * (ww + 2.0 * alphas * wd + alphas * alphas * dd) + loss(z, zd, SVM_LADDER)      # [K, C]
+            f_now = 0.5 * ww + loss(z, None, 1)[0]
+            ok = (f_at - f_now <= SVM_ARMIJO * alphas * gd) & (gd < 0)
+            first = ok.to(torch.int32).argmax(0)
+            found = ok.any(0) & active
+            step = torch.where(found, alphas[first, 0], torch.zeros_like(ww)).to(torch.float32)
+            stalled = stalled | (active & ~found)
+            iterations = iterations + found.to(torch.int64)
+            w = (w[0] + step[:, None] * d[0], w[1] + step * d[1])
+            z = scores(w)
+            g = grad(w, z)
+        objective = 0.5 * _svm_dot(w, w) + loss(z, None, 1)[0]
+        info = {"objective": objective, "grad_norm": gn, "grad_norm0": gn0, "iterations": iterations, "converged": conv}
+        return w[0], w[1] * s, info

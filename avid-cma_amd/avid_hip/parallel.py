@@ -2013,6 +2013,136 @@ class MultiLabelEval:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Linear SVM evaluation of frozen features: the sound-classification protocol (ESC-50, DCASE) of the paper, L3 and XDC
+# ---------------------------------------------------------------------------------------------------------------------
+class SVMEval:
+    """A linear one-vs-all SVM (``ops.svm_fit``: liblinear's L2-regularised L2-loss primal) trained on the frozen features of
+    a tower, clip predictions averaged per sample — on the device from the embedding to the counts.
+
+    ``model``: anything ``Inference`` runs — ``R2Plus1D`` / ``Conv2D`` (the output, flattened to ``[rows, F]``), ``AV_Wrapper``
+    (the first embedding; pass ``(video, audio)`` where a clip batch is expected) — or ``None`` to work on features ``[rows, F]``
+    the caller extracted (``MOSTModel``'s pooled taps, say).  A 2-D tensor is always taken as features.
+
+    Training rows are clip-level, as in the protocol: ``add_train(clips, labels, clips_per_sample)`` takes
+    ``[B * clips_per_sample, ...]`` (a sample's clips adjacent; video also as ``[B, clips_per_sample, 3, T, H, W]``,
+    spectrograms ``[B * clips_per_sample, 1, T, F]`` in the flat form only, as for ``KNNEval``) and integer labels ``[B]`` on
+    the device, which are repeated per clip.  ``fit()`` standardises its own copy of the features with the training rows'
+    per-feature mean and (biased) standard deviation when ``standardize`` is set (a constant feature is left unscaled),
+    after the per-row L2 normalisation when ``normalize`` is set, and solves.  ``decision_function`` returns the clip scores
+    ``[rows, n_classes]``; ``evaluate`` averages a sample's clip scores (``view(B, clips, C).mean(1)``) and returns
+    ``{"n", "top1_hits", "top5_hits"}`` as int64 device scalars — counts, so that batches and ranks add up.
+    ``info`` is ``ops.svm_fit``'s.  Nothing here is distributed."""
+
+    def __init__(self, model=None, n_classes=None, cost=1.0, standardize=True, normalize=False, tol=1e-4, pos_weight=None,
+                 intercept_scaling=1.0, max_iter=100):
+        if n_classes is None or int(n_classes) < 1:
+            raise ValueError("SVMEval: n_classes is required")
+        self.model, self.n_classes, self.cost, self.tol = model, int(n_classes), float(cost), float(tol)
+        self.standardize, self.normalize = bool(standardize), bool(normalize)
+        self.pos_weight, self.intercept_scaling, self.max_iter = pos_weight, float(intercept_scaling), int(max_iter)
+        self._infer = Inference(model) if model is not None else None
+        self._chunks = []
+        self.coef = self.intercept = self.mean = self.std = self.info = None
+
+    # ---- features
+    def _features(self, x):
+        """Clip-level features [rows, F], fp32 contiguous (L2-normalised per row when ``normalize``)."""
+        from . import ops
+        with torch.no_grad():
+            if not (isinstance(x, torch.Tensor) and x.dim() == 2):
+                if self._infer is None:
+                    raise ValueError("SVMEval was built without a model: pass features [rows, F]")
+                inputs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
+                inputs = tuple((t.flatten(0, 1) if t.dim() == 6 else t).contiguous() for t in inputs)
+                x = self._infer(*inputs)
+                if isinstance(x, (tuple, list)):
+                    x = x[0]
+            x = x.flatten(1).float().contiguous()
+            return ops.l2_normalize(x) if self.normalize else x
+
+    def _labels(self, labels, n):
+        if labels.is_floating_point() or labels.dtype == torch.bool or tuple(labels.shape) != (n,):
+            raise ValueError(f"SVMEval: labels must be an integer tensor [{n}] (got {labels.dtype} {tuple(labels.shape)})")
+        return labels.to(torch.int64)
+
+    def _samples(self, rows, clips):
+        if clips < 1 or rows % clips:
+            raise ValueError(f"SVMEval: {rows} rows are not a multiple of clips_per_sample = {clips}")
+        return rows // clips
+
+    # ---- training
+    def add_train(self, clips_or_features, labels, clips_per_sample=1):
+        """Embed a batch of training clips (or take features ``[rows, F]``) and keep the rows and their labels on the device."""
+        feats = self._features(clips_or_features)
+        clips = int(clips_per_sample)
+        labels = self._labels(labels, self._samples(feats.shape[0], clips))
+        self._chunks.append((feats, labels.repeat_interleave(clips) if clips > 1 else labels))
+
+    def fit(self, init=None):
+        """Train on everything added so far; returns ``self``.  ``init=(coef, intercept)`` warm-starts (a sweep over ``cost``)."""
+        from . import ops
+        if not self._chunks:
+            raise ValueError("SVMEval.fit: no training rows")
+        with torch.no_grad():
+            X = torch.cat([f for f, _ in self._chunks], 0)
+            y = torch.cat([l for _, l in self._chunks], 0)
+            self._chunks = [(X, y)]
+            if self.standardize:
+                self.mean = X.mean(0)
+                std = X.std(0, unbiased=False)
+                self.std = torch.where(std > 0, std, torch.ones_like(std))
+            else:
+                self.mean = self.std = None
+            self.coef, self.intercept, self.info = ops.svm_fit(
+                self._scaled(X), y, self.n_classes, cost=self.cost, pos_weight=self.pos_weight,
+                intercept_scaling=self.intercept_scaling, tol=self.tol, max_iter=self.max_iter, init=init)
+        return self
+
+    def _scaled(self, feats):
+        return feats if self.mean is None else ((feats - self.mean) / self.std).contiguous()
+
+    # ---- prediction
+    def decision_function(self, clips_or_features):
+        """Clip scores ``[rows, n_classes]`` (``ops.svm_scores`` on the standardised features)."""
+        from . import ops
+        if self.coef is None:
+            raise ValueError("SVMEval: fit() or load_state_dict() first")
+        with torch.no_grad():
+            return ops.svm_scores(self._scaled(self._features(clips_or_features)), self.coef, self.intercept)
+
+    def evaluate(self, clips_or_features, labels, clips_per_sample=1):
+        scores = self.decision_function(clips_or_features)
+        clips = int(clips_per_sample)
+        B = self._samples(scores.shape[0], clips)
+        labels = self._labels(labels, B)
+        scores = scores.view(B, clips, self.n_classes).mean(1)
+        top5 = scores.topk(min(5, self.n_classes), dim=1).indices
+        return {"n": torch.full((), B, dtype=torch.int64, device=scores.device),
+                "top1_hits": (scores.argmax(1) == labels).sum(),
+                "top5_hits": (top5 == labels[:, None]).any(1).sum()}
+
+    # ---- persistence
+    def state_dict(self):
+        if self.coef is None:
+            raise ValueError("SVMEval: fit() first")
+        sd = {"coef": self.coef, "intercept": self.intercept}
+        if self.mean is not None:
+            sd["mean"], sd["std"] = self.mean, self.std
+        return sd
+
+    def load_state_dict(self, sd):
+        coef, intercept = sd["coef"], sd["intercept"]
+        if coef.dim() != 2 or coef.shape[0] != self.n_classes or tuple(intercept.shape) != (self.n_classes,):
+            raise ValueError(f"SVMEval.load_state_dict: coef {tuple(coef.shape)} / intercept {tuple(intercept.shape)} do not "
+                             f"fit {self.n_classes} classes")
+        if ("mean" in sd) != ("std" in sd) or ("mean" in sd) != self.standardize:
+            raise ValueError("SVMEval.load_state_dict: mean and std come together, exactly when standardize is set")
+        self.coef, self.intercept = coef.float().contiguous(), intercept.float().contiguous()
+        self.mean = sd["mean"].float().contiguous() if "mean" in sd else None
+        self.std = sd["std"].float().contiguous() if "std" in sd else None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Action-recognition fine-tuning (eval-action-recg.py: run_phase 'train' / 'test_dense', the warm-up epochs of the classifier)
 # ---------------------------------------------------------------------------------------------------------------------
 class FinetuneStep(AdamStep):

@@ -423,6 +423,7 @@ int avid_counter_add(uint64_t* counter, uint64_t inc, avid_stream_t stream);
 #define AVID_DEVERR_RANK_SCORE 32  /* avid_rank_metrics: NaN score */
 #define AVID_DEVERR_SOFT_TARGET 64 /* avid_soft_ce_loss: target negative or not finite */
 #define AVID_DEVERR_MIX_INDEX 128  /* avid_batch_mix: perm[b] outside [0, B) */
+#define AVID_DEVERR_SVM_LABEL 256  /* avid_svm_hinge / avid_svm_loss: label outside [0, C) */
 
 /* Action-recognition fine-tuning head (utils/eval_utils.py:193-214, eval-action-recg.py:150-165) — classify.hip.
  *
@@ -747,6 +748,36 @@ int avid_knn_vote(int nq, int k, const int32_t* idx, const float* sim, const int
 size_t avid_rank_metrics_workspace_bytes(int64_t N, int C);
 int avid_rank_metrics(int64_t N, int C, const float* scores, const float* targets, double* ap, double* auc, int64_t* n_pos,
                       void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream);
+
+/* Linear one-vs-all SVM on frozen features (version >= 173) — svm.hip: the passes of a full-batch solver of the L2-regularised
+ * L2-loss primal (liblinear's, scikit-learn's LinearSVC default; ops.svm_fit is the solver) over x [N][F] fp32 row-major,
+ * 1 <= N < 2^31 (N * F may pass 2^31: 64-bit offsets), any F >= 1, any C >= 1 (more than 64 classes: blocks of 64).
+ * Products are exact fp32 (v_mfma_f32_32x32x2_f32); every result is one sum in an order fixed by (N, F, C): no atomics, the
+ * same bits on every run, under every CU budget, and for a row of x whatever block of rows it is passed in.
+ *   avid_svm_scores: z [N][C] = x . w^T + bias (w [C][F], bias [C] nullable).  One workgroup owns 64 rows x 64 classes and
+ *     the whole reduction over F: element = (s0 + s1) + bias, s0 / s1 the fmaf chains over the features f with f % 4 in
+ *     {0, 1} / {2, 3} in ascending f.  Also serves the Hessian-vector products (w = a direction) and prediction.
+ *   avid_svm_xt: g [C][F] = d^T . x and gb [C] = column sums of d (nullable) for d [N][C].  Rows are cut into slices of 512
+ *     (their count depends on N only); a slice's partial element is (s0 + s1) as above over its rows (row index % 4), the
+ *     partial tiles go to ws and are added in slice order in double, rounded once.  gb: double sums, rows r % 4 == j of a
+ *     slice in ascending order, j = 0..3 in order, slices in order, rounded once.
+ *   avid_svm_hinge: with y = +1 where labels[i] == c else -1, cost_ic = y > 0 ? cost * pos_weight[c] : cost (pos_weight
+ *     nullable), m = fma(-y, z, 1): xv == NULL: out = (y * m) * cost_ic where m > 0, else 0 (the hinge residual; the
+ *     gradient is w - 2 x^T out); xv != NULL: out = cost_ic * xv where m > 0, else 0 (the active set applied to x . v).
+ *   avid_svm_loss: out [K][C] double, out[k][c] = sum_i cost_ic max(0, 1 - y (z + 2^-k zd))^2 evaluated in double from the
+ *     fp32 inputs, 1 <= K <= 16 (zd nullable when K == 1: the loss at z); rows in partial sums of 256 (in ws), then in order.
+ * labels: int32 [N]; one outside [0, C) ORs AVID_DEVERR_SVM_LABEL into err (nullable) and counts as no class.
+ * ws: avid_svm_workspace_bytes(N, F, C) bytes, 8-byte aligned, covers avid_svm_xt and avid_svm_loss (0 = unsupported
+ * arguments).  Null pointers, shapes outside the limits and a short workspace are refused before any launch. */
+size_t avid_svm_workspace_bytes(int64_t N, int F, int C);
+int avid_svm_scores(int64_t N, int F, int C, const float* x, const float* w, const float* bias, float* z,
+                    avid_stream_t stream);
+int avid_svm_xt(int64_t N, int F, int C, const float* x, const float* d, float* g, float* gb, void* ws, size_t ws_bytes,
+                avid_stream_t stream);
+int avid_svm_hinge(int64_t N, int C, const float* z, const int32_t* labels, float cost, const float* pos_weight,
+                   const float* xv, float* out, int32_t* err, avid_stream_t stream);
+int avid_svm_loss(int64_t N, int C, int K, const float* z, const float* zd, const int32_t* labels, float cost,
+                  const float* pos_weight, double* out, void* ws, size_t ws_bytes, int32_t* err, avid_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: torch.optim.Adam semantics (L2 weight decay folded into the gradient; bias-corrected)
